@@ -1,6 +1,6 @@
 """bench.py — headline benchmark of the Surface-Network hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N>1: one rank per GPU.  Either the caller starts the ranks (python -m torch.distributed.run --nproc-per-node N bench.py
 --gpus N ...: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment) or — when WORLD_SIZE is not set — bench.py
@@ -12,7 +12,14 @@ as_rigid_as_possible temporal prediction, Dirac model (15 blocks @128 ch, 1 018 
 GPU + forward + masked smooth-L1 loss + backward + flat-bucket RCCL gradient all-reduce (N>1) + Adam update.
 Weak scaling: every rank owns its own 64 meshes (the path shards by mesh; no data-path collective).
 
-The line on stdout is COMPACT (compact_line: < 4 KB — the contract keys, config / roofline / cpu_baseline as scalars, one number
+A plain run does only what the headline needs: set-up, 3 untimed steps + W warm-up steps, the K timed steps, and one JSON line
+(the contract keys and `config`; `roofline` and `cpu_baseline` are null, no detail file).  `--dump-outputs DIR` then writes what
+the last timed step left its caller (the loss, the updated parameters, their gradients, the BatchNorm running statistics) as
+DIR/<name>.npy; data, weights and batch draws are seeded, so the same arguments give the same inputs.  `--full` adds everything
+described below: the per-launch kernel timing, the in-run counter passes, the secondary configurations, the CPU baseline, the
+host-enqueue figure and the replica check after the timed steps.
+
+With --full the line on stdout is COMPACT (compact_line: < 4 KB — the contract keys, config / roofline / cpu_baseline as scalars, one number
 per secondary configuration); the FULL result described below goes to bench_detail.json next to this script (and to gpurun_out/
 when present), path named in the line under "detail".
 
@@ -180,6 +187,28 @@ def emit(full: dict, result_fd: int, detail_name: str = DETAIL_FILE):
         line = json.dumps(slim, separators=(",", ":"))
     sys.stdout.flush()
     os.write(result_fd, (line + "\n").encode())
+
+
+def emit_line(full: dict, result_fd: int):
+    """A plain run's result: the compact line alone (nothing beyond the headline was measured, so no detail file)."""
+    sys.stdout.flush()
+    os.write(result_fd, (json.dumps(compact_line(full), separators=(",", ":")) + "\n").encode())
+
+
+def dump_outputs(path: str, model, loss) -> None:
+    """--dump-outputs: what the caller of the timed training step holds after the last one — the loss it returned, the
+    updated parameters, their gradients and the floating-point buffers (BatchNorm running statistics) — as
+    <path>/loss.npy, param.<name>.npy, grad.<name>.npy, buffer.<name>.npy in the dtype computed (float32; ~8 MB in all)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": loss}
+    for k, p in model.named_parameters():
+        arrays[f"param.{k}"] = p
+        if p.grad is not None:
+            arrays[f"grad.{k}"] = p.grad
+    arrays.update((f"buffer.{k}", b) for k, b in model.named_buffers() if b.is_floating_point())
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
 
 
 def _cpu_leg(sample_meshes: int, seed: int, threads: int, budget_s: float, max_reps: int):
@@ -635,11 +664,12 @@ def c4_pair_secondary(device, steps: int = 60, warm: int = 10):
             "eager_ms_per_step": eager * 1e3}
 
 
-def c4_dp_step(device, rank: int, world: int, steps: int = 40, warm: int = 8):
+def c4_dp_step(device, rank: int, world: int, steps: int = 40, warm: int = 8, check_replicas: bool = True, dump_dir=None):
     """BASELINE configs[3] as the N-rank job it is (src/dense_correspondence/main.py:40,299-327: batch 1 per device): every
     rank trains on ITS OWN pair of FAUST-sized bodies per step — forward + loss + backward replayed from one hipGraph —, then
     one flat-bucket all-reduce (SUM; the loss is normalised by the number of pairs in the job) and Adam.  Returns the local
-    seconds per step and the bookkeeping of the run; the caller takes the MAX over ranks."""
+    seconds per step and the bookkeeping of the run; the caller takes the MAX over ranks.  check_replicas: compare the ranks'
+    parameters after the run (None in the bookkeeping otherwise); dump_dir: rank 0 writes the last step's outputs there."""
     import torch.distributed as dist
 
     from surfacenetworks_amd import dense_correspondence as dc
@@ -685,9 +715,11 @@ def c4_dp_step(device, rank: int, world: int, steps: int = 40, warm: int = 8):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     assert torch.isfinite(loss.detach()).item(), "FAUST step diverged"
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, model, loss)
     return dt / steps, {"steps": steps, "warmup": warm, "host_enqueue_ms_per_step": t_enq / steps * 1e3,
                         "grad_bucket_bytes": bucket.nbytes, "launch": launch,
-                        "replicas_identical_after_the_run": replicas_agree(model, world)}
+                        "replicas_identical_after_the_run": replicas_agree(model, world) if check_replicas else None}
 
 
 def gpu_numa_node(device_index: int, sysfs: str = "/sys") -> int:
@@ -757,8 +789,8 @@ def pmc_in_run(args, steps: int = 4):
     if exe is None:
         return None, "rocprofv3 not found"
     tmp = tempfile.mkdtemp(prefix="sn_pmc_", dir="/tmp")
-    child = [sys.executable, os.path.abspath(__file__), "--steps", str(steps), "--warmup", "1", "--no-cpu-baseline", "--no-secondary",
-             "--no-pmc", "--backend", "none", "--meshes", str(args.meshes), "--format", args.format, "--operators", args.operators,
+    child = [sys.executable, os.path.abspath(__file__), "--full", "--steps", str(steps), "--warmup", "1", "--no-cpu-baseline",
+             "--no-secondary", "--no-pmc", "--backend", "none", "--meshes", str(args.meshes), "--format", args.format, "--operators", args.operators,
              "--linear-timing-steps", "0"]
     env = dict(os.environ, TMPDIR="/tmp")
     env.pop("RANK", None), env.pop("WORLD_SIZE", None), env.pop("LOCAL_RANK", None)
@@ -817,237 +849,10 @@ def self_launch(args, argv):
     return subprocess.call(cmd, env=env)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--meshes", type=int, default=MESHES_PER_GPU, help="meshes per GPU (default: the BASELINE config)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--graph", action="store_true",
-                    help="replay forward+loss+backward from one captured hipGraph per step instead of launching every "
-                         "kernel from Python (same kernels; pays off when the step is launch-bound: small batches, busy hosts). "
-                         "Default with more than one rank (N eager-launching Python processes share one host); --eager overrides")
-    ap.add_argument("--eager", action="store_true", help="launch every kernel from Python also with more than one rank")
-    ap.add_argument("--workload", default="arap", choices=["arap", "faust"],
-                    help="arap (default): BASELINE configs[2], the headline; faust: BASELINE configs[3] — dense correspondence, one "
-                         "pair of 6890-vertex bodies per rank and step, Laplacian towers, hipGraph replay + flat-bucket all-reduce")
-    ap.add_argument("--no-pmc", action="store_true",
-                    help="skip the in-run counter passes (rocprofv3 --pmc over a few steps of this same workload, N = 1 only)")
-    ap.add_argument("--roofline-steps", type=int, default=5,
-                    help="eager steps run AFTER the timed region with per-launch HIP events (graph mode only)")
-    ap.add_argument("--linear-timing-steps", type=int, default=5,
-                    help="timed steps whose Linear-layer launches carry start/stop events as well (roofline.linear_kernels).  An event "
-                         "pair costs a launch ~2 us: 0.3 ms on all of a step's launches")
-    ap.add_argument("--spmm-timing-steps", type=int, default=5,
-                    help="timed steps (the first ones of the timed region) whose sparse products carry start/stop events (roofline."
-                         "achieved): 32 launches per step, 0.10-0.15 ms per step when carried on all 20 (same box, three reps: 19.17 / "
-                         "19.24 / 19.30 ms against 19.08 / 19.11 / 19.15 with 5); 0 or less: every timed step")
-    ap.add_argument("--format", default="q3", choices=["q3", "bsr4", "csr"],
-                    help="Dirac operator form: quaternion-packed blocks (default), 4x4 blocks, generic CSR")
-    ap.add_argument("--operators", default="pool", choices=["pool", "device"],
-                    help="pool: precomputed per-frame operators resident in HBM (default, = the reference's dataset); "
-                         "device: Dirac operators rebuilt on the GPU from the frame coordinates every step")
-    ap.add_argument("--backend", default=None, choices=[None, "nccl", "gloo", "none"],
-                    help="default nccl (= RCCL) — also with ONE rank: a one-rank communicator, the gradient bucket goes "
-                         "through ncclAllReduce every step; gloo only for functional tests of the N>1 path on a 1-GPU box "
-                         "(chosen automatically when there are fewer visible GPUs than ranks); none: no process group at N = 1")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the config-5 SpMM roofline block")
-    ap.add_argument("--cpu-leg", default=None, help=argparse.SUPPRESS)      # internal: one time-boxed leg of cpu_baseline()
-    ap.add_argument("--c5-pmc-child", default=None, help=argparse.SUPPRESS)  # internal: the config-5 products under the profiler
-    args = ap.parse_args()
-    world_hint = int(os.environ.get("WORLD_SIZE", str(args.gpus)))
-    # N ranks on N devices: replay unless --eager (N eager-launching Python processes share one host).  Ranks that SHARE a
-    # device (the functional run of the N > 1 path on a 1-GPU box) stay eager: replaying two processes' graphs on one device
-    # measured 1.4 s per step against 42 ms eager
-    try:
-        n_dev = torch.cuda.device_count()
-    except Exception:  # noqa: BLE001
-        n_dev = 0
-    args.graph_default = (world_hint > 1 and not args.eager and n_dev >= world_hint)
-    args.no_graph = not (args.graph or args.graph_default)
-    if args.cpu_leg:
-        n_, seed_, thr_, bud_, reps_ = args.cpu_leg.split(",")
-        v, reps = _cpu_leg(int(n_), int(seed_), int(thr_), float(bud_), int(reps_))
-        print(json.dumps({"value": v, "reps": reps, "threads": int(thr_), "meshes": int(n_)}), flush=True)
-        return
-    if args.c5_pmc_child:
-        plan_path, n_ = args.c5_pmc_child.rsplit(",", 1)
-        c5_pmc_child(plan_path, int(n_))
-        return
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        raise SystemExit(self_launch(args, sys.argv[1:]))
-
-    # The contract is ONE JSON line on stdout.  Libraries write there too (RCCL prints a version banner through C stdio when
-    # its communicator goes away — after our line, once a one-rank group is part of every run): from here on file
-    # descriptor 1 is stderr for everybody, and the line goes to the saved descriptor.
-    sys.stdout.flush()
-    result_fd = os.dup(1)
-    os.dup2(2, 1)
-
-    import torch.distributed as dist
-
-    from surfacenetworks_amd import arap, dp, plans
-    from surfacenetworks_amd import functional as snF
-
-    if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs an MI355X (no CPU path in the product)")
-    world_env = int(os.environ.get("WORLD_SIZE", "1"))
-    oversubscribed = world_env > torch.cuda.device_count()
-    backend = args.backend or ("gloo" if oversubscribed else "nccl")    # RCCL cannot put two ranks on one device
-    group_note = None
-    if world_env == 1 and backend != "none":
-        # one rank: still a process group, so that the step's gradient reduction is a real collective call
-        if "MASTER_PORT" not in os.environ:
-            sock = socket.socket()
-            sock.bind(("127.0.0.1", 0))
-            os.environ["MASTER_PORT"] = str(sock.getsockname()[1])
-            sock.close()
-        os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        try:
-            rank, local_rank, world, device = dp.init_distributed(backend, single_rank_group=True)
-        except Exception as exc:  # noqa: BLE001 — the headline number must not depend on the one-rank communicator coming up
-            group_note = f"one-rank {backend} group failed to initialise: {exc!r}"[:200]
-            rank, local_rank, world, device = dp.init_distributed(None)
-    else:
-        rank, local_rank, world, device = dp.init_distributed(None if backend == "none" else backend)
-    if world != args.gpus:
-        raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run --nproc-per-node {args.gpus}")
-    n_local_ranks = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
-    affinity = pin_to_gpu_numa(local_rank, n_local_ranks) if world > 1 else "single rank: not pinned"
-    snF.set_dirac_format(args.format)
-    torch.manual_seed(1234)
-    if args.workload == "faust":
-        # BASELINE configs[3] as its own line: N ranks, one pair per rank and step (same contract: barrier + synchronize on both
-        # sides inside c4_dp_step, MAX over ranks, rank 0 prints)
-        steps_f, warm_f = args.steps, args.warmup
-        dt_f, info = c4_dp_step(device, rank, world, steps_f, warm_f)
-        t = torch.tensor([dt_f], dtype=torch.float64, device=device)
-        if world > 1:
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt_f = float(t.item())
-        line = {"metric": "pairs/sec fwd+bwd, FAUST dense correspondence (BASELINE configs[3])", "value": world / dt_f, "unit": "pairs/s",
-                "n_gpus": world, "steps": steps_f, "warmup": warm_f, "ms_per_step": dt_f * 1e3, "higher_is_better": True,
-                "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "meshes_per_s": 2 * world / dt_f,
-                "config": {"workload": "FAUST dense correspondence: one pair of torus-grid bodies (6890 vertices padded to 7000) per rank "
-                                       "and step, Laplacian towers C=128, 15 blocks, score matrix never materialised, delta cross entropy, "
-                                       "hipGraph replay of fwd+loss+bwd, pack + all-reduce(SUM) of the flat gradient bucket, Adam",
-                           "global_pairs": world, "parallelism": f"dp{world} (one pair per rank, flat-bucket all-reduce)",
-                           "world_size": world, "rccl_ranks": world if (dist.is_initialized() and dist.get_backend() == "nccl") else 0,
-                           "collective_backend": dist.get_backend() if dist.is_initialized() else "none",
-                           "devices_visible": torch.cuda.device_count(), "ranks_share_devices": bool(oversubscribed),
-                           "host_affinity": affinity, **info},
-                "roofline": None, "cpu_baseline": None}
-        if rank == 0:
-            emit(line, result_fd, "bench_detail_faust.json")
-        if dist.is_initialized():
-            if world > 1:
-                dist.barrier()
-            dist.destroy_process_group()
-        return
-
-    # ---- data: this rank's shard (own meshes; weak scaling) -----------------------------------------
-    n_local = args.meshes
-    ds = arap.ClothSequences([GRID] * n_local, frames=arap.INPUT_FRAMES + arap.OUTPUT_FRAMES + 2, op_frames=2,
-                             seed=3 + 1000 * rank, device=device, model="dir", operators=args.operators)
-    model = arap.DirModel().to(device).train()
-    dp.broadcast_parameters(model, 0)
-    bucket = dp.FlatGradBucket(model.parameters(), always_reduce=dist.is_initialized())
-    opt = arap.make_optimizer(model)
-    global_batch = n_local * world
-    rng = np.random.default_rng(10 + rank)
-    seq_ids = np.arange(n_local)
-
-    def eager_step():
-        batch = ds.sample_batch(n_local, rng, seq_ids=seq_ids)          # every local mesh once, random start frame
-        # gradients are stored, not accumulated (.grad = None before the backward); bucket.sync() packs + all-reduces them
-        return arap.train_step(model, opt, batch, global_batch=global_batch, grad_sync=bucket.sync, zero_grads=bucket.detach_grads)
-
-    graphed = None
-
-    def graph_step():
-        batch = ds.sample_batch(n_local, rng, seq_ids=seq_ids)
-        return graphed(batch, grad_sync=bucket.sync)                    # load -> one hipGraphLaunch -> pack + all-reduce -> Adam
-
-    one_step = eager_step if args.no_graph else graph_step
-
-    def sync():
-        if world > 1:
-            dist.barrier()
-        torch.cuda.synchronize()
-
-    # untimed: lazy code-object loading, allocator growth and clock ramp (3 eager steps; in graph mode the capture of
-    # forward+loss+backward follows), then the W warm-up steps asked for
-    for _ in range(3):
-        eager_step()
-    graph_fallback = None
-    if not args.no_graph:
-        try:
-            graphed = arap.GraphedTrainStep(model, opt, ds.sample_batch(n_local, rng, seq_ids=seq_ids),
-                                            global_batch=global_batch, bucket=bucket)
-        except Exception as exc:  # noqa: BLE001  (a rank whose capture fails runs eagerly: same step, same collective; the line says so)
-            graph_fallback = f"{type(exc).__name__}: {exc}"[:300]
-            graphed = None
-            args.no_graph = True
-            one_step = eager_step
-            try:
-                torch.cuda.synchronize()
-            except Exception:  # noqa: BLE001
-                pass
-    for _ in range(args.warmup):
-        one_step()
-    sync()
-    timer = snF.SpmmTimer()
-    ms0 = torch.cuda.memory_stats()
-    t0 = time.perf_counter()
-    if args.no_graph:
-        n_ev = args.steps if args.spmm_timing_steps <= 0 else min(args.spmm_timing_steps, args.steps)
-        with timer:                                  # per-launch HIP events on every SpMM of the first n_ev timed steps
-            for i in range(n_ev):
-                if i == args.linear_timing_steps:    # the ~120 Linear launches of a step carry events on the first steps only
-                    timer.time_linear(False)
-                loss = one_step().detach()           # (keeping the loss itself would keep the step's autograd graph alive)
-        for i in range(n_ev, args.steps):            # the rest of the timed region without events
-            loss = one_step().detach()
-    else:
-        for _ in range(args.steps):
-            loss = one_step().detach()
-    t_enqueue = time.perf_counter() - t0               # the host has issued every step; the device may still be running
-    sync()
-    dt = time.perf_counter() - t0
-    ms1 = torch.cuda.memory_stats()
-    alloc = {"hipMalloc_calls_in_timed_region": ms1.get("num_device_alloc", 0) - ms0.get("num_device_alloc", 0),
-             "hipFree_calls_in_timed_region": ms1.get("num_device_free", 0) - ms0.get("num_device_free", 0),
-             "alloc_retries": ms1.get("num_alloc_retries", 0) - ms0.get("num_alloc_retries", 0),
-             "reserved_GiB": round(ms1.get("reserved_bytes.all.peak", 0) / 2**30, 2),
-             "allocated_peak_GiB": round(ms1.get("allocated_bytes.all.peak", 0) / 2**30, 2)}
-    if not args.no_graph:
-        # kernels inside a replayed hipGraph cannot carry start/stop events, so the SpMM launches are timed on the same
-        # steps launched eagerly right after the timed region (same kernels, operands and preceding kernels; the
-        # rocprofv3 summary under profiles/ covers the replayed launches and agrees)
-        with timer:
-            for _ in range(max(1, args.roofline_steps)):
-                eager_step()
-        sync()
-    # host cost of issuing ONE step into an idle queue (after the timed region): inside the timed loop the host runs ahead of a
-    # GPU-bound step until the launch queue is full and then waits for the device — the in-loop figure measures the queue depth,
-    # not the host
-    host_alone = []
-    for _ in range(5):
-        torch.cuda.synchronize()
-        th = time.perf_counter()
-        one_step()
-        host_alone.append(time.perf_counter() - th)
-    sync()
-    t_host_alone = float(np.median(host_alone))
-    dt_t = torch.tensor([dt], dtype=torch.float64, device=device)
-    if world > 1:
-        dist.all_reduce(dt_t, op=dist.ReduceOp.MAX)
-    dt = float(dt_t.item())
-    assert torch.isfinite(loss).item(), "training diverged"
-    replicas_identical = replicas_agree(model, world)
-
-    # ---- roofline of the dominant kernel, from the HIP events recorded during the timed steps ---------
+def roofline_result(args, timer, rank: int, world: int) -> dict:
+    """--full: the roofline of the dominant SpMM kernel of the timed steps, from the HIP events `timer` recorded (eager runs:
+    the first timed steps; replayed runs: eager steps right after them), with the HBM traffic of the in-run counter passes
+    (or the stamped profile) and the Linear-layer kernels of the same steps."""
     recs = timer.results()
     # group by KERNEL (as rocprofv3 --stats does): one template instantiation serves the four Dirac products
     # (Di, DiA forward; Di^T, DiA^T backward), which differ only in which side is the face side.
@@ -1138,6 +943,284 @@ def main():
                               "ms_per_step": float(np.sum(v)) / n_lin_steps} for k, v in lin.items()),
                             key=lambda d: -d["ms_per_step"])
 
+    return {"bound": "hbm", "kernel": dom_name + (" (the backward products Di^T, DiA^T, ELU backward fused into the store)" if "_epi" in dom_name
+                                                 else " (the Dirac products launched without epilogue)"),
+            # `frac` is the MORE CONSERVATIVE of the two defensible readings of the fused launch: algorithmic bytes of the
+            # product plus the epilogue operands it must read, or — when a counter file of these very sources exists —
+            # the HBM traffic the counters measured; the three conventions stay side by side below
+            "achieved": frac_top * HBM_PEAK / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": frac_top,
+            "frac_convention": frac_conv,
+            "traffic": traffic, "traffic_source": traffic_src, "step_traffic": step_traffic,
+            "algorithmic_bytes_definition": "SURVEY.md §8(d) CSR/int32/fp32 bytes of the product (nnz*8 + (M+1)*4 + K*N*4 + M*N*4) "
+                                            "plus, for the fused ELU-backward launches, the epilogue operands E and G (M*N*4 each) "
+                                            "that the fused kernel must read; the three figures below separate the conventions",
+            "frac_by_convention": {
+                "product_plus_epilogue_operands": frac_alg,
+                "product_bytes_only": product_bytes / (tot_ms * 1e-3) / HBM_PEAK,
+                "measured_hbm_traffic": frac_meas},
+            "algorithmic_bytes_per_launch": ab, "avg_launch_ms": avg_ms,
+            "timing": "hipExtLaunchKernelGGL start/stop events on the launch stream, " +
+                      (f"every launch of the first {n_ev_steps} of the {args.steps} timed steps" if args.no_graph else
+                       f"every launch of {max(1, args.roofline_steps)} eager steps run right after the timed hipGraph replays"),
+            "launches_timed": len(dom), "spmm_ms_per_step_all_kernels": spmm_ms_per_step, "per_product": per_shape,
+            "other_spmm_kernels": [
+                {"kernel": k, "launches": len(v), "avg_launch_ms": sum(r[5] for r in v) / len(v),
+                 "frac": sum(alg_bytes(r[1], r[2], r[3], r[4], r[0]) for r in v) / (sum(r[5] for r in v) * 1e-3) / HBM_PEAK}
+                for k, v in by_kernel.items() if k != dom_name],
+            "linear_kernels": linear_kernels,
+            "linear_kernels_note": "kernel[variant]: linear_fwd bits 1 elu copy, 2 residual, 4 y written, 8 per-mesh bias; "
+                                   "linear_dgrad bits 1 BatchNorm tail, 2 through the activation, 4 gadd, 8 per-mesh vector; "
+                                   "bytes = operands read + results written (weights excluded), timed like the SpMM launches"
+                                   + (f" on the first {n_lin_steps} of the {args.steps} timed steps (an event pair costs a launch ~2 us; "
+                                      f"the sparse products on the first {n_ev_steps})" if args.no_graph else ""),
+            "linear_ms_per_step": float(sum(d["ms_per_step"] for d in linear_kernels))}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--meshes", type=int, default=MESHES_PER_GPU, help="meshes per GPU (default: the BASELINE config)")
+    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--graph", action="store_true",
+                    help="replay forward+loss+backward from one captured hipGraph per step instead of launching every "
+                         "kernel from Python (same kernels; pays off when the step is launch-bound: small batches, busy hosts). "
+                         "Default with more than one rank (N eager-launching Python processes share one host); --eager overrides")
+    ap.add_argument("--eager", action="store_true", help="launch every kernel from Python also with more than one rank")
+    ap.add_argument("--workload", default="arap", choices=["arap", "faust"],
+                    help="arap (default): BASELINE configs[2], the headline; faust: BASELINE configs[3] — dense correspondence, one "
+                         "pair of 6890-vertex bodies per rank and step, Laplacian towers, hipGraph replay + flat-bucket all-reduce")
+    ap.add_argument("--no-pmc", action="store_true",
+                    help="skip the in-run counter passes (rocprofv3 --pmc over a few steps of this same workload, N = 1 only)")
+    ap.add_argument("--roofline-steps", type=int, default=5,
+                    help="eager steps run AFTER the timed region with per-launch HIP events (graph mode only)")
+    ap.add_argument("--linear-timing-steps", type=int, default=5,
+                    help="timed steps whose Linear-layer launches carry start/stop events as well (roofline.linear_kernels).  An event "
+                         "pair costs a launch ~2 us: 0.3 ms on all of a step's launches")
+    ap.add_argument("--spmm-timing-steps", type=int, default=5,
+                    help="timed steps (the first ones of the timed region) whose sparse products carry start/stop events (roofline."
+                         "achieved): 32 launches per step, 0.10-0.15 ms per step when carried on all 20 (same box, three reps: 19.17 / "
+                         "19.24 / 19.30 ms against 19.08 / 19.11 / 19.15 with 5); 0 or less: every timed step")
+    ap.add_argument("--format", default="q3", choices=["q3", "bsr4", "csr"],
+                    help="Dirac operator form: quaternion-packed blocks (default), 4x4 blocks, generic CSR")
+    ap.add_argument("--operators", default="pool", choices=["pool", "device"],
+                    help="pool: precomputed per-frame operators resident in HBM (default, = the reference's dataset); "
+                         "device: Dirac operators rebuilt on the GPU from the frame coordinates every step")
+    ap.add_argument("--backend", default=None, choices=[None, "nccl", "gloo", "none"],
+                    help="default nccl (= RCCL) — also with ONE rank: a one-rank communicator, the gradient bucket goes "
+                         "through ncclAllReduce every step; gloo only for functional tests of the N>1 path on a 1-GPU box "
+                         "(chosen automatically when there are fewer visible GPUs than ranks); none: no process group at N = 1")
+    ap.add_argument("--no-secondary", action="store_true", help="skip the config-5 SpMM roofline block")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline as well (off: set-up, warm-up, the timed steps and the "
+                         "line): per-launch SpMM / Linear timing in the timed steps (roofline), the in-run counter passes, the "
+                         "secondary configurations, the CPU baseline, host enqueue time, the replica check; writes the detail file. "
+                         "--no-secondary / --no-cpu-baseline / --no-pmc leave parts of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, updated parameters, gradients, BatchNorm "
+                         "running statistics) as DIR/<name>.npy")
+    ap.add_argument("--cpu-leg", default=None, help=argparse.SUPPRESS)      # internal: one time-boxed leg of cpu_baseline()
+    ap.add_argument("--c5-pmc-child", default=None, help=argparse.SUPPRESS)  # internal: the config-5 products under the profiler
+    args = ap.parse_args()
+    world_hint = int(os.environ.get("WORLD_SIZE", str(args.gpus)))
+    # N ranks on N devices: replay unless --eager (N eager-launching Python processes share one host).  Ranks that SHARE a
+    # device (the functional run of the N > 1 path on a 1-GPU box) stay eager: replaying two processes' graphs on one device
+    # measured 1.4 s per step against 42 ms eager
+    try:
+        n_dev = torch.cuda.device_count()
+    except Exception:  # noqa: BLE001
+        n_dev = 0
+    args.graph_default = (world_hint > 1 and not args.eager and n_dev >= world_hint)
+    args.no_graph = not (args.graph or args.graph_default)
+    if args.cpu_leg:
+        n_, seed_, thr_, bud_, reps_ = args.cpu_leg.split(",")
+        v, reps = _cpu_leg(int(n_), int(seed_), int(thr_), float(bud_), int(reps_))
+        print(json.dumps({"value": v, "reps": reps, "threads": int(thr_), "meshes": int(n_)}), flush=True)
+        return
+    if args.c5_pmc_child:
+        plan_path, n_ = args.c5_pmc_child.rsplit(",", 1)
+        c5_pmc_child(plan_path, int(n_))
+        return
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        raise SystemExit(self_launch(args, sys.argv[1:]))
+
+    # The contract is ONE JSON line on stdout.  Libraries write there too (RCCL prints a version banner through C stdio when
+    # its communicator goes away — after our line, once a one-rank group is part of every run): from here on file
+    # descriptor 1 is stderr for everybody, and the line goes to the saved descriptor.
+    sys.stdout.flush()
+    result_fd = os.dup(1)
+    os.dup2(2, 1)
+
+    import torch.distributed as dist
+
+    from surfacenetworks_amd import arap, dp, plans
+    from surfacenetworks_amd import functional as snF
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench.py needs an MI355X (no CPU path in the product)")
+    world_env = int(os.environ.get("WORLD_SIZE", "1"))
+    oversubscribed = world_env > torch.cuda.device_count()
+    backend = args.backend or ("gloo" if oversubscribed else "nccl")    # RCCL cannot put two ranks on one device
+    group_note = None
+    if world_env == 1 and backend != "none":
+        # one rank: still a process group, so that the step's gradient reduction is a real collective call
+        if "MASTER_PORT" not in os.environ:
+            sock = socket.socket()
+            sock.bind(("127.0.0.1", 0))
+            os.environ["MASTER_PORT"] = str(sock.getsockname()[1])
+            sock.close()
+        os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+        try:
+            rank, local_rank, world, device = dp.init_distributed(backend, single_rank_group=True)
+        except Exception as exc:  # noqa: BLE001 — the headline number must not depend on the one-rank communicator coming up
+            group_note = f"one-rank {backend} group failed to initialise: {exc!r}"[:200]
+            rank, local_rank, world, device = dp.init_distributed(None)
+    else:
+        rank, local_rank, world, device = dp.init_distributed(None if backend == "none" else backend)
+    if world != args.gpus:
+        raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run --nproc-per-node {args.gpus}")
+    n_local_ranks = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
+    affinity = pin_to_gpu_numa(local_rank, n_local_ranks) if world > 1 else "single rank: not pinned"
+    snF.set_dirac_format(args.format)
+    torch.manual_seed(1234)
+    if args.workload == "faust":
+        # BASELINE configs[3] as its own line: N ranks, one pair per rank and step (same contract: barrier + synchronize on both
+        # sides inside c4_dp_step, MAX over ranks, rank 0 prints)
+        steps_f, warm_f = args.steps, args.warmup
+        dt_f, info = c4_dp_step(device, rank, world, steps_f, warm_f, check_replicas=args.full, dump_dir=args.dump_outputs)
+        t = torch.tensor([dt_f], dtype=torch.float64, device=device)
+        if world > 1:
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt_f = float(t.item())
+        line = {"metric": "pairs/sec fwd+bwd, FAUST dense correspondence (BASELINE configs[3])", "value": world / dt_f, "unit": "pairs/s",
+                "n_gpus": world, "steps": steps_f, "warmup": warm_f, "ms_per_step": dt_f * 1e3, "higher_is_better": True,
+                "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "meshes_per_s": 2 * world / dt_f,
+                "config": {"workload": "FAUST dense correspondence: one pair of torus-grid bodies (6890 vertices padded to 7000) per rank "
+                                       "and step, Laplacian towers C=128, 15 blocks, score matrix never materialised, delta cross entropy, "
+                                       "hipGraph replay of fwd+loss+bwd, pack + all-reduce(SUM) of the flat gradient bucket, Adam",
+                           "global_pairs": world, "parallelism": f"dp{world} (one pair per rank, flat-bucket all-reduce)",
+                           "world_size": world, "rccl_ranks": world if (dist.is_initialized() and dist.get_backend() == "nccl") else 0,
+                           "collective_backend": dist.get_backend() if dist.is_initialized() else "none",
+                           "devices_visible": torch.cuda.device_count(), "ranks_share_devices": bool(oversubscribed),
+                           "host_affinity": affinity, **info},
+                "roofline": None, "cpu_baseline": None}
+        if rank == 0:
+            if args.full:
+                emit(line, result_fd, "bench_detail_faust.json")
+            else:
+                emit_line(line, result_fd)
+        if dist.is_initialized():
+            if world > 1:
+                dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- data: this rank's shard (own meshes; weak scaling) -----------------------------------------
+    n_local = args.meshes
+    ds = arap.ClothSequences([GRID] * n_local, frames=arap.INPUT_FRAMES + arap.OUTPUT_FRAMES + 2, op_frames=2,
+                             seed=3 + 1000 * rank, device=device, model="dir", operators=args.operators)
+    model = arap.DirModel().to(device).train()
+    dp.broadcast_parameters(model, 0)
+    bucket = dp.FlatGradBucket(model.parameters(), always_reduce=dist.is_initialized())
+    opt = arap.make_optimizer(model)
+    global_batch = n_local * world
+    rng = np.random.default_rng(10 + rank)
+    seq_ids = np.arange(n_local)
+
+    def eager_step():
+        batch = ds.sample_batch(n_local, rng, seq_ids=seq_ids)          # every local mesh once, random start frame
+        # gradients are stored, not accumulated (.grad = None before the backward); bucket.sync() packs + all-reduces them
+        return arap.train_step(model, opt, batch, global_batch=global_batch, grad_sync=bucket.sync, zero_grads=bucket.detach_grads)
+
+    graphed = None
+
+    def graph_step():
+        batch = ds.sample_batch(n_local, rng, seq_ids=seq_ids)
+        return graphed(batch, grad_sync=bucket.sync)                    # load -> one hipGraphLaunch -> pack + all-reduce -> Adam
+
+    one_step = eager_step if args.no_graph else graph_step
+
+    def sync():
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+
+    # untimed: lazy code-object loading, allocator growth and clock ramp (3 eager steps; in graph mode the capture of
+    # forward+loss+backward follows), then the W warm-up steps asked for
+    for _ in range(3):
+        eager_step()
+    graph_fallback = None
+    if not args.no_graph:
+        try:
+            graphed = arap.GraphedTrainStep(model, opt, ds.sample_batch(n_local, rng, seq_ids=seq_ids),
+                                            global_batch=global_batch, bucket=bucket)
+        except Exception as exc:  # noqa: BLE001  (a rank whose capture fails runs eagerly: same step, same collective; the line says so)
+            graph_fallback = f"{type(exc).__name__}: {exc}"[:300]
+            graphed = None
+            args.no_graph = True
+            one_step = eager_step
+            try:
+                torch.cuda.synchronize()
+            except Exception:  # noqa: BLE001
+                pass
+    for _ in range(args.warmup):
+        one_step()
+    sync()
+    timer = snF.SpmmTimer()
+    ms0 = torch.cuda.memory_stats()
+    t0 = time.perf_counter()
+    if args.no_graph and args.full:
+        n_ev = args.steps if args.spmm_timing_steps <= 0 else min(args.spmm_timing_steps, args.steps)
+        with timer:                                  # per-launch HIP events on every SpMM of the first n_ev timed steps
+            for i in range(n_ev):
+                if i == args.linear_timing_steps:    # the ~120 Linear launches of a step carry events on the first steps only
+                    timer.time_linear(False)
+                loss = one_step().detach()           # (keeping the loss itself would keep the step's autograd graph alive)
+        for i in range(n_ev, args.steps):            # the rest of the timed region without events
+            loss = one_step().detach()
+    else:
+        for _ in range(args.steps):
+            loss = one_step().detach()
+    t_enqueue = time.perf_counter() - t0               # the host has issued every step; the device may still be running
+    sync()
+    dt = time.perf_counter() - t0
+    ms1 = torch.cuda.memory_stats()
+    alloc = {"hipMalloc_calls_in_timed_region": ms1.get("num_device_alloc", 0) - ms0.get("num_device_alloc", 0),
+             "hipFree_calls_in_timed_region": ms1.get("num_device_free", 0) - ms0.get("num_device_free", 0),
+             "alloc_retries": ms1.get("num_alloc_retries", 0) - ms0.get("num_alloc_retries", 0),
+             "reserved_GiB": round(ms1.get("reserved_bytes.all.peak", 0) / 2**30, 2),
+             "allocated_peak_GiB": round(ms1.get("allocated_bytes.all.peak", 0) / 2**30, 2)}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss)
+    if args.full and not args.no_graph:
+        # kernels inside a replayed hipGraph cannot carry start/stop events, so the SpMM launches are timed on the same
+        # steps launched eagerly right after the timed region (same kernels, operands and preceding kernels; the
+        # rocprofv3 summary under profiles/ covers the replayed launches and agrees)
+        with timer:
+            for _ in range(max(1, args.roofline_steps)):
+                eager_step()
+        sync()
+    # host cost of issuing ONE step into an idle queue (after the timed region): inside the timed loop the host runs ahead of a
+    # GPU-bound step until the launch queue is full and then waits for the device — the in-loop figure measures the queue depth,
+    # not the host
+    t_host_alone = None
+    if args.full:
+        host_alone = []
+        for _ in range(5):
+            torch.cuda.synchronize()
+            th = time.perf_counter()
+            one_step()
+            host_alone.append(time.perf_counter() - th)
+        sync()
+        t_host_alone = float(np.median(host_alone))
+    dt_t = torch.tensor([dt], dtype=torch.float64, device=device)
+    if world > 1:
+        dist.all_reduce(dt_t, op=dist.ReduceOp.MAX)
+    dt = float(dt_t.item())
+    assert torch.isfinite(loss).item(), "training diverged"
+    replicas_identical = replicas_agree(model, world) if args.full else None
+
     out = {
         "metric": "meshes/sec fwd+bwd, Dirac temporal-predict",
         "value": global_batch * args.steps / dt,
@@ -1163,7 +1246,7 @@ def main():
                                      "three-piece bf16 form, 0 the fp32-MFMA kernels; the weight gradient (wgrad_h_k) uses two fp16 pieces of each "
                                      "operand with the row / column bounds the step already holds, the first layer's (K = 6) wgrad_u_k"),
                    "allocator": alloc, "operator_format": args.format, "operators": args.operators,
-                   "host_enqueue_ms_per_step": t_host_alone * 1e3,
+                   "host_enqueue_ms_per_step": t_host_alone * 1e3 if t_host_alone is not None else None,
                    "host_enqueue_definition": "host time to issue one step into an idle launch queue (median of 5, after the timed "
                                               "region); in_loop: the same inside the timed loop, where a GPU-bound step makes the host "
                                               "wait for queue space",
@@ -1174,39 +1257,11 @@ def main():
                    "launch_plans": {k: v["replayed"] for k, v in plans.stats().items() if v["replayed"] or v["refused"]},
                    "plan_graph_launches": plans.graph_stats()["launched"],
                    "graph_fallback": graph_fallback, "grad_bucket_bytes": bucket.nbytes},
-        "roofline": {"bound": "hbm", "kernel": dom_name + (" (the backward products Di^T, DiA^T, ELU backward fused into the store)" if "_epi" in dom_name
-                                                          else " (the Dirac products launched without epilogue)"),
-                     # `frac` is the MORE CONSERVATIVE of the two defensible readings of the fused launch: algorithmic bytes of the
-                     # product plus the epilogue operands it must read, or — when a counter file of these very sources exists —
-                     # the HBM traffic the counters measured; the three conventions stay side by side below
-                     "achieved": frac_top * HBM_PEAK / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": frac_top,
-                     "frac_convention": frac_conv,
-                     "traffic": traffic, "traffic_source": traffic_src, "step_traffic": step_traffic,
-                     "algorithmic_bytes_definition": "SURVEY.md §8(d) CSR/int32/fp32 bytes of the product (nnz*8 + (M+1)*4 + K*N*4 + M*N*4) "
-                                                     "plus, for the fused ELU-backward launches, the epilogue operands E and G (M*N*4 each) "
-                                                     "that the fused kernel must read; the three figures below separate the conventions",
-                     "frac_by_convention": {
-                         "product_plus_epilogue_operands": frac_alg,
-                         "product_bytes_only": product_bytes / (tot_ms * 1e-3) / HBM_PEAK,
-                         "measured_hbm_traffic": frac_meas},
-                     "algorithmic_bytes_per_launch": ab, "avg_launch_ms": avg_ms,
-                     "timing": "hipExtLaunchKernelGGL start/stop events on the launch stream, " +
-                               (f"every launch of the first {n_ev_steps} of the {args.steps} timed steps" if args.no_graph else
-                                f"every launch of {max(1, args.roofline_steps)} eager steps run right after the timed hipGraph replays"),
-                     "launches_timed": len(dom), "spmm_ms_per_step_all_kernels": spmm_ms_per_step, "per_product": per_shape,
-                     "other_spmm_kernels": [
-                         {"kernel": k, "launches": len(v), "avg_launch_ms": sum(r[5] for r in v) / len(v),
-                          "frac": sum(alg_bytes(r[1], r[2], r[3], r[4], r[0]) for r in v) / (sum(r[5] for r in v) * 1e-3) / HBM_PEAK}
-                         for k, v in by_kernel.items() if k != dom_name],
-                     "linear_kernels": linear_kernels,
-                     "linear_kernels_note": "kernel[variant]: linear_fwd bits 1 elu copy, 2 residual, 4 y written, 8 per-mesh bias; "
-                                            "linear_dgrad bits 1 BatchNorm tail, 2 through the activation, 4 gadd, 8 per-mesh vector; "
-                                            "bytes = operands read + results written (weights excluded), timed like the SpMM launches"
-                                            + (f" on the first {n_lin_steps} of the {args.steps} timed steps (an event pair costs a launch ~2 us; "
-                                               f"the sparse products on the first {n_ev_steps})" if args.no_graph else ""),
-                     "linear_ms_per_step": float(sum(d["ms_per_step"] for d in linear_kernels))},
+        "roofline": None,
     }
-    if not args.no_secondary:
+    if args.full:
+        out["roofline"] = roofline_result(args, timer, rank, world)
+    if args.full and not args.no_secondary:
         # config 5: every rank runs its own replica of the microbench (no collective on this path: aggregate = sum)
         del ds, model, opt, bucket, graphed
         torch.cuda.empty_cache()
@@ -1257,12 +1312,15 @@ def main():
                 except Exception as exc:  # noqa: BLE001
                     sec[key] = {"error": repr(exc)[:300]}
         out["secondary"] = sec
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(seed=3)
     elif rank == 0:
         out["cpu_baseline"] = None
     if rank == 0:
-        emit(out, result_fd)
+        if args.full:
+            emit(out, result_fd)
+        else:
+            emit_line(out, result_fd)
     if dist.is_initialized():
         if world > 1:
             dist.barrier()

@@ -1,8 +1,26 @@
 """Shared test helpers: seeded meshes/operators and comparison utilities."""
+import os
+
 import numpy as np
 import scipy.sparse as sp
 
 from surfacenetworks_amd import mesh_ops
+
+
+def load_golden(golden_dir, name):
+    """The arrays of the fixture tests/golden/<name>: the file itself or, for a fixture written in parts to keep every file
+    under 1 MiB (make_golden.save), <stem>_part0.npz, <stem>_part1.npz, ... merged in order."""
+    path = os.path.join(golden_dir, name)
+    if os.path.exists(path):
+        return np.load(path, allow_pickle=False)
+    out, i = {}, 0
+    while os.path.exists(part := os.path.join(golden_dir, f"{name[:-len('.npz')]}_part{i}.npz")):
+        with np.load(part, allow_pickle=False) as z:
+            out.update((k, z[k]) for k in z.files)
+        i += 1
+    if not i:
+        raise FileNotFoundError(path)
+    return out
 
 
 def rel_err(a, b):

@@ -6,7 +6,7 @@ import numpy as np
 import scipy.sparse as sp
 import torch
 
-from helpers import deterministic_init, det_tensor, grad_signature, rel_err, sigs_close
+from helpers import deterministic_init, det_tensor, grad_signature, load_golden, rel_err, sigs_close
 from oracle import ref_blocks as OB
 
 # Model-level criterion.  The deep fixtures are ill-conditioned in fp32 (the reference's OWN fp32 gradients of the FAUST fixture
@@ -39,7 +39,7 @@ BLOCKS = [("LapResNet2", 64), ("LapResNet2", 128), ("DirResNet2", 64), ("DirResN
 
 
 def load(golden_dir, name):
-    return np.load(os.path.join(golden_dir, name), allow_pickle=False)
+    return load_golden(golden_dir, name)
 
 
 def csr_of(z, k):

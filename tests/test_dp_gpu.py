@@ -159,7 +159,7 @@ def test_two_ranks_on_gpu_reproduce_full_batch(mode):
 def test_bench_self_launches_two_ranks():
     """`python bench.py --gpus 2` without a launcher environment starts its two ranks itself and rank 0 prints ONE JSON line."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
                           "--meshes", "4", "--no-secondary"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -228,7 +228,7 @@ def test_rccl_all_reduce_of_the_flat_bucket_in_a_one_rank_group():
 def test_bench_runs_its_one_rank_through_rccl():
     """`python bench.py --gpus 1` puts the gradient bucket through a one-rank RCCL communicator every step."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "2", "--warmup", "1",
                           "--meshes", "4", "--no-secondary", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = out.stdout.splitlines()
@@ -347,7 +347,7 @@ def test_bench_starts_eight_ranks_on_the_one_device(workload):
     eager, ranks sharing cuda:0): eight ranks come up, rendezvous, shard, all-reduce and step; ONE JSON line with
     n_gpus = world_size = 8, a finite value, and replicas that are still bit-identical after the run."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--steps", "2", "--warmup", "1"]
     cmd += ["--workload", "faust"] if workload == "faust" else ["--meshes", "2", "--no-secondary", "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, out.stderr[-3000:]

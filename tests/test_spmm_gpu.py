@@ -634,11 +634,11 @@ def test_hip_products_match_the_references_stored_results(golden_dir, mesh, fmt,
 
     import scipy.sparse as sp
 
-    from helpers import rel_err
+    from helpers import load_golden, rel_err
     from surfacenetworks_amd import functional as snF, kernels
     from surfacenetworks_amd.operators import SparseOperator
 
-    g = np.load(os.path.join(golden_dir, "spmm_reference.npz"))
+    g = load_golden(golden_dir, "spmm_reference.npz")
     z = np.load(os.path.join(golden_dir, f"ops_{mesh}.npz"))
     monkeypatch.setattr(kernels, "RING_MIN_ROWS", 8)                 # (the sliding-window kernel is chosen from 131 072 rows on)
     dirac = fmt in ("bsr4", "q3")

@@ -19,12 +19,12 @@ for w in $what; do case $w in
 tests)
   (cd $root && timeout 2400 python -m pytest tests -q -m gpu 2>&1 | tail -6) > $out/gpu_tests.txt ;;
 bench)
-  (cd $root && timeout 1500 python bench.py > $out/bench_c3_final.json 2> $out/bench_c3_final.err; cp bench_detail.json $out/bench_c3_final_detail.json)
-  (cd $root && timeout 600 python bench.py --graph --no-cpu-baseline --no-secondary --no-pmc > $out/bench_c3_graph.json 2>/dev/null)
-  (cd $root && timeout 600 python bench.py --workload faust > $out/bench_faust_n1.json 2>/dev/null)
-  (cd $root && timeout 900 python bench.py --gpus 2 --steps 10 --warmup 3 --no-secondary --no-cpu-baseline > $out/bench_gpus2_gloo_one_device.json 2>/dev/null) ;;
+  (cd $root && timeout 1500 python bench.py --full > $out/bench_c3_final.json 2> $out/bench_c3_final.err; cp bench_detail.json $out/bench_c3_final_detail.json)
+  (cd $root && timeout 600 python bench.py --full --graph --no-cpu-baseline --no-secondary --no-pmc > $out/bench_c3_graph.json 2>/dev/null)
+  (cd $root && timeout 600 python bench.py --full --workload faust > $out/bench_faust_n1.json 2>/dev/null)
+  (cd $root && timeout 900 python bench.py --full --gpus 2 --steps 10 --warmup 3 --no-secondary --no-cpu-baseline > $out/bench_gpus2_gloo_one_device.json 2>/dev/null) ;;
 trace)
-  kstats bench_c3 -- python $root/bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-secondary --no-pmc
+  kstats bench_c3 -- python $root/bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-secondary --no-pmc
   grep '^{' $out/bench_c3_under_rocprof.log > $out/bench_c3_under_rocprof.json; rm -f $out/bench_c3_under_rocprof.log
   for o in grid permuted permuted_both permuted_both+reorder; do
     n=spmm_microbench_c5_$(echo $o | tr '+' '_')
@@ -40,7 +40,7 @@ orders)
 pmc)
   for ctr in TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum; do
     rm -rf /tmp/pmc_$ctr
-    rocprofv3 --pmc $ctr -d /tmp/pmc_$ctr -o pmc --output-format csv -- python $root/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-secondary --no-pmc --backend none > /dev/null 2>&1
+    rocprofv3 --pmc $ctr -d /tmp/pmc_$ctr -o pmc --output-format csv -- python $root/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-secondary --no-pmc --backend none > /dev/null 2>&1
   done
   rd=$(find /tmp/pmc_TCC_EA0_RDREQ_sum -name '*counter_collection.csv' | head -1); wr=$(find /tmp/pmc_TCC_EA0_WRREQ_sum -name '*counter_collection.csv' | head -1)
   (cd $root && python tools/pmc_bench.py $out/pmc_traffic_c3 $rd $wr last=6 > $out/pmc_traffic_c3_top.txt 2>&1)

@@ -93,7 +93,7 @@ def summarize(rd_csv, wr_csv, skip=0.5, last_steps=None):
         tot_r += rb
         tot_w += wb
     res = {"_comment": "HBM traffic per launch, measured IN the training step: rocprofv3 --pmc TCC_EA0_RDREQ_sum / TCC_EA0_WRREQ_sum "
-                       "(one counter per pass) over `python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-secondary`; "
+                       "(one counter per pass) over `python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-secondary`; "
                        "bytes = RDREQ*128 + WRREQ*64 (gfx950 correction); the first half of the dispatches (set-up and warm-up) dropped",
            "_total_bytes_counted": {"read": tot_r, "write": tot_w}}
     from bench import csrc_digest           # the kernel sources these counters belong to (bench.py withholds them on a mismatch)

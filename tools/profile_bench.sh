@@ -5,7 +5,7 @@ out=${1:-gpurun_out/prof_bench}; tag=${2:-r2}
 mkdir -p $out
 root=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
-args="--steps 6 --warmup 2 --no-cpu-baseline --no-secondary --no-pmc"
+args="--full --steps 6 --warmup 2 --no-cpu-baseline --no-secondary --no-pmc"
 rocprofv3 --kernel-trace --stats -d $root/$out/trace -o bench --output-format csv -- python $root/bench.py $args > $root/$out/trace.log 2>&1
 rocprofv3 --pmc TCC_EA0_RDREQ_sum -d $root/$out/rd -o pmc --output-format csv -- python $root/bench.py $args > $root/$out/rd.log 2>&1
 rocprofv3 --pmc TCC_EA0_WRREQ_sum -d $root/$out/wr -o pmc --output-format csv -- python $root/bench.py $args > $root/$out/wr.log 2>&1
