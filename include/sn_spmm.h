@@ -518,6 +518,40 @@ int sn_pair_fused_fwd_f32(const float *FA, int64_t lda, const float *FB, int64_t
 int sn_pair_fused_bwd_f32(const int64_t *target, const float *lse, const float *gloss, int64_t NA, int64_t NB, int64_t rowsA,
                           int64_t rowsB, int32_t K, float *dFA, int64_t ldda, float *dFB, int64_t lddb, void *workspace,
                           size_t workspace_bytes, void *stream);
+/* sn_pair_soft_* / sn_pair_sl1_*: the other two losses of the FAUST driver FROM THE TOWER FEATURES — the soft-target cross
+ * entropy `cel` (loss_fun_cross_entropy, src/dense_correspondence/main.py:216-227) and the smooth-L1 `sl1` (loss_fun_sl1 with
+ * aggregate_batch_G, main.py:197-214) — replacing bmm(FA, FB^T) (models.py:203), the two gathered matrices
+ * GA[:, liA[lB]] and GB[liB[lA], :], their sum, softmin / log_softmax / smooth_l1 and all their backward passes.  Neither the
+ * scores nor any other NA x NB temporary is written.  Arithmetic and workspace of sn_pair_fused_*.
+ * The geodesic sum is read in LABEL ORDER: geo is a DEVICE array of two device pointers {HA, HB}, row-major fp32 with leading
+ * dimensions ldgA, ldgB >= NB, and G[u][v] = HA[u][v] + HB[u][v] (fp32 + fp32) for u < NA, v < NB.  Row u of G belongs to
+ * row mapA[u] of FA and column v to row mapB[v] of FB (int64 permutations of [0, NA) / [0, NB) on the device; NULL =
+ * identity); rows of FA / FB past NA / NB are the padding of the batch and keep their place.  With label / label_inv
+ * mutually inverse, H = G_frame[label_inv][:, label_inv] and map = label_inv reproduce main.py:200-201 / 219-220.
+ *   soft fwd: stats[u] = log sum_v exp(S[u][v]), stats[NA + u] = min_v G[u][v] - log sum_v exp(min - G[u][v]) (so that
+ *             softmin(G[u])[v] = exp(stats[NA + u] - G[u][v])), rowloss[u] = stats[u] - sum_v softmin(G[u])[v] S[u][v], u < NA,
+ *             v < NB; the loss is the SUM of rowloss (main.py:225 sums, it does not average).
+ *   soft bwd: dS = *gloss (softmax(S[u]) - softmin(G[u])) inside the corner, 0 outside; dFA = dS·FB, dFB = dS^T·FA written to
+ *             rows mapA[u] / mapB[v]; rows >= NA / NB are set to 0.
+ *   sl1 fwd : rowloss[u] (fp64, u < rowsA) = sum_{v < rowsB} l(S[u][v] - FullG[u][v]), FullG = G in the corner and 0 in the
+ *             padding (main.py:206-210), l(d) = d^2/2 for |d| < 1, |d| - 1/2 otherwise; the loss is sum / (rowsA rowsB).
+ *   sl1 bwd : dS = *gloss clamp(S - FullG, -1, 1) / (rowsA rowsB) over the whole rectangle: padding rows of dFA / dFB are
+ *             in general not 0.
+ * The backward calls read the workspace their forward call filled (sn_pair_loss_workspace_bytes, 16-byte aligned) with the
+ * same maps and geo.  Fixed summation order: run-to-run identical.  gloss is a DEVICE scalar. */
+size_t sn_pair_loss_workspace_bytes(int64_t rowsA, int64_t rowsB);
+int sn_pair_soft_fwd_f32(const float *FA, int64_t lda, const float *FB, int64_t ldb, const int64_t *mapA, const int64_t *mapB,
+                         const float *const *geo, int64_t ldgA, int64_t ldgB, int64_t NA, int64_t NB, int64_t rowsA, int64_t rowsB,
+                         int32_t K, float *stats, float *rowloss, void *workspace, size_t workspace_bytes, void *stream);
+int sn_pair_soft_bwd_f32(const int64_t *mapA, const int64_t *mapB, const float *const *geo, int64_t ldgA, int64_t ldgB,
+                         const float *stats, const float *gloss, int64_t NA, int64_t NB, int64_t rowsA, int64_t rowsB, int32_t K,
+                         float *dFA, int64_t ldda, float *dFB, int64_t lddb, void *workspace, size_t workspace_bytes, void *stream);
+int sn_pair_sl1_fwd_f32(const float *FA, int64_t lda, const float *FB, int64_t ldb, const int64_t *mapA, const int64_t *mapB,
+                        const float *const *geo, int64_t ldgA, int64_t ldgB, int64_t NA, int64_t NB, int64_t rowsA, int64_t rowsB,
+                        int32_t K, double *rowloss, void *workspace, size_t workspace_bytes, void *stream);
+int sn_pair_sl1_bwd_f32(const int64_t *mapA, const int64_t *mapB, const float *const *geo, int64_t ldgA, int64_t ldgB,
+                        const float *gloss, int64_t NA, int64_t NB, int64_t rowsA, int64_t rowsB, int32_t K, float *dFA, int64_t ldda,
+                        float *dFB, int64_t lddb, void *workspace, size_t workspace_bytes, void *stream);
 /* sn_linear_thin_fwd_f32: forward of that first layer, y = x·W^T + bias (x: rows x C, C <= 8; W: J x C), and optionally
  * elu(y) into y_elu (the first half of the next block's concat buffer; replaces the F.elu of utils_pt.py:161,195).  y or
  * y_elu may be NULL (not both).  Ascending-k fp32 FMA chain on top of the bias. */

@@ -1931,10 +1931,13 @@ __global__ __launch_bounds__(kWG) void pair_maxabs_k(const float *__restrict__ F
 }
 
 // one thread per (row, 4 features) of a side (blockIdx.y): rows [0, npad), feature quads [0, 32)
+// MAP: position `row` of R / T takes row map[row] of F for row < nmap (a permutation of [0, nmap)), row `row` itself past it
+template <bool MAP>
 __global__ __launch_bounds__(kWG) void pair_split_k(const float *__restrict__ FA, int64_t lda, int rowsA, int npadA, unsigned short *__restrict__ RA,
                                                     unsigned short *__restrict__ TA, const float *__restrict__ FB, int64_t ldb, int rowsB,
                                                     int npadB, unsigned short *__restrict__ RB, unsigned short *__restrict__ TB, int K,
-                                                    const unsigned *__restrict__ header) {
+                                                    const unsigned *__restrict__ header, const int64_t *__restrict__ mapA, int nmapA,
+                                                    const int64_t *__restrict__ mapB, int nmapB) {
   const bool sb = blockIdx.y != 0;
   const float *F = sb ? FB : FA;
   const int64_t ld = sb ? ldb : lda;
@@ -1945,10 +1948,15 @@ __global__ __launch_bounds__(kWG) void pair_split_k(const float *__restrict__ FA
   float up, down;
   pair_scales(header[sb ? 1 : 0], up, down);
   const int row = (int)(id >> 5), kq = (int)(id & 31) * 4;
+  int64_t src = row;
+  if (MAP) {
+    const int64_t *map = sb ? mapB : mapA;
+    if (map && row < (sb ? nmapB : nmapA)) src = map[row];
+  }
   _Float16 h[4], l[4];
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
-    const float v = ((row < n && kq + c < K) ? F[(int64_t)row * ld + kq + c] : 0.f) * up;
+    const float v = ((row < n && kq + c < K) ? F[src * ld + kq + c] : 0.f) * up;
     h[c] = (_Float16)v;
     l[c] = (_Float16)(v - (float)h[c]);
   }
@@ -2238,6 +2246,354 @@ __global__ __launch_bounds__(kWG) void pair_reduce_k(PairGradSide A, PairGradSid
     v *= gloss[0] / (float)NA * (1.f / 16384.f) * down;
   }
   float *o = d + (int64_t)r * ldd + k;
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+    if (k + c < K) o[c] = v[c];
+}
+
+
+// ------------------------------------------------------------------------------------------------
+// The other two dense-correspondence losses from the tower features (src/dense_correspondence/main.py:197-227): the
+// soft-target cross entropy `cel` (loss_fun_cross_entropy, main.py:216-227) and the smooth-L1 `sl1` (loss_fun_sl1 +
+// aggregate_batch_G, main.py:197-214).  Both compare the scores S = FA·FB^T with the geodesic sum
+// G[r][j] = GA[r][liA[lB[j]]] + GB[liB[lA[r]]][j] ELEMENT BY ELEMENT, so G has to be read in the 32 x 32 tiles of the score
+// kernels.  In the vertex numbering that is a gather of scattered columns; with label / label_inv mutually inverse it is
+// (HA + HB)[lA[r]][lB[j]], H = G_frame[label_inv][:, label_inv] built once per frame.  The kernels therefore run in LABEL
+// ORDER: row u of the tile grid is vertex mapA[u] = liA[u] of shape A, column v is vertex mapB[v] of shape B, both
+// matrices are read as contiguous row segments, and the only permutation left is on the feature rows (pair_split_k<true>
+// on the way in, pair_loss_reduce_k on the way out).  Every sum involved runs over all (r, j) or over all j of a row, so
+// the numbering changes the order of summation and nothing else.
+// The two base addresses come from a DEVICE table (two pointers): a captured step replays on another pair by rewriting
+// 16 bytes, not by copying 2 x 190 MB into static buffers.
+// Arithmetic, fragment layout, staging and the fixed-order range reduction are those of pair_lse_k / pair_grad_k above.
+//   cel: t[u][:] = softmin(G[u][:NB]);  rowloss[u] = lse_S[u] - sum_v t[u][v] S[u][v];  P = softmax(S) - t  in [-1, 1]
+//   sl1: D = S - FullG over the WHOLE rowsA x rowsB rectangle (FullG = G in the corner, 0 in the padding);
+//        rowloss[u] = sum_v l(D[u][v]) in fp64;  P = clamp(D, -1, 1)
+// ------------------------------------------------------------------------------------------------
+struct PairGeo {
+  const float *const *base;      // device table: {HA, HB}
+  int64_t ldA, ldB;
+  int NA, NB;                    // the corner that has geodesics
+};
+__device__ __forceinline__ bool pair_geo_vec(const float *ga, const float *gb, const PairGeo &G) {
+  return (((reinterpret_cast<uintptr_t>(ga) | reinterpret_cast<uintptr_t>(gb)) & 15) == 0) && (G.ldA % 4) == 0 && (G.ldB % 4) == 0;
+}
+// columns c .. c + 3 (c a multiple of 4) of a row; 0 past ncols
+__device__ __forceinline__ f4 pair_geo4(const float *__restrict__ row, int c, int ncols, bool vec) {
+  if (vec && c + 3 < ncols) return *reinterpret_cast<const f4 *>(row + c);
+  f4 v;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = c + e < ncols ? row[c + e] : 0.f;
+  return v;
+}
+// G for the 16 elements of a transposed tile whose OWN rows are rows of G (lane's row u fixed, streamed columns c0 + ...):
+// element e <-> column c0 + (e & 3) + 8 (e >> 2), c0 = 32 t + 4 kh
+__device__ __forceinline__ void pair_geo_own_row(float (&g)[16], const float *rowa, const float *rowb, bool row_ok, int c0, int ncols, bool vec) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    f4 a = f4{0.f, 0.f, 0.f, 0.f}, b = a;
+    if (row_ok && c0 + 8 * q < ncols) {
+      a = pair_geo4(rowa, c0 + 8 * q, ncols, vec);
+      b = pair_geo4(rowb, c0 + 8 * q, ncols, vec);
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) g[4 * q + c] = a[c] + b[c];
+  }
+}
+// ... whose own rows are COLUMNS of G (lane's column v fixed, streamed rows u0 + ...)
+__device__ __forceinline__ void pair_geo_own_col(float (&g)[16], const float *ga, const float *gb, const PairGeo &G, bool col_ok, int v, int u0) {
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const int u = u0 + (e & 3) + 8 * (e >> 2);
+    g[e] = (col_ok && u < G.NA) ? ga[(int64_t)u * G.ldA + v] + gb[(int64_t)u * G.ldB + v] : 0.f;
+  }
+}
+__device__ __forceinline__ float pair_sl1(float d) {
+  const float a = fabsf(d);
+  return a < 1.f ? 0.5f * d * d : a - 0.5f;
+}
+
+// grid (ceil(tiles_rows / 4), splits).  SL1 = false: part[split][row] = (max, sum, -, -), part2[split][row] = (min G,
+// sum exp(-(G - min)), sum exp(-(G - min)) S, -) over the NA x NB corner.  SL1 = true: part (as doubles)[split][row] = the
+// row's share of sum l(S - FullG) over rows x cols.
+template <bool SL1>
+__global__ __launch_bounds__(kWG, 2) void pair_loss_fwd_k(const unsigned short *__restrict__ RA, const unsigned short *__restrict__ RB, PairGeo G,
+                                                          int rows, int cols, int npadA, const unsigned *__restrict__ header,
+                                                          float *__restrict__ part, float *__restrict__ part2) {
+  __shared__ __attribute__((aligned(16))) unsigned short stage[2][kPairTile];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int n = lane & 31, kh = lane >> 5;
+  const int tilesA = (rows + 31) / 32, tilesB = (cols + 31) / 32;
+  const int mytile = blockIdx.x * 4 + wave;
+  const int n0 = mytile * 32;
+  const int u = n0 + n;
+  u4 own[8][2];
+  pair_load_own(own, RA, mytile < tilesA ? mytile : tilesA - 1, lane);
+  float upA, downA, upB, downB;
+  pair_scales(header[0], upA, downA);
+  pair_scales(header[1], upB, downB);
+  const float sAB = downA * downB;
+  const float *ga = G.base[0], *gb = G.base[1];
+  const bool vec = pair_geo_vec(ga, gb, G);
+  const bool row_geo = u < G.NA;
+  const float *rowa = ga + (int64_t)(row_geo ? u : 0) * G.ldA, *rowb = gb + (int64_t)(row_geo ? u : 0) * G.ldB;
+  const int per = (tilesB + (int)gridDim.y - 1) / (int)gridDim.y;
+  const int t0 = blockIdx.y * per, t1 = min(tilesB, t0 + per);
+  float m = -INFINITY, l = 0.f, gm = INFINITY, gl = 0.f, gts = 0.f;
+  double acc64 = 0.0;
+  pair_wait_vmcnt<0>();
+  if (t0 < t1) pair_stage<16>(RB + (size_t)t0 * kPairTile, stage[0], wave, lane);
+  for (int t = t0; t < t1; ++t) {
+    const int buf = (t - t0) & 1;
+    if (t + 1 < t1) {
+      pair_stage<16>(RB + (size_t)(t + 1) * kPairTile, stage[buf ^ 1], wave, lane);
+      pair_wait_vmcnt<4>();
+    } else {
+      pair_wait_vmcnt<0>();
+    }
+    __builtin_amdgcn_s_barrier();
+    float gv[16];                                    // (issued before the products: the loads land while the matrix pipe works)
+    pair_geo_own_row(gv, rowa, rowb, row_geo, t * 32 + 4 * kh, G.NB, vec);
+    const f16v acc = pair_tile(own, stage[buf], lane);
+    if (SL1) {
+      float ts = 0.f;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int i = t * 32 + (e & 3) + 8 * (e >> 2) + 4 * kh;
+        const float d = acc[e] * sAB - gv[e];        // (gv = 0 outside the corner: FullG)
+        ts += i < cols ? pair_sl1(d) : 0.f;
+      }
+      acc64 += (double)ts;
+    } else {
+      float sv[16], tmax = -INFINITY, tmin = INFINITY;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int i = t * 32 + (e & 3) + 8 * (e >> 2) + 4 * kh;
+        sv[e] = acc[e] * sAB;
+        if (i >= cols) gv[e] = INFINITY;
+        tmax = fmaxf(tmax, i < cols ? sv[e] : -INFINITY);
+        tmin = fminf(tmin, gv[e]);
+      }
+      if (tmax > -INFINITY) {                        // (the lane holds at least one column of the corner)
+        const float mn = fmaxf(m, tmax), gn = fminf(gm, tmin);
+        float add = 0.f, gadd = 0.f, gsadd = 0.f;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int i = t * 32 + (e & 3) + 8 * (e >> 2) + 4 * kh;
+          add += i < cols ? __expf(sv[e] - mn) : 0.f;
+          const float w = __expf(gn - gv[e]);        // (exp(-inf) = 0 for the columns past NB)
+          gadd += w;
+          gsadd += w * sv[e];
+        }
+        l = l * __expf(m - mn) + add;
+        m = mn;
+        const float sc = __expf(gn - gm);            // (first tile: exp(-inf) = 0 times 0)
+        gl = gl * sc + gadd;
+        gts = gts * sc + gsadd;
+        gm = gn;
+      }
+    }
+    __builtin_amdgcn_s_barrier();
+  }
+  if (SL1) {
+    acc64 += __shfl_xor(acc64, 32);
+    if (kh == 0 && u < rows) reinterpret_cast<double *>(part)[(size_t)blockIdx.y * npadA + u] = acc64;
+  } else {
+    const float m2 = __shfl_xor(m, 32), l2 = __shfl_xor(l, 32);
+    const float gm2 = __shfl_xor(gm, 32), gl2 = __shfl_xor(gl, 32), gts2 = __shfl_xor(gts, 32);
+    const float mn = fmaxf(m, m2), gn = fminf(gm, gm2);
+    l = (m > -INFINITY ? l * __expf(m - mn) : 0.f) + (m2 > -INFINITY ? l2 * __expf(m2 - mn) : 0.f);
+    const float c1 = gm < INFINITY ? __expf(gn - gm) : 0.f, c2 = gm2 < INFINITY ? __expf(gn - gm2) : 0.f;
+    if (kh == 0 && u < rows) {
+      const size_t o = ((size_t)blockIdx.y * npadA + u) * 4;
+      *reinterpret_cast<f4 *>(part + o) = f4{mn, l, 0.f, 0.f};
+      *reinterpret_cast<f4 *>(part2 + o) = f4{gn, gl * c1 + gl2 * c2, gts * c1 + gts2 * c2, 0.f};
+    }
+  }
+}
+
+// stats[r] = lse_S[r], stats[NA + r] = min_G[r] - log sum_j exp(-(G[r][j] - min_G[r]))  (softmin(G[r])[j] = exp(stats[NA + r] - G[r][j]))
+__global__ __launch_bounds__(kWG) void pair_soft_combine_k(const float *__restrict__ part, const float *__restrict__ part2, int splits, int npadA,
+                                                           int NA, float *__restrict__ stats, float *__restrict__ rowloss) {
+  const int r = blockIdx.x * kWG + threadIdx.x;
+  if (r >= NA) return;
+  float mm = -INFINITY, gmm = INFINITY;
+  for (int s = 0; s < splits; ++s) {
+    mm = fmaxf(mm, part[((size_t)s * npadA + r) * 4]);
+    gmm = fminf(gmm, part2[((size_t)s * npadA + r) * 4]);
+  }
+  float ll = 0.f, gl = 0.f, gts = 0.f;
+  for (int s = 0; s < splits; ++s) {
+    const f4 v = *reinterpret_cast<const f4 *>(part + ((size_t)s * npadA + r) * 4);
+    const f4 w = *reinterpret_cast<const f4 *>(part2 + ((size_t)s * npadA + r) * 4);
+    ll += v.x > -INFINITY ? v.y * expf(v.x - mm) : 0.f;
+    const float c = w.x < INFINITY ? expf(gmm - w.x) : 0.f;
+    gl += w.y * c;
+    gts += w.z * c;
+  }
+  const float ls = mm + logf(ll);
+  stats[r] = ls;
+  stats[NA + r] = gmm - logf(gl);
+  rowloss[r] = ls - gts / gl;
+}
+__global__ __launch_bounds__(kWG) void pair_sl1_combine_k(const double *__restrict__ part, int splits, int npadA, int rows, double *__restrict__ rowloss) {
+  const int r = blockIdx.x * kWG + threadIdx.x;
+  if (r >= rows) return;
+  double v = 0.0;
+  for (int s = 0; s < splits; ++s) v += part[(size_t)s * npadA + r];
+  rowloss[r] = v;
+}
+
+// pair_grad_k with the factor of the loss at hand: SL1 = false: P = exp(S - lse[u]) - exp(dmin[u] - G) inside the corner
+// (stats = lse | dmin); SL1 = true: P = clamp(S - FullG, -1, 1) over the whole rectangle (A.Nown x A.Noth).
+template <bool SL1>
+__global__ __launch_bounds__(kWG, 2) void pair_loss_grad_k(PairGradSide A, PairGradSide B, PairGeo G, const float *__restrict__ stats,
+                                                           const unsigned *__restrict__ header) {
+  extern __shared__ __attribute__((aligned(16))) unsigned short gstage[];      // 2 x (R tile | T tile | 4 x 256 B lse / dmin)
+  constexpr int kStage = 2 * kPairTile + 4 * 128;                              // halfs
+  const bool ownA = blockIdx.x < (unsigned)(A.nblk * A.splits);
+  const PairGradSide &S = ownA ? A : B;
+  const int bid = ownA ? blockIdx.x : blockIdx.x - A.nblk * A.splits;
+  const int blk = bid % S.nblk, split = bid / S.nblk;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int n = lane & 31, kh = lane >> 5;
+  const int tiles_own = (S.Nown + 31) / 32, tiles_oth = (S.Noth + 31) / 32;
+  const int mytile = blk * 4 + wave;
+  const int n0 = mytile * 32;
+  const bool own_ok = n0 + n < S.Nown;
+  u4 own[8][2];
+  pair_load_own(own, S.Rown, mytile < tiles_own ? mytile : tiles_own - 1, lane);
+  float upA, downA, upB, downB;
+  pair_scales(header[0], upA, downA);
+  pair_scales(header[1], upB, downB);
+  const float sAB = downA * downB;
+  const float *ga = G.base[0], *gb = G.base[1];
+  const bool vec = pair_geo_vec(ga, gb, G);
+  const bool own_geo = n0 + n < (ownA ? G.NA : G.NB);       // my own row / column lies inside the corner
+  const float *rowa = ga + (int64_t)((ownA && own_geo) ? n0 + n : 0) * G.ldA, *rowb = gb + (int64_t)((ownA && own_geo) ? n0 + n : 0) * G.ldB;
+  float my_lse = 0.f, my_d = 0.f;
+  if (!SL1 && ownA && own_ok) {
+    my_lse = stats[n0 + n];
+    my_d = stats[G.NA + n0 + n];
+  }
+  const int per = (tiles_oth + S.splits - 1) / S.splits;
+  const int t0 = split * per, t1 = min(tiles_oth, t0 + per);
+  f16v g[4];                                   // dOwn[n][32 f + (e&3) + 8 (e>>2) + 4 kh], f = 0..3
+#pragma unroll
+  for (int f = 0; f < 4; ++f)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) g[f][e] = 0.f;
+  auto issue = [&](int t, int buf) {
+    unsigned short *st = gstage + buf * kStage;
+    pair_stage<16>(S.Roth + (size_t)t * kPairTile, st, wave, lane);
+    pair_stage<16>(S.Toth + (size_t)t * kPairTile, st + kPairTile, wave, lane);
+    if (!SL1) {
+      // lanes 0..31: lse of the streamed rows, lanes 32..63: their dmin — a private copy per wave
+      const int i = min(t * 32 + n, G.NA - 1);
+      __builtin_amdgcn_global_load_lds(reinterpret_cast<const unsigned *>(stats + (kh ? G.NA : 0) + i), st + 2 * kPairTile + wave * 128, 4, 0, 0);
+    }
+  };
+  pair_wait_vmcnt<0>();
+  if (t0 < t1) issue(t0, 0);
+  for (int t = t0; t < t1; ++t) {
+    const int buf = (t - t0) & 1;
+    if (t + 1 < t1) {
+      issue(t + 1, buf ^ 1);
+      pair_wait_vmcnt<SL1 ? 8 : 9>();
+    } else {
+      pair_wait_vmcnt<0>();
+    }
+    __builtin_amdgcn_s_barrier();
+    const unsigned short *st = gstage + buf * kStage;
+    float gv[16];                                    // element 8 s2 + 4 jq + c <-> streamed row 16 s2 + 8 jq + 4 kh + c of the tile
+    if (ownA) pair_geo_own_row(gv, rowa, rowb, own_geo, t * 32 + 4 * kh, G.NB, vec);
+    else pair_geo_own_col(gv, ga, gb, G, own_geo, n0 + n, t * 32 + 4 * kh);
+    const f16v acc = pair_tile(own, st, lane);
+    const float *aux = reinterpret_cast<const float *>(st + 2 * kPairTile + wave * 128);
+    u4 PH[2], PL[2];
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2) {
+      float pv[8];
+#pragma unroll
+      for (int jq = 0; jq < 2; ++jq) {
+        const int il = 16 * s2 + 8 * jq + 4 * kh;
+        f4 ls4 = f4{my_lse, my_lse, my_lse, my_lse}, d4 = f4{my_d, my_d, my_d, my_d};
+        if (!SL1 && !ownA) {
+          ls4 = *reinterpret_cast<const f4 *>(aux + il);
+          d4 = *reinterpret_cast<const f4 *>(aux + 32 + il);
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const int e = 8 * s2 + 4 * jq + c;
+          const int i = t * 32 + il + c;                                // streamed (other) row
+          const float s = acc[e] * sAB;
+          float p;
+          if (SL1) p = fminf(fmaxf(s - gv[e], -1.f), 1.f);
+          else p = __expf(s - ls4[c]) - __expf(d4[c] - gv[e]);
+          pv[4 * jq + c] = (own_ok && i < S.Noth) ? p * 16384.f : 0.f;
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const h2v h = __builtin_convertvector(f2v{pv[2 * q], pv[2 * q + 1]}, h2v);
+        const h2v lo = __builtin_convertvector(f2v{pv[2 * q] - (float)h.x, pv[2 * q + 1] - (float)h.y}, h2v);
+        PH[s2][q] = __builtin_bit_cast(unsigned, h);
+        PL[s2][q] = __builtin_bit_cast(unsigned, lo);
+      }
+    }
+    const u4 *t4 = reinterpret_cast<const u4 *>(st + kPairTile) + lane;
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2) {
+      u4 th[4], tl_[4];
+#pragma unroll
+      for (int f = 0; f < 4; ++f) {
+        th[f] = t4[((f * 2 + s2) * 2) * 64];
+        tl_[f] = t4[((f * 2 + s2) * 2 + 1) * 64];
+      }
+#pragma unroll
+      for (int f = 0; f < 4; ++f) g[f] = mfma_f16(tl_[f], PH[s2], g[f]);
+#pragma unroll
+      for (int f = 0; f < 4; ++f) g[f] = mfma_f16(th[f], PL[s2], g[f]);
+#pragma unroll
+      for (int f = 0; f < 4; ++f) g[f] = mfma_f16(th[f], PH[s2], g[f]);
+    }
+    __builtin_amdgcn_s_barrier();
+  }
+  if (mytile < tiles_own) {
+    float *p = S.part + ((size_t)split * S.npad_own + n0 + n) * kPairKP;
+#pragma unroll
+    for (int f = 0; f < 4; ++f)
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        *reinterpret_cast<f4 *>(p + 32 * f + 8 * q + 4 * kh) = f4{g[f][4 * q], g[f][4 * q + 1], g[f][4 * q + 2], g[f][4 * q + 3]};
+  }
+}
+
+// dOwn[map[r]][k] = gloss · mul · 2^-14 down_other · sum_splits part[s][r][k] for r < Nown (label order; map = identity past
+// nmap), 0 for the rows past Nown; one thread per (row, 4 features) of a side (blockIdx.y)
+__global__ __launch_bounds__(kWG) void pair_loss_reduce_k(PairGradSide A, PairGradSide B, float *__restrict__ dFA, int64_t ldda, int rowsA,
+                                                          float *__restrict__ dFB, int64_t lddb, int rowsB, int K,
+                                                          const float *__restrict__ gloss, const unsigned *__restrict__ header, float mul,
+                                                          const int64_t *__restrict__ mapA, int nmapA, const int64_t *__restrict__ mapB, int nmapB) {
+  const bool sb = blockIdx.y != 0;
+  const PairGradSide &S = sb ? B : A;
+  float *d = sb ? dFB : dFA;
+  const int64_t ldd = sb ? lddb : ldda;
+  const int rows = sb ? rowsB : rowsA;
+  const int64_t *map = sb ? mapB : mapA;
+  const int nmap = sb ? nmapB : nmapA;
+  const int64_t id = (int64_t)blockIdx.x * kWG + threadIdx.x;
+  const int r = (int)(id >> 5), k = (int)(id & 31) * 4;
+  if (r >= rows || k >= K) return;
+  f4 v = f4{0.f, 0.f, 0.f, 0.f};
+  if (r < S.Nown) {
+    for (int s = 0; s < S.splits; ++s) v += *reinterpret_cast<const f4 *>(S.part + ((size_t)s * S.npad_own + r) * kPairKP + k);
+    float up, down;
+    pair_scales(header[sb ? 0 : 1], up, down);      // the OTHER side's features were scaled up
+    v *= gloss[0] * mul * (1.f / 16384.f) * down;
+  }
+  const int64_t dst = (map && r < nmap) ? map[r] : r;
+  float *o = d + dst * ldd + k;
 #pragma unroll
   for (int c = 0; c < 4; ++c)
     if (k + c < K) o[c] = v[c];
@@ -3260,8 +3616,8 @@ int sn_pair_fused_fwd_f32(const float *FA, int64_t lda, const float *FB, int64_t
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(pair_maxabs_k, dim3((unsigned)std::min<int64_t>(1024, (std::max(rowsA, rowsB) * K + 4 * kWG - 1) / (4 * kWG)), 2), dim3(kWG), 0, s, FA, lda, (int)rowsA, FB, ldb, (int)rowsB, (int)K, w.header);
   const int64_t quads = (int64_t)std::max(w.pa, w.pb) * 32;
-  hipLaunchKernelGGL(pair_split_k, dim3((unsigned)((quads + kWG - 1) / kWG), 2), dim3(kWG), 0, s, FA, lda, (int)rowsA, w.pa, w.RA, w.TA, FB, ldb,
-                     (int)rowsB, w.pb, w.RB, w.TB, (int)K, w.header);
+  hipLaunchKernelGGL((pair_split_k<false>), dim3((unsigned)((quads + kWG - 1) / kWG), 2), dim3(kWG), 0, s, FA, lda, (int)rowsA, w.pa, w.RA, w.TA, FB, ldb,
+                     (int)rowsB, w.pb, w.RB, w.TB, (int)K, w.header, (const int64_t *)nullptr, 0, (const int64_t *)nullptr, 0);
   const int tilesA = (int)((NA + 31) / 32), tilesB = (int)((NB + 31) / 32);
   const int nblk = (tilesA + 3) / 4;
   const int splits = std::max(1, std::min({kPairMaxLseSplits, 512 / nblk, tilesB}));
@@ -3296,6 +3652,143 @@ int sn_pair_fused_bwd_f32(const int64_t *target, const float *lse, const float *
   const int64_t quads = (int64_t)std::max(rowsA, rowsB) * 32;
   hipLaunchKernelGGL(pair_reduce_k, dim3((unsigned)((quads + kWG - 1) / kWG), 2), dim3(kWG), 0, s, A, B, dFA, ldda, (int)rowsA, dFB, lddb,
                      (int)rowsB, (int)K, gloss, w.header, (int)NA);
+  return launch_status();
+}
+
+extern "C++" {
+namespace {
+struct PairLossWs {
+  PairWs w;
+  float *part2;
+  size_t bytes;
+};
+PairLossWs pair_loss_ws(void *workspace, int64_t rowsA, int64_t rowsB) {
+  PairLossWs q;
+  q.w = pair_ws(workspace, rowsA, rowsB);
+  q.part2 = reinterpret_cast<float *>(static_cast<char *>(workspace) + q.w.bytes);
+  q.bytes = q.w.bytes + (size_t)kPairMaxLseSplits * q.w.pa * 4 * sizeof(float);
+  return q;
+}
+int pair_loss_check(int64_t NA, int64_t NB, int64_t rowsA, int64_t rowsB, int32_t K, int64_t ldgA, int64_t ldgB) {
+  if (NA < 1 || NB < 1 || rowsA < NA || rowsB < NB || K < 1 || ldgA < NB || ldgB < NB) return SN_E_SHAPE;
+  if (K > kPairKP) return SN_E_UNSUPPORTED;
+  if (rowsA > INT_MAX - 64 || rowsB > INT_MAX - 64) return SN_E_RANGE;
+  return SN_OK;
+}
+// features -> fragment order in the workspace (rows taken through the maps), shared by both forward entries
+int pair_loss_split(const float *FA, int64_t lda, const float *FB, int64_t ldb, const int64_t *mapA, const int64_t *mapB, int64_t NA,
+                    int64_t NB, int64_t rowsA, int64_t rowsB, int32_t K, const PairWs &w, hipStream_t s) {
+  hipError_t e = sn_internal_fill(w.header, 0, kPairHeader, s);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(pair_maxabs_k, dim3((unsigned)std::min<int64_t>(1024, (std::max(rowsA, rowsB) * K + 4 * kWG - 1) / (4 * kWG)), 2), dim3(kWG), 0, s, FA, lda, (int)rowsA, FB, ldb, (int)rowsB, (int)K, w.header);
+  const int64_t quads = (int64_t)std::max(w.pa, w.pb) * 32;
+  hipLaunchKernelGGL((pair_split_k<true>), dim3((unsigned)((quads + kWG - 1) / kWG), 2), dim3(kWG), 0, s, FA, lda, (int)rowsA, w.pa, w.RA, w.TA, FB, ldb,
+                     (int)rowsB, w.pb, w.RB, w.TB, (int)K, w.header, mapA, (int)NA, mapB, (int)NB);
+  return SN_OK;
+}
+template <bool SL1>
+int pair_loss_fwd(PairGeo G, int64_t rows, int64_t cols, const PairLossWs &q, hipStream_t s, int &splits) {
+  const int tilesA = (int)((rows + 31) / 32), tilesB = (int)((cols + 31) / 32);
+  const int nblk = (tilesA + 3) / 4;
+  splits = std::max(1, std::min({kPairMaxLseSplits, 512 / nblk, tilesB}));
+  hipLaunchKernelGGL((pair_loss_fwd_k<SL1>), dim3((unsigned)nblk, (unsigned)splits), dim3(kWG), 0, s, q.w.RA, q.w.RB, G, (int)rows, (int)cols, q.w.pa,
+                     q.w.header, q.w.lse_part, q.part2);
+  return SN_OK;
+}
+template <bool SL1>
+int pair_loss_bwd(PairGeo G, const int64_t *mapA, const int64_t *mapB, const float *stats, const float *gloss, int64_t Nrows, int64_t Ncols,
+                  int64_t rowsA, int64_t rowsB, int32_t K, float mul, float *dFA, int64_t ldda, float *dFB, int64_t lddb, const PairWs &w,
+                  hipStream_t s) {
+  const int tilesA = (int)((Nrows + 31) / 32), tilesB = (int)((Ncols + 31) / 32);
+  PairGradSide A{w.RA, w.RB, w.TB, w.gradA, (int)Nrows, (int)Ncols, w.pa, (tilesA + 3) / 4, 1};
+  PairGradSide B{w.RB, w.RA, w.TA, w.gradB, (int)Ncols, (int)Nrows, w.pb, (tilesB + 3) / 4, 1};
+  const int want = std::max(1, 512 / (A.nblk + B.nblk));
+  A.splits = std::max(1, std::min({kPairMaxGradSplits, want, tilesB}));
+  B.splits = std::max(1, std::min({kPairMaxGradSplits, want, tilesA}));
+  constexpr size_t lds = (size_t)2 * (2 * kPairTile + 4 * 128) * sizeof(unsigned short);
+  static const hipError_t attr =
+      hipFuncSetAttribute(reinterpret_cast<const void *>(pair_loss_grad_k<SL1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (attr != hipSuccess) return (int)attr;
+  hipLaunchKernelGGL((pair_loss_grad_k<SL1>), dim3((unsigned)(A.nblk * A.splits + B.nblk * B.splits)), dim3(kWG), lds, s, A, B, G, stats, w.header);
+  const int64_t quads = (int64_t)std::max(rowsA, rowsB) * 32;
+  hipLaunchKernelGGL(pair_loss_reduce_k, dim3((unsigned)((quads + kWG - 1) / kWG), 2), dim3(kWG), 0, s, A, B, dFA, ldda, (int)rowsA, dFB, lddb,
+                     (int)rowsB, (int)K, gloss, w.header, mul, mapA, (int)G.NA, mapB, (int)G.NB);
+  return SN_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+size_t sn_pair_loss_workspace_bytes(int64_t rowsA, int64_t rowsB) {
+  if (rowsA < 0 || rowsB < 0 || rowsA > INT_MAX - 64 || rowsB > INT_MAX - 64) return 0;
+  return pair_loss_ws(nullptr, rowsA, rowsB).bytes;
+}
+
+int sn_pair_soft_fwd_f32(const float *FA, int64_t lda, const float *FB, int64_t ldb, const int64_t *mapA, const int64_t *mapB,
+                         const float *const *geo, int64_t ldgA, int64_t ldgB, int64_t NA, int64_t NB, int64_t rowsA, int64_t rowsB,
+                         int32_t K, float *stats, float *rowloss, void *workspace, size_t workspace_bytes, void *stream) {
+  (void)hipGetLastError();      // a stale error left by an earlier runtime call of this thread is not ours to report
+  if (int st = pair_loss_check(NA, NB, rowsA, rowsB, K, ldgA, ldgB)) return st;
+  if (lda < K || ldb < K) return SN_E_SHAPE;
+  if (!FA || !FB || !geo || !workspace || !stats || !rowloss) return SN_E_NULL;
+  if (!aligned16(workspace)) return SN_E_ALIGN;
+  if (workspace_bytes < sn_pair_loss_workspace_bytes(rowsA, rowsB)) return SN_E_WORKSPACE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const PairLossWs q = pair_loss_ws(workspace, rowsA, rowsB);
+  if (int st = pair_loss_split(FA, lda, FB, ldb, mapA, mapB, NA, NB, rowsA, rowsB, K, q.w, s)) return st;
+  int splits = 1;
+  pair_loss_fwd<false>(PairGeo{geo, ldgA, ldgB, (int)NA, (int)NB}, NA, NB, q, s, splits);
+  hipLaunchKernelGGL(pair_soft_combine_k, dim3((unsigned)((NA + kWG - 1) / kWG)), dim3(kWG), 0, s, q.w.lse_part, q.part2, splits, q.w.pa, (int)NA,
+                     stats, rowloss);
+  return launch_status();
+}
+
+int sn_pair_soft_bwd_f32(const int64_t *mapA, const int64_t *mapB, const float *const *geo, int64_t ldgA, int64_t ldgB, const float *stats,
+                         const float *gloss, int64_t NA, int64_t NB, int64_t rowsA, int64_t rowsB, int32_t K, float *dFA, int64_t ldda,
+                         float *dFB, int64_t lddb, void *workspace, size_t workspace_bytes, void *stream) {
+  (void)hipGetLastError();      // a stale error left by an earlier runtime call of this thread is not ours to report
+  if (int st = pair_loss_check(NA, NB, rowsA, rowsB, K, ldgA, ldgB)) return st;
+  if (ldda < K || lddb < K) return SN_E_SHAPE;
+  if (!geo || !stats || !gloss || !dFA || !dFB || !workspace) return SN_E_NULL;
+  if (workspace_bytes < sn_pair_loss_workspace_bytes(rowsA, rowsB)) return SN_E_WORKSPACE;
+  const PairLossWs q = pair_loss_ws(workspace, rowsA, rowsB);
+  if (int st = pair_loss_bwd<false>(PairGeo{geo, ldgA, ldgB, (int)NA, (int)NB}, mapA, mapB, stats, gloss, NA, NB, rowsA, rowsB, K, 1.f, dFA, ldda,
+                                    dFB, lddb, q.w, static_cast<hipStream_t>(stream)))
+    return st;
+  return launch_status();
+}
+
+int sn_pair_sl1_fwd_f32(const float *FA, int64_t lda, const float *FB, int64_t ldb, const int64_t *mapA, const int64_t *mapB,
+                        const float *const *geo, int64_t ldgA, int64_t ldgB, int64_t NA, int64_t NB, int64_t rowsA, int64_t rowsB,
+                        int32_t K, double *rowloss, void *workspace, size_t workspace_bytes, void *stream) {
+  (void)hipGetLastError();      // a stale error left by an earlier runtime call of this thread is not ours to report
+  if (int st = pair_loss_check(NA, NB, rowsA, rowsB, K, ldgA, ldgB)) return st;
+  if (lda < K || ldb < K) return SN_E_SHAPE;
+  if (!FA || !FB || !geo || !workspace || !rowloss) return SN_E_NULL;
+  if (!aligned16(workspace)) return SN_E_ALIGN;
+  if (workspace_bytes < sn_pair_loss_workspace_bytes(rowsA, rowsB)) return SN_E_WORKSPACE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const PairLossWs q = pair_loss_ws(workspace, rowsA, rowsB);
+  if (int st = pair_loss_split(FA, lda, FB, ldb, mapA, mapB, NA, NB, rowsA, rowsB, K, q.w, s)) return st;
+  int splits = 1;
+  pair_loss_fwd<true>(PairGeo{geo, ldgA, ldgB, (int)NA, (int)NB}, rowsA, rowsB, q, s, splits);
+  hipLaunchKernelGGL(pair_sl1_combine_k, dim3((unsigned)((rowsA + kWG - 1) / kWG)), dim3(kWG), 0, s, reinterpret_cast<const double *>(q.w.lse_part),
+                     splits, q.w.pa, (int)rowsA, rowloss);
+  return launch_status();
+}
+
+int sn_pair_sl1_bwd_f32(const int64_t *mapA, const int64_t *mapB, const float *const *geo, int64_t ldgA, int64_t ldgB, const float *gloss,
+                        int64_t NA, int64_t NB, int64_t rowsA, int64_t rowsB, int32_t K, float *dFA, int64_t ldda, float *dFB, int64_t lddb,
+                        void *workspace, size_t workspace_bytes, void *stream) {
+  (void)hipGetLastError();      // a stale error left by an earlier runtime call of this thread is not ours to report
+  if (int st = pair_loss_check(NA, NB, rowsA, rowsB, K, ldgA, ldgB)) return st;
+  if (ldda < K || lddb < K) return SN_E_SHAPE;
+  if (!geo || !gloss || !dFA || !dFB || !workspace) return SN_E_NULL;
+  if (workspace_bytes < sn_pair_loss_workspace_bytes(rowsA, rowsB)) return SN_E_WORKSPACE;
+  const PairLossWs q = pair_loss_ws(workspace, rowsA, rowsB);
+  const float mul = (float)(1.0 / ((double)rowsA * (double)rowsB));
+  if (int st = pair_loss_bwd<true>(PairGeo{geo, ldgA, ldgB, (int)NA, (int)NB}, mapA, mapB, nullptr, gloss, rowsA, rowsB, rowsA, rowsB, K, mul, dFA,
+                                   ldda, dFB, lddb, q.w, static_cast<hipStream_t>(stream)))
+    return st;
   return launch_status();
 }
 

@@ -2,7 +2,8 @@
 
 One tower (`Model`: Laplacian, `DirModel`: Dirac; conv1 3->128, 15 residual blocks at 128 channels, conv2 128->120 plus
 the input coordinates repeated 40x) is applied to both shapes; `SiameseModel` returns bmm(FA, FB^T), a (B, NA, NB)
-score matrix, trained with the argmin-target cross entropy of loss_fun_delta_cross_entropy (main.py:229-240).
+score matrix, trained with one of the three losses of main.py:197-240 (`LOSSES`: "dcel" argmin-target cross entropy,
+"cel" soft-target cross entropy, "sl1" smooth-L1 against the geodesic sum).
 `state_dict` keys match the reference (model.conv1.*, model.rn{i}.*, model.conv2.*).
 """
 from __future__ import annotations
@@ -449,6 +450,152 @@ def streamed_delta_cross_entropy(FA, FB, targetX, targetY, block=1024):
     return loss / B
 
 
+def pair_geodesic_sum(GA, lA, liA, GB, lB, liB):
+    """`GA[:, liA[lB]] + GB[liB[lA], :]` (main.py:206,224), materialised: NA x NB, fp32 + fp32."""
+    return GA[:, liA[lB]] + GB[liB[lA], :]
+
+
+def loss_fun_cross_entropy(outputs, targetX, targetY):
+    """main.py:216-227 on the materialised (B, N, N) scores: -sum(softmin(G) * log_softmax(outputs[0, :NA, :NB])) per pair — a
+    SUM over the rows, not a mean — divided by the batch size.  The reference writes the sum as `torch.dot` of two 2-D
+    tensors (old torch flattened them; current torch refuses): the sum of the elementwise products is what is meant.  Like
+    the delta loss it scores outputs[0] for every i (the reference runs batch 1, main.py:40).  Plain torch operations in
+    the dtype of `outputs`; from the tower features: fused_pair_soft_cross_entropy."""
+    loss = outputs.new_zeros(1)
+    for i in range(outputs.size(0)):
+        GA, lA, liA = targetX[i]
+        GB, lB, liB = targetY[i]
+        NA, NB = lA.size(0), lB.size(0)
+        t = F.softmin(pair_geodesic_sum(GA, lA, liA, GB, lB, liB).to(outputs.dtype), dim=1)
+        loss = loss - (t * F.log_softmax(outputs[0, :NA, :NB], dim=1)).sum()
+    return loss / outputs.size(0)
+
+
+def aggregate_batch_G(outputs, targetX, targetY):
+    """main.py:197-210: the geodesic sums of the batch in the corner of zero matrices of the scores' shape."""
+    FullG = outputs.new_zeros(outputs.shape)
+    for i in range(outputs.size(0)):
+        GA, lA, liA = targetX[i]
+        GB, lB, liB = targetY[i]
+        FullG[i, :lA.size(0), :lB.size(0)] = pair_geodesic_sum(GA, lA, liA, GB, lB, liB).to(outputs.dtype)
+    return FullG
+
+
+def loss_fun_sl1(outputs, targetX, targetY):
+    """main.py:212-214: smooth-L1 between the (B, N, N) scores and the zero-padded geodesic sums, mean over ALL entries (the
+    padding is scored against 0), divided by the batch size.  Plain torch operations; from the tower features:
+    fused_pair_smooth_l1."""
+    return F.smooth_l1_loss(outputs, aggregate_batch_G(outputs, targetX, targetY)) / outputs.size(0)
+
+
+LOSSES = {"sl1": loss_fun_sl1, "cel": loss_fun_cross_entropy, "dcel": loss_fun_delta_cross_entropy}      # main.py:46,288-293
+
+
+def labels_are_inverse(label, label_inv) -> bool:
+    """label / label_inv are permutations of [0, n) and each other's inverse (what the label-order form of the geodesic
+    matrices rests on; main.py:66-102 stores them so, TorusBodies builds them with argsort).  One host check per frame."""
+    n = label.numel()
+    if label.dim() != 1 or label_inv.shape != label.shape or n == 0 or label.dtype != torch.int64 or label_inv.dtype != torch.int64:
+        return False
+    if int(label.min()) < 0 or int(label.max()) >= n or int(label_inv.min()) < 0 or int(label_inv.max()) >= n:
+        return False
+    ar = torch.arange(n, device=label.device)
+    return bool(torch.equal(label_inv[label], ar)) and bool(torch.equal(label[label_inv], ar))
+
+
+def label_order_matrix(G, label_inv):
+    """H = G[label_inv][:, label_inv]: the frame's geodesic matrix with rows and columns in LABEL order.  For two frames with
+    mutually inverse labels, GA[:, liA[lB]] + GB[liB[lA], :] == (HA + HB)[lA][:, lB]: in label order both terms are read as
+    they lie in memory, and a pair needs no gathered copy (the kernels' comment in csrc/sn_dense.hip)."""
+    return G[label_inv][:, label_inv].contiguous()
+
+
+def label_order_geodesics(ds, idx):
+    """(H, label_inv) of frame `idx` of a TorusBodies / FaustFrames dataset, built on first use and kept with the dataset (one
+    extra N x N matrix per frame; users of the delta loss never build it); None when the frame's labels are not mutually
+    inverse permutations or its matrix is not square fp32 on the device."""
+    cache = ds.__dict__.setdefault("_label_order", {})
+    if idx not in cache:
+        fr = ds.frames[idx]
+        G, label, label_inv = fr["G"], fr["label"], fr["label_inv"]
+        ok = (G.is_cuda and G.dtype == torch.float32 and G.dim() == 2 and G.shape[0] == G.shape[1] == label.numel()
+              and labels_are_inverse(label, label_inv))
+        cache[idx] = (label_order_matrix(G, label_inv), label_inv.contiguous()) if ok else None
+        if ok:
+            torch.cuda.synchronize(G.device)           # (read from whatever stream a later step runs on)
+    return cache[idx]
+
+
+def pair_geo_table(HA, HB):
+    """int64[2] on the device: the addresses of the two label-order matrices, as the sn_pair_soft_* / sn_pair_sl1_* kernels
+    read them.  The caller keeps HA and HB alive for as long as the table is used."""
+    return torch.tensor([HA.data_ptr(), HB.data_ptr()], dtype=torch.int64, device=HA.device)
+
+
+def _check_geo(HA, HB, NA, NB):
+    for H in (HA, HB):
+        if not (H.is_cuda and H.dtype == torch.float32 and H.dim() == 2 and H.stride(1) == 1 and H.shape[0] >= NA and H.shape[1] >= NB):
+            raise ValueError("label-order geodesic matrices: row-major fp32 on the device, at least NA x NB")
+
+
+class _FusedSoftCE(torch.autograd.Function):
+    """sum_u ( lse_S[u] - sum_v softmin(G[u])[v] S[u][v] ) over the NA x NB corner from the (rows, K) tower features
+    (sn_pair_soft_fwd/bwd_f32; replaces models.py:203 + main.py:224-226 and their backward passes)."""
+
+    @staticmethod
+    def forward(ctx, FA, FB, HA, HB, mapA, mapB, geo, NA, NB):
+        stats, rowloss, ws = kernels.pair_soft_fwd(FA, FB, mapA, mapB, geo, HA.stride(0), HB.stride(0), NA, NB)
+        ctx.save_for_backward(stats, ws, HA, HB, mapA, mapB, geo)
+        ctx.dims = (NA, NB, FA.shape[0], FB.shape[0], FA.shape[1])
+        return rowloss.sum()
+
+    @staticmethod
+    def backward(ctx, g):
+        stats, ws, HA, HB, mapA, mapB, geo = ctx.saved_tensors
+        dFA, dFB = kernels.pair_soft_bwd(mapA, mapB, geo, HA.stride(0), HB.stride(0), stats, g.reshape(1).contiguous(), ws, *ctx.dims)
+        return (dFA, dFB) + (None,) * 7
+
+
+class _FusedSmoothL1(torch.autograd.Function):
+    """mean over rowsA x rowsB of smooth_l1(S - FullG) from the tower features (sn_pair_sl1_fwd/bwd_f32; replaces models.py:203
+    + main.py:197-214 and their backward passes); the sum in fp64."""
+
+    @staticmethod
+    def forward(ctx, FA, FB, HA, HB, mapA, mapB, geo, NA, NB):
+        rowloss, ws = kernels.pair_sl1_fwd(FA, FB, mapA, mapB, geo, HA.stride(0), HB.stride(0), NA, NB)
+        ctx.save_for_backward(ws, HA, HB, mapA, mapB, geo)
+        ctx.dims = (NA, NB, FA.shape[0], FB.shape[0], FA.shape[1])
+        return (rowloss.sum() / float(FA.shape[0] * FB.shape[0])).to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, g):
+        ws, HA, HB, mapA, mapB, geo = ctx.saved_tensors
+        dFA, dFB = kernels.pair_sl1_bwd(mapA, mapB, geo, HA.stride(0), HB.stride(0), g.reshape(1).contiguous(), ws, *ctx.dims)
+        return (dFA, dFB) + (None,) * 7
+
+
+def fused_pair_soft_cross_entropy(FA, FB, HA, HB, mapA, mapB, NA: int, NB: int, geo=None):
+    """loss_fun_cross_entropy (main.py:216-227) of one pair from the (B, N, K) tower outputs — sample 0 is the one scored —
+    with the score matrix, the gathered geodesic matrices and their sum never in memory.  HA, HB: the two frames'
+    label-order matrices (label_order_matrix), mapA, mapB their label_inv (row u of H <-> feature row map[u]; None =
+    identity); geo: pair_geo_table(HA, HB) when the caller already holds one.
+    The evaluation loop's `outputs * (maskX·maskY^T)` (main.py:352-353) equals scoring FA * maskX against FB * maskY: pass the
+    masked features, no other mode is needed."""
+    _check_geo(HA, HB, NA, NB)
+    return _FusedSoftCE.apply(FA[0], FB[0], HA, HB, mapA, mapB, pair_geo_table(HA, HB) if geo is None else geo, NA, NB)
+
+
+def fused_pair_smooth_l1(FA, FB, HA, HB, mapA, mapB, NA: int, NB: int, geo=None):
+    """loss_fun_sl1 (main.py:197-214) of one pair from the (B, N, K) tower outputs at batch size 1, arguments as
+    fused_pair_soft_cross_entropy; the padding of the batch is scored against 0 as in the reference, masked evaluation
+    (main.py:352-353) by passing the masked features."""
+    _check_geo(HA, HB, NA, NB)
+    return _FusedSmoothL1.apply(FA[0], FB[0], HA, HB, mapA, mapB, pair_geo_table(HA, HB) if geo is None else geo, NA, NB)
+
+
+_FUSED_LOSSES = {"cel": fused_pair_soft_cross_entropy, "sl1": fused_pair_smooth_l1}
+
+
 def make_optimizer(model):
     return make_adam(model)       # main.py:285
 
@@ -505,11 +652,25 @@ class PairBatch:
     dataset's resident geodesic matrices: the replay then takes a 6890-entry index vector as input instead of two
     190 MB matrices copied into static buffers every step."""
 
-    def __init__(self, ds: TorusBodies, ia: int, ib: int):
+    def __init__(self, ds: TorusBodies, ia: int, ib: int, loss: str = "dcel"):
+        """loss: "dcel" (default), "cel" or "sl1" (`LOSSES`).  The last two compare every score with the geodesic sum, so there
+        is no target vector: the batch carries the two frames' label-order matrices (label_order_geodesics: dataset-resident,
+        built once per frame, never copied), their label_inv as row maps and a 2-entry address table.  A captured step reads
+        the matrices THROUGH that table, so replaying on another pair rewrites 16 bytes and two index vectors."""
+        if loss not in LOSSES:
+            raise ValueError(f"loss: one of {sorted(LOSSES)}")
+        self.loss = loss
         self.inX, self.tX, self.mX, self.LX = ds.sample(ia)
         self.inY, self.tY, self.mY, self.LY = ds.sample(ib)
         (GA, lA, liA), (GB, lB, liB) = self.tX[0], self.tY[0]
         self.NA, self.NB = int(lA.size(0)), int(lB.size(0))
+        self.target, self._target_ready, self.geo = None, None, None
+        if loss != "dcel":
+            a, b = label_order_geodesics(ds, ia), label_order_geodesics(ds, ib)
+            if a is not None and b is not None and self.NA == self.NB:
+                (self.HA, self.mapA), (self.HB, self.mapB) = a, b
+                self.geo = pair_geo_table(self.HA, self.HB)
+            return
         # The target reads two resident 190 MB matrices (~0.14 ms) and depends on nothing of the model: on a device it is
         # computed on a stream of its own, so that the target of the NEXT pair overlaps the step of the current one; the
         # consumer waits for `_target_ready` (target_tensor()).
@@ -537,30 +698,68 @@ class PairBatch:
         import copy
 
         b = copy.copy(self)
-        b.inX, b.inY, b.mX, b.mY, b.target = (t.clone() for t in (self.inX, self.inY, self.mX, self.mY, self.target_tensor()))
+        b.inX, b.inY, b.mX, b.mY = (t.clone() for t in (self.inX, self.inY, self.mX, self.mY))
+        if self.loss == "dcel":
+            b.target = self.target_tensor().clone()
+        elif self.geo is not None:                       # (the matrices themselves stay the dataset's: only their addresses are copied)
+            b.mapA, b.mapB, b.geo = self.mapA.clone(), self.mapB.clone(), self.geo.clone()
         b._target_ready = None
         own = lambda ops: type(ops)(o.clone() for o in ops) if isinstance(ops, (tuple, list)) else ops.clone()
         b.LX, b.LY = own(self.LX), own(self.LY)
-        b.tX = b.tY = None
+        if self.loss == "dcel" or self.geo is not None:
+            b.tX = b.tY = None                           # (the materialised composition of "cel" / "sl1" reads the triples)
         return b
 
     def graph_constants(self):
         """Host values baked into the captured kernels' arguments (the corner of the score matrix the cross entropy reads):
         part of the batch signature, so a pair with other vertex counts cannot be replayed through this capture."""
-        return (self.NA, self.NB)
+        if self.loss == "dcel":
+            return (self.NA, self.NB)
+        if self.geo is None:                             # (materialised composition: the capture would bake this pair's matrices in)
+            return (self.NA, self.NB, self.loss, id(self.tX[0][0]), id(self.tY[0][0]))
+        return (self.NA, self.NB, self.loss, self.HA.stride(0), self.HB.stride(0))
+
+    def keep_alive(self, loaded: "PairBatch") -> None:
+        """(static batch of a capture) the matrices whose addresses `load` just copied stay referenced until the next load."""
+        if self.geo is not None:
+            self.HA, self.HB = loaded.HA, loaded.HB
 
     def graph_tensors(self):
         from .graphs import operator_tensors
 
-        out = [self.inX, self.inY, self.mX, self.mY, self.target_tensor()]
+        out = [self.inX, self.inY, self.mX, self.mY]
+        if self.loss == "dcel":
+            out.append(self.target_tensor())
+        elif self.geo is not None:
+            out += [self.mapA, self.mapB, self.geo]
         for ops in (self.LX, self.LY):
             for o in (ops if isinstance(ops, (tuple, list)) else (ops,)):
                 out += operator_tensors(o)
         return out
 
 
+def _forward_geodesic_loss(model, b: PairBatch):
+    """`cel` / `sl1` of a PairBatch: from the tower features when the batch carries label-order matrices, else the
+    materialised composition (an error under SN_STRICT=1: it runs the score product on the library GEMM)."""
+    if isinstance(model, SiameseModel) and b.geo is not None:
+        FA, FB = model.towers(_operation(b.LX, b.mX), _operation(b.LY, b.mY), b.inX, b.inY)
+        if fused_pair_supported(FA, FB):
+            return _FUSED_LOSSES[b.loss](FA, FB, b.HA, b.HB, b.mapA, b.mapB, b.NA, b.NB, b.geo).reshape(1)
+        out = torch.bmm(FA, FB.transpose(1, 2))
+    else:
+        out = model(_operation(b.LX, b.mX), _operation(b.LY, b.mY), b.inX, b.inY)
+    if os.environ.get("SN_STRICT", "0") == "1" and out.is_cuda:
+        raise RuntimeError(f"SN_STRICT: the '{b.loss}' loss of this pair would run on the materialised score matrix (labels that "
+                           "are not mutually inverse permutations, or features the fused kernels do not take)")
+    if b.tX is None:
+        raise RuntimeError("the materialised composition needs the dataset's target triples (not kept by PairBatch.owned())")
+    return LOSSES[b.loss](out, b.tX, b.tY).reshape(1)
+
+
 def forward_loss(model, b: PairBatch):
-    """loss_fun_delta_cross_entropy for the one pair of a PairBatch (main.py:229-240 at batch size 1), target precomputed."""
+    """The loss `b.loss` (main.py:197-240 at batch size 1) for the one pair of a PairBatch; "dcel": target precomputed."""
+    if b.loss != "dcel":
+        return _forward_geodesic_loss(model, b)
     if isinstance(model, SiameseModel):
         # same value as model(...) + pair_cross_entropy, without the (1, N, N) score matrix in between
         FA, FB = model.towers(_operation(b.LX, b.mX), _operation(b.LY, b.mY), b.inX, b.inY)

@@ -252,6 +252,9 @@ class GraphedStep:
                     g[1].append(s_)
             for dst, srcs in groups.values():
                 torch._foreach_copy_(dst, srcs)
+        keep = getattr(self.static, "keep_alive", None)
+        if keep is not None:                                # (a batch that hands the graph ADDRESSES of resident tensors)
+            keep(batch)
 
     def replay(self) -> torch.Tensor:
         self.graph.replay()

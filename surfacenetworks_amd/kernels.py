@@ -1228,6 +1228,66 @@ def pair_fused_bwd(target, lse, gloss, ws, NA: int, NB: int, rowsA: int, rowsB: 
     return dFA, dFB
 
 
+def _pair_loss_args(who, FA, FB, mapA, mapB, geo, NA, NB):
+    _dev(FA, FB, mapA, mapB, geo)
+    for t in (FA, FB):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
+            raise TypeError(f"{who}: row-major float32 feature matrices expected")
+    if FA.shape[1] != FB.shape[1] or geo.dtype != torch.int64 or geo.numel() != 2 or not geo.is_contiguous():
+        raise TypeError(f"{who}: features of one width and a table of two device addresses (int64) expected")
+    for m, n in ((mapA, NA), (mapB, NB)):
+        if m is not None and (m.dtype != torch.int64 or m.numel() != n or not m.is_contiguous()):
+            raise TypeError(f"{who}: row maps are contiguous int64 permutations of the scored rows")
+    if not (0 < NA <= FA.shape[0] and 0 < NB <= FB.shape[0]):
+        raise ValueError(f"{who}: NA / NB do not fit the feature matrices")
+
+
+def pair_soft_fwd(FA, FB, mapA, mapB, geo, ldgA: int, ldgB: int, NA: int, NB: int):
+    """(stats, rowloss, workspace) of the soft-target cross entropy (main.py:216-227) from the tower features FA (rowsA x K),
+    FB (rowsB x K) and the two label-order geodesic matrices whose device addresses `geo` (int64[2] on the device) holds
+    (sn_pair_soft_fwd_f32).  stats = lse | softmin offset, 2 NA floats; the loss is rowloss.sum()."""
+    _pair_loss_args("pair_soft_fwd", FA, FB, mapA, mapB, geo, NA, NB)
+    nbytes = _lib.load().sn_pair_loss_workspace_bytes(FA.shape[0], FB.shape[0])
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=FA.device)
+    stats = torch.empty(2 * NA, dtype=torch.float32, device=FA.device)
+    rowloss = torch.empty(NA, dtype=torch.float32, device=FA.device)
+    _lib.call("sn_pair_soft_fwd_f32", _p(FA), FA.stride(0), _p(FB), FB.stride(0), _p(mapA), _p(mapB), _p(geo), ldgA, ldgB, NA, NB,
+              FA.shape[0], FB.shape[0], FA.shape[1], _p(stats), _p(rowloss), _p(ws), nbytes, _stream())
+    return stats, rowloss, ws
+
+
+def pair_soft_bwd(mapA, mapB, geo, ldgA: int, ldgB: int, stats, gloss, ws, NA: int, NB: int, rowsA: int, rowsB: int, K: int):
+    """(dFA, dFB) of rowloss.sum() times the device scalar gloss (sn_pair_soft_bwd_f32); rows past NA / NB are zero."""
+    _dev(mapA, mapB, geo, stats, gloss, ws)
+    dFA = torch.empty((rowsA, K), dtype=torch.float32, device=stats.device)
+    dFB = torch.empty((rowsB, K), dtype=torch.float32, device=stats.device)
+    _lib.call("sn_pair_soft_bwd_f32", _p(mapA), _p(mapB), _p(geo), ldgA, ldgB, _p(stats), _p(gloss), NA, NB, rowsA, rowsB, K, _p(dFA), K,
+              _p(dFB), K, _p(ws), ws.numel(), _stream())
+    return dFA, dFB
+
+
+def pair_sl1_fwd(FA, FB, mapA, mapB, geo, ldgA: int, ldgB: int, NA: int, NB: int):
+    """(rowloss (fp64, rowsA), workspace) of the smooth-L1 loss against the zero-padded geodesic sum (main.py:197-214):
+    sn_pair_sl1_fwd_f32; the loss is rowloss.sum() / (rowsA rowsB)."""
+    _pair_loss_args("pair_sl1_fwd", FA, FB, mapA, mapB, geo, NA, NB)
+    nbytes = _lib.load().sn_pair_loss_workspace_bytes(FA.shape[0], FB.shape[0])
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=FA.device)
+    rowloss = torch.empty(FA.shape[0], dtype=torch.float64, device=FA.device)
+    _lib.call("sn_pair_sl1_fwd_f32", _p(FA), FA.stride(0), _p(FB), FB.stride(0), _p(mapA), _p(mapB), _p(geo), ldgA, ldgB, NA, NB,
+              FA.shape[0], FB.shape[0], FA.shape[1], _p(rowloss), _p(ws), nbytes, _stream())
+    return rowloss, ws
+
+
+def pair_sl1_bwd(mapA, mapB, geo, ldgA: int, ldgB: int, gloss, ws, NA: int, NB: int, rowsA: int, rowsB: int, K: int):
+    """(dFA, dFB) of the mean smooth-L1 times the device scalar gloss (sn_pair_sl1_bwd_f32); the padding rows are scored too."""
+    _dev(mapA, mapB, geo, gloss, ws)
+    dFA = torch.empty((rowsA, K), dtype=torch.float32, device=gloss.device)
+    dFB = torch.empty((rowsB, K), dtype=torch.float32, device=gloss.device)
+    _lib.call("sn_pair_sl1_bwd_f32", _p(mapA), _p(mapB), _p(geo), ldgA, ldgB, _p(gloss), NA, NB, rowsA, rowsB, K, _p(dFA), K, _p(dFB), K,
+              _p(ws), ws.numel(), _stream())
+    return dFA, dFB
+
+
 def masked_smooth_l1_fwd(out2d, target2d, rowmask, scale: float):
     """scale * sum smooth_l1(out*rowmask - target) as a 0-dim fp32 tensor (sn_masked_smooth_l1_fwd_f32)."""
     _dev(out2d, target2d, rowmask)
