@@ -112,3 +112,110 @@ def sigs_close(sigs, ref_of, tol=1e-4):
         if not (np.abs(np.asarray(s) - r) <= tol * abs(r[0]) + 1e-5 * top).all():
             bad.append((k, s, r))
     return bad
+
+
+# ---- the two-piece fp16 weight gradient (wgrad_h_k, csrc/sn_dense.hip): a numpy model of its split and probe operands ----------
+def pow2_up_for(bound):
+    """The power of two wgrad_h_k scales an operand by: bound = f * 2^E, f in [0.5, 1)  ->  2^(15 - E), which brings the bound
+    into [2^14, 2^15) (the exponent is clamped to +-100 for zero / denormal / non-finite bounds, as in the kernel)."""
+    b = np.ascontiguousarray(bound, dtype=np.float32)
+    e = ((b.view(np.uint32) >> np.uint32(23)) & np.uint32(0xFF)).astype(np.int64) - 126
+    return np.exp2(15 - np.clip(e, -100, 100)).astype(np.float32)
+
+
+def wgrad_xbound(xinvstd, stat_rows):
+    """The bound of |x - center| per column that the kernel really scales by: sqrtf(stat_rows) * 1.0625f / xinvstd[c] in fp32
+    (make_bounds; the factor covers the rounding of the statistics)."""
+    xfac = np.float32(np.sqrt(np.float32(stat_rows))) * np.float32(1.0625)
+    return (xfac / np.asarray(xinvstd, dtype=np.float32)).astype(np.float32)
+
+
+def wgrad_split_model(dy, x, center, dybound, xinvstd, stat_rows, drop=()):
+    """G = dy^T (x - center) as the two-piece kernel forms it: operands scaled by pow2_up_for of their bounds, a = h + l with
+    h = fp16(a), l = fp16(a - h), the products l*h, h*l, h*h (never l*l) accumulated in fp32 row by row, exact inverse scales.
+    `drop` names products to leave out ("hh", "hl", "lh": dy piece first) and "ll" may be ADDED with drop=("-ll",)."""
+    f32, f16 = np.float32, np.float16
+    sdy = pow2_up_for(f32(np.max(dybound)))
+    sx = pow2_up_for(wgrad_xbound(xinvstd, stat_rows))
+    a = np.asarray(dy, f32) * sdy
+    b = np.clip((np.asarray(x, f32) - np.asarray(center, f32)[None, :]) * sx[None, :], f32(-65504), f32(65504))
+    ah, bh = a.astype(f16).astype(f32), b.astype(f16).astype(f32)
+    al, bl = (a - ah).astype(f16).astype(f32), (b - bh).astype(f16).astype(f32)
+    acc = np.zeros((a.shape[1], b.shape[1]), f32)
+    terms = [("lh", al, bh), ("hl", ah, bl), ("hh", ah, bh)] + ([("ll", al, bl)] if "-ll" in drop else [])
+    for r in np.flatnonzero(np.any(a != 0, axis=1) & np.any(b != 0, axis=1)):
+        for name, p, q in terms:
+            if name not in drop:
+                acc = acc + np.outer(p[r], q[r]).astype(f32)
+    return acc * ((f32(1) / sx) * (f32(1) / sdy))[None, :]
+
+
+_PROBE_PATTERNS = ((1.0, 1), (1.0 + 2.0 ** -10, 11), (1.0 + 2.0 ** -21, 22), (1.5, 2))      # (mantissa, significant bits)
+
+
+def _probe_row(n, unit, seed):
+    """n elements unit[i] * 2^-k * u: k = i % 40, u cycling through _PROBE_PATTERNS every 40 elements (k = 0: u = 1, the
+    element then sits AT the power of two below its bound), alternating signs.  -> values (fp64), k, significant bits."""
+    i = np.arange(n)
+    k = i % 40
+    pat = (i // 40 + seed) % len(_PROBE_PATTERNS)
+    u = np.array([p[0] for p in _PROBE_PATTERNS])[pat]
+    bits = np.array([p[1] for p in _PROBE_PATTERNS])[pat]
+    u = np.where(k == 0, 1.0, u)
+    bits = np.where(k == 0, 1, bits)
+    return np.where(i % 2 == 0, 1.0, -1.0) * unit * np.exp2(-k.astype(np.float64)) * u, k, bits
+
+
+def split_probe_operands(J, C, rows, nz_row, seed=0):
+    """Operands that probe the split of wgrad_h_k element by element: dy and x are zero except in row `nz_row`, so
+    G[j, c] = dy[j] * x[c] is ONE product per output (nothing for the fp32 accumulation to round but the pieces of that term).
+    dy[j] = unit_dy * 2^-k_j * u_j and x[c] = unit_c * 2^-m_c * w_c, unit = the power of two at or below the operand's bound
+    (what the kernel's scale maps to 2^14).  Returns a dict with the operands, the bounds and, per pair (j, c):
+      exact   k, m <= 17, one factor of <= 11 bits (its low piece is zero: the dropped l*l product is absent) and a product
+              of <= 24 bits (the fp32 accumulator holds it): the kernel must reproduce float64 exactly;
+      loose_dy / loose_x   that operand 17 < k <= 39 below its bound, the other a power of two with k <= 17: the header's
+              absolute error, 2^-39 of the bound times the other operand."""
+    rng = np.random.default_rng(seed)
+    bound = np.float32(1.75 * 2.0 ** int(rng.integers(-6, 7)))
+    xinvstd = (np.exp2(rng.integers(-8, 9, size=C)) * rng.uniform(1.0, 2.0, size=C)).astype(np.float32)
+    stat_rows = max(rows, 1000)
+    xb = wgrad_xbound(xinvstd, stat_rows)
+    unit_dy = 2.0 ** 14 / float(pow2_up_for(bound).reshape(-1)[0])
+    unit_x = 2.0 ** 14 / pow2_up_for(xb).astype(np.float64)
+    dyr, k, kb = _probe_row(J, unit_dy, seed)
+    xr, m, mb = _probe_row(C, unit_x, seed + 1)
+    dy = np.zeros((rows, J), np.float32)
+    x = np.zeros((rows, C), np.float32)
+    dy[nz_row] = dyr.astype(np.float32)
+    x[nz_row] = xr.astype(np.float32)
+    assert np.array_equal(dy[nz_row].astype(np.float64), dyr) and np.array_equal(x[nz_row].astype(np.float64), xr)
+    assert np.abs(dy).max() <= bound and (np.abs(x).max(0) <= xb).all()          # the bounds handed over are true
+    K, M, KB, MB = k[:, None], m[None, :], kb[:, None], mb[None, :]
+    return dict(dy=dy, x=x, center=np.zeros(C, np.float32), bound=bound, xinvstd=xinvstd, stat_rows=stat_rows, xbound=xb,
+                ref=np.outer(dyr, xr), dy_row=dyr, x_row=xr, k=k, m=m, kbits=kb, mbits=mb,
+                exact=(K <= 17) & (M <= 17) & (np.minimum(KB, MB) <= 11) & (KB + MB <= 24),
+                loose_dy=(K > 17) & (M <= 17) & (MB == 1), loose_x=(M > 17) & (K <= 17) & (KB == 1))
+
+
+def top_of_binade_operands(J, C, rows, nz_row):
+    """One non-zero row whose dy elements ARE the bound and whose bound sits at the top of its binade (mantissa all ones:
+    scaled by pow2_up_for it lands just below 2^15, the largest scaled value the contract allows — one more binary order would
+    pass fp16's 65504), times powers of two in x; and in the even columns of x an element equal to the column's own bound,
+    itself chosen within 2^-12 of a power of two."""
+    bound = np.nextafter(np.float32(8.0), np.float32(0))
+    stat_rows = max(rows, 1000)
+    xfac = np.float32(np.sqrt(np.float32(stat_rows))) * np.float32(1.0625)
+    target = (np.exp2(np.arange(C) % 9 - 4) * (1 - 2.0 ** -13)).astype(np.float32)
+    xinvstd = (xfac / target).astype(np.float32)
+    xb = wgrad_xbound(xinvstd, stat_rows)
+    assert (np.frexp(xb)[0] > 65520.0 / 65536.0).all() and float(np.frexp(bound)[0]) > 65520.0 / 65536.0
+    unit_x = 2.0 ** 14 / pow2_up_for(xb).astype(np.float64)
+    j, c = np.arange(J), np.arange(C)
+    dyr = np.where(j % 2 == 0, 1.0, -1.0) * float(bound) * np.exp2(-(j % 8).astype(np.float64))
+    xr = np.where(c % 2 == 0, xb.astype(np.float64), unit_x * np.exp2(-(c % 8).astype(np.float64)))
+    dy = np.zeros((rows, J), np.float32)
+    x = np.zeros((rows, C), np.float32)
+    dy[nz_row], x[nz_row] = dyr.astype(np.float32), xr.astype(np.float32)
+    assert np.array_equal(dy[nz_row].astype(np.float64), dyr) and np.array_equal(x[nz_row].astype(np.float64), xr)
+    return dict(dy=dy, x=x, center=np.zeros(C, np.float32), bound=bound, xinvstd=xinvstd, stat_rows=stat_rows, xbound=xb,
+                ref=np.outer(dyr, xr), pow2_x=(c % 2 == 1))
