@@ -1,10 +1,13 @@
-// sn_dense.hip — kernels around the per-node BatchNorm+Linear of the residual blocks (gfx950).
+// sn_dense.hip — the dense kernels of the residual blocks and of the models' heads that are not GEMMs (gfx950).
 //
 //   colstats_k / colstats_final_k   per-channel sum and sum of squares, fp64 accumulation (HBM-bound, one pass)
 //   wgrad_mfma_k / wgrad_reduce_k   G = dyᵀ·x for tall-skinny operands: split-K over row slabs on the fp32 MFMA
-//                                   (v_mfma_f32_32x32x2_f32: exact fp32, 64 FLOP/clk/SIMD) — the only MFMA use in
-//                                   this library, as the dense per-node MLP is the only GEMM-shaped work on the path
+//                                   (v_mfma_f32_32x32x2_f32: exact fp32, 64 FLOP/clk/SIMD)
+//   wgrad_u_k / wgrad_h_k           the same product on three bf16 / two scaled fp16 pieces
 //   affine_cols_acc_k               dx += x*B[c] + C[c]  (tail of the BatchNorm backward)
+//   ... and, each under its own banner below: BatchNorm fold and backward coefficients, the thin Linear layers, segment sums,
+//   global average, masked smooth-L1, segment gathers, and the losses on a MATERIALISED score matrix (pair_argmin*, pair_ce_*).
+//   The pair losses computed from the features, without the score matrix, are in sn_pair.hip.
 //
 // Interfaces and the reference code they replace: include/sn_spmm.h.
 
@@ -14,21 +17,12 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-#include "sn_spmm.h"
-
-// per-launch timing shared with sn_kernels.hip (the facility behind sn_timing_*)
-int sn_internal_cu_count();
-hipError_t sn_internal_fill(void *dst, int value, size_t bytes, hipStream_t s);
-hipError_t sn_internal_copy2d(void *dst, int64_t dpitch, const void *src, int64_t spitch, int64_t width, int64_t rows, hipStream_t s);
-bool sn_internal_timing_slot(int kind, int64_t rows, int64_t width, int64_t bytes, int outw, hipEvent_t *s, hipEvent_t *e);
+#include "sn_dense_common.h"
 
 namespace {
 
-constexpr int kWG = 256;
 #define kCUs sn_internal_cu_count()      // compute units of the current device (256 on an MI355X in SPX mode)
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f16v __attribute__((ext_vector_type(16)));
 __device__ __forceinline__ f4 ld4_s(const float *p, int nt) {
   return nt ? __builtin_nontemporal_load(reinterpret_cast<const f4 *>(p)) : *reinterpret_cast<const f4 *>(p);
 }
@@ -40,12 +34,6 @@ __device__ __forceinline__ void st4_s(float *p, f4 v, int nt) {
 __device__ __forceinline__ f4 ld4_stat(const float *p) { return ld4_s(p, 0); }
 
 constexpr int kStreamNT = 1;     // elementwise passes stream with non-temporal loads/stores (see sn_kernels.hip)
-
-inline int launch_status() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? SN_OK : (int)e;
-}
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // ------------------------------------------------------------------------------------------------
 // column statistics
@@ -309,7 +297,6 @@ __global__ __launch_bounds__(kWG, 2) void wgrad_mfma_k(const float *__restrict__
 // wave-specialised and LDS-DMA forms are described in LABNOTES (k23, wgrad_d).
 // ------------------------------------------------------------------------------------------------
 typedef __bf16 bf8v __attribute__((ext_vector_type(8)));
-typedef unsigned int u4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ f16v mfma_bf16(const u4 &a, const u4 &b, const f16v &c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf8v, a), __builtin_bit_cast(bf8v, b), c, 0, 0, 0);
@@ -1859,747 +1846,6 @@ inline int wgrad_slabs(int64_t rows) {
   return (int)b;
 }
 
-
-// ------------------------------------------------------------------------------------------------
-// Dense-correspondence loss WITHOUT the score matrix (src/dense_correspondence/models.py:203 bmm(FA, FB^T) and
-// main.py:229-240 argmin-target cross entropy over outputs[0, :NA, :NB]): the 7000 x 7000 scores are formed tile by tile on
-// the fp16 matrix pipe and reduced on the spot; forward and backward never write them.
-//
-// Arithmetic: the two-piece fp16 split of the Linear kernels (sn_gemm.hip).  x·up = h + l with h = rn16(x·up),
-// l = rn16(x·up - h) holds 22+ significant bits, `up` an exact power of two taken from the MATRIX's absolute maximum (so it
-// factors out of every contraction); a product is the three partial products l·h + h·l + h·h, each exact in the fp32
-// accumulator of v_mfma_f32_32x32x16_f16 (the dropped l·l is below 2^-24 of the term).  Elements more than 2^16 below the
-// matrix maximum lose low-order bits of l: an ABSOLUTE error below 2^-39 of the maximum, nothing next to the fp32 rounding of
-// a 120-term sum.  The soft-max factor P = softmax - onehot in [-1, 1] is split the same way after scaling by 2^14.
-//
-// Layout: every operand is stored in MFMA FRAGMENT ORDER, 32 rows (a "tile") at a time — [tile][k-step][piece][lane][8 halfs],
-// lane (i, kh) holding row i's elements 8 kh .. 8 kh + 7 of the k-step — so that one wave-wide LDS-DMA instruction moves 1 KiB
-// of contiguous global memory into 1 KiB of LDS that ds_read_b128 then reads without bank conflicts: no transposition, no
-// address arithmetic per element.  R holds the features for the score product (contraction over the feature index), T holds
-// them transposed for the gradient product (contraction over the streamed rows, in the order the accumulator of the score
-// tile hands them over: pair_perm).
-//   pair_maxabs_k   absolute maximum of both feature matrices -> the two scales
-//   pair_split_k    F -> R, T of both sides
-//   pair_lse_k      a workgroup owns 128 rows of A (4 waves x 32, fragments in registers) and streams a RANGE of B's tiles
-//                   through a double-buffered LDS stage; the tile is computed TRANSPOSED (lane = row of A), so the soft-max
-//                   reductions of a row stay inside a lane; (max, sum, target logit) per row and range -> pair_combine_k
-//   pair_grad_k     both gradients in one launch: a workgroup owns 128 rows of one side and streams a range of the other
-//                   side's tiles (R and T); scores recomputed, P split in registers — the accumulator layout of the transposed
-//                   tile IS the operand layout of the second product — dOwn += P·Other; partial sums per range
-//   pair_reduce_k   sums the ranges in fixed order, applies gloss / NA and the scales, zero-fills the padding rows
-// ------------------------------------------------------------------------------------------------
-constexpr int kPairKP = 128;                       // padded feature count (K <= 128)
-constexpr int kPairTile = 32 * kPairKP * 2;        // halfs of one tile of R (or T): 8 (or 4 x 2) k-steps x 2 pieces x 64 lanes x 8
-constexpr int kPairChunk = 512;                    // halfs per DMA instruction (64 lanes x 16 B)
-constexpr int kPairMaxLseSplits = 8, kPairMaxGradSplits = 4;
-constexpr int kPairHeader = 256;                   // bytes: [0] max|FA| bits, [1] max|FB| bits
-
-typedef _Float16 h8v __attribute__((ext_vector_type(8)));
-typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-typedef float f2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f16v mfma_f16(const u4 &a, const u4 &b, const f16v &c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8v, a), __builtin_bit_cast(h8v, b), c, 0, 0, 0);
-}
-template <int N_>
-__device__ __forceinline__ void pair_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_) : "memory");
-}
-// up = 2^(14 - E), down = 2^(E - 14) for an absolute maximum m = f·2^E, f in [0.5, 1)
-__device__ __forceinline__ void pair_scales(unsigned mbits, float &up, float &down) {
-  int e = (int)((mbits >> 23) & 0xffu) - 126;
-  e = e < -100 ? -100 : (e > 100 ? 100 : e);       // zero / denormal / non-finite matrices: any finite scale will do
-  up = __uint_as_float((unsigned)(127 + 14 - e) << 23);
-  down = __uint_as_float((unsigned)(127 - 14 + e) << 23);
-}
-
-__global__ __launch_bounds__(kWG) void pair_maxabs_k(const float *__restrict__ FA, int64_t lda, int rowsA, const float *__restrict__ FB,
-                                                     int64_t ldb, int rowsB, int K, unsigned *__restrict__ header) {
-  const float *F = blockIdx.y ? FB : FA;
-  const int64_t ld = blockIdx.y ? ldb : lda;
-  const int64_t total = (int64_t)(blockIdx.y ? rowsB : rowsA) * K;
-  unsigned m = 0;
-  for (int64_t id = (int64_t)blockIdx.x * kWG + threadIdx.x; id < total; id += (int64_t)gridDim.x * kWG) {
-    const unsigned b = __float_as_uint(F[id / K * ld + id % K]) & 0x7fffffffu;
-    m = b > m ? b : m;
-  }
-#pragma unroll
-  for (int o = 32; o; o >>= 1) {
-    const unsigned q = (unsigned)__shfl_xor((int)m, o);
-    m = q > m ? q : m;
-  }
-  if ((threadIdx.x & 63) == 0 && m) atomicMax(header + blockIdx.y, m);
-}
-
-// one thread per (row, 4 features) of a side (blockIdx.y): rows [0, npad), feature quads [0, 32)
-// MAP: position `row` of R / T takes row map[row] of F for row < nmap (a permutation of [0, nmap)), row `row` itself past it
-template <bool MAP>
-__global__ __launch_bounds__(kWG) void pair_split_k(const float *__restrict__ FA, int64_t lda, int rowsA, int npadA, unsigned short *__restrict__ RA,
-                                                    unsigned short *__restrict__ TA, const float *__restrict__ FB, int64_t ldb, int rowsB,
-                                                    int npadB, unsigned short *__restrict__ RB, unsigned short *__restrict__ TB, int K,
-                                                    const unsigned *__restrict__ header, const int64_t *__restrict__ mapA, int nmapA,
-                                                    const int64_t *__restrict__ mapB, int nmapB) {
-  const bool sb = blockIdx.y != 0;
-  const float *F = sb ? FB : FA;
-  const int64_t ld = sb ? ldb : lda;
-  const int n = sb ? rowsB : rowsA, npad = sb ? npadB : npadA;
-  unsigned short *R = sb ? RB : RA, *T = sb ? TB : TA;
-  const int64_t id = (int64_t)blockIdx.x * kWG + threadIdx.x;
-  if (id >= (int64_t)npad * 32) return;
-  float up, down;
-  pair_scales(header[sb ? 1 : 0], up, down);
-  const int row = (int)(id >> 5), kq = (int)(id & 31) * 4;
-  int64_t src = row;
-  if (MAP) {
-    const int64_t *map = sb ? mapB : mapA;
-    if (map && row < (sb ? nmapB : nmapA)) src = map[row];
-  }
-  _Float16 h[4], l[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const float v = ((row < n && kq + c < K) ? F[src * ld + kq + c] : 0.f) * up;
-    h[c] = (_Float16)v;
-    l[c] = (_Float16)(v - (float)h[c]);
-  }
-  const int t = row >> 5, i = row & 31;
-  {  // R: [t][ks][p][kh*32 + i][j], k = 16 ks + 8 kh + j
-    const int ks = kq >> 4, kh = (kq >> 3) & 1, j = kq & 7;
-    _Float16 *r = reinterpret_cast<_Float16 *>(R) + (size_t)t * kPairTile + ((size_t)(ks * 2) * 64 + kh * 32 + i) * 8 + j;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      r[c] = h[c];
-      r[512 + c] = l[c];
-    }
-  }
-  {  // T: [t][f][s2][p][kh*32 + kfl][j], feature 32 f + kfl, streamed row 16 s2 + 8 (j >> 2) + 4 kh + (j & 3)  (pair_perm)
-    const int s2 = i >> 4, r16 = i & 15, kh = (r16 >> 2) & 1, j = 4 * (r16 >> 3) + (r16 & 3);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int kf = kq + c, f = kf >> 5, kfl = kf & 31;
-      _Float16 *q = reinterpret_cast<_Float16 *>(T) + (size_t)t * kPairTile + ((size_t)((f * 2 + s2) * 2) * 64 + kh * 32 + kfl) * 8 + j;
-      q[0] = h[c];
-      q[512] = l[c];
-    }
-  }
-}
-
-// the wave's share (chunks wave, wave + 4, ...) of NCH 1 KiB chunks from global memory into the LDS stage
-template <int NCH>
-__device__ __forceinline__ void pair_stage(const unsigned short *__restrict__ src, unsigned short *dst, int wave, int lane) {
-#pragma unroll
-  for (int q = 0; q < NCH / 4; ++q) {
-    const int c = wave + 4 * q;
-    __builtin_amdgcn_global_load_lds(reinterpret_cast<const u4 *>(src + (size_t)c * kPairChunk) + lane, dst + c * kPairChunk, 16, 0, 0);
-  }
-}
-
-// transposed score tile from the staged R tile: D[i][n] = sum_k Other[i][k] · Own[n][k]   (lane & 31 = n; element e <-> streamed
-// row i = (e & 3) + 8 (e >> 2) + 4 (lane >> 5)); two accumulators (even / odd k-steps) halve the dependent chain
-__device__ __forceinline__ f16v pair_tile(const u4 (&own)[8][2], const unsigned short *st, int lane) {
-  const u4 *s4 = reinterpret_cast<const u4 *>(st) + lane;
-  f16v a0, a1;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) a0[e] = a1[e] = 0.f;
-#pragma unroll
-  for (int ks = 0; ks < 8; ks += 2) {
-    const u4 h0 = s4[(ks * 2) * 64], l0 = s4[(ks * 2 + 1) * 64], h1 = s4[(ks * 2 + 2) * 64], l1 = s4[(ks * 2 + 3) * 64];
-    a0 = mfma_f16(l0, own[ks][0], a0);
-    a1 = mfma_f16(l1, own[ks + 1][0], a1);
-    a0 = mfma_f16(h0, own[ks][1], a0);
-    a1 = mfma_f16(h1, own[ks + 1][1], a1);
-    a0 = mfma_f16(h0, own[ks][0], a0);
-    a1 = mfma_f16(h1, own[ks + 1][0], a1);
-  }
-  return a0 + a1;
-}
-
-__device__ __forceinline__ void pair_load_own(u4 (&own)[8][2], const unsigned short *__restrict__ R, int tile, int lane) {
-  const u4 *g = reinterpret_cast<const u4 *>(R + (size_t)tile * kPairTile) + lane;
-#pragma unroll
-  for (int ks = 0; ks < 8; ++ks) {
-    own[ks][0] = g[(ks * 2) * 64];
-    own[ks][1] = g[(ks * 2 + 1) * 64];
-  }
-}
-
-// grid (ceil(tilesA / 4), splits); part[split][row][4] = (max, sum, target logit, -)
-__global__ __launch_bounds__(kWG, 2) void pair_lse_k(const unsigned short *__restrict__ RA, const unsigned short *__restrict__ RB,
-                                                     const int64_t *__restrict__ target, int NA, int NB, int npadA,
-                                                     const unsigned *__restrict__ header, float *__restrict__ part) {
-  __shared__ __attribute__((aligned(16))) unsigned short stage[2][kPairTile];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int n = lane & 31, kh = lane >> 5;
-  const int tilesA = (NA + 31) / 32, tilesB = (NB + 31) / 32;
-  const int mytile = blockIdx.x * 4 + wave;
-  const int n0 = mytile * 32;
-  u4 own[8][2];
-  pair_load_own(own, RA, mytile < tilesA ? mytile : tilesA - 1, lane);
-  float upA, downA, upB, downB;
-  pair_scales(header[0], upA, downA);
-  pair_scales(header[1], upB, downB);
-  const float sAB = downA * downB;
-  const int tgt = (n0 + n < NA) ? (int)target[n0 + n] : -1;
-  const int per = (tilesB + (int)gridDim.y - 1) / (int)gridDim.y;
-  const int t0 = blockIdx.y * per, t1 = min(tilesB, t0 + per);
-  float m = -INFINITY, l = 0.f, tl = 0.f;
-  pair_wait_vmcnt<0>();                              // (own fragments, target: out of the way of the counted stage loads)
-  if (t0 < t1) pair_stage<16>(RB + (size_t)t0 * kPairTile, stage[0], wave, lane);
-  for (int t = t0; t < t1; ++t) {
-    const int buf = (t - t0) & 1;
-    if (t + 1 < t1) {
-      pair_stage<16>(RB + (size_t)(t + 1) * kPairTile, stage[buf ^ 1], wave, lane);
-      pair_wait_vmcnt<4>();
-    } else {
-      pair_wait_vmcnt<0>();
-    }
-    __builtin_amdgcn_s_barrier();                    // every wave's share of tile t has landed
-    const f16v acc = pair_tile(own, stage[buf], lane);
-    float sv[16], tmax = -INFINITY;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int i = t * 32 + (e & 3) + 8 * (e >> 2) + 4 * kh;
-      const float s = acc[e] * sAB;
-      sv[e] = i < NB ? s : -INFINITY;
-      tl += i == tgt ? s : 0.f;
-      tmax = fmaxf(tmax, sv[e]);
-    }
-    if (tmax > -INFINITY) {
-      const float mn = fmaxf(m, tmax);
-      float add = 0.f;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) add += __expf(sv[e] - mn);          // (exp(-inf) = 0 for the columns past NB)
-      l = l * __expf(m - mn) + add;
-      m = mn;
-    }
-    __builtin_amdgcn_s_barrier();                    // all waves are done with stage[buf] before tile t + 2 lands in it
-  }
-  // the two half-waves hold different columns of the same row
-  const float m2 = __shfl_xor(m, 32), l2 = __shfl_xor(l, 32), t2 = __shfl_xor(tl, 32);
-  const float mn = fmaxf(m, m2);
-  l = (m > -INFINITY ? l * __expf(m - mn) : 0.f) + (m2 > -INFINITY ? l2 * __expf(m2 - mn) : 0.f);
-  tl += t2;
-  if (kh == 0 && n0 + n < NA) {
-    float *p = part + ((size_t)blockIdx.y * npadA + n0 + n) * 4;
-    *reinterpret_cast<f4 *>(p) = f4{mn, l, tl, 0.f};
-  }
-}
-
-__global__ __launch_bounds__(kWG) void pair_combine_k(const float *__restrict__ part, int splits, int npadA, int NA, float *__restrict__ lse,
-                                                      float *__restrict__ rowloss) {
-  const int r = blockIdx.x * kWG + threadIdx.x;
-  if (r >= NA) return;
-  float mm = -INFINITY;
-  for (int s = 0; s < splits; ++s) mm = fmaxf(mm, part[((size_t)s * npadA + r) * 4]);
-  float ll = 0.f, tt = 0.f;
-  for (int s = 0; s < splits; ++s) {
-    const f4 v = *reinterpret_cast<const f4 *>(part + ((size_t)s * npadA + r) * 4);
-    ll += v.x > -INFINITY ? v.y * __expf(v.x - mm) : 0.f;
-    tt += v.z;
-  }
-  const float ls = mm + __logf(ll);
-  lse[r] = ls;
-  rowloss[r] = ls - tt;
-}
-
-struct PairGradSide {
-  const unsigned short *Rown, *Roth, *Toth;
-  float *part;             // [splits][npad_own][128]
-  int Nown, Noth, npad_own, nblk, splits;
-};
-
-// grid: side A's nblk x splits workgroups, then side B's.  Own rows n of side A carry lse / target themselves; for side B
-// (own rows are COLUMNS of the score matrix) they belong to the streamed rows and come through the stage.
-__global__ __launch_bounds__(kWG, 2) void pair_grad_k(PairGradSide A, PairGradSide B, const int64_t *__restrict__ target,
-                                                      const float *__restrict__ lse, const unsigned *__restrict__ header, int NA) {
-  extern __shared__ __attribute__((aligned(16))) unsigned short gstage[];      // 2 x (R tile | T tile | 4 x 256 B lse / target)
-  constexpr int kStage = 2 * kPairTile + 4 * 128;                              // halfs
-  const bool ownA = blockIdx.x < (unsigned)(A.nblk * A.splits);
-  const PairGradSide &S = ownA ? A : B;
-  const int bid = ownA ? blockIdx.x : blockIdx.x - A.nblk * A.splits;
-  const int blk = bid % S.nblk, split = bid / S.nblk;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int n = lane & 31, kh = lane >> 5;
-  const int tiles_own = (S.Nown + 31) / 32, tiles_oth = (S.Noth + 31) / 32;
-  const int mytile = blk * 4 + wave;
-  const int n0 = mytile * 32;
-  const bool own_ok = n0 + n < S.Nown;
-  u4 own[8][2];
-  pair_load_own(own, S.Rown, mytile < tiles_own ? mytile : tiles_own - 1, lane);
-  float upA, downA, upB, downB;
-  pair_scales(header[0], upA, downA);
-  pair_scales(header[1], upB, downB);
-  const float sAB = downA * downB;
-  float my_lse = 0.f;
-  int my_tgt = -1;
-  if (ownA && own_ok) {
-    my_lse = lse[n0 + n];
-    my_tgt = (int)target[n0 + n];
-  }
-  const int per = (tiles_oth + S.splits - 1) / S.splits;
-  const int t0 = split * per, t1 = min(tiles_oth, t0 + per);
-  f16v g[4];                                   // dOwn[n][32 f + (e&3) + 8 (e>>2) + 4 kh], f = 0..3
-#pragma unroll
-  for (int f = 0; f < 4; ++f)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) g[f][e] = 0.f;
-  auto issue = [&](int t, int buf) {
-    unsigned short *st = gstage + buf * kStage;
-    pair_stage<16>(S.Roth + (size_t)t * kPairTile, st, wave, lane);
-    pair_stage<16>(S.Toth + (size_t)t * kPairTile, st + kPairTile, wave, lane);
-    // lanes 0..31: lse of the streamed rows, lanes 32..63: their targets (low words) — a private copy per wave
-    const int i = min(t * 32 + n, NA - 1);
-    const void *src = kh ? static_cast<const void *>(target + i) : static_cast<const void *>(lse + i);
-    __builtin_amdgcn_global_load_lds(static_cast<const unsigned *>(src), st + 2 * kPairTile + wave * 128, 4, 0, 0);
-  };
-  pair_wait_vmcnt<0>();
-  if (t0 < t1) issue(t0, 0);
-  for (int t = t0; t < t1; ++t) {
-    const int buf = (t - t0) & 1;
-    if (t + 1 < t1) {
-      issue(t + 1, buf ^ 1);
-      pair_wait_vmcnt<9>();
-    } else {
-      pair_wait_vmcnt<0>();
-    }
-    __builtin_amdgcn_s_barrier();
-    const unsigned short *st = gstage + buf * kStage;
-    const f16v acc = pair_tile(own, st, lane);
-    const float *aux = reinterpret_cast<const float *>(st + 2 * kPairTile + wave * 128);
-    // P (times 2^14) for my own row and the 16 streamed rows this lane holds, as two fp16 pieces: slot (s2, j) = element 8 s2 + j
-    u4 PH[2], PL[2];
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {
-      float pv[8];
-#pragma unroll
-      for (int jq = 0; jq < 2; ++jq) {
-        const int il = 16 * s2 + 8 * jq + 4 * kh;                       // streamed rows il .. il + 3 of the tile (elements 8 s2 + 4 jq + 0..3)
-        f4 ls4 = f4{my_lse, my_lse, my_lse, my_lse};
-        int tg[4] = {my_tgt, my_tgt, my_tgt, my_tgt};
-        if (!ownA) {
-          ls4 = *reinterpret_cast<const f4 *>(aux + il);
-          const int4 q4 = *reinterpret_cast<const int4 *>(aux + 32 + il);
-          tg[0] = q4.x; tg[1] = q4.y; tg[2] = q4.z; tg[3] = q4.w;
-        }
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const int e = 8 * s2 + 4 * jq + c;
-          const int i = t * 32 + il + c;                                // streamed (other) row
-          const bool hit = ownA ? (i == tg[c]) : (tg[c] == n0 + n);
-          const float p = __expf(acc[e] * sAB - ls4[c]) - (hit ? 1.f : 0.f);
-          pv[4 * jq + c] = (own_ok && i < S.Noth) ? p * 16384.f : 0.f;
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const h2v h = __builtin_convertvector(f2v{pv[2 * q], pv[2 * q + 1]}, h2v);
-        const h2v lo = __builtin_convertvector(f2v{pv[2 * q] - (float)h.x, pv[2 * q + 1] - (float)h.y}, h2v);
-        PH[s2][q] = __builtin_bit_cast(unsigned, h);
-        PL[s2][q] = __builtin_bit_cast(unsigned, lo);
-      }
-    }
-    // dOwn[n][kf] += sum_i P[n][i] Other[i][kf]: D2[kf][n], operand A = T tile (feature-major, pair_perm order), operand B = P
-    const u4 *t4 = reinterpret_cast<const u4 *>(st + kPairTile) + lane;
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {
-      u4 th[4], tl_[4];
-#pragma unroll
-      for (int f = 0; f < 4; ++f) {
-        th[f] = t4[((f * 2 + s2) * 2) * 64];
-        tl_[f] = t4[((f * 2 + s2) * 2 + 1) * 64];
-      }
-#pragma unroll
-      for (int f = 0; f < 4; ++f) g[f] = mfma_f16(tl_[f], PH[s2], g[f]);
-#pragma unroll
-      for (int f = 0; f < 4; ++f) g[f] = mfma_f16(th[f], PL[s2], g[f]);
-#pragma unroll
-      for (int f = 0; f < 4; ++f) g[f] = mfma_f16(th[f], PH[s2], g[f]);
-    }
-    __builtin_amdgcn_s_barrier();
-  }
-  if (mytile < tiles_own) {
-    float *p = S.part + ((size_t)split * S.npad_own + n0 + n) * kPairKP;
-#pragma unroll
-    for (int f = 0; f < 4; ++f)
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        *reinterpret_cast<f4 *>(p + 32 * f + 8 * q + 4 * kh) = f4{g[f][4 * q], g[f][4 * q + 1], g[f][4 * q + 2], g[f][4 * q + 3]};
-  }
-}
-
-// dOwn[r][k] = (gloss / NA) 2^-14 down_other · sum_splits part[s][r][k] for r < Nown, 0 for the padding rows; one thread per
-// (row, 4 features) of a side (blockIdx.y)
-__global__ __launch_bounds__(kWG) void pair_reduce_k(PairGradSide A, PairGradSide B, float *__restrict__ dFA, int64_t ldda, int rowsA,
-                                                     float *__restrict__ dFB, int64_t lddb, int rowsB, int K,
-                                                     const float *__restrict__ gloss, const unsigned *__restrict__ header, int NA) {
-  const bool sb = blockIdx.y != 0;
-  const PairGradSide &S = sb ? B : A;
-  float *d = sb ? dFB : dFA;
-  const int64_t ldd = sb ? lddb : ldda;
-  const int rows = sb ? rowsB : rowsA;
-  const int64_t id = (int64_t)blockIdx.x * kWG + threadIdx.x;
-  const int r = (int)(id >> 5), k = (int)(id & 31) * 4;
-  if (r >= rows || k >= K) return;
-  f4 v = f4{0.f, 0.f, 0.f, 0.f};
-  if (r < S.Nown) {
-    for (int s = 0; s < S.splits; ++s) v += *reinterpret_cast<const f4 *>(S.part + ((size_t)s * S.npad_own + r) * kPairKP + k);
-    float up, down;
-    pair_scales(header[sb ? 0 : 1], up, down);      // the OTHER side's features were scaled up
-    v *= gloss[0] / (float)NA * (1.f / 16384.f) * down;
-  }
-  float *o = d + (int64_t)r * ldd + k;
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-    if (k + c < K) o[c] = v[c];
-}
-
-
-// ------------------------------------------------------------------------------------------------
-// The other two dense-correspondence losses from the tower features (src/dense_correspondence/main.py:197-227): the
-// soft-target cross entropy `cel` (loss_fun_cross_entropy, main.py:216-227) and the smooth-L1 `sl1` (loss_fun_sl1 +
-// aggregate_batch_G, main.py:197-214).  Both compare the scores S = FA·FB^T with the geodesic sum
-// G[r][j] = GA[r][liA[lB[j]]] + GB[liB[lA[r]]][j] ELEMENT BY ELEMENT, so G has to be read in the 32 x 32 tiles of the score
-// kernels.  In the vertex numbering that is a gather of scattered columns; with label / label_inv mutually inverse it is
-// (HA + HB)[lA[r]][lB[j]], H = G_frame[label_inv][:, label_inv] built once per frame.  The kernels therefore run in LABEL
-// ORDER: row u of the tile grid is vertex mapA[u] = liA[u] of shape A, column v is vertex mapB[v] of shape B, both
-// matrices are read as contiguous row segments, and the only permutation left is on the feature rows (pair_split_k<true>
-// on the way in, pair_loss_reduce_k on the way out).  Every sum involved runs over all (r, j) or over all j of a row, so
-// the numbering changes the order of summation and nothing else.
-// The two base addresses come from a DEVICE table (two pointers): a captured step replays on another pair by rewriting
-// 16 bytes, not by copying 2 x 190 MB into static buffers.
-// Arithmetic, fragment layout, staging and the fixed-order range reduction are those of pair_lse_k / pair_grad_k above.
-//   cel: t[u][:] = softmin(G[u][:NB]);  rowloss[u] = lse_S[u] - sum_v t[u][v] S[u][v];  P = softmax(S) - t  in [-1, 1]
-//   sl1: D = S - FullG over the WHOLE rowsA x rowsB rectangle (FullG = G in the corner, 0 in the padding);
-//        rowloss[u] = sum_v l(D[u][v]) in fp64;  P = clamp(D, -1, 1)
-// ------------------------------------------------------------------------------------------------
-struct PairGeo {
-  const float *const *base;      // device table: {HA, HB}
-  int64_t ldA, ldB;
-  int NA, NB;                    // the corner that has geodesics
-};
-__device__ __forceinline__ bool pair_geo_vec(const float *ga, const float *gb, const PairGeo &G) {
-  return (((reinterpret_cast<uintptr_t>(ga) | reinterpret_cast<uintptr_t>(gb)) & 15) == 0) && (G.ldA % 4) == 0 && (G.ldB % 4) == 0;
-}
-// columns c .. c + 3 (c a multiple of 4) of a row; 0 past ncols
-__device__ __forceinline__ f4 pair_geo4(const float *__restrict__ row, int c, int ncols, bool vec) {
-  if (vec && c + 3 < ncols) return *reinterpret_cast<const f4 *>(row + c);
-  f4 v;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = c + e < ncols ? row[c + e] : 0.f;
-  return v;
-}
-// G for the 16 elements of a transposed tile whose OWN rows are rows of G (lane's row u fixed, streamed columns c0 + ...):
-// element e <-> column c0 + (e & 3) + 8 (e >> 2), c0 = 32 t + 4 kh
-__device__ __forceinline__ void pair_geo_own_row(float (&g)[16], const float *rowa, const float *rowb, bool row_ok, int c0, int ncols, bool vec) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    f4 a = f4{0.f, 0.f, 0.f, 0.f}, b = a;
-    if (row_ok && c0 + 8 * q < ncols) {
-      a = pair_geo4(rowa, c0 + 8 * q, ncols, vec);
-      b = pair_geo4(rowb, c0 + 8 * q, ncols, vec);
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) g[4 * q + c] = a[c] + b[c];
-  }
-}
-// ... whose own rows are COLUMNS of G (lane's column v fixed, streamed rows u0 + ...)
-__device__ __forceinline__ void pair_geo_own_col(float (&g)[16], const float *ga, const float *gb, const PairGeo &G, bool col_ok, int v, int u0) {
-#pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    const int u = u0 + (e & 3) + 8 * (e >> 2);
-    g[e] = (col_ok && u < G.NA) ? ga[(int64_t)u * G.ldA + v] + gb[(int64_t)u * G.ldB + v] : 0.f;
-  }
-}
-__device__ __forceinline__ float pair_sl1(float d) {
-  const float a = fabsf(d);
-  return a < 1.f ? 0.5f * d * d : a - 0.5f;
-}
-
-// grid (ceil(tiles_rows / 4), splits).  SL1 = false: part[split][row] = (max, sum, -, -), part2[split][row] = (min G,
-// sum exp(-(G - min)), sum exp(-(G - min)) S, -) over the NA x NB corner.  SL1 = true: part (as doubles)[split][row] = the
-// row's share of sum l(S - FullG) over rows x cols.
-template <bool SL1>
-__global__ __launch_bounds__(kWG, 2) void pair_loss_fwd_k(const unsigned short *__restrict__ RA, const unsigned short *__restrict__ RB, PairGeo G,
-                                                          int rows, int cols, int npadA, const unsigned *__restrict__ header,
-                                                          float *__restrict__ part, float *__restrict__ part2) {
-  __shared__ __attribute__((aligned(16))) unsigned short stage[2][kPairTile];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int n = lane & 31, kh = lane >> 5;
-  const int tilesA = (rows + 31) / 32, tilesB = (cols + 31) / 32;
-  const int mytile = blockIdx.x * 4 + wave;
-  const int n0 = mytile * 32;
-  const int u = n0 + n;
-  u4 own[8][2];
-  pair_load_own(own, RA, mytile < tilesA ? mytile : tilesA - 1, lane);
-  float upA, downA, upB, downB;
-  pair_scales(header[0], upA, downA);
-  pair_scales(header[1], upB, downB);
-  const float sAB = downA * downB;
-  const float *ga = G.base[0], *gb = G.base[1];
-  const bool vec = pair_geo_vec(ga, gb, G);
-  const bool row_geo = u < G.NA;
-  const float *rowa = ga + (int64_t)(row_geo ? u : 0) * G.ldA, *rowb = gb + (int64_t)(row_geo ? u : 0) * G.ldB;
-  const int per = (tilesB + (int)gridDim.y - 1) / (int)gridDim.y;
-  const int t0 = blockIdx.y * per, t1 = min(tilesB, t0 + per);
-  float m = -INFINITY, l = 0.f, gm = INFINITY, gl = 0.f, gts = 0.f;
-  double acc64 = 0.0;
-  pair_wait_vmcnt<0>();
-  if (t0 < t1) pair_stage<16>(RB + (size_t)t0 * kPairTile, stage[0], wave, lane);
-  for (int t = t0; t < t1; ++t) {
-    const int buf = (t - t0) & 1;
-    if (t + 1 < t1) {
-      pair_stage<16>(RB + (size_t)(t + 1) * kPairTile, stage[buf ^ 1], wave, lane);
-      pair_wait_vmcnt<4>();
-    } else {
-      pair_wait_vmcnt<0>();
-    }
-    __builtin_amdgcn_s_barrier();
-    float gv[16];                                    // (issued before the products: the loads land while the matrix pipe works)
-    pair_geo_own_row(gv, rowa, rowb, row_geo, t * 32 + 4 * kh, G.NB, vec);
-    const f16v acc = pair_tile(own, stage[buf], lane);
-    if (SL1) {
-      float ts = 0.f;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int i = t * 32 + (e & 3) + 8 * (e >> 2) + 4 * kh;
-        const float d = acc[e] * sAB - gv[e];        // (gv = 0 outside the corner: FullG)
-        ts += i < cols ? pair_sl1(d) : 0.f;
-      }
-      acc64 += (double)ts;
-    } else {
-      float sv[16], tmax = -INFINITY, tmin = INFINITY;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int i = t * 32 + (e & 3) + 8 * (e >> 2) + 4 * kh;
-        sv[e] = acc[e] * sAB;
-        if (i >= cols) gv[e] = INFINITY;
-        tmax = fmaxf(tmax, i < cols ? sv[e] : -INFINITY);
-        tmin = fminf(tmin, gv[e]);
-      }
-      if (tmax > -INFINITY) {                        // (the lane holds at least one column of the corner)
-        const float mn = fmaxf(m, tmax), gn = fminf(gm, tmin);
-        float add = 0.f, gadd = 0.f, gsadd = 0.f;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int i = t * 32 + (e & 3) + 8 * (e >> 2) + 4 * kh;
-          add += i < cols ? __expf(sv[e] - mn) : 0.f;
-          const float w = __expf(gn - gv[e]);        // (exp(-inf) = 0 for the columns past NB)
-          gadd += w;
-          gsadd += w * sv[e];
-        }
-        l = l * __expf(m - mn) + add;
-        m = mn;
-        const float sc = __expf(gn - gm);            // (first tile: exp(-inf) = 0 times 0)
-        gl = gl * sc + gadd;
-        gts = gts * sc + gsadd;
-        gm = gn;
-      }
-    }
-    __builtin_amdgcn_s_barrier();
-  }
-  if (SL1) {
-    acc64 += __shfl_xor(acc64, 32);
-    if (kh == 0 && u < rows) reinterpret_cast<double *>(part)[(size_t)blockIdx.y * npadA + u] = acc64;
-  } else {
-    const float m2 = __shfl_xor(m, 32), l2 = __shfl_xor(l, 32);
-    const float gm2 = __shfl_xor(gm, 32), gl2 = __shfl_xor(gl, 32), gts2 = __shfl_xor(gts, 32);
-    const float mn = fmaxf(m, m2), gn = fminf(gm, gm2);
-    l = (m > -INFINITY ? l * __expf(m - mn) : 0.f) + (m2 > -INFINITY ? l2 * __expf(m2 - mn) : 0.f);
-    const float c1 = gm < INFINITY ? __expf(gn - gm) : 0.f, c2 = gm2 < INFINITY ? __expf(gn - gm2) : 0.f;
-    if (kh == 0 && u < rows) {
-      const size_t o = ((size_t)blockIdx.y * npadA + u) * 4;
-      *reinterpret_cast<f4 *>(part + o) = f4{mn, l, 0.f, 0.f};
-      *reinterpret_cast<f4 *>(part2 + o) = f4{gn, gl * c1 + gl2 * c2, gts * c1 + gts2 * c2, 0.f};
-    }
-  }
-}
-
-// stats[r] = lse_S[r], stats[NA + r] = min_G[r] - log sum_j exp(-(G[r][j] - min_G[r]))  (softmin(G[r])[j] = exp(stats[NA + r] - G[r][j]))
-__global__ __launch_bounds__(kWG) void pair_soft_combine_k(const float *__restrict__ part, const float *__restrict__ part2, int splits, int npadA,
-                                                           int NA, float *__restrict__ stats, float *__restrict__ rowloss) {
-  const int r = blockIdx.x * kWG + threadIdx.x;
-  if (r >= NA) return;
-  float mm = -INFINITY, gmm = INFINITY;
-  for (int s = 0; s < splits; ++s) {
-    mm = fmaxf(mm, part[((size_t)s * npadA + r) * 4]);
-    gmm = fminf(gmm, part2[((size_t)s * npadA + r) * 4]);
-  }
-  float ll = 0.f, gl = 0.f, gts = 0.f;
-  for (int s = 0; s < splits; ++s) {
-    const f4 v = *reinterpret_cast<const f4 *>(part + ((size_t)s * npadA + r) * 4);
-    const f4 w = *reinterpret_cast<const f4 *>(part2 + ((size_t)s * npadA + r) * 4);
-    ll += v.x > -INFINITY ? v.y * expf(v.x - mm) : 0.f;
-    const float c = w.x < INFINITY ? expf(gmm - w.x) : 0.f;
-    gl += w.y * c;
-    gts += w.z * c;
-  }
-  const float ls = mm + logf(ll);
-  stats[r] = ls;
-  stats[NA + r] = gmm - logf(gl);
-  rowloss[r] = ls - gts / gl;
-}
-__global__ __launch_bounds__(kWG) void pair_sl1_combine_k(const double *__restrict__ part, int splits, int npadA, int rows, double *__restrict__ rowloss) {
-  const int r = blockIdx.x * kWG + threadIdx.x;
-  if (r >= rows) return;
-  double v = 0.0;
-  for (int s = 0; s < splits; ++s) v += part[(size_t)s * npadA + r];
-  rowloss[r] = v;
-}
-
-// pair_grad_k with the factor of the loss at hand: SL1 = false: P = exp(S - lse[u]) - exp(dmin[u] - G) inside the corner
-// (stats = lse | dmin); SL1 = true: P = clamp(S - FullG, -1, 1) over the whole rectangle (A.Nown x A.Noth).
-template <bool SL1>
-__global__ __launch_bounds__(kWG, 2) void pair_loss_grad_k(PairGradSide A, PairGradSide B, PairGeo G, const float *__restrict__ stats,
-                                                           const unsigned *__restrict__ header) {
-  extern __shared__ __attribute__((aligned(16))) unsigned short gstage[];      // 2 x (R tile | T tile | 4 x 256 B lse / dmin)
-  constexpr int kStage = 2 * kPairTile + 4 * 128;                              // halfs
-  const bool ownA = blockIdx.x < (unsigned)(A.nblk * A.splits);
-  const PairGradSide &S = ownA ? A : B;
-  const int bid = ownA ? blockIdx.x : blockIdx.x - A.nblk * A.splits;
-  const int blk = bid % S.nblk, split = bid / S.nblk;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int n = lane & 31, kh = lane >> 5;
-  const int tiles_own = (S.Nown + 31) / 32, tiles_oth = (S.Noth + 31) / 32;
-  const int mytile = blk * 4 + wave;
-  const int n0 = mytile * 32;
-  const bool own_ok = n0 + n < S.Nown;
-  u4 own[8][2];
-  pair_load_own(own, S.Rown, mytile < tiles_own ? mytile : tiles_own - 1, lane);
-  float upA, downA, upB, downB;
-  pair_scales(header[0], upA, downA);
-  pair_scales(header[1], upB, downB);
-  const float sAB = downA * downB;
-  const float *ga = G.base[0], *gb = G.base[1];
-  const bool vec = pair_geo_vec(ga, gb, G);
-  const bool own_geo = n0 + n < (ownA ? G.NA : G.NB);       // my own row / column lies inside the corner
-  const float *rowa = ga + (int64_t)((ownA && own_geo) ? n0 + n : 0) * G.ldA, *rowb = gb + (int64_t)((ownA && own_geo) ? n0 + n : 0) * G.ldB;
-  float my_lse = 0.f, my_d = 0.f;
-  if (!SL1 && ownA && own_ok) {
-    my_lse = stats[n0 + n];
-    my_d = stats[G.NA + n0 + n];
-  }
-  const int per = (tiles_oth + S.splits - 1) / S.splits;
-  const int t0 = split * per, t1 = min(tiles_oth, t0 + per);
-  f16v g[4];                                   // dOwn[n][32 f + (e&3) + 8 (e>>2) + 4 kh], f = 0..3
-#pragma unroll
-  for (int f = 0; f < 4; ++f)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) g[f][e] = 0.f;
-  auto issue = [&](int t, int buf) {
-    unsigned short *st = gstage + buf * kStage;
-    pair_stage<16>(S.Roth + (size_t)t * kPairTile, st, wave, lane);
-    pair_stage<16>(S.Toth + (size_t)t * kPairTile, st + kPairTile, wave, lane);
-    if (!SL1) {
-      // lanes 0..31: lse of the streamed rows, lanes 32..63: their dmin — a private copy per wave
-      const int i = min(t * 32 + n, G.NA - 1);
-      __builtin_amdgcn_global_load_lds(reinterpret_cast<const unsigned *>(stats + (kh ? G.NA : 0) + i), st + 2 * kPairTile + wave * 128, 4, 0, 0);
-    }
-  };
-  pair_wait_vmcnt<0>();
-  if (t0 < t1) issue(t0, 0);
-  for (int t = t0; t < t1; ++t) {
-    const int buf = (t - t0) & 1;
-    if (t + 1 < t1) {
-      issue(t + 1, buf ^ 1);
-      pair_wait_vmcnt<SL1 ? 8 : 9>();
-    } else {
-      pair_wait_vmcnt<0>();
-    }
-    __builtin_amdgcn_s_barrier();
-    const unsigned short *st = gstage + buf * kStage;
-    float gv[16];                                    // element 8 s2 + 4 jq + c <-> streamed row 16 s2 + 8 jq + 4 kh + c of the tile
-    if (ownA) pair_geo_own_row(gv, rowa, rowb, own_geo, t * 32 + 4 * kh, G.NB, vec);
-    else pair_geo_own_col(gv, ga, gb, G, own_geo, n0 + n, t * 32 + 4 * kh);
-    const f16v acc = pair_tile(own, st, lane);
-    const float *aux = reinterpret_cast<const float *>(st + 2 * kPairTile + wave * 128);
-    u4 PH[2], PL[2];
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {
-      float pv[8];
-#pragma unroll
-      for (int jq = 0; jq < 2; ++jq) {
-        const int il = 16 * s2 + 8 * jq + 4 * kh;
-        f4 ls4 = f4{my_lse, my_lse, my_lse, my_lse}, d4 = f4{my_d, my_d, my_d, my_d};
-        if (!SL1 && !ownA) {
-          ls4 = *reinterpret_cast<const f4 *>(aux + il);
-          d4 = *reinterpret_cast<const f4 *>(aux + 32 + il);
-        }
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const int e = 8 * s2 + 4 * jq + c;
-          const int i = t * 32 + il + c;                                // streamed (other) row
-          const float s = acc[e] * sAB;
-          float p;
-          if (SL1) p = fminf(fmaxf(s - gv[e], -1.f), 1.f);
-          else p = __expf(s - ls4[c]) - __expf(d4[c] - gv[e]);
-          pv[4 * jq + c] = (own_ok && i < S.Noth) ? p * 16384.f : 0.f;
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const h2v h = __builtin_convertvector(f2v{pv[2 * q], pv[2 * q + 1]}, h2v);
-        const h2v lo = __builtin_convertvector(f2v{pv[2 * q] - (float)h.x, pv[2 * q + 1] - (float)h.y}, h2v);
-        PH[s2][q] = __builtin_bit_cast(unsigned, h);
-        PL[s2][q] = __builtin_bit_cast(unsigned, lo);
-      }
-    }
-    const u4 *t4 = reinterpret_cast<const u4 *>(st + kPairTile) + lane;
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {
-      u4 th[4], tl_[4];
-#pragma unroll
-      for (int f = 0; f < 4; ++f) {
-        th[f] = t4[((f * 2 + s2) * 2) * 64];
-        tl_[f] = t4[((f * 2 + s2) * 2 + 1) * 64];
-      }
-#pragma unroll
-      for (int f = 0; f < 4; ++f) g[f] = mfma_f16(tl_[f], PH[s2], g[f]);
-#pragma unroll
-      for (int f = 0; f < 4; ++f) g[f] = mfma_f16(th[f], PL[s2], g[f]);
-#pragma unroll
-      for (int f = 0; f < 4; ++f) g[f] = mfma_f16(th[f], PH[s2], g[f]);
-    }
-    __builtin_amdgcn_s_barrier();
-  }
-  if (mytile < tiles_own) {
-    float *p = S.part + ((size_t)split * S.npad_own + n0 + n) * kPairKP;
-#pragma unroll
-    for (int f = 0; f < 4; ++f)
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        *reinterpret_cast<f4 *>(p + 32 * f + 8 * q + 4 * kh) = f4{g[f][4 * q], g[f][4 * q + 1], g[f][4 * q + 2], g[f][4 * q + 3]};
-  }
-}
-
-// dOwn[map[r]][k] = gloss · mul · 2^-14 down_other · sum_splits part[s][r][k] for r < Nown (label order; map = identity past
-// nmap), 0 for the rows past Nown; one thread per (row, 4 features) of a side (blockIdx.y)
-__global__ __launch_bounds__(kWG) void pair_loss_reduce_k(PairGradSide A, PairGradSide B, float *__restrict__ dFA, int64_t ldda, int rowsA,
-                                                          float *__restrict__ dFB, int64_t lddb, int rowsB, int K,
-                                                          const float *__restrict__ gloss, const unsigned *__restrict__ header, float mul,
-                                                          const int64_t *__restrict__ mapA, int nmapA, const int64_t *__restrict__ mapB, int nmapB) {
-  const bool sb = blockIdx.y != 0;
-  const PairGradSide &S = sb ? B : A;
-  float *d = sb ? dFB : dFA;
-  const int64_t ldd = sb ? lddb : ldda;
-  const int rows = sb ? rowsB : rowsA;
-  const int64_t *map = sb ? mapB : mapA;
-  const int nmap = sb ? nmapB : nmapA;
-  const int64_t id = (int64_t)blockIdx.x * kWG + threadIdx.x;
-  const int r = (int)(id >> 5), k = (int)(id & 31) * 4;
-  if (r >= rows || k >= K) return;
-  f4 v = f4{0.f, 0.f, 0.f, 0.f};
-  if (r < S.Nown) {
-    for (int s = 0; s < S.splits; ++s) v += *reinterpret_cast<const f4 *>(S.part + ((size_t)s * S.npad_own + r) * kPairKP + k);
-    float up, down;
-    pair_scales(header[sb ? 0 : 1], up, down);      // the OTHER side's features were scaled up
-    v *= gloss[0] * mul * (1.f / 16384.f) * down;
-  }
-  const int64_t dst = (map && r < nmap) ? map[r] : r;
-  float *o = d + dst * ldd + k;
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-    if (k + c < K) o[c] = v[c];
-}
-
-
 // ------------------------------------------------------------------------------------------------
 // wgrad_h_k — the uniform-wave weight gradient on TWO fp16 pieces (three partial products instead of six).
 //
@@ -3564,231 +2810,6 @@ int sn_gather_segments_ragged_f32(const float *src, const int64_t *base, const i
   else
     hipLaunchKernelGGL((gather_segments_ragged_k<1>), dim3((unsigned)blocks), dim3(kWG), 0, static_cast<hipStream_t>(stream), src,
                        base, item_off, (int)nitems, row_stride, (int)len, total, out);
-  return launch_status();
-}
-
-namespace {
-struct PairWs {
-  int pa, pb;
-  unsigned *header;
-  unsigned short *RA, *TA, *RB, *TB;
-  float *lse_part, *gradA, *gradB;
-  size_t bytes;
-};
-PairWs pair_ws(void *workspace, int64_t rowsA, int64_t rowsB) {
-  PairWs w;
-  w.pa = (int)((rowsA + 31) / 32 * 32);
-  w.pb = (int)((rowsB + 31) / 32 * 32);
-  char *p = static_cast<char *>(workspace);
-  w.header = reinterpret_cast<unsigned *>(p);
-  p += kPairHeader;
-  const size_t fa = (size_t)w.pa * kPairKP * 2 * sizeof(unsigned short), fb = (size_t)w.pb * kPairKP * 2 * sizeof(unsigned short);
-  w.RA = reinterpret_cast<unsigned short *>(p); p += fa;
-  w.TA = reinterpret_cast<unsigned short *>(p); p += fa;
-  w.RB = reinterpret_cast<unsigned short *>(p); p += fb;
-  w.TB = reinterpret_cast<unsigned short *>(p); p += fb;
-  w.lse_part = reinterpret_cast<float *>(p); p += (size_t)kPairMaxLseSplits * w.pa * 4 * sizeof(float);
-  w.gradA = reinterpret_cast<float *>(p); p += (size_t)kPairMaxGradSplits * w.pa * kPairKP * sizeof(float);
-  w.gradB = reinterpret_cast<float *>(p); p += (size_t)kPairMaxGradSplits * w.pb * kPairKP * sizeof(float);
-  w.bytes = (size_t)(p - static_cast<char *>(workspace));
-  return w;
-}
-}  // namespace
-
-size_t sn_pair_fused_workspace_bytes(int64_t rowsA, int64_t rowsB) {
-  if (rowsA < 0 || rowsB < 0 || rowsA > INT_MAX - 64 || rowsB > INT_MAX - 64) return 0;
-  return pair_ws(nullptr, rowsA, rowsB).bytes;
-}
-
-int sn_pair_fused_fwd_f32(const float *FA, int64_t lda, const float *FB, int64_t ldb, const int64_t *target, int64_t NA, int64_t NB,
-                          int64_t rowsA, int64_t rowsB, int32_t K, float *lse, float *rowloss, void *workspace,
-                          size_t workspace_bytes, void *stream) {
-  (void)hipGetLastError();      // a stale error left by an earlier runtime call of this thread is not ours to report
-  if (NA < 1 || NB < 1 || rowsA < NA || rowsB < NB || K < 1 || lda < K || ldb < K) return SN_E_SHAPE;
-  if (K > kPairKP) return SN_E_UNSUPPORTED;
-  if (rowsA > INT_MAX - 64 || rowsB > INT_MAX - 64) return SN_E_RANGE;
-  if (!FA || !FB || !target || !workspace || !lse || !rowloss) return SN_E_NULL;
-  if (!aligned16(workspace)) return SN_E_ALIGN;
-  if (workspace_bytes < sn_pair_fused_workspace_bytes(rowsA, rowsB)) return SN_E_WORKSPACE;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const PairWs w = pair_ws(workspace, rowsA, rowsB);
-  hipError_t e = sn_internal_fill(w.header, 0, kPairHeader, s);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(pair_maxabs_k, dim3((unsigned)std::min<int64_t>(1024, (std::max(rowsA, rowsB) * K + 4 * kWG - 1) / (4 * kWG)), 2), dim3(kWG), 0, s, FA, lda, (int)rowsA, FB, ldb, (int)rowsB, (int)K, w.header);
-  const int64_t quads = (int64_t)std::max(w.pa, w.pb) * 32;
-  hipLaunchKernelGGL((pair_split_k<false>), dim3((unsigned)((quads + kWG - 1) / kWG), 2), dim3(kWG), 0, s, FA, lda, (int)rowsA, w.pa, w.RA, w.TA, FB, ldb,
-                     (int)rowsB, w.pb, w.RB, w.TB, (int)K, w.header, (const int64_t *)nullptr, 0, (const int64_t *)nullptr, 0);
-  const int tilesA = (int)((NA + 31) / 32), tilesB = (int)((NB + 31) / 32);
-  const int nblk = (tilesA + 3) / 4;
-  const int splits = std::max(1, std::min({kPairMaxLseSplits, 512 / nblk, tilesB}));
-  hipLaunchKernelGGL(pair_lse_k, dim3((unsigned)nblk, (unsigned)splits), dim3(kWG), 0, s, w.RA, w.RB, target, (int)NA, (int)NB, w.pa, w.header,
-                     w.lse_part);
-  hipLaunchKernelGGL(pair_combine_k, dim3((unsigned)((NA + kWG - 1) / kWG)), dim3(kWG), 0, s, w.lse_part, splits, w.pa, (int)NA, lse, rowloss);
-  return launch_status();
-}
-
-int sn_pair_fused_bwd_f32(const int64_t *target, const float *lse, const float *gloss, int64_t NA, int64_t NB, int64_t rowsA,
-                          int64_t rowsB, int32_t K, float *dFA, int64_t ldda, float *dFB, int64_t lddb, void *workspace,
-                          size_t workspace_bytes, void *stream) {
-  (void)hipGetLastError();      // a stale error left by an earlier runtime call of this thread is not ours to report
-  if (NA < 1 || NB < 1 || rowsA < NA || rowsB < NB || K < 1 || K > kPairKP || ldda < K || lddb < K) return SN_E_SHAPE;
-  if (rowsA > INT_MAX - 64 || rowsB > INT_MAX - 64) return SN_E_RANGE;
-  if (!target || !lse || !gloss || !dFA || !dFB || !workspace) return SN_E_NULL;
-  if (workspace_bytes < sn_pair_fused_workspace_bytes(rowsA, rowsB)) return SN_E_WORKSPACE;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const PairWs w = pair_ws(workspace, rowsA, rowsB);
-  const int tilesA = (int)((NA + 31) / 32), tilesB = (int)((NB + 31) / 32);
-  PairGradSide A{w.RA, w.RB, w.TB, w.gradA, (int)NA, (int)NB, w.pa, (tilesA + 3) / 4, 1};
-  PairGradSide B{w.RB, w.RA, w.TA, w.gradB, (int)NB, (int)NA, w.pb, (tilesB + 3) / 4, 1};
-  const int want = std::max(1, 512 / (A.nblk + B.nblk));
-  A.splits = std::max(1, std::min({kPairMaxGradSplits, want, tilesB}));
-  B.splits = std::max(1, std::min({kPairMaxGradSplits, want, tilesA}));
-  constexpr size_t lds = (size_t)2 * (2 * kPairTile + 4 * 128) * sizeof(unsigned short);
-  static const hipError_t attr =
-      hipFuncSetAttribute(reinterpret_cast<const void *>(pair_grad_k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (attr != hipSuccess) return (int)attr;
-  hipLaunchKernelGGL(pair_grad_k, dim3((unsigned)(A.nblk * A.splits + B.nblk * B.splits)), dim3(kWG), lds, s, A, B, target, lse, w.header,
-                     (int)NA);
-  const int64_t quads = (int64_t)std::max(rowsA, rowsB) * 32;
-  hipLaunchKernelGGL(pair_reduce_k, dim3((unsigned)((quads + kWG - 1) / kWG), 2), dim3(kWG), 0, s, A, B, dFA, ldda, (int)rowsA, dFB, lddb,
-                     (int)rowsB, (int)K, gloss, w.header, (int)NA);
-  return launch_status();
-}
-
-extern "C++" {
-namespace {
-struct PairLossWs {
-  PairWs w;
-  float *part2;
-  size_t bytes;
-};
-PairLossWs pair_loss_ws(void *workspace, int64_t rowsA, int64_t rowsB) {
-  PairLossWs q;
-  q.w = pair_ws(workspace, rowsA, rowsB);
-  q.part2 = reinterpret_cast<float *>(static_cast<char *>(workspace) + q.w.bytes);
-  q.bytes = q.w.bytes + (size_t)kPairMaxLseSplits * q.w.pa * 4 * sizeof(float);
-  return q;
-}
-int pair_loss_check(int64_t NA, int64_t NB, int64_t rowsA, int64_t rowsB, int32_t K, int64_t ldgA, int64_t ldgB) {
-  if (NA < 1 || NB < 1 || rowsA < NA || rowsB < NB || K < 1 || ldgA < NB || ldgB < NB) return SN_E_SHAPE;
-  if (K > kPairKP) return SN_E_UNSUPPORTED;
-  if (rowsA > INT_MAX - 64 || rowsB > INT_MAX - 64) return SN_E_RANGE;
-  return SN_OK;
-}
-// features -> fragment order in the workspace (rows taken through the maps), shared by both forward entries
-int pair_loss_split(const float *FA, int64_t lda, const float *FB, int64_t ldb, const int64_t *mapA, const int64_t *mapB, int64_t NA,
-                    int64_t NB, int64_t rowsA, int64_t rowsB, int32_t K, const PairWs &w, hipStream_t s) {
-  hipError_t e = sn_internal_fill(w.header, 0, kPairHeader, s);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(pair_maxabs_k, dim3((unsigned)std::min<int64_t>(1024, (std::max(rowsA, rowsB) * K + 4 * kWG - 1) / (4 * kWG)), 2), dim3(kWG), 0, s, FA, lda, (int)rowsA, FB, ldb, (int)rowsB, (int)K, w.header);
-  const int64_t quads = (int64_t)std::max(w.pa, w.pb) * 32;
-  hipLaunchKernelGGL((pair_split_k<true>), dim3((unsigned)((quads + kWG - 1) / kWG), 2), dim3(kWG), 0, s, FA, lda, (int)rowsA, w.pa, w.RA, w.TA, FB, ldb,
-                     (int)rowsB, w.pb, w.RB, w.TB, (int)K, w.header, mapA, (int)NA, mapB, (int)NB);
-  return SN_OK;
-}
-template <bool SL1>
-int pair_loss_fwd(PairGeo G, int64_t rows, int64_t cols, const PairLossWs &q, hipStream_t s, int &splits) {
-  const int tilesA = (int)((rows + 31) / 32), tilesB = (int)((cols + 31) / 32);
-  const int nblk = (tilesA + 3) / 4;
-  splits = std::max(1, std::min({kPairMaxLseSplits, 512 / nblk, tilesB}));
-  hipLaunchKernelGGL((pair_loss_fwd_k<SL1>), dim3((unsigned)nblk, (unsigned)splits), dim3(kWG), 0, s, q.w.RA, q.w.RB, G, (int)rows, (int)cols, q.w.pa,
-                     q.w.header, q.w.lse_part, q.part2);
-  return SN_OK;
-}
-template <bool SL1>
-int pair_loss_bwd(PairGeo G, const int64_t *mapA, const int64_t *mapB, const float *stats, const float *gloss, int64_t Nrows, int64_t Ncols,
-                  int64_t rowsA, int64_t rowsB, int32_t K, float mul, float *dFA, int64_t ldda, float *dFB, int64_t lddb, const PairWs &w,
-                  hipStream_t s) {
-  const int tilesA = (int)((Nrows + 31) / 32), tilesB = (int)((Ncols + 31) / 32);
-  PairGradSide A{w.RA, w.RB, w.TB, w.gradA, (int)Nrows, (int)Ncols, w.pa, (tilesA + 3) / 4, 1};
-  PairGradSide B{w.RB, w.RA, w.TA, w.gradB, (int)Ncols, (int)Nrows, w.pb, (tilesB + 3) / 4, 1};
-  const int want = std::max(1, 512 / (A.nblk + B.nblk));
-  A.splits = std::max(1, std::min({kPairMaxGradSplits, want, tilesB}));
-  B.splits = std::max(1, std::min({kPairMaxGradSplits, want, tilesA}));
-  constexpr size_t lds = (size_t)2 * (2 * kPairTile + 4 * 128) * sizeof(unsigned short);
-  static const hipError_t attr =
-      hipFuncSetAttribute(reinterpret_cast<const void *>(pair_loss_grad_k<SL1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (attr != hipSuccess) return (int)attr;
-  hipLaunchKernelGGL((pair_loss_grad_k<SL1>), dim3((unsigned)(A.nblk * A.splits + B.nblk * B.splits)), dim3(kWG), lds, s, A, B, G, stats, w.header);
-  const int64_t quads = (int64_t)std::max(rowsA, rowsB) * 32;
-  hipLaunchKernelGGL(pair_loss_reduce_k, dim3((unsigned)((quads + kWG - 1) / kWG), 2), dim3(kWG), 0, s, A, B, dFA, ldda, (int)rowsA, dFB, lddb,
-                     (int)rowsB, (int)K, gloss, w.header, mul, mapA, (int)G.NA, mapB, (int)G.NB);
-  return SN_OK;
-}
-}  // namespace
-}  // extern "C++"
-
-size_t sn_pair_loss_workspace_bytes(int64_t rowsA, int64_t rowsB) {
-  if (rowsA < 0 || rowsB < 0 || rowsA > INT_MAX - 64 || rowsB > INT_MAX - 64) return 0;
-  return pair_loss_ws(nullptr, rowsA, rowsB).bytes;
-}
-
-int sn_pair_soft_fwd_f32(const float *FA, int64_t lda, const float *FB, int64_t ldb, const int64_t *mapA, const int64_t *mapB,
-                         const float *const *geo, int64_t ldgA, int64_t ldgB, int64_t NA, int64_t NB, int64_t rowsA, int64_t rowsB,
-                         int32_t K, float *stats, float *rowloss, void *workspace, size_t workspace_bytes, void *stream) {
-  (void)hipGetLastError();      // a stale error left by an earlier runtime call of this thread is not ours to report
-  if (int st = pair_loss_check(NA, NB, rowsA, rowsB, K, ldgA, ldgB)) return st;
-  if (lda < K || ldb < K) return SN_E_SHAPE;
-  if (!FA || !FB || !geo || !workspace || !stats || !rowloss) return SN_E_NULL;
-  if (!aligned16(workspace)) return SN_E_ALIGN;
-  if (workspace_bytes < sn_pair_loss_workspace_bytes(rowsA, rowsB)) return SN_E_WORKSPACE;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const PairLossWs q = pair_loss_ws(workspace, rowsA, rowsB);
-  if (int st = pair_loss_split(FA, lda, FB, ldb, mapA, mapB, NA, NB, rowsA, rowsB, K, q.w, s)) return st;
-  int splits = 1;
-  pair_loss_fwd<false>(PairGeo{geo, ldgA, ldgB, (int)NA, (int)NB}, NA, NB, q, s, splits);
-  hipLaunchKernelGGL(pair_soft_combine_k, dim3((unsigned)((NA + kWG - 1) / kWG)), dim3(kWG), 0, s, q.w.lse_part, q.part2, splits, q.w.pa, (int)NA,
-                     stats, rowloss);
-  return launch_status();
-}
-
-int sn_pair_soft_bwd_f32(const int64_t *mapA, const int64_t *mapB, const float *const *geo, int64_t ldgA, int64_t ldgB, const float *stats,
-                         const float *gloss, int64_t NA, int64_t NB, int64_t rowsA, int64_t rowsB, int32_t K, float *dFA, int64_t ldda,
-                         float *dFB, int64_t lddb, void *workspace, size_t workspace_bytes, void *stream) {
-  (void)hipGetLastError();      // a stale error left by an earlier runtime call of this thread is not ours to report
-  if (int st = pair_loss_check(NA, NB, rowsA, rowsB, K, ldgA, ldgB)) return st;
-  if (ldda < K || lddb < K) return SN_E_SHAPE;
-  if (!geo || !stats || !gloss || !dFA || !dFB || !workspace) return SN_E_NULL;
-  if (workspace_bytes < sn_pair_loss_workspace_bytes(rowsA, rowsB)) return SN_E_WORKSPACE;
-  const PairLossWs q = pair_loss_ws(workspace, rowsA, rowsB);
-  if (int st = pair_loss_bwd<false>(PairGeo{geo, ldgA, ldgB, (int)NA, (int)NB}, mapA, mapB, stats, gloss, NA, NB, rowsA, rowsB, K, 1.f, dFA, ldda,
-                                    dFB, lddb, q.w, static_cast<hipStream_t>(stream)))
-    return st;
-  return launch_status();
-}
-
-int sn_pair_sl1_fwd_f32(const float *FA, int64_t lda, const float *FB, int64_t ldb, const int64_t *mapA, const int64_t *mapB,
-                        const float *const *geo, int64_t ldgA, int64_t ldgB, int64_t NA, int64_t NB, int64_t rowsA, int64_t rowsB,
-                        int32_t K, double *rowloss, void *workspace, size_t workspace_bytes, void *stream) {
-  (void)hipGetLastError();      // a stale error left by an earlier runtime call of this thread is not ours to report
-  if (int st = pair_loss_check(NA, NB, rowsA, rowsB, K, ldgA, ldgB)) return st;
-  if (lda < K || ldb < K) return SN_E_SHAPE;
-  if (!FA || !FB || !geo || !workspace || !rowloss) return SN_E_NULL;
-  if (!aligned16(workspace)) return SN_E_ALIGN;
-  if (workspace_bytes < sn_pair_loss_workspace_bytes(rowsA, rowsB)) return SN_E_WORKSPACE;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const PairLossWs q = pair_loss_ws(workspace, rowsA, rowsB);
-  if (int st = pair_loss_split(FA, lda, FB, ldb, mapA, mapB, NA, NB, rowsA, rowsB, K, q.w, s)) return st;
-  int splits = 1;
-  pair_loss_fwd<true>(PairGeo{geo, ldgA, ldgB, (int)NA, (int)NB}, rowsA, rowsB, q, s, splits);
-  hipLaunchKernelGGL(pair_sl1_combine_k, dim3((unsigned)((rowsA + kWG - 1) / kWG)), dim3(kWG), 0, s, reinterpret_cast<const double *>(q.w.lse_part),
-                     splits, q.w.pa, (int)rowsA, rowloss);
-  return launch_status();
-}
-
-int sn_pair_sl1_bwd_f32(const int64_t *mapA, const int64_t *mapB, const float *const *geo, int64_t ldgA, int64_t ldgB, const float *gloss,
-                        int64_t NA, int64_t NB, int64_t rowsA, int64_t rowsB, int32_t K, float *dFA, int64_t ldda, float *dFB, int64_t lddb,
-                        void *workspace, size_t workspace_bytes, void *stream) {
-  (void)hipGetLastError();      // a stale error left by an earlier runtime call of this thread is not ours to report
-  if (int st = pair_loss_check(NA, NB, rowsA, rowsB, K, ldgA, ldgB)) return st;
-  if (ldda < K || lddb < K) return SN_E_SHAPE;
-  if (!geo || !gloss || !dFA || !dFB || !workspace) return SN_E_NULL;
-  if (workspace_bytes < sn_pair_loss_workspace_bytes(rowsA, rowsB)) return SN_E_WORKSPACE;
-  const PairLossWs q = pair_loss_ws(workspace, rowsA, rowsB);
-  const float mul = (float)(1.0 / ((double)rowsA * (double)rowsB));
-  if (int st = pair_loss_bwd<true>(PairGeo{geo, ldgA, ldgB, (int)NA, (int)NB}, mapA, mapB, nullptr, gloss, rowsA, rowsB, rowsA, rowsB, K, mul, dFA,
-                                   ldda, dFB, lddb, q.w, static_cast<hipStream_t>(stream)))
-    return st;
   return launch_status();
 }
 

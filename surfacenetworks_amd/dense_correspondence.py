@@ -506,7 +506,7 @@ def labels_are_inverse(label, label_inv) -> bool:
 def label_order_matrix(G, label_inv):
     """H = G[label_inv][:, label_inv]: the frame's geodesic matrix with rows and columns in LABEL order.  For two frames with
     mutually inverse labels, GA[:, liA[lB]] + GB[liB[lA], :] == (HA + HB)[lA][:, lB]: in label order both terms are read as
-    they lie in memory, and a pair needs no gathered copy (the kernels' comment in csrc/sn_dense.hip)."""
+    they lie in memory, and a pair needs no gathered copy (the kernels' comment in csrc/sn_pair.hip)."""
     return G[label_inv][:, label_inv].contiguous()
 
 

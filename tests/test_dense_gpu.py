@@ -827,7 +827,7 @@ def test_pair_cross_entropy_matches_torch(N, NA, NB):
 @pytest.mark.parametrize("rows,NA,NB,K", [(7, 7, 7, 120), (80, 63, 70, 120), (33, 33, 1, 5), (300, 257, 290, 128), (1024, 1000, 1021, 64),
                                           (7000, 6890, 6890, 120)])
 def test_fused_pair_cross_entropy_matches_the_score_matrix_path(rows, NA, NB, K):
-    """sn_pair_fused_fwd/bwd_f32 (scores formed on the matrix pipe from three-piece bf16 splits, never written) against the
+    """sn_pair_fused_fwd/bwd_f32 (scores formed on the matrix pipe from two-piece fp16 splits, never written) against the
     cross entropy of the materialised bmm(FA, FBᵀ) (models.py:203, main.py:238-239) in fp64: value, both feature gradients,
     exact zeros for the padding rows, targets on the last column / row of the corner, run-to-run identical results."""
     import torch.nn.functional as F
