@@ -552,6 +552,25 @@ int sn_pair_sl1_fwd_f32(const float *FA, int64_t lda, const float *FB, int64_t l
 int sn_pair_sl1_bwd_f32(const int64_t *mapA, const int64_t *mapB, const float *const *geo, int64_t ldgA, int64_t ldgB,
                         const float *gloss, int64_t NA, int64_t NB, int64_t rowsA, int64_t rowsB, int32_t K, float *dFA, int64_t ldda,
                         float *dFB, int64_t lddb, void *workspace, size_t workspace_bytes, void *stream);
+/* sn_pair_match_f32: what the trained network PREDICTS, from the tower features — for every vertex of shape A the vertex of
+ * shape B with the largest score and, optionally, the reverse and the geodesic error of the match.  Replaces
+ * `torch.bmm(FA, FB.transpose(1, 2))` (src/dense_correspondence/models.py:203) followed by a row maximum (and a column
+ * maximum, and a gather from the geodesic matrix): the scores are formed tile by tile as in sn_pair_fused_fwd_f32 (the same
+ * two-piece products per element, plain vertex order; the per-matrix scale is taken over the scored rows only, where that
+ * entry point takes it over all rowsA / rowsB) and reduced on the spot; no NA x NB temporary is written.
+ *   colA[r] = argmax_{j < NB} S[r][j], bestA[r] = that score, r < NA; rowB[j] = argmax_{r < NA} S[r][j], bestB[j], j < NB
+ *   (rowB and bestB may be NULL together: the second direction is then not computed).  A strictly larger score wins and on
+ *   equal scores the smaller index (numpy.argmax); a NaN score never wins, and every index lies inside the corner whatever
+ *   the features hold.  Only the scored rows are read: the padding of the batch (rows >= NA / NB) cannot move a result.
+ *   errA[r] = geoB[truthA[r] * ldgB + colA[r]] for 0 <= truthA[r] < NB, NaN otherwise: geoB is row-major fp32 with at least NB
+ *   rows and ldgB >= NB, truthA (int64[NA]) the vertex of B that row r of A truly corresponds to; geoB, truthA and errA are all
+ *   NULL or all set.
+ * workspace: sn_pair_match_workspace_bytes(rowsA, rowsB) bytes, 16-byte aligned (the split features and the per-range
+ * partials; smaller than sn_pair_fused_workspace_bytes: no transposed copies, no gradient partials).  Run-to-run identical. */
+size_t sn_pair_match_workspace_bytes(int64_t rowsA, int64_t rowsB);
+int sn_pair_match_f32(const float *FA, int64_t lda, const float *FB, int64_t ldb, int64_t NA, int64_t NB, int64_t rowsA,
+                      int64_t rowsB, int32_t K, int64_t *colA, float *bestA, int64_t *rowB, float *bestB, const float *geoB,
+                      int64_t ldgB, const int64_t *truthA, float *errA, void *workspace, size_t workspace_bytes, void *stream);
 /* sn_linear_thin_fwd_f32: forward of that first layer, y = x·W^T + bias (x: rows x C, C <= 8; W: J x C), and optionally
  * elu(y) into y_elu (the first half of the next block's concat buffer; replaces the F.elu of utils_pt.py:161,195).  y or
  * y_elu may be NULL (not both).  Ascending-k fp32 FMA chain on top of the bias. */

@@ -103,6 +103,9 @@ SIGNATURES = {
     "sn_pair_soft_bwd_f32": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i64, C.c_int32, _vp, _i64, _vp, _i64, _vp, C.c_size_t, _vp]),
     "sn_pair_sl1_fwd_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, C.c_int32, _vp, _vp, C.c_size_t, _vp]),
     "sn_pair_sl1_bwd_f32": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, C.c_int32, _vp, _i64, _vp, _i64, _vp, C.c_size_t, _vp]),
+    "sn_pair_match_workspace_bytes": (C.c_size_t, [_i64, _i64]),
+    "sn_pair_match_f32": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, C.c_int32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                                    C.c_size_t, _vp]),
     "sn_gather_segments_f32": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp]),
     "sn_gather_segments_ragged_f32": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp]),
     "sn_linear_thin_fwd_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp]),

@@ -1,5 +1,7 @@
 // sn_pair.hip — the three dense-correspondence losses computed from the tower features, WITHOUT the score matrix (gfx950):
-// `dcel` (hard argmin target, sn_pair_fused_*), `cel` (soft target, sn_pair_soft_*) and `sl1` (smooth-L1, sn_pair_sl1_*).
+// `dcel` (hard argmin target, sn_pair_fused_*), `cel` (soft target, sn_pair_soft_*) and `sl1` (smooth-L1, sn_pair_sl1_*); and
+// what the trained network PREDICTS, from the same streamed score tiles: the arg-max of every row and of every column
+// (sn_pair_match_f32).
 // src/dense_correspondence/models.py:203 bmm(FA, FB^T) followed by one of main.py:197-240: the 7000 x 7000 scores are formed
 // tile by tile on the fp16 matrix pipe and reduced on the spot; forward and backward never write them.
 // (The losses on a materialised score matrix, pair_argmin* and pair_ce_*, are in sn_dense.hip.)
@@ -29,6 +31,7 @@
 //   pair_reduce_k      sums the ranges in fixed order, applies gloss and the scales, scatters the rows through the map,
 //                      zero-fills the padding rows
 // Loss = PairHard | PairSoft | PairSl1: what differs between the losses, and nothing else (see "The loss policies").
+// PairMatch is a fourth, forward-only policy of pair_fwd_k (row arg-max; pair_match_combine_k folds the ranges).
 
 #include <algorithm>
 #include <limits.h>
@@ -75,7 +78,8 @@ __global__ __launch_bounds__(kWG) void pair_maxabs_k(const float *__restrict__ F
 
 // one thread per (row, 4 features) of a side (blockIdx.y): rows [0, npad), feature quads [0, 32)
 // MAP: position `row` of R / T takes row map[row] of F for row < nmap (a permutation of [0, nmap)), row `row` itself past it
-template <bool MAP>
+// WITH_T = false: R only (forward-only users; TA / TB are not touched)
+template <bool MAP, bool WITH_T = true>
 __global__ __launch_bounds__(kWG) void pair_split_k(const float *__restrict__ FA, int64_t lda, int rowsA, int npadA, unsigned short *__restrict__ RA,
                                                     unsigned short *__restrict__ TA, const float *__restrict__ FB, int64_t ldb, int rowsB,
                                                     int npadB, unsigned short *__restrict__ RB, unsigned short *__restrict__ TB, int K,
@@ -113,7 +117,7 @@ __global__ __launch_bounds__(kWG) void pair_split_k(const float *__restrict__ FA
       r[512 + c] = l[c];
     }
   }
-  {  // T: [t][f][s2][p][kh*32 + kfl][j], feature 32 f + kfl, streamed row 16 s2 + 8 (j >> 2) + 4 kh + (j & 3)  (pair_perm)
+  if constexpr (WITH_T) {  // T: [t][f][s2][p][kh*32 + kfl][j], feature 32 f + kfl, streamed row 16 s2 + 8 (j >> 2) + 4 kh + (j & 3)  (pair_perm)
     const int s2 = i >> 4, r16 = i & 15, kh = (r16 >> 2) & 1, j = 4 * (r16 >> 3) + (r16 & 3);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -375,7 +379,37 @@ struct PairSl1 {
   static __device__ __forceinline__ float grad_p(float s, float, float, float gv, int) { return fminf(fmaxf(s - gv, -1.f), 1.f); }
 };
 
-// grid (ceil(tiles_rows / 4), splits): rows x cols is the NA x NB corner (hard, soft) or the whole rectangle (sl1)
+// the prediction: (best, col) = the largest score of the row and the streamed column it came from.  A strictly larger score
+// wins, on equal scores the smaller column: numpy.argmax on the score row.  Forward only: no gradient members, so neither
+// pair_grad_k nor pair_reduce_k is instantiated for it.  A NaN score never wins; col starts at 0, so it is always a column
+// of the corner whatever the features hold.
+struct PairMatch {
+  static constexpr bool kGeo = false;
+  struct Fwd { float best; int col; };
+  static __device__ __forceinline__ bool better(float s, int c, float best, int col) { return s > best || (s == best && c < col); }
+  static __device__ __forceinline__ Fwd fwd_init(const PairIn &, int, int) { return Fwd{-INFINITY, 0}; }
+  static __device__ __forceinline__ void fwd_tile(Fwd &st, const f16v &acc, float sAB, int c0, int cols, float (&)[16]) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {                   // (pair_col ascends with e: inside a lane `>` alone is the tie rule)
+      const int i = c0 + pair_col(e);
+      const float s = acc[e] * sAB;
+      if (i < cols && s > st.best) {
+        st.best = s;
+        st.col = i;
+      }
+    }
+  }
+  // part[split][row][4] = (best, column as a BIT PATTERN, -, -): moved and compared as an integer, never computed on.
+  // The two half-waves hold disjoint, interleaved columns of the same row.
+  static __device__ __forceinline__ void fwd_store(const Fwd &st, bool write, size_t slot, float *part, float *) {
+    const float b2 = __shfl_xor(st.best, 32);
+    const int c2 = __shfl_xor(st.col, 32);
+    const bool other = better(b2, c2, st.best, st.col);
+    if (write) *reinterpret_cast<f4 *>(part + slot * 4) = f4{other ? b2 : st.best, __int_as_float(other ? c2 : st.col), 0.f, 0.f};
+  }
+};
+
+// grid (ceil(tiles_rows / 4), splits): rows x cols is the NA x NB corner (hard, soft, match) or the whole rectangle (sl1)
 template <class Loss>
 __global__ __launch_bounds__(kWG, 2) void pair_fwd_k(const unsigned short *__restrict__ RA, const unsigned short *__restrict__ RB, PairIn G,
                                                      int rows, int cols, int npadA, const unsigned *__restrict__ header,
@@ -471,6 +505,29 @@ __global__ __launch_bounds__(kWG) void pair_sl1_combine_k(const double *__restri
   double v = 0.0;
   for (int s = 0; s < splits; ++s) v += part[(size_t)s * npadA + r];
   rowloss[r] = v;
+}
+
+// the winner over the ranges, in range order, by PairMatch::better (an empty range holds (-inf, 0), and column 0 belongs to
+// range 0, so it never displaces one); err[r] = geo[truth[r]][col[r]] when geo is given, NaN where truth[r] is not a row of
+// it: N scattered reads
+__global__ __launch_bounds__(kWG) void pair_match_combine_k(const float *__restrict__ part, int splits, int npad, int N, int ncols,
+                                                            int64_t *__restrict__ col, float *__restrict__ best,
+                                                            const float *__restrict__ geo, int64_t ldg,
+                                                            const int64_t *__restrict__ truth, float *__restrict__ err) {
+  const int r = blockIdx.x * kWG + threadIdx.x;
+  if (r >= N) return;
+  f4 w = *reinterpret_cast<const f4 *>(part + (size_t)r * 4);
+  for (int s = 1; s < splits; ++s) {
+    const f4 v = *reinterpret_cast<const f4 *>(part + ((size_t)s * npad + r) * 4);
+    if (PairMatch::better(v.x, __float_as_int(v.y), w.x, __float_as_int(w.y))) w = v;
+  }
+  const int c = __float_as_int(w.y);
+  col[r] = c;
+  best[r] = w.x;
+  if (geo) {
+    const int64_t t = truth[r];
+    err[r] = (t >= 0 && t < ncols) ? geo[t * ldg + c] : __uint_as_float(0x7fc00000u);
+  }
 }
 
 // grid: side A's nblk x splits workgroups, then side B's.  Own rows n of side A carry (v0, v1) themselves; for side B (own
@@ -672,6 +729,29 @@ PairWs pair_ws(void *workspace, int64_t rowsA, int64_t rowsB) {
   return w;
 }
 
+// sn_pair_match_f32: header | RA | RB | partials of the rows of A | partials of the rows of B — no T, no gradient partials.
+// `ab` scores the rows of A against the streamed rows of B; `ba` is the same memory with the sides exchanged.
+struct PairMatchWs {
+  PairWs ab, ba;
+  size_t bytes;
+};
+PairMatchWs pair_match_ws(void *workspace, int64_t rowsA, int64_t rowsB) {
+  PairWs w{};
+  w.pa = (int)((rowsA + 31) / 32 * 32);
+  w.pb = (int)((rowsB + 31) / 32 * 32);
+  char *p = static_cast<char *>(workspace);
+  w.header = reinterpret_cast<unsigned *>(p);
+  p += kPairHeader;
+  w.RA = reinterpret_cast<unsigned short *>(p); p += (size_t)w.pa * kPairKP * 2 * sizeof(unsigned short);
+  w.RB = reinterpret_cast<unsigned short *>(p); p += (size_t)w.pb * kPairKP * 2 * sizeof(unsigned short);
+  w.lse_part = reinterpret_cast<float *>(p); p += (size_t)kPairMaxLseSplits * w.pa * 4 * sizeof(float);
+  PairWs x = w;
+  x.pa = w.pb; x.pb = w.pa;
+  x.RA = w.RB; x.RB = w.RA;
+  x.lse_part = reinterpret_cast<float *>(p); p += (size_t)kPairMaxLseSplits * w.pb * 4 * sizeof(float);
+  return PairMatchWs{w, x, (size_t)(p - static_cast<char *>(workspace))};
+}
+
 // the checks `cel` and `sl1` share
 int pair_loss_check(int64_t NA, int64_t NB, int64_t rowsA, int64_t rowsB, int32_t K, int64_t ldgA, int64_t ldgB) {
   if (NA < 1 || NB < 1 || rowsA < NA || rowsB < NB || K < 1 || ldgA < NB || ldgB < NB) return SN_E_SHAPE;
@@ -682,14 +762,14 @@ int pair_loss_check(int64_t NA, int64_t NB, int64_t rowsA, int64_t rowsB, int32_
 
 // features -> fragment order in the workspace: header fill, absolute maxima, split (MAP, the losses in label order: rows
 // [0, NA) / [0, NB) taken through the maps, where there are any)
-template <bool MAP>
+template <bool MAP, bool WITH_T = true>
 int pair_split(const float *FA, int64_t lda, const float *FB, int64_t ldb, const int64_t *mapA, const int64_t *mapB, int64_t NA,
                int64_t NB, int64_t rowsA, int64_t rowsB, int32_t K, const PairWs &w, hipStream_t s) {
   hipError_t e = sn_internal_fill(w.header, 0, kPairHeader, s);
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(pair_maxabs_k, dim3((unsigned)std::min<int64_t>(1024, (std::max(rowsA, rowsB) * K + 4 * kWG - 1) / (4 * kWG)), 2), dim3(kWG), 0, s, FA, lda, (int)rowsA, FB, ldb, (int)rowsB, (int)K, w.header);
   const int64_t quads = (int64_t)std::max(w.pa, w.pb) * 32;
-  hipLaunchKernelGGL((pair_split_k<MAP>), dim3((unsigned)((quads + kWG - 1) / kWG), 2), dim3(kWG), 0, s, FA, lda, (int)rowsA, w.pa, w.RA, w.TA, FB,
+  hipLaunchKernelGGL((pair_split_k<MAP, WITH_T>), dim3((unsigned)((quads + kWG - 1) / kWG), 2), dim3(kWG), 0, s, FA, lda, (int)rowsA, w.pa, w.RA, w.TA, FB,
                      ldb, (int)rowsB, w.pb, w.RB, w.TB, (int)K, w.header, mapA, (int)NA, mapB, (int)NB);
   return SN_OK;
 }
@@ -832,6 +912,39 @@ int sn_pair_sl1_bwd_f32(const int64_t *mapA, const int64_t *mapB, const float *c
   const float mul = (float)(1.0 / ((double)rowsA * (double)rowsB));
   return pair_bwd_launch<PairSl1>(PairIn{geo, ldgA, ldgB, (int)NA, (int)NB, nullptr, nullptr}, mapA, mapB, gloss, rowsA, rowsB, rowsA,
                                   rowsB, K, mul, dFA, ldda, dFB, lddb, pair_ws(workspace, rowsA, rowsB), static_cast<hipStream_t>(stream));
+}
+
+size_t sn_pair_match_workspace_bytes(int64_t rowsA, int64_t rowsB) {
+  if (rowsA < 0 || rowsB < 0 || rowsA > INT_MAX - 64 || rowsB > INT_MAX - 64) return 0;
+  return pair_match_ws(nullptr, rowsA, rowsB).bytes;
+}
+
+int sn_pair_match_f32(const float *FA, int64_t lda, const float *FB, int64_t ldb, int64_t NA, int64_t NB, int64_t rowsA, int64_t rowsB,
+                      int32_t K, int64_t *colA, float *bestA, int64_t *rowB, float *bestB, const float *geoB, int64_t ldgB,
+                      const int64_t *truthA, float *errA, void *workspace, size_t workspace_bytes, void *stream) {
+  (void)hipGetLastError();      // a stale error left by an earlier runtime call of this thread is not ours to report
+  if (NA < 1 || NB < 1 || rowsA < NA || rowsB < NB || K < 1 || lda < K || ldb < K || (geoB && ldgB < NB)) return SN_E_SHAPE;
+  if (K > kPairKP) return SN_E_UNSUPPORTED;
+  if (rowsA > INT_MAX - 64 || rowsB > INT_MAX - 64) return SN_E_RANGE;
+  if (!FA || !FB || !colA || !bestA || !workspace || !rowB != !bestB) return SN_E_NULL;
+  if (!geoB != !truthA || !geoB != !errA) return SN_E_NULL;
+  if (!aligned16(workspace)) return SN_E_ALIGN;
+  if (workspace_bytes < sn_pair_match_workspace_bytes(rowsA, rowsB)) return SN_E_WORKSPACE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const PairMatchWs w = pair_match_ws(workspace, rowsA, rowsB);
+  // (the scales and the split see the scored rows only: what the padding of the batch holds cannot move a prediction)
+  if (int st = pair_split<false, false>(FA, lda, FB, ldb, nullptr, nullptr, NA, NB, NA, NB, K, w.ab, s)) return st;
+  const PairIn none{nullptr, 0, 0, (int)NA, (int)NB, nullptr, nullptr};
+  int splits = pair_fwd_launch<PairMatch>(none, NA, NB, w.ab, s);
+  hipLaunchKernelGGL(pair_match_combine_k, dim3((unsigned)((NA + kWG - 1) / kWG)), dim3(kWG), 0, s, w.ab.lse_part, splits, w.ab.pa, (int)NA,
+                     (int)NB, colA, bestA, geoB, ldgB, truthA, errA);
+  if (rowB) {                   // the column arg-max: the same kernel with the sides exchanged
+    splits = pair_fwd_launch<PairMatch>(none, NB, NA, w.ba, s);
+    hipLaunchKernelGGL(pair_match_combine_k, dim3((unsigned)((NB + kWG - 1) / kWG)), dim3(kWG), 0, s, w.ba.lse_part, splits, w.ba.pa, (int)NB,
+                       (int)NA, rowB, bestB, static_cast<const float *>(nullptr), (int64_t)0, static_cast<const int64_t *>(nullptr),
+                       static_cast<float *>(nullptr));
+  }
+  return launch_status();
 }
 
 }  // extern "C"

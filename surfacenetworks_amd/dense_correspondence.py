@@ -425,9 +425,12 @@ def _target_stream(device):
 _FUSED_SCORES = os.environ.get("SN_PAIR_FUSED", "1") != "0"      # A/B switch: "0" = bmm + sn_pair_ce_* on the score matrix
 
 
-def fused_pair_supported(FA, FB) -> bool:
+def fused_pair_supported(FA, FB, strided_rows: bool = False) -> bool:
+    """strided_rows: rows with a leading dimension larger than K are fine too (the forward-only matching: the kernels read
+    through lda / ldb, and nothing comes back in the features' layout)."""
+    laid_out = (lambda t: t.stride(-1) == 1) if strided_rows else (lambda t: t[0].is_contiguous())
     return (_FUSED_SCORES and FA.is_cuda and FA.dtype == torch.float32 and FB.dtype == torch.float32 and FA.dim() == 3
-            and FA.shape[-1] == FB.shape[-1] <= 128 and FA[0].is_contiguous() and FB[0].is_contiguous())
+            and FA.shape[-1] == FB.shape[-1] <= 128 and laid_out(FA) and laid_out(FB))
 
 
 def fused_pair_cross_entropy(FA, FB, target, NA: int, NB: int):
@@ -594,6 +597,131 @@ def fused_pair_smooth_l1(FA, FB, HA, HB, mapA, mapB, NA: int, NB: int, geo=None)
 
 
 _FUSED_LOSSES = {"cel": fused_pair_soft_cross_entropy, "sl1": fused_pair_smooth_l1}
+
+
+# ---- evaluation: what the network predicts ----------------------------------------------------------------------------------
+class PairMatches:
+    """The matches of one pair: a2b[r] = the vertex of B matched to vertex r of A (int64[NA]) and score_a[r] its score; b2a /
+    score_b the reverse direction (None when not asked for); err the geodesic error of a2b when the matching was given the
+    geodesic matrix and the true matches (None otherwise)."""
+
+    __slots__ = ("a2b", "score_a", "b2a", "score_b", "err")
+
+    def __init__(self, a2b, score_a, b2a=None, score_b=None, err=None):
+        self.a2b, self.score_a, self.b2a, self.score_b, self.err = a2b, score_a, b2a, score_b, err
+
+
+def match_features(FA, FB, NA: int, NB: int, both: bool = True, geoB=None, truthA=None) -> PairMatches:
+    """The prediction of a dense-correspondence network from the (B, N, K) tower outputs — sample 0 is the one matched, as in
+    every loss here: for every vertex r < NA of shape A the vertex of B with the largest score FA[r]·FB[j], j < NB, and with
+    `both` the reverse.  The score matrix (models.py:203) is never written (sn_pair_match_f32); equal scores go to the smaller
+    index.  geoB, truthA (true_matches): also the geodesic error of every match, from the same launch.  Features the kernel
+    does not take (fused_pair_supported) go through the materialised product."""
+    kernels._dev(FA, FB)
+    if FB.dim() == 3 and fused_pair_supported(FA, FB, strided_rows=True):
+        return PairMatches(*kernels.pair_match(FA[0], FB[0], NA, NB, both, geoB, truthA))
+    S = torch.bmm(FA[:1, :NA], FB[:1, :NB].transpose(1, 2))[0]
+    score_a, a2b = S.max(dim=1)
+    score_b, b2a = S.max(dim=0) if both else (None, None)
+    err = None
+    if geoB is not None:
+        err = torch.where(truthA >= 0, geoB[truthA.clamp(min=0), a2b], geoB.new_full((), float("nan")))
+    return PairMatches(a2b, score_a, b2a, score_b, err)
+
+
+def true_matches(targetX, targetY):
+    """For every vertex r of A the vertex of B that carries the same label, liB[lA[r]] — the row index of the `GB[liB[lA], :]`
+    term of main.py:206 — and -1 where B has no such label (lA[r] >= NB).  targetX, targetY: the datasets' target lists
+    [(G, label, label_inv)]; sample 0, as in the losses."""
+    lA, liB = targetX[0][1], targetY[0][2]
+    NB = liB.numel()
+    return torch.where(lA < NB, liB[lA.clamp(max=NB - 1)], lA.new_full((), -1))
+
+
+def geodesic_errors(a2b, targetX, targetY):
+    """err[r] = GB[true_matches[r], a2b[r]]: the second term of the reference's geodesic sum (main.py:206) taken at the
+    predicted column — how far, on shape B, the predicted vertex lies from the true one; NaN where there is no true match.
+    a2b: a PairMatches that already carries the errors (match_features given geoB and truthA: the kernel read them on its way
+    out) or an index vector, for which this is one NA-element gather."""
+    if isinstance(a2b, PairMatches):
+        if a2b.err is not None:
+            return a2b.err
+        a2b = a2b.a2b
+    GB = targetY[0][0]
+    t = true_matches(targetX, targetY)
+    return torch.where(t >= 0, GB[t.clamp(min=0), a2b].float(), GB.new_full((), float("nan"), dtype=torch.float32))
+
+
+def correspondence_curve(err, thresholds):
+    """The cumulative match curve: for every threshold t the fraction of the FINITE errors that are <= t (float64, on the device
+    of `err`; NaN when no error is finite).  One sort and one binary search over the NA errors."""
+    th = torch.as_tensor(thresholds, dtype=torch.float32, device=err.device).reshape(-1)
+    e = err.reshape(-1).float()
+    finite = torch.isfinite(e)
+    n = finite.sum()
+    srt = torch.where(finite, e, e.new_full((), float("inf"))).sort().values
+    count = torch.minimum(torch.searchsorted(srt, th, right=True), n)      # (a threshold of +inf counts the finite ones only)
+    return count.double() / n.double()
+
+
+def matches_to_dataset_order(ds, ia: int, ib: int, a2b):
+    """Matches of the pair (ia, ib) from the STORED numbering into the dataset's own vertex ids, positions and values both:
+    out[orders[ia].vorder[r]] = orders[ib].vorder[a2b[r]].  A dataset without stored orders (TorusBodies) is returned as is."""
+    orders = getattr(ds, "orders", None)
+    if orders is None or (orders[ia].identity and orders[ib].identity):
+        return a2b
+    voA = torch.from_numpy(orders[ia].vorder).to(a2b.device)
+    voB = torch.from_numpy(orders[ib].vorder).to(a2b.device)
+    out = torch.empty_like(a2b)
+    out[voA[:a2b.numel()]] = voB[a2b]
+    return out
+
+
+def evaluate_pair(model, ds, ia: int, ib: int, thresholds=None):
+    """What `model` predicts for the pair (ia, ib) of a TorusBodies / FaustFrames dataset and how good it is: the towers in
+    evaluation mode (BatchNorm on its running statistics, dropout off; the modules' modes are put back afterwards) under
+    no_grad, the matches in both directions and their geodesic errors from the features (match_features: no N x N matrix).
+    Returns device tensors, nothing is read back:
+      a2b, b2a      matched vertex of B per vertex of A and the reverse (int64)
+      err           geodesic error of a2b (geodesic_errors), mean_error its mean over the vertices that have a true match
+      exact         share of those vertices with a2b == true_matches
+      curve         correspondence_curve(err, thresholds); thresholds=None: 101 steps from 0 to a quarter of B's largest
+                    geodesic distance (returned as `thresholds`).  That default costs one read of the dataset's NB x NB
+                    geodesic matrix per call (190 MB at FAUST size, no temporary): pass thresholds to avoid it
+      mutual        share of the vertices of A with b2a[a2b[r]] == r
+    Matches are in the STORED numbering of the dataset.  FaustFrames stores its frames renumbered: stored vertex k of frame i
+    is vertex `ds.orders[i].vorder[k]` of the file, so row r of a2b speaks of the file's vertex orders[ia].vorder[r] and its
+    value of the file's vertex orders[ib].vorder[a2b[r]]; matches_to_dataset_order does both.  err, mean_error, exact, curve
+    and mutual do not depend on the numbering."""
+    inX, tX, mX, LX = ds.sample(ia)
+    inY, tY, mY, LY = ds.sample(ib)
+    GB = tY[0][0]
+    NA, NB = int(tX[0][1].size(0)), int(tY[0][1].size(0))
+    modes = [(m, m.training) for m in model.modules()]
+    model.eval()
+    try:
+        with torch.no_grad():
+            FA, FB = model.towers(_operation(LX, mX), _operation(LY, mY), inX, inY)
+    finally:
+        for m, was in modes:
+            m.training = was
+    with torch.no_grad():
+        truth = true_matches(tX, tY)
+        in_kernel = GB.is_cuda and GB.dtype == torch.float32 and GB.dim() == 2 and GB.stride(1) == 1 and min(GB.shape) >= NB
+        m = match_features(FA, FB, NA, NB, True, GB if in_kernel else None, truth if in_kernel else None)
+        err = geodesic_errors(m, tX, tY)
+        has = truth >= 0
+        count = has.sum().double()
+        if thresholds is None:
+            thresholds = torch.linspace(0.0, 1.0, 101, device=err.device) * (0.25 * GB[:NB, :NB].max())
+        thresholds = torch.as_tensor(thresholds, dtype=torch.float32, device=err.device)
+        return {
+            "a2b": m.a2b, "b2a": m.b2a, "err": err, "thresholds": thresholds,
+            "mean_error": torch.where(has, err, torch.zeros_like(err)).double().sum() / count,
+            "exact": (m.a2b == truth).sum().double() / count,
+            "curve": correspondence_curve(err, thresholds),
+            "mutual": (m.b2a[m.a2b] == torch.arange(NA, device=err.device)).sum().double() / has.new_full((), NA, dtype=torch.float64),
+        }
 
 
 def make_optimizer(model):

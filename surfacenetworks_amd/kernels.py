@@ -1288,6 +1288,42 @@ def pair_sl1_bwd(mapA, mapB, geo, ldgA: int, ldgB: int, gloss, ws, NA: int, NB: 
     return dFA, dFB
 
 
+def pair_match(FA, FB, NA: int, NB: int, both: bool = True, geoB=None, truthA=None):
+    """(colA, bestA, rowB, bestB, errA) from the tower features FA (rowsA x K), FB (rowsB x K): colA[r] = argmax_j S[r][j] over
+    the NA x NB corner of S = FA·FBᵀ (models.py:203) and bestA[r] that score; with `both`, rowB[j] = argmax_r S[r][j] and
+    bestB[j]; with geoB (fp32, at least NB x NB) and truthA (int64[NA], the true vertex of B per row, -1 = none),
+    errA[r] = geoB[truthA[r], colA[r]] (NaN where there is no truth).  None where not asked for.  Ties go to the smaller index
+    (numpy.argmax).  The scores are never written (sn_pair_match_f32)."""
+    _dev(FA, FB, geoB, truthA)
+    for t in (FA, FB):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
+            raise TypeError("pair_match: row-major float32 feature matrices expected")
+    if FA.shape[1] != FB.shape[1]:
+        raise TypeError("pair_match: features of one width expected")
+    if not (0 < NA <= FA.shape[0] and 0 < NB <= FB.shape[0]):
+        raise ValueError("pair_match: NA / NB do not fit the feature matrices")
+    if (geoB is None) != (truthA is None):
+        raise ValueError("pair_match: geoB and truthA come together")
+    if geoB is not None:
+        if geoB.dtype != torch.float32 or geoB.dim() != 2 or geoB.stride(1) != 1 or truthA.dtype != torch.int64:
+            raise TypeError("pair_match: a row-major float32 geodesic matrix and int64 true matches expected")
+        if geoB.shape[0] < NB or geoB.shape[1] < NB or truthA.numel() != NA:
+            raise ValueError("pair_match: geoB holds fewer than NB x NB entries, or truthA not NA")
+        truthA = truthA.contiguous()
+    dev = FA.device
+    nbytes = _lib.load().sn_pair_match_workspace_bytes(FA.shape[0], FB.shape[0])
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    colA = torch.empty(NA, dtype=torch.int64, device=dev)
+    bestA = torch.empty(NA, dtype=torch.float32, device=dev)
+    rowB = torch.empty(NB, dtype=torch.int64, device=dev) if both else None
+    bestB = torch.empty(NB, dtype=torch.float32, device=dev) if both else None
+    errA = torch.empty(NA, dtype=torch.float32, device=dev) if geoB is not None else None
+    _lib.call("sn_pair_match_f32", _p(FA), FA.stride(0), _p(FB), FB.stride(0), NA, NB, FA.shape[0], FB.shape[0], FA.shape[1], _p(colA),
+              _p(bestA), _p(rowB), _p(bestB), _p(geoB), geoB.stride(0) if geoB is not None else 0, _p(truthA), _p(errA), _p(ws), nbytes,
+              _stream())
+    return colA, bestA, rowB, bestB, errA
+
+
 def masked_smooth_l1_fwd(out2d, target2d, rowmask, scale: float):
     """scale * sum smooth_l1(out*rowmask - target) as a 0-dim fp32 tensor (sn_masked_smooth_l1_fwd_f32)."""
     _dev(out2d, target2d, rowmask)
