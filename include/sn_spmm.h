@@ -756,6 +756,46 @@ int sn_laplacian_csr_from_mesh(const float *V, const int32_t *F, int64_t nV, int
                                void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Geodesic distance matrices: all-pairs shortest paths along the edges of a graph (a mesh's vertex adjacency).
+ *
+ * Replaces: nothing computed by the reference — it loads `dist_mat` from its .npz frames (src/dense_correspondence/main.py:65-104);
+ *           this is the one input of the dense-correspondence job that could not be produced from (V, F).
+ *
+ * Definition.  Graph: vertices 0..n-1 in CSR, int32 rowptr/colind, fp32 weights w >= 0; self-loops and explicit zeros allowed.
+ *   Row v lists the edges INTO v: a stored entry (v, u) is the edge u -> v (the sweep pulls along its row).  A mesh's graph
+ *   stores both directions with bit-identical weights.
+ *   Mesh edge weight of a stored entry (i, j): d = V[i] - V[j] in fp64 from the fp32 coordinates,
+ *   w = (float) sqrt((dx*dx + dy*dy) + dz*dz), every product and sum rounded on its own (no fused multiply-add) — numpy's value.
+ *   D[s][s] = 0; D[s][v] = the minimum over all edge paths s -> ... -> v of the length accumulated in fp32 from the source
+ *   outward, fl(fl(fl(0 + w1) + w2) + ...); +inf where there is no path.  fp32 addition of a non-negative number is monotone,
+ *   so this is what a textbook Dijkstra adding in fp32 returns, and equally the unique fixed point of
+ *   d[v] = min(d[v], min_u fl(d[u] + w_uv)) from d = inf, d[s] = 0 under ANY relaxation order: results are bit-reproducible.
+ *   D is not exactly symmetric (the reverse path accumulates in the other order); the symmetric matrix is min(D, D^T).
+ *
+ * sn_edge_lengths_csr_f32 : w[e] for every stored entry of an n x n CSR pattern (a column outside 0..n-1 gets +inf).  On the
+ *                           pattern of sn_laplacian_csr_from_mesh this is the vertex adjacency with a zero self-loop per row.
+ * sn_graph_apsp_f32       : rows src_begin .. src_begin+src_count-1 of D:  out[(s - src_begin) * ldo + v].  One workgroup holds
+ *                           the distance vectors of S consecutive sources in LDS (S = sn_graph_apsp_group(n): the largest of
+ *                           8, 4, 2, 1 with S * n <= sn_graph_apsp_max_vertices()) and sweeps them to the fixed point, at most n
+ *                           sweeps whatever the arrays hold.  *unreached (may be NULL) is OR-ed with 1 when a written row holds
+ *                           +inf; the caller clears it.  colind == w == NULL declares a graph without entries.
+ *                           n > sn_graph_apsp_max_vertices(): SN_E_UNSUPPORTED, nothing is launched (there is no fallback).
+ *                           src_begin + src_count > n: SN_E_SHAPE;  ldo < n: SN_E_LD.
+ * sn_graph_apsp_sweeps_f32: the same, and sweeps[g] (may be NULL) = the number of sweeps workgroup g ran (measurement).
+ * sn_graph_apsp_threads   : threads per workgroup for n vertices (1024 / 512 / 256 when the LDS holds one / two / more workgroups).
+ * sn_symmetrize_min_f32   : G[i][j] = G[j][i] = min(G[i][j], G[j][i]) in place, any n, any ld >= n, no second matrix.
+ * ------------------------------------------------------------------------------------------ */
+int sn_edge_lengths_csr_f32(const float *V, const int32_t *rowptr, const int32_t *colind, int64_t n, float *w, void *stream);
+int64_t sn_graph_apsp_max_vertices(void);
+int32_t sn_graph_apsp_group(int64_t n);
+int32_t sn_graph_apsp_threads(int64_t n);
+int sn_graph_apsp_f32(const int32_t *rowptr, const int32_t *colind, const float *w, int64_t n, int64_t src_begin,
+                      int64_t src_count, float *out, int64_t ldo, int32_t *unreached, void *stream);
+int sn_graph_apsp_sweeps_f32(const int32_t *rowptr, const int32_t *colind, const float *w, int64_t n, int64_t src_begin,
+                             int64_t src_count, float *out, int64_t ldo, int32_t *unreached, int32_t *sweeps, void *stream);
+int sn_symmetrize_min_f32(float *G, int64_t n, int64_t ld, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Row-streaming fp32 GEMMs of the per-node Linear layers with the weights held in registers
  * (v_mfma_f32_32x32x2_f32; the operands are tall-skinny: rows ~ 1e5..1e6, K and N in {128, 256}).
  *

@@ -131,6 +131,13 @@ SIGNATURES = {
     "sn_timing_drain": (C.c_int, [_vp, _vp, _i64, _vp]),
     "sn_laplacian_workspace_bytes": (_sz, [_i64, _i64]),
     "sn_laplacian_csr_from_mesh": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sn_edge_lengths_csr_f32": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "sn_graph_apsp_max_vertices": (_i64, []),
+    "sn_graph_apsp_group": (_i32, [_i64]),
+    "sn_graph_apsp_threads": (_i32, [_i64]),
+    "sn_graph_apsp_f32": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "sn_graph_apsp_sweeps_f32": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "sn_symmetrize_min_f32": (C.c_int, [_vp, _i64, _i64, _vp]),
     "sn_linear_fwd_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
     "sn_linear_fwd_stats_blocks": (_i32, [_i64]),
     "sn_linear_fwd_tiles_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),

@@ -325,6 +325,130 @@ __global__ __launch_bounds__(kWG) void laplacian_rows_k(const float *__restrict_
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Geodesic (edge-path) distance matrices: all-pairs shortest paths on a CSR graph, fp32 (definition: sn_spmm.h).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kWG) void edge_lengths_csr_k(const float *__restrict__ V, const int *__restrict__ rowptr,
+                                                          const int *__restrict__ colind, int64_t n, float *__restrict__ w) {
+  for (int64_t v = (int64_t)blockIdx.x * kWG + threadIdx.x; v < n; v += (int64_t)gridDim.x * kWG)
+    for (int e = rowptr[v]; e < rowptr[v + 1]; ++e) {
+      const int u = colind[e];
+      w[e] = ((unsigned)u < (unsigned)n) ? (float)edge_len(V, (int)v, u) : INFINITY;   // a column outside the mesh: no edge
+    }
+}
+
+constexpr int kApspLds = 160 * 1024;      // the CU's whole LDS: one workgroup may take it all
+constexpr int kApspHead = 16;             // three rotating "changed" flags, padded so that the vectors stay 16-byte aligned
+constexpr int kApspMaxN = (kApspLds - kApspHead) / 4;
+constexpr int kApspMaxWG = 1024;
+
+// S: sources per workgroup — the largest of {8, 4, 2, 1} whose S distance vectors fit the LDS
+inline int apsp_group(int64_t n) {
+  for (int S = 8; S > 1; S >>= 1)
+    if (S * n <= kApspMaxN) return S;
+  return n <= kApspMaxN ? 1 : 0;
+}
+// threads per workgroup: 16 waves when the vectors leave room for one workgroup per CU, 8 for two, 4 for more (then
+// several small workgroups share the CU and none of them leaves it with one or two waves)
+inline int apsp_threads(int64_t n) {
+  const int S = apsp_group(n);
+  if (!S) return 0;
+  const int64_t per_cu = kApspLds / (kApspHead + 4 * S * (n > 0 ? n : 1));
+  return per_cu <= 1 ? 1024 : per_cu == 2 ? 512 : 256;
+}
+
+// Pull sweeps to the fixed point of d[v] = min(d[v], min_u fl(d[u] + w_uv)).  d[v*S + j]: distance from source s0 + j, in
+// LDS; the owner of v (thread v mod blockDim) is the only writer of d[v*S..]; a neighbour's word is read either old or new,
+// both are lengths of real paths, and fp32 addition of w >= 0 is monotone, so the fixed point does not depend on the order.
+// At most n sweeps whatever the arrays hold (NaN and negative weights included): sweep k settles every k-hop path.
+template <int S>
+__global__ __launch_bounds__(kApspMaxWG) void graph_apsp_k(const int *__restrict__ rowptr, const int *__restrict__ colind,
+                                                            const float *__restrict__ w, int n, int src_begin, int src_count,
+                                                            float *__restrict__ out, int64_t ldo, int *__restrict__ unreached,
+                                                            int *__restrict__ sweeps) {
+  extern __shared__ __align__(16) unsigned char apsp_lds[];
+  int *flag = reinterpret_cast<int *>(apsp_lds);
+  float *d = reinterpret_cast<float *>(apsp_lds + kApspHead);
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int s0 = src_begin + (int)blockIdx.x * S;
+  const int ns = min(S, src_begin + src_count - s0);           // the last group of a window may be partial
+  for (int i = tid; i < n * S; i += nt) d[i] = INFINITY;
+  if (tid < 3) flag[tid] = 0;
+  __syncthreads();
+  if (tid < ns) d[(s0 + tid) * S + tid] = 0.0f;
+  __syncthreads();
+  int it = 0;
+  if (colind != nullptr)
+    for (; it < n; ++it) {
+      if (tid == 0) flag[(it + 1) % 3] = 0;                    // read last before the previous barrier, set next after this one
+      bool changed = false;
+      for (int v = tid; v < n; v += nt) {
+        float cur[S], best[S];
+#pragma unroll
+        for (int j = 0; j < S; ++j) best[j] = cur[j] = d[v * S + j];
+        const int eb = rowptr[v], ee = rowptr[v + 1];
+        for (int e = eb; e < ee; ++e) {
+          const int u = colind[e];
+          const float we = w[e];
+          if ((unsigned)u >= (unsigned)n) continue;            // never index LDS by a column the graph does not have
+#pragma unroll
+          for (int j = 0; j < S; ++j) best[j] = fminf(best[j], d[u * S + j] + we);
+        }
+#pragma unroll
+        for (int j = 0; j < S; ++j)
+          if (best[j] < cur[j]) {
+            d[v * S + j] = best[j];
+            changed = true;
+          }
+      }
+      if (changed) flag[it % 3] = 1;
+      __syncthreads();
+      if (!flag[it % 3]) break;
+    }
+  if (sweeps != nullptr && tid == 0) sweeps[blockIdx.x] = it < n ? it + 1 : n;
+  bool inf_left = false;
+  for (int j = 0; j < ns; ++j) {
+    float *row = out + (int64_t)(s0 - src_begin + j) * ldo;
+    for (int v = tid; v < n; v += nt) {
+      const float x = d[v * S + j];
+      inf_left |= (x == INFINITY);
+      __builtin_nontemporal_store(x, row + v);
+    }
+  }
+  if (inf_left && unreached != nullptr) atomicOr(unreached, 1);
+}
+
+// G[i][j] = G[j][i] = min(G[i][j], G[j][i]) in place: block (bi <= bj) holds tiles (bi,bj) and (bj,bi) in LDS, then writes both
+constexpr int kSymTile = 32;
+__global__ __launch_bounds__(kWG) void symmetrize_min_k(float *__restrict__ G, int64_t n, int64_t ld) {
+  const int bi = blockIdx.y, bj = blockIdx.x;
+  if (bi > bj) return;
+  __shared__ float a[kSymTile][kSymTile + 1], b[kSymTile][kSymTile + 1];
+  const int tx = threadIdx.x % kSymTile, ty = threadIdx.x / kSymTile;
+  const int64_t i0 = (int64_t)bi * kSymTile, j0 = (int64_t)bj * kSymTile;
+  for (int r = ty; r < kSymTile; r += kWG / kSymTile) {
+    a[r][tx] = (i0 + r < n && j0 + tx < n) ? G[(i0 + r) * ld + j0 + tx] : INFINITY;
+    b[r][tx] = (j0 + r < n && i0 + tx < n) ? G[(j0 + r) * ld + i0 + tx] : INFINITY;
+  }
+  __syncthreads();
+  for (int r = ty; r < kSymTile; r += kWG / kSymTile) {
+    if (i0 + r < n && j0 + tx < n) G[(i0 + r) * ld + j0 + tx] = fminf(a[r][tx], b[tx][r]);
+    if (bi != bj && j0 + r < n && i0 + tx < n) G[(j0 + r) * ld + i0 + tx] = fminf(b[r][tx], a[tx][r]);
+  }
+}
+
+template <int S>
+int apsp_launch(const int *rowptr, const int *colind, const float *w, int n, int src_begin, int src_count, float *out,
+                int64_t ldo, int *unreached, int *sweeps, hipStream_t s) {
+  const size_t lds = (size_t)kApspHead + (size_t)4 * S * n;
+  static const hipError_t attr =
+      hipFuncSetAttribute(reinterpret_cast<const void *>(graph_apsp_k<S>), hipFuncAttributeMaxDynamicSharedMemorySize, kApspLds);
+  if (attr != hipSuccess) return (int)attr;
+  hipLaunchKernelGGL((graph_apsp_k<S>), dim3((unsigned)((src_count + S - 1) / S)), dim3(apsp_threads(n)), lds, s, rowptr, colind, w,
+                     n, src_begin, src_count, out, ldo, unreached, sweeps);
+  return launch_status();
+}
+
 inline size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 }  // namespace
@@ -423,6 +547,58 @@ int sn_laplacian_csr_from_mesh(const float *V, const int32_t *F, int64_t nV, int
     hipLaunchKernelGGL((laplacian_rows_k<true>), dim3(grid_for(nV)), dim3(kWG), 0, s, V, F, nV, vptr, inc, Af, rowptr, colind,
                        vals, (int *)nullptr);
   }
+  return launch_status();
+}
+
+int sn_edge_lengths_csr_f32(const float *V, const int32_t *rowptr, const int32_t *colind, int64_t n, float *w, void *stream) {
+  (void)hipGetLastError();
+  if (n < 0) return SN_E_SHAPE;
+  if (n + 1 > INT_MAX) return SN_E_RANGE;
+  if (n == 0) return SN_OK;
+  if (!V || !rowptr) return SN_E_NULL;
+  if (!colind != !w) return SN_E_NULL;
+  if (!colind) return SN_OK;                                     // a pattern without entries
+  hipLaunchKernelGGL(edge_lengths_csr_k, dim3(grid_for(n)), dim3(kWG), 0, static_cast<hipStream_t>(stream), V, rowptr, colind, n, w);
+  return launch_status();
+}
+
+int64_t sn_graph_apsp_max_vertices(void) { return kApspMaxN; }
+int32_t sn_graph_apsp_group(int64_t n) { return n < 0 ? 0 : apsp_group(n); }
+int32_t sn_graph_apsp_threads(int64_t n) { return n < 0 ? 0 : apsp_threads(n); }
+
+int sn_graph_apsp_sweeps_f32(const int32_t *rowptr, const int32_t *colind, const float *w, int64_t n, int64_t src_begin,
+                             int64_t src_count, float *out, int64_t ldo, int32_t *unreached, int32_t *sweeps, void *stream) {
+  (void)hipGetLastError();
+  if (n < 0 || src_begin < 0 || src_count < 0 || src_begin + src_count > n) return SN_E_SHAPE;
+  if (n > kApspMaxN) return SN_E_UNSUPPORTED;                    // S = 1 no longer fits the LDS: nothing is launched
+  if (src_count == 0) return SN_OK;
+  if (!rowptr || !out) return SN_E_NULL;
+  if (!colind != !w) return SN_E_NULL;                           // both NULL: a graph without entries
+  if (ldo < n) return SN_E_LD;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int ni = (int)n, sb = (int)src_begin, sc = (int)src_count;
+  switch (apsp_group(n)) {
+    case 8: return apsp_launch<8>(rowptr, colind, w, ni, sb, sc, out, ldo, unreached, sweeps, s);
+    case 4: return apsp_launch<4>(rowptr, colind, w, ni, sb, sc, out, ldo, unreached, sweeps, s);
+    case 2: return apsp_launch<2>(rowptr, colind, w, ni, sb, sc, out, ldo, unreached, sweeps, s);
+    default: return apsp_launch<1>(rowptr, colind, w, ni, sb, sc, out, ldo, unreached, sweeps, s);
+  }
+}
+
+int sn_graph_apsp_f32(const int32_t *rowptr, const int32_t *colind, const float *w, int64_t n, int64_t src_begin,
+                      int64_t src_count, float *out, int64_t ldo, int32_t *unreached, void *stream) {
+  return sn_graph_apsp_sweeps_f32(rowptr, colind, w, n, src_begin, src_count, out, ldo, unreached, nullptr, stream);
+}
+
+int sn_symmetrize_min_f32(float *G, int64_t n, int64_t ld, void *stream) {
+  (void)hipGetLastError();
+  if (n < 0) return SN_E_SHAPE;
+  if (n == 0) return SN_OK;
+  if (!G) return SN_E_NULL;
+  if (ld < n) return SN_E_LD;
+  const int64_t nt = (n + kSymTile - 1) / kSymTile;
+  if (nt > 65535) return SN_E_RANGE;
+  hipLaunchKernelGGL(symmetrize_min_k, dim3((unsigned)nt, (unsigned)nt), dim3(kWG), 0, static_cast<hipStream_t>(stream), G, n, ld);
   return launch_status();
 }
 

@@ -24,7 +24,7 @@ from . import arap as _arap
 from . import mesh_ops
 from .operators import OperatorPool
 
-__all__ = ["load_arap_sequence", "arap_from_files", "load_mesh_mnist", "mnist_from_samples", "load_faust_frame", "faust_from_files",
+__all__ = ["load_arap_sequence", "arap_from_files", "load_mesh_mnist", "mnist_from_samples", "load_faust_frame", "faust_from_files", "faust_frame_from_mesh",
            "write_arap_sequence", "write_mesh_mnist", "write_faust_frame"]
 
 
@@ -157,6 +157,30 @@ def load_faust_frame(path: str, device="cuda") -> Dict:
             "G": torch.from_numpy(z["dist_mat"].astype("f")).to(device),
         }
     return fr
+
+
+def faust_frame_from_mesh(V, F, label=None, device="cuda", symmetric=True) -> Dict:
+    """The frame dict of load_faust_frame from a raw triangle mesh: V (nV, 3), F (nF, 3) (numpy or tensors), host scipy
+    L / Di / DiA from mesh_ops.mesh_operators, and G — the `dist_mat` the reference's files bring along — computed on the device
+    by operators.geodesic_matrix_from_mesh (edge-path distances; symmetric: min(D, D^T)).  label: the permutation of
+    main.py:98-99 (vertex -> canonical id), None = identity.  A list of such frames is what FaustFrames takes."""
+    from .operators import geodesic_matrix_from_mesh
+
+    Vn = np.asarray(V.detach().cpu() if torch.is_tensor(V) else V)
+    Fn = np.asarray(F.detach().cpu() if torch.is_tensor(F) else F)
+    nv = Vn.shape[0]
+    label = np.arange(nv) if label is None else np.asarray(label.detach().cpu() if torch.is_tensor(label) else label)
+    if label.shape != (nv,) or not np.array_equal(np.sort(label), np.arange(nv)):
+        raise ValueError("faust_frame_from_mesh: label must be a permutation of the vertex ids")
+    ops = mesh_ops.mesh_operators(Vn.astype(np.float32).astype(np.float64), Fn)
+    Vd = torch.from_numpy(Vn.astype("f")).to(device)
+    Fd = torch.from_numpy(Fn.astype(np.int64)).to(device)
+    return {
+        "V": Vd, "F": Fd, "L": ops["L"], "Di": ops["Di"], "DiA": ops["DiA"],
+        "label": torch.from_numpy(label.astype(np.int64)).to(device),
+        "label_inv": torch.from_numpy(np.argsort(label).astype(np.int64)).to(device),
+        "G": geodesic_matrix_from_mesh(Vd, Fd, symmetric=symmetric),
+    }
 
 
 def faust_from_files(paths: Sequence[str], device="cuda", model="lap", pad_to=None, reorder="auto"):

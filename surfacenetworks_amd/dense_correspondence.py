@@ -19,7 +19,7 @@ import torch.nn.functional as F
 from . import kernels, mesh_ops
 from . import utils_pt as utils
 from .arap import make_adam
-from .operators import OperatorPool, SparseOperator
+from .operators import OperatorPool, SparseOperator, geodesic_matrix_from_mesh
 
 
 
@@ -731,9 +731,12 @@ def make_optimizer(model):
 class TorusBodies:
     """Synthetic stand-in for the FAUST .npz frames (main.py:65-104): torus-grid meshes (65 x 106 -> 6890 vertices,
     13 780 faces), padded to 7000 vertices (main.py:193), a random label permutation pair and a synthetic
-    'geodesic' matrix per shape."""
+    'geodesic' matrix per shape: geodesics="euclidean" (default) straight-line distances, "graph" shortest paths along the
+    mesh edges (operators.geodesic_matrix_from_mesh)."""
 
-    def __init__(self, count, n=65, m=106, pad_to=7000, seed=4, device="cuda"):
+    def __init__(self, count, n=65, m=106, pad_to=7000, seed=4, device="cuda", geodesics="euclidean"):
+        if geodesics not in ("euclidean", "graph"):
+            raise ValueError('geodesics: "euclidean" or "graph"')
         rng = np.random.default_rng(seed)
         self.device = torch.device(device)
         self.pad_to = pad_to
@@ -749,7 +752,8 @@ class TorusBodies:
                 "V": torch.from_numpy(V.astype(np.float32)).to(self.device),
                 "label": torch.from_numpy(label).to(self.device),
                 "label_inv": torch.from_numpy(np.argsort(label)).to(self.device),
-                "G": torch.cdist(G, G),                    # synthetic stand-in for dist_mat
+                "G": torch.cdist(G, G) if geodesics == "euclidean" else        # synthetic stand-in for dist_mat
+                     geodesic_matrix_from_mesh(G, torch.from_numpy(F_).to(self.device)),
             })
         self.pool_L = OperatorPool(mats, self.device)
         self.n = count

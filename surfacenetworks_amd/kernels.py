@@ -685,6 +685,94 @@ def laplacian_from_mesh(V, F):
     return rowptr, colind, vals
 
 
+def _check_graph(who: str, rowptr, colind, n: int) -> None:
+    if rowptr.dtype != torch.int32 or colind.dtype != torch.int32:
+        raise TypeError(f"{who} wants int32 rowptr and colind")
+    if rowptr.dim() != 1 or colind.dim() != 1 or rowptr.numel() != n + 1:
+        raise ValueError(f"{who}: rowptr must hold n + 1 = {n + 1} entries, got {tuple(rowptr.shape)}")
+    if not (rowptr.is_contiguous() and colind.is_contiguous()):
+        raise ValueError(f"{who} wants contiguous CSR arrays")
+
+
+def edge_lengths_csr(V, rowptr, colind):
+    """Euclidean length of every stored entry (i, colind[e]) of an n x n CSR pattern over the vertices V (n, 3) fp32:
+    (float) sqrt((dx*dx + dy*dy) + dz*dz) in fp64 without fused multiply-add (sn_edge_lengths_csr_f32), numpy's value bit for bit."""
+    _dev(V, rowptr, colind)
+    if V.dtype != torch.float32 or V.dim() != 2 or V.shape[1] != 3:
+        raise TypeError("edge_lengths_csr wants V (n, 3) float32")
+    n = V.shape[0]
+    _check_graph("edge_lengths_csr", rowptr, colind, n)
+    V = V.contiguous()
+    w = torch.empty(colind.numel(), dtype=torch.float32, device=V.device)
+    _lib.call("sn_edge_lengths_csr_f32", _p(V), _p(rowptr), _p(colind), n, _p(w), _stream())
+    return w
+
+
+def graph_apsp_max_vertices() -> int:
+    """The largest graph graph_apsp takes: one fp32 distance vector has to fit the LDS of a CU."""
+    return int(_lib.load().sn_graph_apsp_max_vertices())
+
+
+def graph_apsp(rowptr, colind, w, n: int, sources=None, out=None, sweeps=None):
+    """Shortest-path distances along the edges of a CSR graph with fp32 weights w >= 0 (sn_graph_apsp_f32; the definition is
+    in include/sn_spmm.h: path lengths accumulate in fp32 from the source outward, +inf where there is no path).
+    sources: None = every vertex, or a range(begin, end) of consecutive sources; row k of the result belongs to source
+    sources[k].  out: a (>= len(sources), >= n) float32 tensor with unit column stride to write into (its other elements are
+    left alone), else a new (len(sources), n) tensor.  sweeps: an int32 tensor that takes the sweep count of every workgroup.
+    Returns (D, unreached): unreached is a 1-element int32 device tensor, non-zero when a row holds +inf (not read here).
+    Raises for n > graph_apsp_max_vertices(): there is no other path."""
+    _dev(rowptr, colind, w, out, sweeps)
+    n = int(n)
+    _check_graph("graph_apsp", rowptr, colind, n)
+    if w.dtype != torch.float32 or w.shape != colind.shape or not w.is_contiguous():
+        raise TypeError("graph_apsp wants contiguous float32 weights, one per stored entry")
+    if sources is None:
+        sources = range(n)
+    if not isinstance(sources, range) or sources.step != 1:
+        raise TypeError("graph_apsp: sources must be None or a range of consecutive vertices")
+    begin, count = (sources.start, len(sources)) if len(sources) else (0, 0)
+    if begin < 0 or begin + count > n:
+        raise ValueError(f"graph_apsp: sources {sources} outside 0..{n}")
+    if n > graph_apsp_max_vertices():
+        raise _lib.SnError(f"graph_apsp: {n} vertices, the kernel holds at most {graph_apsp_max_vertices()} "
+                           "(one distance vector per LDS); there is no fallback")
+    if _debug_validate() and w.numel() and not bool((w >= 0).all()):
+        raise ValueError("graph_apsp: negative or NaN edge weight")
+    if out is None:
+        out = torch.empty(count, n, dtype=torch.float32, device=rowptr.device)
+    elif out.dtype != torch.float32 or out.shape[0] < count or out.shape[1] < n:
+        raise ValueError(f"graph_apsp: out must be float32 and at least ({count}, {n}), got {out.dtype} {tuple(out.shape)}")
+    unreached = torch.zeros(1, dtype=torch.int32, device=rowptr.device)
+    if sweeps is not None:
+        groups = -(-count // max(int(_lib.load().sn_graph_apsp_group(n)), 1))
+        if sweeps.dtype != torch.int32 or not sweeps.is_contiguous() or sweeps.numel() < groups:
+            raise ValueError(f"graph_apsp: sweeps must be contiguous int32 with at least {groups} entries")
+        _lib.call("sn_graph_apsp_sweeps_f32", _p(rowptr), _p(colind), _p(w), n, begin, count, _p(out), _ld(out), _p(unreached),
+                  _p(sweeps), _stream())
+    else:
+        _lib.call("sn_graph_apsp_f32", _p(rowptr), _p(colind), _p(w), n, begin, count, _p(out), _ld(out), _p(unreached), _stream())
+    return out, unreached
+
+
+def symmetrize_min_(G, n: int = None):
+    """In place G[i][j] = G[j][i] = min(G[i][j], G[j][i]) on the leading n x n block (default: all rows) of a float32 matrix
+    with unit column stride (sn_symmetrize_min_f32: tile pairs through LDS, no second matrix).  Returns G."""
+    _dev(G)
+    if G.dtype != torch.float32 or G.dim() != 2:
+        raise TypeError("symmetrize_min_ wants a 2-D float32 tensor")
+    n = G.shape[0] if n is None else int(n)
+    if n > G.shape[0] or n > G.shape[1]:
+        raise ValueError(f"symmetrize_min_: n = {n} exceeds the matrix {tuple(G.shape)}")
+    _lib.call("sn_symmetrize_min_f32", _p(G), n, _ld(G), _stream())
+    return G
+
+
+def _debug_validate() -> bool:
+    from . import operators
+
+    return operators._DEBUG_VALIDATE
+
+
 _gemm_variant = None
 
 

@@ -25,7 +25,7 @@ import torch
 from . import kernels
 
 __all__ = ["SparseOperator", "OperatorPool", "PackedSegments", "as_operator", "dirac_operators_from_mesh",
-           "laplacian_operator_from_mesh"]
+           "laplacian_operator_from_mesh", "geodesic_matrix_from_mesh"]
 
 # A BSR4 copy is kept when zero-fill costs at most this much extra storage over CSR entries.
 _BSR4_MAX_FILL = 1.6
@@ -419,6 +419,33 @@ def laplacian_operator_from_mesh(V: torch.Tensor, F: torch.Tensor) -> SparseOper
         Vg, Fg = V, F.to(torch.int32)
     rowptr, colind, vals = kernels.laplacian_from_mesh(Vg.float(), Fg)
     return SparseOperator(rowptr, colind, vals, (B * nV, B * nV), batch=B)
+
+
+def geodesic_matrix_from_mesh(V: torch.Tensor, F: torch.Tensor, symmetric: bool = True, require_connected: bool = True) -> torch.Tensor:
+    """(nV, nV) float32 matrix of shortest-path distances along the mesh edges, built on the device — the `dist_mat` the
+    reference reads from its FAUST frames (src/dense_correspondence/main.py:65-104) and computes nowhere.
+    The graph is the pattern of the device Laplacian (sn_laplacian_csr_from_mesh: the vertex adjacency plus the diagonal; an
+    edge whose cotangent weight is exactly zero is not stored there and is not walked here) with Euclidean edge lengths;
+    path lengths accumulate in fp32 from the source outward (definition and kernels: include/sn_spmm.h, sn_graph_apsp_f32).
+    symmetric: min(D, D^T) — D itself differs from its transpose by ulps.  A disconnected mesh raises ValueError when
+    require_connected, else keeps +inf between its components.  Synchronises (the pattern's size, the `unreached` flag).
+    Raises for more than kernels.graph_apsp_max_vertices() vertices: there is no other path."""
+    if V.dim() != 2 or V.shape[1] != 3 or F.dim() != 2 or F.shape[1] != 3:
+        raise ValueError(f"geodesic_matrix_from_mesh wants V (nV, 3) and F (nF, 3), got {tuple(V.shape)} and {tuple(F.shape)}")
+    kernels._dev(V, F)
+    nV = V.shape[0]
+    if nV > kernels.graph_apsp_max_vertices():
+        raise ValueError(f"geodesic_matrix_from_mesh: {nV} vertices, at most {kernels.graph_apsp_max_vertices()} are supported")
+    Vf = V.float().contiguous()
+    rowptr, colind, _ = kernels.laplacian_from_mesh(Vf, F.to(torch.int32))
+    w = kernels.edge_lengths_csr(Vf, rowptr, colind)
+    G, unreached = kernels.graph_apsp(rowptr, colind, w, nV)
+    if symmetric:
+        kernels.symmetrize_min_(G)
+    if require_connected and int(unreached.item()):
+        raise ValueError("geodesic_matrix_from_mesh: the mesh is disconnected (some vertex pairs have no edge path); pass "
+                         "require_connected=False to keep +inf between components")
+    return G
 
 
 class PackedSegments:
