@@ -796,6 +796,58 @@ int sn_graph_apsp_sweeps_f32(const int32_t *rowptr, const int32_t *colind, const
 int sn_symmetrize_min_f32(float *G, int64_t n, int64_t ld, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Geodesic distance matrices that cross triangles: first-order Eikonal sweeps on a triangle mesh (the Hopf-Lax form of the
+ * fast-marching / fast-iterative update, after Bornemann & Rasch).  A vertex pulls from the opposite edge of each incident
+ * triangle, not only from its neighbours; the edge paths above are the special case lambda = 0 or 1.
+ *
+ * Definition.  A corner is a face (i, j, k) seen from one of its vertices: (v; a, b), the other two vertices in face order —
+ *   (i; j, k), (j; k, i), (k; i, j).  A face with an index outside 0..nV-1 or with two equal indices contributes no corner and
+ *   raises the builder's flag.  Per-corner constants, P = the fp32 coordinates widened to fp64, every product and sum rounded
+ *   on its own (no fused multiply-add), three-term sums as (x + y) + z:
+ *     e = P_a - P_b,  c = sqrt(e.e),  q = P_b - P_v,  s_b = (q.e) / c,  h = sqrt((q x e).(q x e)) / c   (the cross-product
+ *     form, not q.q - s_b^2),  l_a, l_b = the fp32 edge weights of (v, a) and (v, b) by the formula above: bit-identical to
+ *     what sn_edge_lengths_csr_f32 returns.  In the plane of the triangle with the line through a and b as an axis, v's foot is
+ *     the origin, b lies at s_b, a at s_b + c, and v at height h.
+ *   Update of d[v] from one corner, d_a and d_b the stored fp32 values:
+ *     cand = min(fl32(d_a + l_a), fl32(d_b + l_b));
+ *     in fp64, Delta = d_a - d_b; only if c > 0, h > 0 and |Delta| < c (a NaN or infinite Delta fails this, as intended):
+ *       r = sqrt((c - Delta) * (c + Delta));  if s_b * r <= -(h * Delta) <= (s_b + c) * r:
+ *       t = d_b + (h * r - s_b * Delta) / c,  cand = min(cand, (float) t).
+ *     t is min over lambda in [0, 1] of d_b + lambda * Delta + |P_b + lambda * e - P_v| when the minimiser is interior; the
+ *     update is monotone and non-expansive in (d_a, d_b) and needs no causality test.
+ *   D[s][.] = the fixed point of d[v] = min(d[v], min over the corners of v of cand) reached from d = +inf, d[s] = 0; only
+ *   strict decreases are accepted.  Because the edge candidates are the edge kernel's own fp32 sums and fp32 addition is
+ *   monotone, D_triangles <= D_edges elementwise and EXACTLY (sn_graph_apsp_f32 on the same mesh).  Unlike the edge paths the
+ *   value is not bit-reproducible across relaxation orders: the fp64 evaluation is monotone only up to its rounding, so two
+ *   orders may differ by a few fp32 ulps.  First order: the error against the true surface distance falls with the mesh
+ *   width; obtuse triangles are not unfolded (the scheme stays valid there, only less accurate).  Not exact polyhedral
+ *   geodesics.
+ *
+ * Corner table: CSR by vertex.  cptr[nV + 1] int32, then per corner one record of SN_MESH_CORNER_BYTES = 40 bytes:
+ *   int32 a, b; float l_a, l_b; double c, s_b, h.  The order of the corners of a vertex is not deterministic (atomic cursor);
+ *   the minimum does not depend on it.
+ *
+ * sn_mesh_corners_f32        : cptr and the records from (V, F) on the device: count, scan, fill; `corners` holds 3 * nF
+ *                              records, the first cptr[nV] of them are written.  *status_flag (may be NULL) is cleared, then set
+ *                              to 1 when a face was dropped.  workspace: sn_mesh_corners_workspace_bytes(nV), else SN_E_WORKSPACE.
+ * sn_mesh_geodesics_f32      : rows src_begin .. src_begin+src_count-1 of D, out[(s - src_begin) * ldo + v]; dispatch, LDS
+ *                              layout and limits of sn_graph_apsp_f32 (sn_graph_apsp_group / _threads / _max_vertices).  At
+ *                              most n sweeps.  A corner whose a or b lies outside 0..n-1 is skipped.  *flags (may be NULL;
+ *                              the caller clears it) is OR-ed with 1 when a written row holds +inf and with 2 when the n-th
+ *                              sweep of a workgroup still changed something (not converged).  corners == NULL declares a
+ *                              table without corners.  Status codes as sn_graph_apsp_f32.
+ * sn_mesh_geodesics_sweeps_f32: the same, and sweeps[g] (may be NULL) = the number of sweeps workgroup g ran.
+ * ------------------------------------------------------------------------------------------ */
+#define SN_MESH_CORNER_BYTES 40
+size_t sn_mesh_corners_workspace_bytes(int64_t nV);
+int sn_mesh_corners_f32(const float *V, const int32_t *F, int64_t nV, int64_t nF, int32_t *cptr, void *corners,
+                        int32_t *status_flag, void *workspace, size_t workspace_bytes, void *stream);
+int sn_mesh_geodesics_f32(const int32_t *cptr, const void *corners, int64_t n, int64_t src_begin, int64_t src_count,
+                          float *out, int64_t ldo, int32_t *flags, void *stream);
+int sn_mesh_geodesics_sweeps_f32(const int32_t *cptr, const void *corners, int64_t n, int64_t src_begin, int64_t src_count,
+                                 float *out, int64_t ldo, int32_t *flags, int32_t *sweeps, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Row-streaming fp32 GEMMs of the per-node Linear layers with the weights held in registers
  * (v_mfma_f32_32x32x2_f32; the operands are tall-skinny: rows ~ 1e5..1e6, K and N in {128, 256}).
  *

@@ -138,6 +138,10 @@ SIGNATURES = {
     "sn_graph_apsp_f32": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
     "sn_graph_apsp_sweeps_f32": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
     "sn_symmetrize_min_f32": (C.c_int, [_vp, _i64, _i64, _vp]),
+    "sn_mesh_corners_workspace_bytes": (_sz, [_i64]),
+    "sn_mesh_corners_f32": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sn_mesh_geodesics_f32": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "sn_mesh_geodesics_sweeps_f32": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
     "sn_linear_fwd_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
     "sn_linear_fwd_stats_blocks": (_i32, [_i64]),
     "sn_linear_fwd_tiles_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),

@@ -449,6 +449,146 @@ int apsp_launch(const int *rowptr, const int *colind, const float *w, int n, int
   return launch_status();
 }
 
+// ------------------------------------------------------------------------------------------------
+// Geodesic distance matrices that cross triangles: first-order Eikonal sweeps (definition: sn_spmm.h).
+// ------------------------------------------------------------------------------------------------
+struct MeshCorner {      // (v; a, b): the record of the header, 40 bytes
+  int a, b;
+  float la, lb;
+  double c, sb, h;
+};
+static_assert(sizeof(MeshCorner) == SN_MESH_CORNER_BYTES, "corner record layout");
+
+// a face contributes its three corners only when its indices are three distinct vertices of the mesh
+__device__ __forceinline__ bool face_ok(int i, int j, int k, int64_t nV) {
+  return (unsigned)i < (unsigned)nV && (unsigned)j < (unsigned)nV && (unsigned)k < (unsigned)nV && i != j && j != k && k != i;
+}
+
+__global__ __launch_bounds__(kWG) void corner_count_k(const int *__restrict__ F, int64_t nF, int64_t nV, int *__restrict__ count,
+                                                      int *__restrict__ status_flag) {
+  for (int64_t f = (int64_t)blockIdx.x * kWG + threadIdx.x; f < nF; f += (int64_t)gridDim.x * kWG) {
+    const int i = F[3 * f], j = F[3 * f + 1], k = F[3 * f + 2];
+    if (!face_ok(i, j, k, nV)) {
+      if (status_flag) atomicExch(status_flag, 1);
+      continue;
+    }
+    atomicAdd(&count[i], 1);
+    atomicAdd(&count[j], 1);
+    atomicAdd(&count[k], 1);
+  }
+}
+
+__global__ __launch_bounds__(kWG) void corner_fill_k(const float *__restrict__ V, const int *__restrict__ F, int64_t nF, int64_t nV,
+                                                     int *__restrict__ cursor, MeshCorner *__restrict__ rec) {
+  for (int64_t f = (int64_t)blockIdx.x * kWG + threadIdx.x; f < nF; f += (int64_t)gridDim.x * kWG) {
+    const int idx[3] = {F[3 * f], F[3 * f + 1], F[3 * f + 2]};
+    if (!face_ok(idx[0], idx[1], idx[2], nV)) continue;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const int v = idx[k], a = idx[(k + 1) % 3], b = idx[(k + 2) % 3];
+      const double ex = (double)V[3 * a] - (double)V[3 * b], ey = (double)V[3 * a + 1] - (double)V[3 * b + 1],
+                   ez = (double)V[3 * a + 2] - (double)V[3 * b + 2];
+      const double qx = (double)V[3 * b] - (double)V[3 * v], qy = (double)V[3 * b + 1] - (double)V[3 * v + 1],
+                   qz = (double)V[3 * b + 2] - (double)V[3 * v + 2];
+      const double nx = qy * ez - qz * ey, ny = qz * ex - qx * ez, nz = qx * ey - qy * ex;
+      MeshCorner r;
+      r.a = a;
+      r.b = b;
+      r.la = (float)edge_len(V, v, a);
+      r.lb = (float)edge_len(V, v, b);
+      r.c = sqrt((ex * ex + ey * ey) + ez * ez);
+      r.sb = ((qx * ex + qy * ey) + qz * ez) / r.c;
+      r.h = sqrt((nx * nx + ny * ny) + nz * nz) / r.c;
+      rec[atomicAdd(&cursor[v], 1)] = r;
+    }
+  }
+}
+
+// graph_apsp_k with a richer candidate set: thread t owns vertices t, t + threads, ... and loops over their corners; a
+// corner's constants are loaded once and applied to all S sources.  Same LDS layout, flags, barrier and single-writer rule.
+// A neighbour's word is read old or new; both are upper bounds that some path realises, so what a sweep writes is one too,
+// and a sweep that changed nothing has read only final values: the result is a fixed point of the header's update.
+template <int S>
+__global__ __launch_bounds__(kApspMaxWG) void mesh_geodesics_k(const int *__restrict__ cptr, const MeshCorner *__restrict__ rec, int n,
+                                                                int src_begin, int src_count, float *__restrict__ out, int64_t ldo,
+                                                                int *__restrict__ flags, int *__restrict__ sweeps) {
+  extern __shared__ __align__(16) unsigned char apsp_lds[];
+  int *flag = reinterpret_cast<int *>(apsp_lds);
+  float *d = reinterpret_cast<float *>(apsp_lds + kApspHead);
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int s0 = src_begin + (int)blockIdx.x * S;
+  const int ns = min(S, src_begin + src_count - s0);
+  for (int i = tid; i < n * S; i += nt) d[i] = INFINITY;
+  if (tid < 3) flag[tid] = 0;
+  __syncthreads();
+  if (tid < ns) d[(s0 + tid) * S + tid] = 0.0f;
+  __syncthreads();
+  int it = 0;
+  if (rec != nullptr)
+    for (; it < n; ++it) {
+      if (tid == 0) flag[(it + 1) % 3] = 0;
+      bool changed = false;
+      for (int v = tid; v < n; v += nt) {
+        float cur[S], best[S];
+#pragma unroll
+        for (int j = 0; j < S; ++j) best[j] = cur[j] = d[v * S + j];
+        const int cb = cptr[v], ce = cptr[v + 1];
+        for (int e = cb; e < ce; ++e) {
+          const MeshCorner k = rec[e];
+          if ((unsigned)k.a >= (unsigned)n || (unsigned)k.b >= (unsigned)n) continue;      // never index LDS by a vertex the mesh does not have
+          const bool tri = k.c > 0 && k.h > 0;
+#pragma unroll
+          for (int j = 0; j < S; ++j) {
+            const float da = d[k.a * S + j], db = d[k.b * S + j];
+            float cand = fminf(da + k.la, db + k.lb);
+            const double delta = (double)da - (double)db;
+            if (tri && fabs(delta) < k.c) {                       // false for a NaN or infinite delta
+              const double r = sqrt((k.c - delta) * (k.c + delta));
+              const double m = -(k.h * delta);
+              if (k.sb * r <= m && m <= (k.sb + k.c) * r) cand = fminf(cand, (float)((double)db + (k.h * r - k.sb * delta) / k.c));
+            }
+            best[j] = fminf(best[j], cand);
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < S; ++j)
+          if (best[j] < cur[j]) {
+            d[v * S + j] = best[j];
+            changed = true;
+          }
+      }
+      if (changed) flag[it % 3] = 1;
+      __syncthreads();
+      if (!flag[it % 3]) break;
+    }
+  if (sweeps != nullptr && tid == 0) sweeps[blockIdx.x] = it < n ? it + 1 : n;
+  bool inf_left = false;
+  for (int j = 0; j < ns; ++j) {
+    float *row = out + (int64_t)(s0 - src_begin + j) * ldo;
+    for (int v = tid; v < n; v += nt) {
+      const float x = d[v * S + j];
+      inf_left |= (x == INFINITY);
+      __builtin_nontemporal_store(x, row + v);
+    }
+  }
+  if (flags != nullptr) {
+    if (inf_left) atomicOr(flags, 1);
+    if (it == n && tid == 0) atomicOr(flags, 2);                  // the n-th sweep still changed something
+  }
+}
+
+template <int S>
+int mesh_geodesics_launch(const int *cptr, const MeshCorner *rec, int n, int src_begin, int src_count, float *out, int64_t ldo,
+                          int *flags, int *sweeps, hipStream_t s) {
+  const size_t lds = (size_t)kApspHead + (size_t)4 * S * n;
+  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(mesh_geodesics_k<S>),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, kApspLds);
+  if (attr != hipSuccess) return (int)attr;
+  hipLaunchKernelGGL((mesh_geodesics_k<S>), dim3((unsigned)((src_count + S - 1) / S)), dim3(apsp_threads(n)), lds, s, cptr, rec, n,
+                     src_begin, src_count, out, ldo, flags, sweeps);
+  return launch_status();
+}
+
 inline size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 }  // namespace
@@ -600,6 +740,67 @@ int sn_symmetrize_min_f32(float *G, int64_t n, int64_t ld, void *stream) {
   if (nt > 65535) return SN_E_RANGE;
   hipLaunchKernelGGL(symmetrize_min_k, dim3((unsigned)nt, (unsigned)nt), dim3(kWG), 0, static_cast<hipStream_t>(stream), G, n, ld);
   return launch_status();
+}
+
+size_t sn_mesh_corners_workspace_bytes(int64_t nV) {
+  if (nV < 0) nV = 0;
+  const size_t scan = (size_t)((nV + 1 + kScanTile - 1) / kScanTile + 1) * sizeof(int);
+  return align16((size_t)(nV + 1) * sizeof(int)) + align16(scan);
+}
+
+int sn_mesh_corners_f32(const float *V, const int32_t *F, int64_t nV, int64_t nF, int32_t *cptr, void *corners,
+                        int32_t *status_flag, void *workspace, size_t workspace_bytes, void *stream) {
+  (void)hipGetLastError();
+  if (nV < 0 || nF < 0) return SN_E_SHAPE;
+  if (nV + 1 > INT_MAX || 3 * nF > INT_MAX) return SN_E_RANGE;
+  if (!cptr) return SN_E_NULL;
+  if (nF > 0 && (!V || !F || !corners)) return SN_E_NULL;
+  if (workspace_bytes < sn_mesh_corners_workspace_bytes(nV) || !workspace) return SN_E_WORKSPACE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  char *w = static_cast<char *>(workspace);
+  int *cursor = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
+  int *sums = reinterpret_cast<int *>(w);
+  hipError_t e = sn_internal_fill(cptr, 0, (size_t)(nV + 1) * sizeof(int), s);
+  if (e != hipSuccess) return (int)e;
+  if (status_flag) {
+    e = sn_internal_fill(status_flag, 0, sizeof(int), s);
+    if (e != hipSuccess) return (int)e;
+  }
+  if (nF > 0) hipLaunchKernelGGL(corner_count_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, nV, cptr, status_flag);
+  const int64_t n = nV + 1;
+  const int nblk = (int)((n + kScanTile - 1) / kScanTile);
+  hipLaunchKernelGGL(scan_sums_k, dim3(nblk), dim3(kWG), 0, s, cptr, n, sums);
+  hipLaunchKernelGGL(scan_top_k, dim3(1), dim3(kWG), 0, s, sums, nblk);
+  hipLaunchKernelGGL(scan_apply_k, dim3(nblk), dim3(kWG), 0, s, cptr, n, sums, cptr);
+  e = sn_internal_copy2d(cursor, 0, cptr, 0, (int64_t)((size_t)(nV + 1) * sizeof(int)), 1, s);
+  if (e != hipSuccess) return (int)e;
+  if (nF > 0)
+    hipLaunchKernelGGL(corner_fill_k, dim3(grid_for(nF)), dim3(kWG), 0, s, V, F, nF, nV, cursor, static_cast<MeshCorner *>(corners));
+  return launch_status();
+}
+
+int sn_mesh_geodesics_sweeps_f32(const int32_t *cptr, const void *corners, int64_t n, int64_t src_begin, int64_t src_count,
+                                 float *out, int64_t ldo, int32_t *flags, int32_t *sweeps, void *stream) {
+  (void)hipGetLastError();
+  if (n < 0 || src_begin < 0 || src_count < 0 || src_begin + src_count > n) return SN_E_SHAPE;
+  if (n > kApspMaxN) return SN_E_UNSUPPORTED;                    // S = 1 no longer fits the LDS: nothing is launched
+  if (src_count == 0) return SN_OK;
+  if (!cptr || !out) return SN_E_NULL;
+  if (ldo < n) return SN_E_LD;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const MeshCorner *rec = static_cast<const MeshCorner *>(corners);
+  const int ni = (int)n, sb = (int)src_begin, sc = (int)src_count;
+  switch (apsp_group(n)) {
+    case 8: return mesh_geodesics_launch<8>(cptr, rec, ni, sb, sc, out, ldo, flags, sweeps, s);
+    case 4: return mesh_geodesics_launch<4>(cptr, rec, ni, sb, sc, out, ldo, flags, sweeps, s);
+    case 2: return mesh_geodesics_launch<2>(cptr, rec, ni, sb, sc, out, ldo, flags, sweeps, s);
+    default: return mesh_geodesics_launch<1>(cptr, rec, ni, sb, sc, out, ldo, flags, sweeps, s);
+  }
+}
+
+int sn_mesh_geodesics_f32(const int32_t *cptr, const void *corners, int64_t n, int64_t src_begin, int64_t src_count,
+                          float *out, int64_t ldo, int32_t *flags, void *stream) {
+  return sn_mesh_geodesics_sweeps_f32(cptr, corners, n, src_begin, src_count, out, ldo, flags, nullptr, stream);
 }
 
 }  // extern "C"

@@ -159,13 +159,16 @@ def load_faust_frame(path: str, device="cuda") -> Dict:
     return fr
 
 
-def faust_frame_from_mesh(V, F, label=None, device="cuda", symmetric=True) -> Dict:
+def faust_frame_from_mesh(V, F, label=None, device="cuda", symmetric=True, geodesics="edges") -> Dict:
     """The frame dict of load_faust_frame from a raw triangle mesh: V (nV, 3), F (nF, 3) (numpy or tensors), host scipy
     L / Di / DiA from mesh_ops.mesh_operators, and G — the `dist_mat` the reference's files bring along — computed on the device
-    by operators.geodesic_matrix_from_mesh (edge-path distances; symmetric: min(D, D^T)).  label: the permutation of
+    by operators.geodesic_matrix_from_mesh (geodesics="edges": edge-path distances, "triangles": paths that cross the faces;
+    symmetric: min(D, D^T)).  label: the permutation of
     main.py:98-99 (vertex -> canonical id), None = identity.  A list of such frames is what FaustFrames takes."""
     from .operators import geodesic_matrix_from_mesh
 
+    if geodesics not in ("edges", "triangles"):
+        raise ValueError(f'faust_frame_from_mesh: geodesics must be "edges" or "triangles", got {geodesics!r}')
     Vn = np.asarray(V.detach().cpu() if torch.is_tensor(V) else V)
     Fn = np.asarray(F.detach().cpu() if torch.is_tensor(F) else F)
     nv = Vn.shape[0]
@@ -179,7 +182,7 @@ def faust_frame_from_mesh(V, F, label=None, device="cuda", symmetric=True) -> Di
         "V": Vd, "F": Fd, "L": ops["L"], "Di": ops["Di"], "DiA": ops["DiA"],
         "label": torch.from_numpy(label.astype(np.int64)).to(device),
         "label_inv": torch.from_numpy(np.argsort(label).astype(np.int64)).to(device),
-        "G": geodesic_matrix_from_mesh(Vd, Fd, symmetric=symmetric),
+        "G": geodesic_matrix_from_mesh(Vd, Fd, symmetric=symmetric, method=geodesics),
     }
 
 

@@ -732,11 +732,11 @@ class TorusBodies:
     """Synthetic stand-in for the FAUST .npz frames (main.py:65-104): torus-grid meshes (65 x 106 -> 6890 vertices,
     13 780 faces), padded to 7000 vertices (main.py:193), a random label permutation pair and a synthetic
     'geodesic' matrix per shape: geodesics="euclidean" (default) straight-line distances, "graph" shortest paths along the
-    mesh edges (operators.geodesic_matrix_from_mesh)."""
+    mesh edges, "triangles" paths that cross the faces (operators.geodesic_matrix_from_mesh, method "edges" / "triangles")."""
 
     def __init__(self, count, n=65, m=106, pad_to=7000, seed=4, device="cuda", geodesics="euclidean"):
-        if geodesics not in ("euclidean", "graph"):
-            raise ValueError('geodesics: "euclidean" or "graph"')
+        if geodesics not in ("euclidean", "graph", "triangles"):
+            raise ValueError('geodesics: "euclidean", "graph" or "triangles"')
         rng = np.random.default_rng(seed)
         self.device = torch.device(device)
         self.pad_to = pad_to
@@ -753,7 +753,8 @@ class TorusBodies:
                 "label": torch.from_numpy(label).to(self.device),
                 "label_inv": torch.from_numpy(np.argsort(label)).to(self.device),
                 "G": torch.cdist(G, G) if geodesics == "euclidean" else        # synthetic stand-in for dist_mat
-                     geodesic_matrix_from_mesh(G, torch.from_numpy(F_).to(self.device)),
+                     geodesic_matrix_from_mesh(G, torch.from_numpy(F_).to(self.device),
+                                               method="edges" if geodesics == "graph" else "triangles"),
             })
         self.pool_L = OperatorPool(mats, self.device)
         self.n = count

@@ -767,6 +767,85 @@ def symmetrize_min_(G, n: int = None):
     return G
 
 
+MESH_CORNER_BYTES = 40        # SN_MESH_CORNER_BYTES: int32 a, b; float l_a, l_b; double c, s_b, h
+
+
+class MeshCorners:
+    """Corner table of a triangle mesh (include/sn_spmm.h, "Geodesic distance matrices that cross triangles"): a CSR by
+    vertex.  cptr: (n + 1,) int32; records: (3 * nF, 40) uint8, the first cptr[n] rows are written, one record per corner
+    (v; a, b): int32 a, b; float l_a, l_b; double c, s_b, h."""
+
+    def __init__(self, cptr, records):
+        self.cptr, self.records = cptr, records
+
+    @property
+    def n(self) -> int:
+        return self.cptr.numel() - 1
+
+
+def _mesh_corner_table(V, F):
+    """(MeshCorners, flag): flag is a 1-element int32 device tensor, 1 when a face was dropped (not read here)."""
+    _dev(V, F)
+    if V.dtype != torch.float32 or F.dtype != torch.int32 or V.dim() != 2 or V.shape[1] != 3 or F.dim() != 2 or F.shape[1] != 3:
+        raise TypeError("mesh_corners wants V (nV, 3) float32 and F (nF, 3) int32")
+    V, F = V.contiguous(), F.contiguous()
+    nV, nF = V.shape[0], F.shape[0]
+    dev = V.device
+    cptr = torch.empty(nV + 1, dtype=torch.int32, device=dev)
+    records = torch.empty(3 * nF, MESH_CORNER_BYTES, dtype=torch.uint8, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws_bytes = int(_lib.load().sn_mesh_corners_workspace_bytes(nV))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    _lib.call("sn_mesh_corners_f32", _p(V), _p(F), nV, nF, _p(cptr), _p(records), _p(flag), _p(ws), ws_bytes, _stream())
+    return MeshCorners(cptr, records), flag
+
+
+def mesh_corners(V, F) -> MeshCorners:
+    """Corner table of one mesh built on the device (sn_mesh_corners_f32): what mesh_geodesics sweeps over.  V: (nV, 3) fp32,
+    F: (nF, 3) int32.  Synchronises once (reads the flag); a face with an index outside the mesh or a repeated index raises."""
+    corners, flag = _mesh_corner_table(V, F)
+    if int(flag.item()):
+        raise _lib.SnError("mesh_corners: a face has an index outside 0..nV-1 or a repeated index")
+    return corners
+
+
+def mesh_geodesics(corners: MeshCorners, n: int, sources=None, out=None, sweeps=None):
+    """Geodesic distances that cross triangles: first-order Eikonal sweeps over a corner table (sn_mesh_geodesics_f32; the
+    definition is in include/sn_spmm.h).  sources / out / sweeps as graph_apsp.  Returns (D, flags): flags is a 1-element int32
+    device tensor, bit 1 when a row holds +inf, bit 2 when a workgroup's n-th sweep still changed something (not read here).
+    Raises for n > graph_apsp_max_vertices(): there is no other path."""
+    _dev(corners.cptr, corners.records, out, sweeps)
+    n = int(n)
+    cptr, rec = corners.cptr, corners.records
+    if cptr.dtype != torch.int32 or cptr.dim() != 1 or cptr.numel() != n + 1 or not cptr.is_contiguous():
+        raise ValueError(f"mesh_geodesics: cptr must be contiguous int32 with n + 1 = {n + 1} entries, got {tuple(cptr.shape)}")
+    if rec.dtype != torch.uint8 or rec.dim() != 2 or rec.shape[1] != MESH_CORNER_BYTES or not rec.is_contiguous():
+        raise TypeError(f"mesh_geodesics wants contiguous (corners, {MESH_CORNER_BYTES}) uint8 records")
+    if sources is None:
+        sources = range(n)
+    if not isinstance(sources, range) or sources.step != 1:
+        raise TypeError("mesh_geodesics: sources must be None or a range of consecutive vertices")
+    begin, count = (sources.start, len(sources)) if len(sources) else (0, 0)
+    if begin < 0 or begin + count > n:
+        raise ValueError(f"mesh_geodesics: sources {sources} outside 0..{n}")
+    if n > graph_apsp_max_vertices():
+        raise _lib.SnError(f"mesh_geodesics: {n} vertices, the kernel holds at most {graph_apsp_max_vertices()} "
+                           "(one distance vector per LDS); there is no fallback")
+    if out is None:
+        out = torch.empty(count, n, dtype=torch.float32, device=cptr.device)
+    elif out.dtype != torch.float32 or out.shape[0] < count or out.shape[1] < n:
+        raise ValueError(f"mesh_geodesics: out must be float32 and at least ({count}, {n}), got {out.dtype} {tuple(out.shape)}")
+    flags = torch.zeros(1, dtype=torch.int32, device=cptr.device)
+    if sweeps is not None:
+        groups = -(-count // max(int(_lib.load().sn_graph_apsp_group(n)), 1))
+        if sweeps.dtype != torch.int32 or not sweeps.is_contiguous() or sweeps.numel() < groups:
+            raise ValueError(f"mesh_geodesics: sweeps must be contiguous int32 with at least {groups} entries")
+        _lib.call("sn_mesh_geodesics_sweeps_f32", _p(cptr), _p(rec), n, begin, count, _p(out), _ld(out), _p(flags), _p(sweeps), _stream())
+    else:
+        _lib.call("sn_mesh_geodesics_f32", _p(cptr), _p(rec), n, begin, count, _p(out), _ld(out), _p(flags), _stream())
+    return out, flags
+
+
 def _debug_validate() -> bool:
     from . import operators
 

@@ -421,7 +421,8 @@ def laplacian_operator_from_mesh(V: torch.Tensor, F: torch.Tensor) -> SparseOper
     return SparseOperator(rowptr, colind, vals, (B * nV, B * nV), batch=B)
 
 
-def geodesic_matrix_from_mesh(V: torch.Tensor, F: torch.Tensor, symmetric: bool = True, require_connected: bool = True) -> torch.Tensor:
+def geodesic_matrix_from_mesh(V: torch.Tensor, F: torch.Tensor, symmetric: bool = True, require_connected: bool = True,
+                              method: str = "edges") -> torch.Tensor:
     """(nV, nV) float32 matrix of shortest-path distances along the mesh edges, built on the device — the `dist_mat` the
     reference reads from its FAUST frames (src/dense_correspondence/main.py:65-104) and computes nowhere.
     The graph is the pattern of the device Laplacian (sn_laplacian_csr_from_mesh: the vertex adjacency plus the diagonal; an
@@ -429,7 +430,13 @@ def geodesic_matrix_from_mesh(V: torch.Tensor, F: torch.Tensor, symmetric: bool 
     path lengths accumulate in fp32 from the source outward (definition and kernels: include/sn_spmm.h, sn_graph_apsp_f32).
     symmetric: min(D, D^T) — D itself differs from its transpose by ulps.  A disconnected mesh raises ValueError when
     require_connected, else keeps +inf between its components.  Synchronises (the pattern's size, the `unreached` flag).
-    Raises for more than kernels.graph_apsp_max_vertices() vertices: there is no other path."""
+    Raises for more than kernels.graph_apsp_max_vertices() vertices: there is no other path.
+    method: "edges" (default) as above; "triangles" lets a path cross the faces — first-order Eikonal sweeps over the mesh's
+    corner table (sn_mesh_corners_f32, sn_mesh_geodesics_f32; every face counts, whatever its cotangent weights), entrywise
+    <= the "edges" matrix and a few fp32 ulps from bit-reproducible.  A face with a repeated or out-of-range index raises
+    there; a run that has not converged after nV sweeps raises RuntimeError."""
+    if method not in ("edges", "triangles"):
+        raise ValueError(f'geodesic_matrix_from_mesh: method must be "edges" or "triangles", got {method!r}')
     if V.dim() != 2 or V.shape[1] != 3 or F.dim() != 2 or F.shape[1] != 3:
         raise ValueError(f"geodesic_matrix_from_mesh wants V (nV, 3) and F (nF, 3), got {tuple(V.shape)} and {tuple(F.shape)}")
     kernels._dev(V, F)
@@ -437,12 +444,18 @@ def geodesic_matrix_from_mesh(V: torch.Tensor, F: torch.Tensor, symmetric: bool 
     if nV > kernels.graph_apsp_max_vertices():
         raise ValueError(f"geodesic_matrix_from_mesh: {nV} vertices, at most {kernels.graph_apsp_max_vertices()} are supported")
     Vf = V.float().contiguous()
-    rowptr, colind, _ = kernels.laplacian_from_mesh(Vf, F.to(torch.int32))
-    w = kernels.edge_lengths_csr(Vf, rowptr, colind)
-    G, unreached = kernels.graph_apsp(rowptr, colind, w, nV)
+    if method == "triangles":
+        G, unreached = kernels.mesh_geodesics(kernels.mesh_corners(Vf, F.to(torch.int32)), nV)
+    else:
+        rowptr, colind, _ = kernels.laplacian_from_mesh(Vf, F.to(torch.int32))
+        w = kernels.edge_lengths_csr(Vf, rowptr, colind)
+        G, unreached = kernels.graph_apsp(rowptr, colind, w, nV)
     if symmetric:
         kernels.symmetrize_min_(G)
-    if require_connected and int(unreached.item()):
+    flags = int(unreached.item())
+    if flags & 2:
+        raise RuntimeError(f"geodesic_matrix_from_mesh: the Eikonal sweeps had not converged after {nV} sweeps")
+    if require_connected and flags & 1:
         raise ValueError("geodesic_matrix_from_mesh: the mesh is disconnected (some vertex pairs have no edge path); pass "
                          "require_connected=False to keep +inf between components")
     return G
