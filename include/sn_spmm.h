@@ -848,6 +848,90 @@ int sn_mesh_geodesics_sweeps_f32(const int32_t *cptr, const void *corners, int64
                                  float *out, int64_t ldo, int32_t *flags, int32_t *sweeps, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Intrinsic Delaunay Laplacian: edge flips from (V, F) on the device, then L = A^-1 (D - W) on the flipped triangulation.
+ *
+ * Replaces: mesh.intrinsic_laplacian(V, F)   src/dense_correspondence/main.py:87, src/normal_predict/sampler.py:68 — the
+ *           reference imports an unpublished module for it.  Scaling and sign of that matrix are unknown: this is the
+ *           project's A^-1 (D - W) on the intrinsic Delaunay triangulation (Bobenko & Springborn 2007; the flip algorithm
+ *           of Fisher et al. 2006), NOT a reproduction of it.
+ *
+ * Input.  V fp32 (nV, 3), F int32 (nF, 3): manifold, consistently oriented, possibly with boundary.  Refusals through the
+ *   status word (nothing is flipped then): SN_IDT_BAD_FACE a face with an index outside 0..nV-1 or a repeated index;
+ *   SN_IDT_NON_MANIFOLD an edge with more than two faces; SN_IDT_ORIENTATION an edge whose two faces traverse it in the same
+ *   direction.
+ * State.  Faces F' (nF, 3); fp64 side lengths l' (nF, 3), l'[f] = (|v0 v1|, |v1 v2|, |v2 v0|); glue map G (nF, 3) of face-side
+ *   codes 3 g + t, -1 on the boundary.  A Delta-complex, not a simplicial complex: after flips two faces may share two edges,
+ *   a face may have a self-edge (both ends the same vertex), one vertex pair may carry several edges — everything is keyed by
+ *   face sides, never by vertex pairs.  Start: F' = F, l' in fp64 from the fp32 coordinates as sqrt((dx*dx + dy*dy) + dz*dz), G
+ *   from F.
+ * Delaunay test of an interior side (f, s) glued to (g, t), f != g: a = the shared length, b, c the other two sides of a face,
+ *   cot = ((b*b + c*c) - a*a) / (4 A), A = sqrt(h (h-a) (h-b) (h-c)), h = ((a + b) + c) / 2 in fp64.  The side is
+ *   non-Delaunay iff cot_f + cot_g < SN_IDT_THRESHOLD = -1e-12 (part of the definition; the sums are dimensionless).  A face
+ *   whose Heron radicand is <= 0 is degenerate: its sides are never flipped and SN_IDT_DEGENERATE is set when one is tested.
+ *   A side glued to another side of its own face is always Delaunay and is never flipped.
+ * Flip.  Both faces rotated so that the shared side is side 0, f = (i, j, k), g = (j, i, m):  f = (k, i, m) with lengths
+ *   (l_ki, l_im, l_km), g = (m, j, k) with (l_mj, l_jk, l_km).  l_km from the planar layout i = (0, 0), j = (a, 0):
+ *   x_k = ((a*a + l_ki*l_ki) - l_jk*l_jk) / (2a), y_k = sqrt(max((l_ki - x_k)(l_ki + x_k), 0)) >= 0, likewise x_m from
+ *   (l_im, l_mj) and y_m <= 0, l_km = sqrt(dx*dx + dy*dy).  Sides 2 of the new faces are glued to each other; the four outer
+ *   sides keep their partners — a partner that is itself one of the four old outer sides is remapped first (the
+ *   Delta-complex case).
+ * Result.  The fixed point: no interior side is non-Delaunay; unique in connectivity unless four vertices are cocircular,
+ *   whatever the flip order.  A round is two launches (kernel boundaries are the only cross-workgroup ordering): idt_claim_k —
+ *   every non-Delaunay side with 3f+s < 3g+t writes its 64-bit word (0xFFFFF - round, a 12-bit hash of (side code, round),
+ *   side code) by integer atomic min into a claim word of f, of g and of the up to four faces across their outer sides;
+ *   idt_flip_k — a side that holds all its claims flips, and nobody else reads or writes those faces in that round.  The
+ *   words of a round are distinct (the code is in them), so the smallest one always wins: every round with work makes
+ *   progress, the schedule is a function of the input alone and two runs are bit-identical.  The hash shuffles the priority
+ *   per round; the bare code leaves chains of waiting sides along the face numbering (1569 rounds instead of 27 on a
+ *   6890-vertex torus).  Rounds past convergence are no-ops.  max_rounds <= 2^20, else SN_E_RANGE.
+ *   SN_IDT_NOT_CONVERGED: round max_rounds - 1 still found a non-Delaunay side.
+ * Laplacian of (F', l'), this project's convention: a = Heron area with the 1e-6 floor; for every face and every ordered
+ *   pair (p, q, r) of its corners (the six permutations in lexicographic order), i = F'[p], j = F'[q]:
+ *     W[i, j] += ((-l_pq^2 + l_qr^2) + l_rp^2) / (8a + 1e-6),  d[i] += ((-l_pq^2 + l_rp^2) + l_qr^2) / (8a + 1e-6)  (the
+ *     mirror term W[j, i]: d = column sums of W),  A[i] += a / 3 / 4;  a pair with i == j (a self-edge) adds its mass only:
+ *     W[i, i] cancels in D - W.  L[i, j] = (0 - W[i, j]) / (A[i] + 1e-9), L[i, i] = d[i] / (A[i] + 1e-9), fp64, rounded once
+ *     to fp32.  Pattern: every vertex pair joined by at least one intrinsic edge plus the whole diagonal, stored whatever the
+ *     value (nothing is dropped for being zero: the pattern does not depend on rounding), columns ascending.  Every sum runs
+ *     serially over its contributions sorted by (face, permutation): no floating-point atomics.  No SN_LAP_MAX_DEGREE limit.
+ *
+ * sn_mesh_glue_i32          : G (3 nF) from F through a by-vertex bucket of sides; *status is cleared, then OR-ed with the
+ *                             refusal bits.  V and l both non-NULL: also the start lengths l (3 nF fp64); both NULL: glue only.
+ *                             A refused face gets G = -1 and l = 0.  workspace: sn_mesh_glue_workspace_bytes(nV, nF).
+ * sn_mesh_idt_rounds_f64    : rounds round_begin .. round_begin + round_count - 1 of at most max_rounds on (F', l', G) in
+ *                             place.  counters (2 * max_rounds int32, caller-owned): counters[2r] = non-Delaunay sides found
+ *                             in round r, counters[2r + 1] = flips done; this call clears its own rounds' pairs first.  The
+ *                             kernels return at once when *status holds a refusal bit.  workspace:
+ *                             sn_mesh_idt_workspace_bytes(nF), the same buffer for every call of one run (round 0 resets it).
+ *                             A caller enqueues rounds in chunks and reads the counters once per chunk; a round that found
+ *                             nothing is the fixed point.
+ * sn_mesh_idt_laplacian_f32 : three phases on one workspace (sn_mesh_idt_laplacian_workspace_bytes(nV, nF)), N =
+ *                             sn_mesh_idt_laplacian_items(nV, nF) = 12 nF + nV.  phase 0 writes keys[N] (int64, one per
+ *                             contribution; INT64_MAX = none) — the caller sorts them ascending and keeps the permutation
+ *                             (order[t] = source index of sorted position t).  phase 1 (count), keys = the SORTED keys: writes
+ *                             rowptr[nV + 1]; the caller reads rowptr[nV] = nnz and allocates.  phase 2 (fill): colind, vals.
+ *                             A face of F' with an index outside 0..nV-1 contributes nothing and sets SN_IDT_BAD_FACE
+ *                             (status may be NULL).  SN_E_RANGE when nV^2 * 16 max(nF, 1) does not fit the int64 key.
+ * ------------------------------------------------------------------------------------------ */
+#define SN_IDT_BAD_FACE       1
+#define SN_IDT_NOT_CONVERGED  2
+#define SN_IDT_DEGENERATE     4
+#define SN_IDT_NON_MANIFOLD   8
+#define SN_IDT_ORIENTATION    16
+#define SN_IDT_THRESHOLD      (-1e-12)
+size_t sn_mesh_glue_workspace_bytes(int64_t nV, int64_t nF);
+int sn_mesh_glue_i32(const float *V, const int32_t *F, int64_t nV, int64_t nF, int32_t *G, double *l, int32_t *status,
+                     void *workspace, size_t workspace_bytes, void *stream);
+size_t sn_mesh_idt_workspace_bytes(int64_t nF);
+int sn_mesh_idt_rounds_f64(int32_t *Fp, double *lp, int32_t *G, int64_t nF, int32_t round_begin, int32_t round_count,
+                           int32_t max_rounds, int32_t *counters, int32_t *status, void *workspace, size_t workspace_bytes,
+                           void *stream);
+int64_t sn_mesh_idt_laplacian_items(int64_t nV, int64_t nF);
+size_t sn_mesh_idt_laplacian_workspace_bytes(int64_t nV, int64_t nF);
+int sn_mesh_idt_laplacian_f32(const int32_t *Fp, const double *lp, int64_t nV, int64_t nF, int32_t phase, int64_t *keys,
+                              const int64_t *order, int32_t *rowptr, int32_t *colind, float *vals, int32_t *status,
+                              void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Row-streaming fp32 GEMMs of the per-node Linear layers with the weights held in registers
  * (v_mfma_f32_32x32x2_f32; the operands are tall-skinny: rows ~ 1e5..1e6, K and N in {128, 256}).
  *

@@ -142,6 +142,13 @@ SIGNATURES = {
     "sn_mesh_corners_f32": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sn_mesh_geodesics_f32": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
     "sn_mesh_geodesics_sweeps_f32": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "sn_mesh_glue_workspace_bytes": (_sz, [_i64, _i64]),
+    "sn_mesh_glue_i32": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sn_mesh_idt_workspace_bytes": (_sz, [_i64]),
+    "sn_mesh_idt_rounds_f64": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "sn_mesh_idt_laplacian_items": (_i64, [_i64, _i64]),
+    "sn_mesh_idt_laplacian_workspace_bytes": (_sz, [_i64, _i64]),
+    "sn_mesh_idt_laplacian_f32": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sn_linear_fwd_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
     "sn_linear_fwd_stats_blocks": (_i32, [_i64]),
     "sn_linear_fwd_tiles_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),

@@ -589,6 +589,286 @@ int mesh_geodesics_launch(const int *cptr, const MeshCorner *rec, int n, int src
   return launch_status();
 }
 
+// ------------------------------------------------------------------------------------------------
+// Intrinsic Delaunay triangulation by edge flips, and the Laplacian on it (definition: sn_spmm.h).  The state is keyed by face
+// sides (code 3 f + s).  No LDS and no corner table on purpose: the working set is 1-2 MB at FAUST size and the access is
+// pointer chasing through the glue map.
+// ------------------------------------------------------------------------------------------------
+constexpr int kIdtRefused = SN_IDT_BAD_FACE | SN_IDT_NON_MANIFOLD | SN_IDT_ORIENTATION;
+typedef unsigned long long idt_claim_t;
+
+// sides bucketed by the vertex they start at (counted by corner_count_k: one side starts at every corner of a valid face)
+__global__ __launch_bounds__(kWG) void side_fill_k(const int *__restrict__ F, int64_t nF, int64_t nV, int *__restrict__ cursor,
+                                                   int *__restrict__ bucket) {
+  for (int64_t f = (int64_t)blockIdx.x * kWG + threadIdx.x; f < nF; f += (int64_t)gridDim.x * kWG) {
+    const int i = F[3 * f], j = F[3 * f + 1], k = F[3 * f + 2];
+    if (!face_ok(i, j, k, nV)) continue;
+    bucket[atomicAdd(&cursor[i], 1)] = (int)(3 * f);
+    bucket[atomicAdd(&cursor[j], 1)] = (int)(3 * f + 1);
+    bucket[atomicAdd(&cursor[k], 1)] = (int)(3 * f + 2);
+  }
+}
+
+// twin of the side a -> b: the one side b -> a in b's bucket.  The order inside a bucket (atomic cursor) does not matter: a
+// twin is stored only when it is the only candidate.
+__global__ __launch_bounds__(kWG) void glue_twin_k(const float *__restrict__ V, const int *__restrict__ F, int64_t nF, int64_t nV,
+                                                   const int *__restrict__ ptr, const int *__restrict__ bucket, int *__restrict__ G,
+                                                   double *__restrict__ l, int *__restrict__ status) {
+  for (int64_t c = (int64_t)blockIdx.x * kWG + threadIdx.x; c < 3 * nF; c += (int64_t)gridDim.x * kWG) {
+    const int64_t f = c / 3;
+    const int s = (int)(c - 3 * f);
+    const int idx[3] = {F[3 * f], F[3 * f + 1], F[3 * f + 2]};
+    if (!face_ok(idx[0], idx[1], idx[2], nV)) {
+      G[c] = -1;
+      if (l) l[c] = 0;
+      continue;
+    }
+    const int a = F[c], b = F[3 * f + (s + 1) % 3];
+    if (l) l[c] = edge_len(V, a, b);
+    int opp = 0, same = 0, twin = -1;
+    for (int e = ptr[b]; e < ptr[b + 1]; ++e) {
+      const int d = bucket[e];
+      if (F[3 * (d / 3) + (d % 3 + 1) % 3] == a) { ++opp; twin = d; }
+    }
+    for (int e = ptr[a]; e < ptr[a + 1]; ++e) {
+      const int d = bucket[e];
+      if (d != (int)c && F[3 * (d / 3) + (d % 3 + 1) % 3] == b) ++same;
+    }
+    if (1 + opp + same > 2) atomicOr(status, SN_IDT_NON_MANIFOLD);
+    else if (same) atomicOr(status, SN_IDT_ORIENTATION);
+    G[c] = (opp == 1 && same == 0) ? twin : -1;
+  }
+}
+
+// cot of the angle opposite side s of face f, (b^2 + c^2 - a^2) / (4 A), A by Heron; false for a degenerate face
+__device__ __forceinline__ bool idt_cot(const double *l, int f, int s, double *cot) {
+  const double a = l[3 * f + s], b = l[3 * f + (s + 1) % 3], c = l[3 * f + (s + 2) % 3];
+  const double h = ((a + b) + c) / 2;
+  const double q = ((h * (h - a)) * (h - b)) * (h - c);
+  if (!(q > 0)) return false;
+  *cot = ((b * b + c * c) - a * a) / (4 * sqrt(q));
+  return true;
+}
+
+// Claim word of side c in a round: [20 bits: 0xFFFFF - round | 12 bits: hash(c, round) | 32 bits: c].  A later round's word is
+// smaller than any stale one; within a round the order is a per-round shuffle of the side codes, unique because c is in it.
+// With the bare code as the priority the losers form chains along the face numbering (a side waits for a smaller one that is
+// itself waiting): 1569 rounds on torus_grid(65, 106, jitter=0.8) against 27 with the shuffle (LABNOTES.md#intrinsic).
+constexpr int kIdtMaxRounds = 1 << 20;
+__device__ __forceinline__ idt_claim_t idt_claim_word(unsigned round, int c) {
+  unsigned h = (unsigned)c * 2654435761u + round * 40503u;
+  h = (h ^ (h >> 15)) * 2246822519u;
+  return ((idt_claim_t)(0xFFFFFu - round) << 44) | ((idt_claim_t)(h >> 20) << 32) | (unsigned)c;
+}
+
+// First launch of a round: one thread per interior side with c < G[c].  A non-Delaunay side writes its word by integer min into
+// the claim of its two faces and of the up to four faces across their outer sides.  Reads l and G, writes neither.
+__global__ __launch_bounds__(kWG) void idt_claim_k(const double *__restrict__ l, const int *__restrict__ G, int64_t nS,
+                                                   idt_claim_t *__restrict__ claim, unsigned round, int last,
+                                                   int *__restrict__ counters, int *__restrict__ status) {
+  if (*status & kIdtRefused) return;
+  for (int64_t c64 = (int64_t)blockIdx.x * kWG + threadIdx.x; c64 < nS; c64 += (int64_t)gridDim.x * kWG) {
+    const int c = (int)c64, p = G[c];
+    if (p <= c || (int64_t)p >= nS) continue;
+    const int f = c / 3, g = p / 3, s = c % 3, t = p % 3;
+    if (f == g) continue;                              // a face glued to itself along this edge: always Delaunay, never flipped
+    double cf, cg;
+    const bool okf = idt_cot(l, f, s, &cf), okg = idt_cot(l, g, t, &cg);
+    if (!okf || !okg) {
+      atomicOr(status, SN_IDT_DEGENERATE);
+      continue;
+    }
+    if (!(cf + cg < SN_IDT_THRESHOLD)) continue;
+    const idt_claim_t w = idt_claim_word(round, c);
+    atomicMin(&claim[f], w);
+    atomicMin(&claim[g], w);
+    const int outer[4] = {3 * f + (s + 1) % 3, 3 * f + (s + 2) % 3, 3 * g + (t + 1) % 3, 3 * g + (t + 2) % 3};
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+      const int q = G[outer[x]];
+      if (q >= 0 && (int64_t)q < nS) atomicMin(&claim[q / 3], w);
+    }
+    atomicAdd(&counters[0], 1);
+    if (last) atomicOr(status, SN_IDT_NOT_CONVERGED);
+  }
+}
+
+// Second launch: the side that holds every one of its claims flips; it is then the only thread of the round that reads or
+// writes those faces (a face is written only by the holder of its claim, and the claims are not written here).
+__global__ __launch_bounds__(kWG) void idt_flip_k(int *F, double *l, int *G, int64_t nS, const idt_claim_t *__restrict__ claim,
+                                                  unsigned round, int *__restrict__ counters, const int *__restrict__ status) {
+  if (*status & kIdtRefused) return;
+  for (int64_t c64 = (int64_t)blockIdx.x * kWG + threadIdx.x; c64 < nS; c64 += (int64_t)gridDim.x * kWG) {
+    const int c = (int)c64, f = c / 3, s = c % 3;
+    const idt_claim_t w = idt_claim_word(round, c);
+    if (claim[f] != w) continue;                       // only a side that claimed in this round can find its own word
+    const int p = G[c];
+    if (p < 0 || (int64_t)p >= nS) continue;
+    const int g = p / 3, t = p % 3;
+    if (claim[g] != w) continue;
+    const int s1 = (s + 1) % 3, s2 = (s + 2) % 3, t1 = (t + 1) % 3, t2 = (t + 2) % 3;
+    const int oldc[4] = {3 * f + s1, 3 * f + s2, 3 * g + t1, 3 * g + t2};
+    const int newc[4] = {3 * g + 1, 3 * f, 3 * f + 1, 3 * g};
+    int part[4];
+    bool held = true;
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+      part[x] = G[oldc[x]];
+      if (part[x] >= 0 && (int64_t)part[x] < nS && claim[part[x] / 3] != w) held = false;
+    }
+    if (!held) continue;
+    // f = (i, j, k), g = (j, i, m)  ->  f = (k, i, m), g = (m, j, k)
+    const int i = F[3 * f + s], j = F[3 * f + s1], k = F[3 * f + s2], m = F[3 * g + t2];
+    const double a = l[3 * f + s], ljk = l[3 * f + s1], lki = l[3 * f + s2], lim = l[3 * g + t1], lmj = l[3 * g + t2];
+    // i at the origin, j at (a, 0), k above and m below the axis
+    const double a2 = a * a;
+    const double xk = ((a2 + lki * lki) - ljk * ljk) / (2 * a);
+    const double xm = ((a2 + lim * lim) - lmj * lmj) / (2 * a);
+    const double yk = sqrt(fmax((lki - xk) * (lki + xk), 0.0));
+    const double ym = -sqrt(fmax((lim - xm) * (lim + xm), 0.0));
+    const double dx = xk - xm, dy = yk - ym;
+    const double lkm = sqrt(dx * dx + dy * dy);
+#pragma unroll
+    for (int x = 0; x < 4; ++x)                        // a partner that is itself one of the four outer sides moves with it
+#pragma unroll
+      for (int y = 0; y < 4; ++y)
+        if (G[oldc[x]] == oldc[y]) part[x] = newc[y];
+    F[3 * f] = k; F[3 * f + 1] = i; F[3 * f + 2] = m;
+    F[3 * g] = m; F[3 * g + 1] = j; F[3 * g + 2] = k;
+    l[3 * f] = lki; l[3 * f + 1] = lim; l[3 * f + 2] = lkm;
+    l[3 * g] = lmj; l[3 * g + 1] = ljk; l[3 * g + 2] = lkm;
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+      const int q = part[x];
+      G[newc[x]] = q;
+      if (q >= 0 && (int64_t)q < nS && q / 3 != f && q / 3 != g) G[q] = newc[x];
+    }
+    G[3 * f + 2] = 3 * g + 2;
+    G[3 * g + 2] = 3 * f + 2;
+    atomicAdd(&counters[1], 1);
+  }
+}
+
+// ---- Laplacian of (F', l'): contributions, [caller sorts the keys], heads + scan + row pointers, masses, entries -------------
+constexpr int64_t kIdtNoKey = INT64_MAX;
+__device__ __forceinline__ int64_t idt_key(int64_t row, int64_t col, int64_t nV, int64_t nFk, int64_t f, int slot) {
+  return ((row * nV + col) * nFk + f) * 16 + slot;
+}
+
+// item < nF: the 12 contributions of a face (slot 2n: W[F[p], F[q]] of permutation n, slot 2n + 1: its mirror for the column
+// sum of F[p], with the mass a/3/4);  item >= nF: the diagonal seed of vertex item - nF (value 0, mass 0, slot 12 of face 0)
+__global__ __launch_bounds__(kWG) void idt_contrib_k(const int *__restrict__ F, const double *__restrict__ l, int64_t nV, int64_t nF,
+                                                     int64_t *__restrict__ keys, double *__restrict__ cval,
+                                                     double *__restrict__ cmass, int *__restrict__ status) {
+  const int64_t nFk = nF > 0 ? nF : 1;
+  for (int64_t it = (int64_t)blockIdx.x * kWG + threadIdx.x; it < nF + nV; it += (int64_t)gridDim.x * kWG) {
+    if (it >= nF) {
+      const int64_t v = it - nF, o = 12 * nF + v;
+      keys[o] = idt_key(v, v, nV, nFk, 0, 12);
+      cval[o] = 0;
+      cmass[o] = 0;
+      continue;
+    }
+    const int64_t f = it;
+    const int idx[3] = {F[3 * f], F[3 * f + 1], F[3 * f + 2]};
+    const bool ok = (unsigned)idx[0] < (unsigned)nV && (unsigned)idx[1] < (unsigned)nV && (unsigned)idx[2] < (unsigned)nV;
+    if (!ok) {
+      if (status) atomicOr(status, SN_IDT_BAD_FACE);
+      for (int x = 0; x < 12; ++x) { keys[12 * f + x] = kIdtNoKey; cval[12 * f + x] = 0; cmass[12 * f + x] = 0; }
+      continue;
+    }
+    const double lij = l[3 * f], ljk = l[3 * f + 1], lki = l[3 * f + 2];
+    const double h = ((lij + ljk) + lki) / 2;
+    const double q = ((h * (h - lij)) * (h - ljk)) * (h - lki);
+    const double ar = q > 0 ? sqrt(q) : 1e-6;
+    const double den = 8 * ar + 1e-6, mass = ar / 3 / 4;
+    const double e01 = lij * lij, e12 = ljk * ljk, e20 = lki * lki;
+    // squared length between local corners x, y: index x + y - 1 of {e01, e20, e12}
+    const double e2[3] = {e01, e20, e12};
+    const int perms[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
+#pragma unroll
+    for (int n = 0; n < 6; ++n) {
+      const int pp = perms[n][0], qq = perms[n][1], rr = perms[n][2];
+      const double epq = e2[pp + qq - 1], eqr = e2[qq + rr - 1], erp = e2[rr + pp - 1];
+      const int64_t row = idx[pp], col = idx[qq], o = 12 * f + 2 * n;
+      const bool loop = row == col;                    // a self-edge: W[i,i] cancels in D - W, only its mass counts
+      keys[o] = loop ? kIdtNoKey : idt_key(row, col, nV, nFk, f, 2 * n);
+      cval[o] = loop ? 0.0 : ((-epq + eqr) + erp) / den;
+      cmass[o] = 0;
+      keys[o + 1] = idt_key(row, row, nV, nFk, f, 2 * n + 1);
+      cval[o + 1] = loop ? 0.0 : ((-epq + erp) + eqr) / den;
+      cmass[o + 1] = mass;
+    }
+  }
+}
+
+// head[t] = 1 where sorted position t starts a new (row, col); head[N] = 0 so that the exclusive scan ends in the entry count
+__global__ __launch_bounds__(kWG) void idt_heads_k(const int64_t *__restrict__ sk, int64_t N, int64_t span, int *__restrict__ head) {
+  for (int64_t t = (int64_t)blockIdx.x * kWG + threadIdx.x; t <= N; t += (int64_t)gridDim.x * kWG)
+    head[t] = (t < N && sk[t] != kIdtNoKey && (t == 0 || sk[t - 1] / span != sk[t] / span)) ? 1 : 0;
+}
+
+// rowptr[r] = entries before the first sorted key of row r (binary search)
+__global__ __launch_bounds__(kWG) void idt_rowptr_k(const int64_t *__restrict__ sk, int64_t N, int64_t nV, int64_t span,
+                                                    const int *__restrict__ hs, int *__restrict__ rowptr) {
+  for (int64_t r = (int64_t)blockIdx.x * kWG + threadIdx.x; r <= nV; r += (int64_t)gridDim.x * kWG) {
+    const int64_t want = r * nV * span;
+    int64_t lo = 0, hi = N;
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) / 2;
+      if (sk[mid] < want) lo = mid + 1; else hi = mid;
+    }
+    rowptr[r] = hs[lo];
+  }
+}
+
+// serial sums over the run of one (row, col) in sorted order: MASS = false writes the entry, MASS = true the vertex mass
+template <bool MASS>
+__global__ __launch_bounds__(kWG) void idt_entries_k(const int64_t *__restrict__ sk, const int64_t *__restrict__ order, int64_t N,
+                                                     int64_t nV, int64_t span, const int *__restrict__ hs,
+                                                     const double *__restrict__ contrib, double *__restrict__ A,
+                                                     int *__restrict__ colind, float *__restrict__ vals) {
+  for (int64_t t = (int64_t)blockIdx.x * kWG + threadIdx.x; t < N; t += (int64_t)gridDim.x * kWG) {
+    if (sk[t] == kIdtNoKey) continue;
+    const int64_t ent = sk[t] / span;
+    if (t > 0 && sk[t - 1] / span == ent) continue;
+    const int64_t row = ent / nV, col = ent - row * nV;
+    if (MASS && row != col) continue;
+    double sum = 0;
+    for (int64_t u = t; u < N && sk[u] / span == ent; ++u) {
+      const int64_t src = order[u];
+      if ((uint64_t)src < (uint64_t)N) sum += contrib[src];
+    }
+    if constexpr (MASS) {
+      A[row] = sum;
+    } else {
+      const double ainv = 1 / (A[row] + 1e-9);
+      const int e = hs[t];
+      colind[e] = (int)col;
+      vals[e] = (float)(row == col ? ainv * sum : ainv * (0 - sum));
+    }
+  }
+}
+
+struct IdtLapWs {
+  double *cval, *cmass, *A;
+  int *hs, *sums;
+};
+inline size_t idt_lap_ws(int64_t nV, int64_t nF, char *w, IdtLapWs *out) {
+  const int64_t N = 12 * nF + nV;
+  const size_t scan = (size_t)((N + 1 + kScanTile - 1) / kScanTile + 1) * sizeof(int);
+  const size_t b0 = ((size_t)N * sizeof(double) + 15) & ~(size_t)15, b1 = ((size_t)nV * sizeof(double) + 15) & ~(size_t)15,
+               b2 = ((size_t)(N + 1) * sizeof(int) + 15) & ~(size_t)15;
+  if (out) {
+    out->cval = reinterpret_cast<double *>(w);
+    out->cmass = reinterpret_cast<double *>(w + b0);
+    out->A = reinterpret_cast<double *>(w + 2 * b0);
+    out->hs = reinterpret_cast<int *>(w + 2 * b0 + b1);
+    out->sums = reinterpret_cast<int *>(w + 2 * b0 + b1 + b2);
+  }
+  return 2 * b0 + b1 + b2 + ((scan + 15) & ~(size_t)15);
+}
+
 inline size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 }  // namespace
@@ -801,6 +1081,119 @@ int sn_mesh_geodesics_sweeps_f32(const int32_t *cptr, const void *corners, int64
 int sn_mesh_geodesics_f32(const int32_t *cptr, const void *corners, int64_t n, int64_t src_begin, int64_t src_count,
                           float *out, int64_t ldo, int32_t *flags, void *stream) {
   return sn_mesh_geodesics_sweeps_f32(cptr, corners, n, src_begin, src_count, out, ldo, flags, nullptr, stream);
+}
+
+size_t sn_mesh_glue_workspace_bytes(int64_t nV, int64_t nF) {
+  if (nV < 0) nV = 0;
+  if (nF < 0) nF = 0;
+  const size_t scan = (size_t)((nV + 1 + kScanTile - 1) / kScanTile + 1) * sizeof(int);
+  return 2 * align16((size_t)(nV + 1) * sizeof(int)) + align16((size_t)3 * nF * sizeof(int)) + align16(scan);
+}
+
+int sn_mesh_glue_i32(const float *V, const int32_t *F, int64_t nV, int64_t nF, int32_t *G, double *l, int32_t *status,
+                     void *workspace, size_t workspace_bytes, void *stream) {
+  (void)hipGetLastError();
+  if (nV < 0 || nF < 0) return SN_E_SHAPE;
+  if (nV + 1 > INT_MAX || 3 * nF > INT_MAX) return SN_E_RANGE;
+  if (!status) return SN_E_NULL;
+  if (nF > 0 && (!F || !G)) return SN_E_NULL;
+  if (!V != !l && nF > 0) return SN_E_NULL;                      // the lengths need the coordinates, and nothing else does
+  if (workspace_bytes < sn_mesh_glue_workspace_bytes(nV, nF) || !workspace) return SN_E_WORKSPACE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  char *w = static_cast<char *>(workspace);
+  int *ptr = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
+  int *cursor = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
+  int *bucket = reinterpret_cast<int *>(w); w += align16((size_t)3 * nF * sizeof(int));
+  int *sums = reinterpret_cast<int *>(w);
+  hipError_t e = sn_internal_fill(ptr, 0, (size_t)(nV + 1) * sizeof(int), s);
+  if (e != hipSuccess) return (int)e;
+  e = sn_internal_fill(status, 0, sizeof(int), s);
+  if (e != hipSuccess) return (int)e;
+  if (nF == 0) return SN_OK;
+  hipLaunchKernelGGL(corner_count_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, nV, ptr, status);      // sets SN_IDT_BAD_FACE = 1
+  const int64_t n = nV + 1;
+  const int nblk = (int)((n + kScanTile - 1) / kScanTile);
+  hipLaunchKernelGGL(scan_sums_k, dim3(nblk), dim3(kWG), 0, s, ptr, n, sums);
+  hipLaunchKernelGGL(scan_top_k, dim3(1), dim3(kWG), 0, s, sums, nblk);
+  hipLaunchKernelGGL(scan_apply_k, dim3(nblk), dim3(kWG), 0, s, ptr, n, sums, ptr);
+  e = sn_internal_copy2d(cursor, 0, ptr, 0, (int64_t)((size_t)(nV + 1) * sizeof(int)), 1, s);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(side_fill_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, nV, cursor, bucket);
+  hipLaunchKernelGGL(glue_twin_k, dim3(grid_for(3 * nF)), dim3(kWG), 0, s, V, F, nF, nV, ptr, bucket, G, l, status);
+  return launch_status();
+}
+
+size_t sn_mesh_idt_workspace_bytes(int64_t nF) { return align16((size_t)(nF > 0 ? nF : 0) * sizeof(idt_claim_t)); }
+
+int sn_mesh_idt_rounds_f64(int32_t *Fp, double *lp, int32_t *G, int64_t nF, int32_t round_begin, int32_t round_count,
+                           int32_t max_rounds, int32_t *counters, int32_t *status, void *workspace, size_t workspace_bytes,
+                           void *stream) {
+  (void)hipGetLastError();
+  if (nF < 0 || round_begin < 0 || round_count < 0 || max_rounds < 0 || (int64_t)round_begin + round_count > max_rounds)
+    return SN_E_SHAPE;
+  if (3 * nF > INT_MAX || max_rounds > kIdtMaxRounds) return SN_E_RANGE;
+  if (!status || (round_count > 0 && !counters)) return SN_E_NULL;
+  if (nF > 0 && (!Fp || !lp || !G)) return SN_E_NULL;
+  if (workspace_bytes < sn_mesh_idt_workspace_bytes(nF) || !workspace) return SN_E_WORKSPACE;
+  if (round_count == 0) return SN_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  idt_claim_t *claim = static_cast<idt_claim_t *>(workspace);
+  hipError_t e = sn_internal_fill(counters + 2 * (int64_t)round_begin, 0, (size_t)round_count * 2 * sizeof(int), s);
+  if (e != hipSuccess) return (int)e;
+  if (nF == 0) return SN_OK;
+  if (round_begin == 0) {
+    e = sn_internal_fill(claim, 0xff, (size_t)nF * sizeof(idt_claim_t), s);
+    if (e != hipSuccess) return (int)e;
+  }
+  const int64_t nS = 3 * nF;
+  for (int r = round_begin; r < round_begin + round_count; ++r) {
+    hipLaunchKernelGGL(idt_claim_k, dim3(grid_for(nS)), dim3(kWG), 0, s, lp, G, nS, claim, (unsigned)r, r == max_rounds - 1 ? 1 : 0,
+                       counters + 2 * (int64_t)r, status);
+    hipLaunchKernelGGL(idt_flip_k, dim3(grid_for(nS)), dim3(kWG), 0, s, Fp, lp, G, nS, claim, (unsigned)r, counters + 2 * (int64_t)r,
+                       status);
+  }
+  return launch_status();
+}
+
+int64_t sn_mesh_idt_laplacian_items(int64_t nV, int64_t nF) { return nV < 0 || nF < 0 ? 0 : 12 * nF + nV; }
+
+size_t sn_mesh_idt_laplacian_workspace_bytes(int64_t nV, int64_t nF) {
+  return idt_lap_ws(nV > 0 ? nV : 0, nF > 0 ? nF : 0, nullptr, nullptr);
+}
+
+int sn_mesh_idt_laplacian_f32(const int32_t *Fp, const double *lp, int64_t nV, int64_t nF, int32_t phase, int64_t *keys,
+                              const int64_t *order, int32_t *rowptr, int32_t *colind, float *vals, int32_t *status,
+                              void *workspace, size_t workspace_bytes, void *stream) {
+  (void)hipGetLastError();
+  if (nV < 0 || nF < 0 || phase < 0 || phase > 2) return SN_E_SHAPE;
+  const int64_t N = 12 * nF + nV, nFk = nF > 0 ? nF : 1, span = 16 * nFk;
+  if (nV + 1 > INT_MAX || N + 1 > INT_MAX) return SN_E_RANGE;
+  if ((long double)nV * (long double)nV * (long double)span >= 9.0e18L) return SN_E_RANGE;      // the sort key is one int64
+  if (workspace_bytes < sn_mesh_idt_laplacian_workspace_bytes(nV, nF) || !workspace) return SN_E_WORKSPACE;
+  if (N > 0 && !keys) return SN_E_NULL;
+  if (nF > 0 && (!Fp || !lp)) return SN_E_NULL;
+  if (phase > 0 && ((N > 0 && !order) || !rowptr)) return SN_E_NULL;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  IdtLapWs ws;
+  idt_lap_ws(nV, nF, static_cast<char *>(workspace), &ws);
+  if (phase == 0) {
+    if (N > 0) hipLaunchKernelGGL(idt_contrib_k, dim3(grid_for(nF + nV)), dim3(kWG), 0, s, Fp, lp, nV, nF, keys, ws.cval, ws.cmass, status);
+  } else if (phase == 1) {
+    const int64_t n = N + 1;
+    const int nblk = (int)((n + kScanTile - 1) / kScanTile);
+    hipLaunchKernelGGL(idt_heads_k, dim3(grid_for(n)), dim3(kWG), 0, s, keys, N, span, ws.hs);
+    hipLaunchKernelGGL(scan_sums_k, dim3(nblk), dim3(kWG), 0, s, ws.hs, n, ws.sums);
+    hipLaunchKernelGGL(scan_top_k, dim3(1), dim3(kWG), 0, s, ws.sums, nblk);
+    hipLaunchKernelGGL(scan_apply_k, dim3(nblk), dim3(kWG), 0, s, ws.hs, n, ws.sums, ws.hs);
+    hipLaunchKernelGGL(idt_rowptr_k, dim3(grid_for(nV + 1)), dim3(kWG), 0, s, keys, N, nV, span, ws.hs, rowptr);
+  } else if (N > 0) {
+    if (!colind || !vals) return SN_E_NULL;
+    hipLaunchKernelGGL((idt_entries_k<true>), dim3(grid_for(N)), dim3(kWG), 0, s, keys, order, N, nV, span, ws.hs, ws.cmass, ws.A,
+                       (int *)nullptr, (float *)nullptr);
+    hipLaunchKernelGGL((idt_entries_k<false>), dim3(grid_for(N)), dim3(kWG), 0, s, keys, order, N, nV, span, ws.hs, ws.cval, ws.A,
+                       colind, vals);
+  }
+  return launch_status();
 }
 
 }  // extern "C"

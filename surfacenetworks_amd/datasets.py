@@ -159,16 +159,21 @@ def load_faust_frame(path: str, device="cuda") -> Dict:
     return fr
 
 
-def faust_frame_from_mesh(V, F, label=None, device="cuda", symmetric=True, geodesics="edges") -> Dict:
+def faust_frame_from_mesh(V, F, label=None, device="cuda", symmetric=True, geodesics="edges", laplacian="extrinsic") -> Dict:
     """The frame dict of load_faust_frame from a raw triangle mesh: V (nV, 3), F (nF, 3) (numpy or tensors), host scipy
     L / Di / DiA from mesh_ops.mesh_operators, and G — the `dist_mat` the reference's files bring along — computed on the device
     by operators.geodesic_matrix_from_mesh (geodesics="edges": edge-path distances, "triangles": paths that cross the faces;
     symmetric: min(D, D^T)).  label: the permutation of
-    main.py:98-99 (vertex -> canonical id), None = identity.  A list of such frames is what FaustFrames takes."""
-    from .operators import geodesic_matrix_from_mesh
+    main.py:98-99 (vertex -> canonical id), None = identity.  A list of such frames is what FaustFrames takes.
+    laplacian: "extrinsic" (default) keeps the host cotangent Laplacian; "intrinsic" takes L from the device builder on the
+    intrinsic Delaunay triangulation (operators.laplacian_operator_from_mesh(intrinsic=True), fp32 scipy CSR) — the frame['L']
+    the reference builds with mesh.intrinsic_laplacian (main.py:87), in this project's scaling, not the unpublished one."""
+    from .operators import geodesic_matrix_from_mesh, laplacian_operator_from_mesh
 
     if geodesics not in ("edges", "triangles"):
         raise ValueError(f'faust_frame_from_mesh: geodesics must be "edges" or "triangles", got {geodesics!r}')
+    if laplacian not in ("extrinsic", "intrinsic"):
+        raise ValueError(f'faust_frame_from_mesh: laplacian must be "extrinsic" or "intrinsic", got {laplacian!r}')
     Vn = np.asarray(V.detach().cpu() if torch.is_tensor(V) else V)
     Fn = np.asarray(F.detach().cpu() if torch.is_tensor(F) else F)
     nv = Vn.shape[0]
@@ -178,8 +183,9 @@ def faust_frame_from_mesh(V, F, label=None, device="cuda", symmetric=True, geode
     ops = mesh_ops.mesh_operators(Vn.astype(np.float32).astype(np.float64), Fn)
     Vd = torch.from_numpy(Vn.astype("f")).to(device)
     Fd = torch.from_numpy(Fn.astype(np.int64)).to(device)
+    L = laplacian_operator_from_mesh(Vd, Fd, intrinsic=True).to_scipy() if laplacian == "intrinsic" else ops["L"]
     return {
-        "V": Vd, "F": Fd, "L": ops["L"], "Di": ops["Di"], "DiA": ops["DiA"],
+        "V": Vd, "F": Fd, "L": L, "Di": ops["Di"], "DiA": ops["DiA"],
         "label": torch.from_numpy(label.astype(np.int64)).to(device),
         "label_inv": torch.from_numpy(np.argsort(label).astype(np.int64)).to(device),
         "G": geodesic_matrix_from_mesh(Vd, Fd, symmetric=symmetric, method=geodesics),

@@ -19,7 +19,7 @@ import torch.nn.functional as F
 from . import kernels, mesh_ops
 from . import utils_pt as utils
 from .arap import make_adam
-from .operators import OperatorPool, SparseOperator, geodesic_matrix_from_mesh
+from .operators import OperatorPool, SparseOperator, geodesic_matrix_from_mesh, laplacian_operator_from_mesh
 
 
 
@@ -732,11 +732,15 @@ class TorusBodies:
     """Synthetic stand-in for the FAUST .npz frames (main.py:65-104): torus-grid meshes (65 x 106 -> 6890 vertices,
     13 780 faces), padded to 7000 vertices (main.py:193), a random label permutation pair and a synthetic
     'geodesic' matrix per shape: geodesics="euclidean" (default) straight-line distances, "graph" shortest paths along the
-    mesh edges, "triangles" paths that cross the faces (operators.geodesic_matrix_from_mesh, method "edges" / "triangles")."""
+    mesh edges, "triangles" paths that cross the faces (operators.geodesic_matrix_from_mesh, method "edges" / "triangles").
+    laplacian="extrinsic" (default) the host cotangent Laplacian, "intrinsic" the device builder on the intrinsic Delaunay
+    triangulation (operators.laplacian_operator_from_mesh(intrinsic=True))."""
 
-    def __init__(self, count, n=65, m=106, pad_to=7000, seed=4, device="cuda", geodesics="euclidean"):
+    def __init__(self, count, n=65, m=106, pad_to=7000, seed=4, device="cuda", geodesics="euclidean", laplacian="extrinsic"):
         if geodesics not in ("euclidean", "graph", "triangles"):
             raise ValueError('geodesics: "euclidean", "graph" or "triangles"')
+        if laplacian not in ("extrinsic", "intrinsic"):
+            raise ValueError('laplacian: "extrinsic" or "intrinsic"')
         rng = np.random.default_rng(seed)
         self.device = torch.device(device)
         self.pad_to = pad_to
@@ -745,9 +749,10 @@ class TorusBodies:
         for _ in range(count):
             V, F_ = mesh_ops.torus_grid(n, m, rng)
             nv = V.shape[0]
-            mats.append(mesh_ops.laplacian(V, F_).astype(np.float32))
             label = rng.permutation(nv)
             G = torch.from_numpy(V.astype(np.float32)).to(self.device)
+            mats.append(mesh_ops.laplacian(V, F_).astype(np.float32) if laplacian == "extrinsic" else
+                        laplacian_operator_from_mesh(G, torch.from_numpy(F_).to(self.device), intrinsic=True).to_scipy())
             self.frames.append({
                 "V": torch.from_numpy(V.astype(np.float32)).to(self.device),
                 "label": torch.from_numpy(label).to(self.device),

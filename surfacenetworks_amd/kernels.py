@@ -685,6 +685,121 @@ def laplacian_from_mesh(V, F):
     return rowptr, colind, vals
 
 
+IDT_BAD_FACE, IDT_NOT_CONVERGED, IDT_DEGENERATE, IDT_NON_MANIFOLD, IDT_ORIENTATION = 1, 2, 4, 8, 16      # SN_IDT_* status bits
+IDT_CHUNK = 8                 # flip rounds enqueued between two reads of the counters
+
+
+def _check_mesh(who: str, V, F) -> None:
+    if F.dtype != torch.int32 or F.dim() != 2 or F.shape[1] != 3:
+        raise TypeError(f"{who} wants F (nF, 3) int32")
+    if V is not None and (V.dtype != torch.float32 or V.dim() != 2 or V.shape[1] != 3):
+        raise TypeError(f"{who} wants V (nV, 3) float32")
+
+
+def mesh_glue(F, num_vertices: int, V=None):
+    """Glue map of a triangle mesh built on the device (sn_mesh_glue_i32; the definition is in include/sn_spmm.h, "Intrinsic
+    Delaunay Laplacian"): G (nF, 3) int32 of face-side codes 3 g + t, -1 on the boundary, and the status word (1-element int32
+    device tensor, not read here: IDT_BAD_FACE / IDT_NON_MANIFOLD / IDT_ORIENTATION).  With V (nV, 3) fp32 also the fp64 side
+    lengths (nF, 3): returns (G, status, l)."""
+    _dev(F, V)
+    _check_mesh("mesh_glue", V, F)
+    F = F.contiguous()
+    nV, nF = int(num_vertices), F.shape[0]
+    dev = F.device
+    G = torch.empty(nF, 3, dtype=torch.int32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    l = None
+    if V is not None:
+        if V.shape[0] != nV:
+            raise ValueError(f"mesh_glue: V has {V.shape[0]} rows for {nV} vertices")
+        V = V.contiguous()
+        l = torch.empty(nF, 3, dtype=torch.float64, device=dev)
+    ws_bytes = int(_lib.load().sn_mesh_glue_workspace_bytes(nV, nF))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    _lib.call("sn_mesh_glue_i32", _p(V) if V is not None else None, _p(F), nV, nF, _p(G), _p(l) if l is not None else None,
+              status.data_ptr(), _p(ws), ws_bytes, _stream())
+    return (G, status) if V is None else (G, status, l)
+
+
+def intrinsic_delaunay(V, F, max_rounds: int = 1024):
+    """Intrinsic Delaunay triangulation of one mesh (or a batch laid out as one disjoint mesh) by edge flips on the device
+    (sn_mesh_glue_i32, sn_mesh_idt_rounds_f64; the definition is in include/sn_spmm.h).  V: (nV, 3) fp32, F: (nF, 3) int32.
+    Returns (F', l', G, status, rounds, flips): faces (nF, 3) int32, fp64 side lengths (nF, 3), glue map (nF, 3) int32, the
+    status word as a Python int (IDT_* bits; with a refusal bit nothing was flipped), the number of rounds run (the last one
+    found nothing unless IDT_NOT_CONVERGED is set) and of flips done.  Rounds are enqueued IDT_CHUNK at a time; synchronises
+    once per chunk (reads the counters and the status word).  Two runs give bit-identical results."""
+    _dev(V, F)
+    _check_mesh("intrinsic_delaunay", V, F)
+    max_rounds = int(max_rounds)
+    if not 1 <= max_rounds <= 1 << 20:
+        raise ValueError("intrinsic_delaunay: max_rounds must be between 1 and 2**20")
+    nV, nF = V.shape[0], F.shape[0]
+    dev = V.device
+    G, status, l = mesh_glue(F, nV, V)
+    Fp = F.contiguous().clone()
+    counters = torch.empty(max_rounds, 2, dtype=torch.int32, device=dev)
+    ws_bytes = int(_lib.load().sn_mesh_idt_workspace_bytes(nF))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    rounds = flips = 0
+    while rounds < max_rounds:
+        n = min(IDT_CHUNK, max_rounds - rounds)
+        _lib.call("sn_mesh_idt_rounds_f64", _p(Fp), _p(l), _p(G), nF, rounds, n, max_rounds, counters.data_ptr(), status.data_ptr(),
+                  _p(ws), ws_bytes, _stream())
+        got = counters[rounds:rounds + n].cpu()
+        idle = (got[:, 0] == 0).nonzero()
+        flips += int(got[:, 1].sum())
+        if idle.numel():
+            rounds += int(idle[0]) + 1
+            break
+        rounds += n
+    return Fp, l, G, int(status.item()), rounds, flips
+
+
+def _raise_for_idt_status(who: str, st: int, max_rounds: int) -> None:
+    if st & IDT_BAD_FACE:
+        raise ValueError(f"{who}: a face has an index outside 0..nV-1 or a repeated index")
+    if st & IDT_NON_MANIFOLD:
+        raise ValueError(f"{who}: an edge has more than two faces (the mesh is not manifold)")
+    if st & IDT_ORIENTATION:
+        raise ValueError(f"{who}: an edge is traversed in the same direction by its two faces (the mesh is not consistently "
+                         "oriented)")
+    if st & IDT_NOT_CONVERGED:
+        raise RuntimeError(f"{who}: round {max_rounds} of max_rounds = {max_rounds} still found a non-Delaunay side")
+
+
+def intrinsic_laplacian_from_mesh(V, F, max_rounds: int = 1024, state=None):
+    """Mass-normalised cotangent Laplacian A^-1 (D - W) on the intrinsic Delaunay triangulation of one mesh (or a batch laid
+    out as one disjoint mesh), built on the device: (rowptr, colind, vals) CSR, columns ascending, explicit zeros kept (the
+    pattern is every intrinsic edge plus the diagonal).  Not the reference's unpublished seism matrix: its scaling and sign are
+    unknown (include/sn_spmm.h).  state: the (F', l', ...) tuple of intrinsic_delaunay to build from, else it is run here.
+    Raises ValueError for a refused mesh (naming the refusal) and RuntimeError when max_rounds rounds did not reach the fixed
+    point.  torch.sort orders the contribution keys; everything else is this library's kernels."""
+    _dev(V, F)
+    _check_mesh("intrinsic_laplacian_from_mesh", V, F)
+    if state is None:
+        state = intrinsic_delaunay(V, F, max_rounds)
+    Fp, l, _, st = state[:4]
+    _raise_for_idt_status("intrinsic_laplacian_from_mesh", st, max_rounds)
+    nV, nF = V.shape[0], Fp.shape[0]
+    dev = V.device
+    lib = _lib.load()
+    N = int(lib.sn_mesh_idt_laplacian_items(nV, nF))
+    ws_bytes = int(lib.sn_mesh_idt_laplacian_workspace_bytes(nV, nF))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    keys = torch.empty(N, dtype=torch.int64, device=dev)
+    rowptr = torch.empty(nV + 1, dtype=torch.int32, device=dev)
+    args = (_p(Fp), _p(l), nV, nF)
+    _lib.call("sn_mesh_idt_laplacian_f32", *args, 0, _p(keys), None, None, None, None, None, _p(ws), ws_bytes, _stream())
+    skeys, order = torch.sort(keys)
+    _lib.call("sn_mesh_idt_laplacian_f32", *args, 1, _p(skeys), _p(order), rowptr.data_ptr(), None, None, None, _p(ws), ws_bytes, _stream())
+    nnz = int(rowptr[-1].item())
+    colind = torch.empty(nnz, dtype=torch.int32, device=dev)
+    vals = torch.empty(nnz, dtype=torch.float32, device=dev)
+    _lib.call("sn_mesh_idt_laplacian_f32", *args, 2, _p(skeys), _p(order), rowptr.data_ptr(), _p(colind), _p(vals), None, _p(ws), ws_bytes,
+              _stream())
+    return rowptr, colind, vals
+
+
 def _check_graph(who: str, rowptr, colind, n: int) -> None:
     if rowptr.dtype != torch.int32 or colind.dtype != torch.int32:
         raise TypeError(f"{who} wants int32 rowptr and colind")

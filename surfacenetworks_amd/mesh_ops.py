@@ -26,6 +26,8 @@ __all__ = [
     "edge_lengths", "heron_areas", "cotangent_weights", "laplacian", "dirac", "mesh_operators",
     "grid_cloth", "torus_grid", "delaunay_disc", "read_ply_ascii",
     "locality_order", "edge_span", "MeshOrder", "permute_operator",
+    "mesh_glue", "intrinsic_delaunay", "intrinsic_laplacian", "intrinsic_laplacian_from_lengths", "delaunay_margin",
+    "IDT_THRESHOLD",
 ]
 
 _PERMS = np.array([[0, 1, 2], [0, 2, 1], [1, 0, 2], [1, 2, 0], [2, 0, 1], [2, 1, 0]])  # itertools.permutations order
@@ -139,6 +141,193 @@ def mesh_operators(V: np.ndarray, F: np.ndarray, dtype=np.float32):
     L = laplacian(V, F)
     Di, DiA = dirac(V, F)
     return {"L": L.astype(dtype), "Di": Di.astype(dtype), "DiA": DiA.astype(dtype)}
+
+
+# --------------------------------------------------------------------------------------------------
+# intrinsic Delaunay triangulation and its Laplacian (definition: include/sn_spmm.h, "Intrinsic Delaunay Laplacian").
+# Bobenko & Springborn 2007 for the triangulation, Fisher et al. 2006 for the edge-flip algorithm.  The state is a
+# Delta-complex keyed by FACE SIDES (code 3 f + s): after flips two faces may share two edges, a face may have a self-edge and
+# one vertex pair may carry several edges, so nothing here is keyed by vertex pairs.
+# --------------------------------------------------------------------------------------------------
+IDT_THRESHOLD = -1e-12       # a glued side is non-Delaunay iff cot_f + cot_g < IDT_THRESHOLD (part of the definition)
+
+
+def mesh_glue(F: np.ndarray, num_vertices: int) -> np.ndarray:
+    """(nF, 3) glue map of a manifold, consistently oriented mesh: G[f, s] = 3 g + t, the side that traverses the edge
+    F[f, s] -> F[f, s+1] the other way, -1 on the boundary.  ValueError names the refusal: a face with an index outside
+    0..nV-1 or a repeated index; an edge with more than two faces; an edge its two faces traverse in the same direction."""
+    F = np.asarray(F)
+    nF = F.shape[0]
+    if nF and (F.min() < 0 or F.max() >= num_vertices):
+        raise ValueError("mesh_glue: a face has an index outside 0..nV-1")
+    if nF and ((F[:, 0] == F[:, 1]) | (F[:, 1] == F[:, 2]) | (F[:, 2] == F[:, 0])).any():
+        raise ValueError("mesh_glue: a face has a repeated index")
+    sides = {}
+    for f in range(nF):
+        for s in range(3):
+            sides.setdefault((int(F[f, s]), int(F[f, (s + 1) % 3])), []).append(3 * f + s)
+    same = any(len(v) > 1 for v in sides.values())
+    if any(len(v) + len(sides.get((b, a), ())) > 2 for (a, b), v in sides.items()):
+        raise ValueError("mesh_glue: an edge has more than two faces (the mesh is not manifold)")
+    if same:
+        raise ValueError("mesh_glue: an edge is traversed in the same direction by its two faces (the mesh is not "
+                         "consistently oriented)")
+    G = np.full((nF, 3), -1, dtype=np.int64)
+    for (a, b), v in sides.items():
+        twin = sides.get((b, a))
+        if twin:
+            G[v[0] // 3, v[0] % 3] = twin[0]
+    return G
+
+
+def _heron_q(a, b, c):
+    s = ((a + b) + c) / 2
+    return ((s * (s - a)) * (s - b)) * (s - c)
+
+
+def _side_cot(l, f, s):
+    """cot of the angle opposite side s of face f, (b^2 + c^2 - a^2) / (4 A); None for a degenerate face (radicand <= 0)."""
+    a, b, c = l[f, s], l[f, (s + 1) % 3], l[f, (s + 2) % 3]
+    q = _heron_q(a, b, c)
+    if not q > 0:
+        return None
+    return ((b * b + c * c) - a * a) / (4 * np.sqrt(q))
+
+
+def delaunay_margin(l: np.ndarray, G: np.ndarray):
+    """(smallest cot_f + cot_g over the interior sides whose two faces are distinct and not degenerate, number of degenerate
+    faces): the state is intrinsic Delaunay iff the first is >= IDT_THRESHOLD."""
+    best, nF = np.inf, l.shape[0]
+    for f in range(nF):
+        for s in range(3):
+            p = int(G[f, s])
+            if p < 0 or p // 3 == f:
+                continue
+            cf, cg = _side_cot(l, f, s), _side_cot(l, p // 3, p % 3)
+            if cf is not None and cg is not None:
+                best = min(best, cf + cg)
+    return best, int(sum(not _heron_q(*l[f]) > 0 for f in range(nF)))
+
+
+def _flip(Fp, l, G, f, s):
+    """Flip the side (f, s) glued to (g, t), as the header defines it: f = (i, j, k), g = (j, i, m) become f = (k, i, m),
+    g = (m, j, k); sides 2 are the new edge."""
+    p = int(G[f, s])
+    g, t = p // 3, p % 3
+    s1, s2, t1, t2 = (s + 1) % 3, (s + 2) % 3, (t + 1) % 3, (t + 2) % 3
+    i, j, k, m = Fp[f, s], Fp[f, s1], Fp[f, s2], Fp[g, t2]
+    a, ljk, lki, lim, lmj = l[f, s], l[f, s1], l[f, s2], l[g, t1], l[g, t2]
+    # i at the origin, j at (a, 0), k above and m below the axis
+    a2 = a * a
+    xk = ((a2 + lki * lki) - ljk * ljk) / (2 * a)
+    xm = ((a2 + lim * lim) - lmj * lmj) / (2 * a)
+    yk = np.sqrt(max((lki - xk) * (lki + xk), 0.0))
+    ym = -np.sqrt(max((lim - xm) * (lim + xm), 0.0))
+    dx, dy = xk - xm, yk - ym
+    lkm = np.sqrt(dx * dx + dy * dy)
+    # the four outer sides: old code -> new code;  a partner that is itself one of them is remapped first
+    remap = {3 * f + s1: 3 * g + 1, 3 * f + s2: 3 * f, 3 * g + t1: 3 * f + 1, 3 * g + t2: 3 * g}
+    partner = {new: remap.get(int(G[old // 3, old % 3]), int(G[old // 3, old % 3])) for old, new in remap.items()}
+    Fp[f] = (k, i, m)
+    Fp[g] = (m, j, k)
+    l[f] = (lki, lim, lkm)
+    l[g] = (lmj, ljk, lkm)
+    for new, q in partner.items():
+        G[new // 3, new % 3] = q
+        if q >= 0:
+            G[q // 3, q % 3] = new
+    G[f, 2], G[g, 2] = 3 * g + 2, 3 * f + 2
+
+
+def intrinsic_delaunay(V: np.ndarray, F: np.ndarray, order: str = "fifo", seed: int = 0):
+    """(F', l', flips): the intrinsic Delaunay triangulation of the mesh (V, F) by edge flips — faces (nF, 3), fp64 side
+    lengths (nF, 3) in the layout of edge_lengths, and the number of flips.  V is rounded to fp32 first (the device reads fp32
+    coordinates), everything after that is fp64.  order: "fifo" | "lifo" | "random" (seeded) — the work-list discipline; the
+    triangulation does not depend on it unless four vertices are cocircular, only the flip count and the last bits of l' do.
+    Plain Python loops over a work list: the yardstick of the device builder and the CPU path of dataset construction, slow at
+    FAUST size (half a second for 13 780 faces and 13 000 flips, some 600 times the device builder: LABNOTES.md#intrinsic).
+    Raises ValueError for a mesh mesh_glue refuses."""
+    if order not in ("fifo", "lifo", "random"):
+        raise ValueError('intrinsic_delaunay: order must be "fifo", "lifo" or "random"')
+    Fp, l, G, flips = _intrinsic_state(V, F, order, seed)
+    return Fp, l, flips
+
+
+def _intrinsic_state(V, F, order="fifo", seed=0):
+    V = np.asarray(V, dtype=np.float32).astype(np.float64)
+    Fp = np.array(F, dtype=np.int64)
+    G = mesh_glue(Fp, V.shape[0])
+    l = edge_lengths(V, Fp)
+    rng = np.random.default_rng(seed)
+    from collections import deque
+
+    work = deque(range(3 * Fp.shape[0]))
+    flips = 0
+    while work:
+        if order == "fifo":
+            c = work.popleft()
+        elif order == "lifo":
+            c = work.pop()
+        else:
+            k = int(rng.integers(len(work)))
+            work[k], work[-1] = work[-1], work[k]
+            c = work.pop()
+        f, s = c // 3, c % 3
+        p = int(G[f, s])
+        if p < 0 or p // 3 == f:
+            continue
+        cf, cg = _side_cot(l, f, s), _side_cot(l, p // 3, p % 3)
+        if cf is None or cg is None or not cf + cg < IDT_THRESHOLD:
+            continue
+        _flip(Fp, l, G, f, s)
+        flips += 1
+        g = p // 3
+        work.extend((3 * f, 3 * f + 1, 3 * g, 3 * g + 1))      # the four outer sides, where they are now
+    return Fp, l, G, flips
+
+
+def intrinsic_laplacian_from_lengths(Fp: np.ndarray, l: np.ndarray, num_vertices: int, dtype=np.float64) -> sp.csr_matrix:
+    """L = A^-1 (D - W) of a Delta-complex given by faces and side lengths, in this project's convention and in the
+    summation order of the device builder: per face and ordered pair (p, q, r), w = (-l_pq^2 + l_qr^2 + l_rp^2)/(8a + 1e-6)
+    goes to W[F[p], F[q]], its mirror (-l_qp^2 + l_pr^2 + l_rq^2)/(8a + 1e-6) to the column sum d[F[p]], a/3/4 to A[F[p]];
+    a pair with F[p] == F[q] (a self-edge) contributes its mass only.  Every entry is the serial sum of its contributions in
+    (face, permutation) order.  Pattern: every vertex pair joined by an edge plus the whole diagonal, zeros kept."""
+    Fp = np.asarray(Fp)
+    nF, nV = Fp.shape[0], int(num_vertices)
+    a = heron_areas(l)
+    l2 = l * l
+    e2 = np.empty((nF, 3, 3))
+    e2[:, 0, 1] = e2[:, 1, 0] = l2[:, 0]
+    e2[:, 1, 2] = e2[:, 2, 1] = l2[:, 1]
+    e2[:, 2, 0] = e2[:, 0, 2] = l2[:, 2]
+    den = 8 * a + 1e-6
+    W, d, A = {}, np.zeros(nV), np.zeros(nV)
+    for f in range(nF):
+        for p, q, r in _PERMS:
+            i, j = int(Fp[f, p]), int(Fp[f, q])
+            A[i] += a[f] / 3 / 4
+            if i == j:
+                continue
+            W[(i, j)] = W.get((i, j), 0.0) + ((-e2[f, p, q] + e2[f, q, r]) + e2[f, r, p]) / den[f]
+            d[i] += ((-e2[f, q, p] + e2[f, p, r]) + e2[f, r, q]) / den[f]
+    ainv = 1 / (A + 1e-9)
+    rows = [i for i, _ in W] + list(range(nV))
+    cols = [j for _, j in W] + list(range(nV))
+    vals = [ainv[i] * (0 - w) for (i, _), w in W.items()] + list(ainv * d)
+    o = np.lexsort((cols, rows))
+    rows, cols, vals = np.asarray(rows)[o], np.asarray(cols)[o], np.asarray(vals)[o]
+    rowptr = np.zeros(nV + 1, dtype=np.int32)
+    np.cumsum(np.bincount(rows, minlength=nV), out=rowptr[1:])
+    return sp.csr_matrix((vals.astype(dtype), cols.astype(np.int32), rowptr), shape=(nV, nV))
+
+
+def intrinsic_laplacian(V: np.ndarray, F: np.ndarray, order: str = "fifo", seed: int = 0) -> sp.csr_matrix:
+    """The reference's mesh.intrinsic_laplacian by name (src/utils/mesh.py imports an unpublished module for it): this
+    project's mass-normalised cotangent Laplacian A^-1 (D - W) on the intrinsic Delaunay triangulation of (V, F), fp64 CSR.
+    Scaling and sign of the unpublished matrix are unknown; this is not a reproduction of it.  Every off-diagonal weight of an
+    interior edge is >= 0 (the maximum principle the extrinsic operator lacks).  Host loops: slow at FAUST size."""
+    Fp, l, _ = intrinsic_delaunay(V, F, order, seed)
+    return intrinsic_laplacian_from_lengths(Fp, l, np.asarray(V).shape[0])
 
 
 # --------------------------------------------------------------------------------------------------

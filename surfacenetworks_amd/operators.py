@@ -404,10 +404,16 @@ def dirac_operators_from_mesh(V: torch.Tensor, F: torch.Tensor):
     return Di, DiA
 
 
-def laplacian_operator_from_mesh(V: torch.Tensor, F: torch.Tensor) -> SparseOperator:
+def laplacian_operator_from_mesh(V: torch.Tensor, F: torch.Tensor, intrinsic: bool = False, max_rounds: int = 1024) -> SparseOperator:
     """L = A^-1 (D - W) built on the device (sn_laplacian_csr_from_mesh) — replaces the host pipeline
     mesh.cotangent_weights + graph.laplacian (src/mesh_mnist/add_laplacian.py:43-48).  V: (nV,3) or (B,nV,3) for a batch
-    of equally sized meshes (block-diagonal result); F: (nF,3) shared or (B,nF,3)."""
+    of equally sized meshes (block-diagonal result); F: (nF,3) shared or (B,nF,3).
+    intrinsic=True: the same operator on the intrinsic Delaunay triangulation of the mesh (edge flips on the device,
+    kernels.intrinsic_laplacian_from_mesh; include/sn_spmm.h has the definition) — what the reference calls
+    mesh.intrinsic_laplacian, although NOT a reproduction of its unpublished matrix, whose scaling and sign are unknown.
+    Every interior edge then has a non-negative weight.  A batch is one launch sequence over the offset faces.  Limits: the
+    mesh must be manifold and consistently oriented (ValueError names what it is not), at most max_rounds parallel flip
+    rounds (RuntimeError), explicit zeros are kept, no vertex-degree limit."""
     if V.dim() == 3:
         B, nV = V.shape[0], V.shape[1]
         Fb = F if F.dim() == 3 else F.unsqueeze(0).expand(B, -1, -1)
@@ -417,7 +423,10 @@ def laplacian_operator_from_mesh(V: torch.Tensor, F: torch.Tensor) -> SparseOper
     else:
         B, nV = 1, V.shape[0]
         Vg, Fg = V, F.to(torch.int32)
-    rowptr, colind, vals = kernels.laplacian_from_mesh(Vg.float(), Fg)
+    if intrinsic:
+        rowptr, colind, vals = kernels.intrinsic_laplacian_from_mesh(Vg.float(), Fg, max_rounds)
+    else:
+        rowptr, colind, vals = kernels.laplacian_from_mesh(Vg.float(), Fg)
     return SparseOperator(rowptr, colind, vals, (B * nV, B * nV), batch=B)
 
 
