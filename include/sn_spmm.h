@@ -155,6 +155,21 @@ int sn_spmm_q3_elubwd_absmax_f32(const int32_t *b_rowptr, const float *q_blk, in
                                  const float *X, int64_t ldx, int32_t x_group, int32_t N, const float *E, int64_t lde,
                                  const float *G, int64_t ldg, float *Y, int64_t ldy, int32_t y_group, float *y_absmax,
                                  void *stream);
+/* The same product for a RAW G: the bare product p that sn_linear_dgrad_elu_rawlow_f32 left in place of the finished input
+ * gradient of the stage whose activated operand is E.  The store finishes it with E in registers, in the operation order of
+ * that GEMM's own epilogue (bit-identical to the two-kernel result):
+ *     g = v + v·min(E, 0),  v = p + ((E - center[c])·B[c] + Cc[c]),      Y = (A·X) ∘ elu'(E) + g
+ * center / B / Cc: device, 4·N floats each, indexed by channel c = N·component + column (16-byte aligned).
+ * sn_spmm_q3_tail_supported(N, y_group): N = 32 | 16 and group-4 rows; anything else is SN_E_UNSUPPORTED — finish G first with
+ * sn_elu_tail_finish_f32 (G <- g in place on a (rows x C) matrix, channel = column: C % 4 = 0, 16-byte aligned) and run the
+ * plain fused product.  y_absmax may be NULL. */
+int32_t sn_spmm_q3_tail_supported(int32_t N, int32_t y_group);
+int sn_spmm_q3_elubwd_tail_absmax_f32(const int32_t *b_rowptr, const float *q_blk, int64_t Mb, int64_t Kb, int64_t nblocks,
+                                      const float *X, int64_t ldx, int32_t x_group, int32_t N, const float *E, int64_t lde,
+                                      const float *G, int64_t ldg, const float *center, const float *B, const float *Cc,
+                                      float *Y, int64_t ldy, int32_t y_group, float *y_absmax, void *stream);
+int sn_elu_tail_finish_f32(float *g, int64_t ldg, const float *E, int64_t lde, const float *center, const float *B,
+                           const float *Cc, int64_t rows, int32_t C, void *stream);
 int sn_bsr4_to_q3_f32(const int32_t *b_colind, const float *b_vals, int64_t nblocks, float *q_blk,
                       int32_t *not_quaternion, void *stream);
 
@@ -988,6 +1003,14 @@ int sn_linear_dgrad_elu_absmax_f32(const float *dy, int64_t lddy, const float *W
                                    const float *center, const float *B, const float *Cc, float *dx_hi, int64_t lddx,
                                    float *gact, int64_t ldga, const float *gadd, int64_t ldgadd,
                                    int64_t rows, int32_t J, int32_t C, float *gact_absmax, void *stream);
+/* The "raw low half" form: dx_hi as above; columns below C/2 leave as the bare product graw = dy·W[:, :C/2] — no BatchNorm
+ * tail, no activation derivative, no maximum — and x[:, :C/2] is NOT READ (the side window starts at column C/2).  The one
+ * consumer of that gradient, a transposed product whose epilogue streams the same elu(.) anyway, finishes it
+ * (sn_spmm_q3_elubwd_tail_absmax_f32, or sn_elu_tail_finish_f32 in place).  center / B / Cc: the full C-wide vectors (only
+ * their high halves are read).  Same shapes, alignment rules and error codes as sn_linear_dgrad_elu_f32. */
+int sn_linear_dgrad_elu_rawlow_f32(const float *dy, int64_t lddy, const float *W, int64_t ldw, const float *x, int64_t ldx,
+                                   const float *center, const float *B, const float *Cc, float *dx_hi, int64_t lddx,
+                                   float *graw, int64_t ldgr, int64_t rows, int32_t J, int32_t C, void *stream);
 int sn_linear_fwd_segbias_f32(const float *x, int64_t ldx, const float *W, int64_t ldw, const float *segbias,
                               int64_t rows_per_seg, const float *residual, int64_t ldr, float *y, int64_t ldy,
                               float *y_elu, int64_t lde, int64_t rows, int32_t K, int32_t J, double *elu_stats_part,

@@ -87,6 +87,12 @@ SIGNATURES = {
     "sn_spmm_q3_absmax_blocks": (_i64, [_i64, _i32]),
     "sn_spmm_q3_elubwd_absmax_f32": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _i32,
                                                _vp, _vp]),
+    "sn_spmm_q3_tail_supported": (_i32, [_i32, _i32]),
+    "sn_spmm_q3_elubwd_tail_absmax_f32": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
+                                                    _vp, _i64, _i32, _vp, _vp]),
+    "sn_elu_tail_finish_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "sn_linear_dgrad_elu_rawlow_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32,
+                                                 _vp]),
     "sn_wgrad_thin_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "sn_wgrad_thin_f32": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "sn_masked_smooth_l1_workspace_bytes": (_sz, [_i64, _i32]),

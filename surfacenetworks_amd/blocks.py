@@ -33,6 +33,12 @@ from .operators import as_operator
 __all__ = ["lap_block", "dirac_block", "avg_block", "avg_block_ragged", "avg_block_ragged_ok", "take_activated", "attach_activated", "zero_faces_ok", "elu_conv", "elu_conv_ok"]
 
 
+# A Dirac block whose face input is the activated hand-off of a block that ran with need_f=False returns the gradient of that
+# input RAW — the bare product of its input-gradient GEMM, which then does not read elu(f) — and the previous block's DiAᵀ
+# product, whose store streams the same elu(f) anyway, finishes it (LABNOTES.md#r7tail).  False: every block finishes its own.
+DEFER_FACE_TAIL = True
+
+
 def _version_of(t: torch.Tensor):
     """The tensor's version counter; None for tensors made under torch.inference_mode() — they carry none (reading it
     raises) and cannot be edited in place outside inference mode either, so there is nothing to compare."""
@@ -215,7 +221,7 @@ def _plan_forward(ctx, site, impl, tensors, ops, consts, ncols, n_dyn, scan):
     site.replayed += 1
     build = plans._Builder(big, small, ext)
     outs = build(plan.result[0])
-    if plan.effects:
+    if plan.effects or plan.tail_effects:
         plans.apply_effects(plan, build)
     # What the backward needs: the arenas and the operands the saved descriptions point into.  Plain attributes, dropped by
     # the backward itself: autograd's saved-tensor slots would tie the arena's version counter — shared by every view of
@@ -235,17 +241,19 @@ def _plan_backward(ctx, site, impl, grads, consts):
     ctx._sn_plan = None
     op_arrays, op_key = _op_operands(ops, ncols) if ops else ((), ())
     maxima = [kernels.take_absmax(g) if g is not None else None for g in grads]
-    ext = [big, small, *kept, *grads, *maxima, *op_arrays]
+    tails = [kernels.take_tail(g) if g is not None else None for g in grads]      # raw gradients: what finishes them is an operand
+    flat_tails = [t for tl in tails for t in (tl if tl is not None else (None, None, None))]
+    ext = [big, small, *kept, *grads, *maxima, *flat_tails, *op_arrays]
     gptrs = [g.data_ptr() if g is not None else 0 for g in grads]
     key = (tuple([None if g is None else (g.shape, g.stride(), g.dtype) for g in grads]), tuple([m is not None for m in maxima]),
-           op_key, consts, tuple([gptrs.index(p_) for p_ in gptrs]))      # (one gradient tensor handed in for two outputs)
+           tuple([tl is not None for tl in tails]), op_key, consts, tuple([gptrs.index(p_) for p_ in gptrs]))      # (one gradient tensor handed in for two outputs)
     plan = fplan.bwd.get(key, _MISSING)
     if plan is _MISSING or plan is None:
         fext = [None] * fplan.n_ext
         for j, t in zip(fplan.saved_ext, kept):
             fext[j] = t
         saved = plans._Builder(big, small, fext)(fplan.result[1])
-        plans.renote(grads, maxima)
+        plans.renote(grads, maxima, tails)
         if plan is None:                                           # not plannable: the eager backward on the saved tensors
             return impl(saved, *[o for o, _ in ops], *grads, *consts)
         g0 = 2 + len(kept)
@@ -253,18 +261,19 @@ def _plan_backward(ctx, site, impl, grads, consts):
                             grads_device(grads, big, small), range(g0, g0 + len(grads)))
         fplan.bwd[key] = plan
         if plan is None:
-            plans.renote(grads, maxima)                            # (the dry run took them)
+            plans.renote(grads, maxima, tails)                            # (the dry run took them)
             return impl(saved, *[o for o, _ in ops], *grads, *consts)
-        for g in grads:                                            # (bounds the dry run did not take)
+        for g in grads:                                            # (bounds and tails the dry run did not take)
             if g is not None:
                 kernels.take_absmax(g)
+                kernels.take_tail(g)
     timer = SpmmTimer.active
     if timer is not None:
         if plan.tags is None:
             fext = [None] * fplan.n_ext
             for j, t in zip(fplan.saved_ext, kept):
                 fext[j] = t
-            plans.renote(grads, maxima)
+            plans.renote(grads, maxima, tails)
             return impl(plans._Builder(big, small, fext)(fplan.result[1]), *[o for o, _ in ops], *grads, *consts)
         timer.tags.extend(plan.tags)
     b2, s2 = plan.new_arenas(grads_device(grads, big, small))
@@ -272,7 +281,7 @@ def _plan_backward(ctx, site, impl, grads, consts):
     site.replayed += 1
     build = plans._Builder(b2, s2, ext)
     out = build(plan.result)
-    if plan.effects:
+    if plan.effects or plan.tail_effects:
         plans.apply_effects(plan, build)
     return out
 
@@ -334,11 +343,16 @@ def _dirac_fwd(v, f, pre_v, pre_f, g0, b0, W0, c0, rm0, rv0, g1, b1, W1, c1, rm1
     return (v_new, f_out, nxt_v, nxt_f), ((cat0, cat1, nxt_f), st0, st1)
 
 
-def _dirac_bwd(saved, opDi, opDiA, g_vnew, g_fo, f_zero, need_gv, need_gf):
-    """Backward of _dirac_fwd: (g_v, g_f, dgamma0, dbeta0, dW0, db0, dgamma1, dbeta1, dW1, db1)."""
+def _dirac_bwd(saved, opDi, opDiA, g_vnew, g_fo, f_zero, need_gv, need_gf, defer=False, expect_raw=False):
+    """Backward of _dirac_fwd: (g_v, g_f, dgamma0, dbeta0, dW0, db0, dgamma1, dbeta1, dW1, db1).
+    defer: g_f leaves raw, its tail noted for the block before (DEFER_FACE_TAIL); expect_raw: the block after this one said it
+    would do that with the gradient arriving here as g_fo."""
     (cat0, cat1, nxt_f), st0, st1 = saved
     C = cat1.shape[1] // 2
     dev = cat1.device
+    tail = kernels.take_tail(g_fo) if g_fo is not None else None
+    if expect_raw and g_fo is not None and tail is None:                        # (_DiracBlock.backward has looked already)
+        raise RuntimeError("dirac_block: a raw face gradient without its tail")
     # Every ELU backward of the block is fused: the dgrad GEMM's epilogue sends the first half of a stage's input
     # gradient through the activation (h = dx[:, :C]·elu'(e) + the gradient of the other branch), and the transposed
     # product's store does the same for the propagated half:  (opᵀ·dx[:, C:])·elu'(e) + h.
@@ -350,14 +364,20 @@ def _dirac_bwd(saved, opDi, opDiA, g_vnew, g_fo, f_zero, need_gv, need_gf):
         gp1 = (dg1, db1, dW1, dc1)
         g_sum = torch.empty((nxt_f.shape[0], C), dtype=torch.float32, device=dev)
         # (DiA^T·dx1_hi)·elu'(e_f)  +  the gradient f_out receives from the next block
-        _launch(opDiA.t(), dx1_hi, g_sum, 4, "bwd", elubwd=(nxt_f[:, :C], g_fo))
+        _launch(opDiA.t(), dx1_hi, g_sum, 4, "bwd", elubwd=(nxt_f[:, :C], g_fo) if tail is None else (nxt_f[:, :C], g_fo, tail))
         g_fo = g_sum
+    elif tail is not None:
+        kernels.elu_tail_finish(g_fo, nxt_f[:, :C], tail)                       # no product to finish it: in place, here
     # ---- first stage (face rows) ----
     gp0 = (None,) * 4
     g_v = g_f = None
     dx0_hi = None
     if g_fo is not None and f_zero:
         dx0_hi, dg0, db0, dW0, dc0 = bnlin_backward_zero_first(st0, g_fo)          # no gradient for the zero half
+        gp0 = (dg0, db0, dW0, dc0)
+    elif g_fo is not None and defer and need_gf:
+        (dx0_hi, g_f), dg0, db0, dW0, dc0, tail_f = bnlin_backward(st0, g_fo, through_elu=(None,), raw_low=True)
+        kernels.note_tail(g_f, tail_f)                                          # g_f = dy·W[:, :C]: the block before finishes it
         gp0 = (dg0, db0, dW0, dc0)
     elif g_fo is not None:
         (dx0_hi, g_f), dg0, db0, dW0, dc0 = bnlin_backward(st0, g_fo, through_elu=(None,))   # g_f = dx0[:, :C]·elu'(e_f)
@@ -384,6 +404,15 @@ class _DiracBlock(torch.autograd.Function):
             f = _rows2d(f)                     # (with a hand-off f is only a carrier — possibly the zero-stride NaN placeholder of
         ctx.f_zero = f is None                 #  need_f=False: making THAT contiguous wrote 321 MB per block at the ARAP batch)
         ctx.ops = (opDi, opDiA)
+        # Raw face gradient (DEFER_FACE_TAIL).  A block that ran with need_f=False hangs a one-element list on its nxt_f: the
+        # only consumer its face gradient can have is the block that takes that hand-off, which says so here — the producer's
+        # backward then expects a raw gradient and refuses anything else.
+        box = pre_f.__dict__.get("_sn_rawbox") if pre_f is not None else None
+        ctx.defer = bool(DEFER_FACE_TAIL and box is not None and tr0 and v.is_cuda and
+                         kernels.linear_dgrad_elu_supported(W0.shape[0], W0.shape[1]) and W0.shape[1] == 2 * v.shape[1])
+        if ctx.defer:
+            box[0] = True
+        ctx.rawbox = [False] if not need_f else None
         tensors = (v, f, pre_v, pre_f, g0, b0, W0, c0, rm0, rv0, g1, b1, W1, c1, rm1, rv1)
         consts = (need_f, avg_next, tr0, mo0, ep0, tr1, mo1, ep1)
         outs = None
@@ -402,6 +431,8 @@ class _DiracBlock(torch.autograd.Function):
             # face features are not written (321 MB per block at the ARAP batch).  What is returned in their place is a
             # zero-stride NaN view, so that any other use of it is loud instead of silently wrong.
             f_out = _nan_placeholder(v.device).expand(nxt_f.shape[0], v.shape[1])
+            if ctx.rawbox is not None:
+                nxt_f._sn_rawbox = ctx.rawbox
         ctx.mark_non_differentiable(nxt_v, nxt_f)
         ctx.set_materialize_grads(False)
         return v_new, f_out, nxt_v, nxt_f
@@ -413,7 +444,12 @@ class _DiracBlock(torch.autograd.Function):
         opDi, opDiA = ctx.ops
         g_vnew = g_vnew.contiguous() if g_vnew is not None else None
         g_fout = g_fout.contiguous() if g_fout is not None else None
-        consts = (ctx.f_zero, bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1]))
+        consts = (ctx.f_zero, bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1]), ctx.defer,
+                  bool(ctx.rawbox is not None and ctx.rawbox[0]))
+        if consts[4] and g_fout is not None and not kernels.has_tail(g_fout):
+            raise RuntimeError("dirac_block: the gradient of the face output was left raw by the next Dirac block (DEFER_FACE_TAIL), but "
+                               "what finishes it is gone — the gradient was copied, edited in place, or kernels.clear_absmax() ran "
+                               "between the two backward calls")
         if ctx._sn_planned:
             r = _plan_backward(ctx, _SITES["dirac_bwd"], _dirac_bwd, (g_vnew, g_fout), consts)
         else:

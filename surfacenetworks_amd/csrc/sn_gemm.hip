@@ -364,7 +364,10 @@ __device__ __forceinline__ void bst4(rsrc_t r, int voff, const f4 &v) {         
   __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, v), r, voff, 0, 2);
 }
 
-template <int PC, int K, int NT, bool TRANSW, int EPI, bool SIDE, bool ELU, bool SMALL = false, int WV = 4>
+// RAWLOW (dgrad+elu only): the low half leaves as the BARE product — no BatchNorm tail, no activation derivative, no maximum —
+// and its side operand is never read: the transposed product that consumes it holds elu(.) in registers already and finishes
+// the gradient in its store (sn_spmm_q3_elubwd_tail_absmax_f32).  ep.v0 then points at column `half` of x.
+template <int PC, int K, int NT, bool TRANSW, int EPI, bool SIDE, bool ELU, bool SMALL = false, int WV = 4, bool RAWLOW = false>
 __global__ __launch_bounds__(64 * WV, (PC == 2 && K == 128 && NT == 1 && WV == 4) ? 2 : 1) void gemm_rows_split_k(const float *__restrict__ In, int64_t ldi,
                                                          const float *__restrict__ W, int64_t ldw,
                                                          float *__restrict__ Out, int64_t ldo, int64_t rows, EpiArgs ep) {
@@ -473,14 +476,17 @@ __global__ __launch_bounds__(64 * WV, (PC == 2 && K == 128 && NT == 1 && WV == 4
   f4 k0 = {0.f, 0.f, 0.f, 0.f}, k1 = k0, k2 = k0;
   constexpr bool DGE = (EPI == EPI_DGRAD_ELU);
   static_assert(!DGE || SIDE, "the ELU variant needs the BatchNorm tail operand");
+  static_assert(!RAWLOW || DGE, "the raw low half is a form of the input gradient through the activation");
   const bool lowhalf = DGE && 32 * NT * wave < ep.half;          // a wave's 32·NT columns lie on one side (scalar condition)
   const bool colv = EPI != EPI_FWD || ecol < ep.jv;          // my 4 output columns exist
   if constexpr (EPI == EPI_FWD) {
     if (colv) k0 = *reinterpret_cast<const f4 *>(ep.v0 + ecol);                      // bias
   } else if constexpr (SIDE) {
-    if (ep.v1) k0 = *reinterpret_cast<const f4 *>(ep.v1 + ecol);                     // center (optional)
-    k1 = *reinterpret_cast<const f4 *>(ep.v2 + ecol);                                // B
-    k2 = *reinterpret_cast<const f4 *>(ep.v3 + ecol);                                // Cc
+    if (!(RAWLOW && lowhalf)) {                                                      // (a raw low half has no tail)
+      if (ep.v1) k0 = *reinterpret_cast<const f4 *>(ep.v1 + ecol);                   // center (optional)
+      k1 = *reinterpret_cast<const f4 *>(ep.v2 + ecol);                              // B
+      k2 = *reinterpret_cast<const f4 *>(ep.v3 + ecol);                              // Cc
+    }
   }
   const f4 kcs = *reinterpret_cast<const f4 *>(s_cs + ecol);                           // inverse scales of my 4 columns
   unsigned char *const sw = &stg[wave][0] + n * SROW + 16 * h;                       // where my accumulators go (+128t + 32g)
@@ -488,8 +494,13 @@ __global__ __launch_bounds__(64 * WV, (PC == 2 && K == 128 && NT == 1 && WV == 4
   // my byte offset inside a tile of each epilogue matrix (row erow, + RPI rows per store instruction), and the windows
   const float *side_p = (EPI == EPI_FWD) ? ep.v1 : ep.v0;   // SIDE: forward: the residual; dgrad: x of the BatchNorm tail
   const bool has_out = (EPI != EPI_FWD && !DGE) || Out != nullptr;
-  const bool has_ga = DGE && lowhalf && ep.v4 != nullptr;
-  const int vo_side = colv ? 4 * (erow * (int)ep.ld1 + ecol) : kOob, js_side = 4 * RPI * (int)ep.ld1;
+  const bool has_ga = DGE && !RAWLOW && lowhalf && ep.v4 != nullptr;
+  // RAWLOW: the side window starts at column `half` of x (ep.v0 points there) and a lane addresses columns scol .. scol + 3 of
+  // it, 0 <= scol <= NOUT - half - 4, i.e. columns >= half of x in every row; the waves of the low half get an EMPTY window and
+  // issue no side load at all.  No byte of x[:, :half] is ever requested — and an offset that would (scol < 0) is sent out of
+  // range here, once per kernel, instead of being trusted
+  const int scol = RAWLOW ? ecol - ep.half : ecol;          // my first column inside the side window
+  const int vo_side = (colv && (!RAWLOW || scol >= 0)) ? 4 * (erow * (int)ep.ld1 + scol) : kOob, js_side = 4 * RPI * (int)ep.ld1;
   const int vo_out = colv ? 4 * (erow * (int)ldo + ecol) : kOob, js_out = 4 * RPI * (int)ldo;
   const int vo_o2 = colv ? 4 * (erow * (int)ep.ld2 + ecol) : kOob, js_o2 = 4 * RPI * (int)ep.ld2;
   const int vo_ga = 4 * (erow * (int)ep.ld3 + ecol), js_ga = 4 * RPI * (int)ep.ld3;
@@ -501,7 +512,10 @@ __global__ __launch_bounds__(64 * WV, (PC == 2 && K == 128 && NT == 1 && WV == 4
   const int ispan = EPI == EPI_FWD ? K : ep.jv;              // columns the operands really have (a window's span must not
   const int ospan = EPI == EPI_FWD ? ep.jv : NOUT;           // exceed its leading dimension, or the row past the end is in range)
   w_in.init(In, ldi, row0, last_nrt, ispan);
-  if constexpr (SIDE) w_side.init(side_p, ep.ld1, row0, last_nrt, ospan);
+  if constexpr (SIDE) {
+    if (RAWLOW && lowhalf) w_side.init_empty();
+    else w_side.init(side_p, ep.ld1, row0, last_nrt, RAWLOW ? NOUT - ep.half : ospan);
+  }
   if (has_out) w_out.init(Out, ldo, row0, last_nrt, ospan);
   else w_out.init_empty();                                   // stores through it are dropped
   if constexpr (DGE || (EPI == EPI_FWD && ELU)) w_o2.init(ep.o2, ep.ld2, row0, last_nrt, DGE ? ep.half : ospan);
@@ -590,9 +604,11 @@ __global__ __launch_bounds__(64 * WV, (PC == 2 && K == 128 && NT == 1 && WV == 4
     // side operand in the epilogue layout (full lines), requested now, consumed after the k loop
     f4 sd[NST];
     if constexpr (SIDE) {
-      const rsrc_t r_side = w_side.rsrc(to_last);
+      if (!(RAWLOW && lowhalf)) {
+        const rsrc_t r_side = w_side.rsrc(to_last);
 #pragma unroll
-      for (int j = 0; j < NST; ++j) sd[j] = bld4(r_side, vo_side + j * js_side);
+        for (int j = 0; j < NST; ++j) sd[j] = bld4(r_side, vo_side + j * js_side);
+      }
     }
     // per-mesh vector of my rows (forward: the bias; dgrad+elu: added before elu'): REQUESTED here, combined in the epilogue —
     // anything computed from these loads before the k loop would wait for them, i.e. drain the row prefetch, once per tile.
@@ -623,7 +639,7 @@ __global__ __launch_bounds__(64 * WV, (PC == 2 && K == 128 && NT == 1 && WV == 4
       }
     }
     f4 ga[NST];                        // dgrad+elu, low half: the gradient added after the activation derivative
-    if constexpr (DGE) {
+    if constexpr (DGE && !RAWLOW) {
       if (lowhalf) {                   // (without the operand: an empty window — the loads return zeros, no traffic)
         const rsrc_t r_ga = w_ga.rsrc(to_last);
 #pragma unroll
@@ -694,7 +710,19 @@ __global__ __launch_bounds__(64 * WV, (PC == 2 && K == 128 && NT == 1 && WV == 4
       }
       return v;
     };
-    if constexpr (DGE) {
+    if constexpr (RAWLOW) {
+      if (lowhalf) {                     // the bare product: out_row's value before the tail (the consumer finishes it)
+#pragma unroll
+        for (int j = 0; j < NST; ++j) {
+          f4 v = *reinterpret_cast<const f4 *>(sr + RPI * j * SROW);
+          v *= kcs;
+          bst4(r_o2, vo_o2 + j * js_o2, v);
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < NST; ++j) bst4(r_out, vo_out + j * js_out, out_row(j));
+      }
+    } else if constexpr (DGE) {
       if (lowhalf) {                     // through the activation: elu'(.) from the activation OUTPUT held in the side operand
 #pragma unroll
         for (int j = 0; j < NST; ++j) {
@@ -1067,6 +1095,17 @@ constexpr int64_t kSmallRows = 131072;      // operands up to this many rows tak
       else hipLaunchKernelGGL((gemm_rows_split_k<2, SN_UNPAREN TARGS>), dim3(grid), dim3(kWG), 0, s, __VA_ARGS__);     \
     }                                                                                                                  \
   } while (0)
+// the raw-low-half form of the input gradient through the activation (gemm_rows_split_k<…, RAWLOW>), NT_ output tiles per wave
+#define SN_SPLIT_LAUNCH_RAW(NT_, ...)                                                                                  \
+  do {                                                                                                                 \
+    if (rows <= kSmallRows) {                                                                                          \
+      if (t_start) hipExtLaunchKernelGGL((gemm_rows_split_k<2, 128, NT_, true, EPI_DGRAD_ELU, true, false, true, 4, true>), dim3(grid), dim3(kWG), 0, s, t_start, t_stop, 0, __VA_ARGS__); \
+      else hipLaunchKernelGGL((gemm_rows_split_k<2, 128, NT_, true, EPI_DGRAD_ELU, true, false, true, 4, true>), dim3(grid), dim3(kWG), 0, s, __VA_ARGS__); \
+    } else {                                                                                                           \
+      if (t_start) hipExtLaunchKernelGGL((gemm_rows_split_k<2, 128, NT_, true, EPI_DGRAD_ELU, true, false, false, 4, true>), dim3(grid), dim3(kWG), 0, s, t_start, t_stop, 0, __VA_ARGS__); \
+      else hipLaunchKernelGGL((gemm_rows_split_k<2, 128, NT_, true, EPI_DGRAD_ELU, true, false, false, 4, true>), dim3(grid), dim3(kWG), 0, s, __VA_ARGS__); \
+    }                                                                                                                  \
+  } while (0)
 #define SN_SPLIT_LAUNCH_NT2(K_, EPI_, SIDE_, ...) SN_SPLIT_LAUNCH((K_, 2, true, EPI_, SIDE_, false), __VA_ARGS__)
 
 // Workgroups per CU.  One 4-wave workgroup per CU is a single wave per SIMD that owns the register file; the K = 128, one-tile
@@ -1230,6 +1269,32 @@ int sn_linear_dgrad_elu_absmax_f32(const float *dy, int64_t lddy, const float *W
   else
     SN_SPLIT_LAUNCH((128, 1, true, EPI_DGRAD_ELU, true, false), dy, lddy, W, ldw, out,
                        lddx, rows, ep);
+  return launch_status();
+}
+
+int sn_linear_dgrad_elu_rawlow_f32(const float *dy, int64_t lddy, const float *W, int64_t ldw, const float *x, int64_t ldx,
+                                   const float *center, const float *B, const float *Cc, float *dx_hi, int64_t lddx, float *graw,
+                                   int64_t ldgr, int64_t rows, int32_t J, int32_t C, void *stream) {
+  (void)hipGetLastError();      // a stale error left by an earlier runtime call of this thread is not ours to report
+  if (rows < 0 || J < 1 || C < 2 || lddy < J || ldw < C || lddx < C / 2 || ldgr < C / 2 || ldx < C) return SN_E_SHAPE;
+  if (J > 128 || (J % 4) || (C != 128 && C != 256) || gemm_variant() == 0 || !ld32(lddy, ldx, lddx, ldgr)) return SN_E_UNSUPPORTED;
+  if (rows == 0) return SN_OK;
+  if (!dy || !W || !dx_hi || !graw || !x || !B || !Cc) return SN_E_NULL;
+  if (!aligned16(dy) || !aligned16(W) || !aligned16(dx_hi) || !aligned16(graw) || !aligned16(x) || !aligned16(B) ||
+      !aligned16(Cc) || (center && !aligned16(center)) || (lddy % 4) || (ldw % 4) || (lddx % 4) || (ldgr % 4) || (ldx % 4))
+    return SN_E_ALIGN;
+  const int half = C / 2;
+  // the side operand as the kernel sees it: x from column `half` on (no lane's offset reaches the low 4·half bytes of a row)
+  EpiArgs ep{x + half, center, B, Cc, graw, ldx, ldgr, nullptr, 0, half, nullptr, 0, 0, nullptr, nullptr, 0, (int)J, nullptr, 0, nullptr, 1, nullptr};
+  float *out = dx_hi - half;           // the kernel indexes absolute columns; only columns >= half are written through `out`
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const unsigned grid = gemm_grid(rows, gemm_wgs(128, C / 128));
+  hipEvent_t t_start = nullptr, t_stop = nullptr;
+  sn_internal_timing_slot(0x200 | 2 | 16, rows, C, rows * 4 * ((int64_t)J + half + C), J, &t_start, &t_stop);
+  if (C == 256)
+    SN_SPLIT_LAUNCH_RAW(2, dy, lddy, W, ldw, out, lddx, rows, ep);
+  else
+    SN_SPLIT_LAUNCH_RAW(1, dy, lddy, W, ldw, out, lddx, rows, ep);
   return launch_status();
 }
 

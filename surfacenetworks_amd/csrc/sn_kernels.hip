@@ -90,6 +90,11 @@ struct SpmmEpi {
   // max |Y| over the rows a workgroup (quaternion-packed kernel: [gridDim.x]) or a wave (row-blocked and sliding-window Laplacian
   // kernels: [gridDim.x * waves]) wrote — sn_spmm_q3_elubwd_absmax_f32, sn_spmm_rb4_elubwd_absmax_f32, sn_spmm_csr_ring_elubwd_absmax_f32
   float *absmax = nullptr;
+  // G is a RAW input gradient (sn_linear_dgrad_elu_rawlow_f32: the bare product p of the consumer stage's GEMM) that this
+  // epilogue finishes with E in registers, in the GEMM epilogue's own operation order (tail_finish4):  g = (p + ((E - center)·B
+  // + Cc))·elu'(E).  Each vector holds 4·N floats, indexed by channel = N·component + column (the low halves of that stage's
+  // mean / B / C vectors).  All NULL: G is finished already.  Quaternion-packed kernels, N = 32 | 16, group-4 rows.
+  const float *center = nullptr, *B = nullptr, *Cc = nullptr;
 };
 __device__ __forceinline__ f4 fabs4(const f4 &a) {
   return f4{__builtin_fabsf(a.x), __builtin_fabsf(a.y), __builtin_fabsf(a.z), __builtin_fabsf(a.w)};
@@ -110,6 +115,32 @@ __device__ __forceinline__ float wave_max_nonneg(float m) {
 __device__ __forceinline__ f4 elu_bwd4(const f4 &a, const f4 &o) {
   return f4{a.x * (o.x > 0.f ? 1.f : o.x + 1.f), a.y * (o.y > 0.f ? 1.f : o.y + 1.f), a.z * (o.z > 0.f ? 1.f : o.z + 1.f),
             a.w * (o.w > 0.f ? 1.f : o.w + 1.f)};
+}
+
+// What the input-gradient GEMM's epilogue does to its product p on the way to the gradient behind the activation
+// (sn_gemm.hip, gemm_rows_split_k: out_row and the `lowhalf` branch) — the SAME operations in the same order, so that a raw
+// gradient finished here is bit-identical to one the GEMM finished itself.  (The product kernels write elu' as a select, the GEMM
+// as fma(v, min(o, 0), v): each form stays with the value it has always been applied to.)
+__device__ __forceinline__ float tail_finish1(float p, float e, float ce, float b, float c) {
+  const float xv = e - ce;
+  const float v = p + __builtin_fmaf(xv, b, c);
+  return __builtin_fmaf(v, fminf(e, 0.f), v);
+}
+__device__ __forceinline__ f4 tail_finish4(const f4 &p, const f4 &e, const f4 &ce, const f4 &b, const f4 &c) {
+  return f4{tail_finish1(p.x, e.x, ce.x, b.x, c.x), tail_finish1(p.y, e.y, ce.y, b.y, c.y),
+            tail_finish1(p.z, e.z, ce.z, b.z, c.z), tail_finish1(p.w, e.w, ce.w, b.w, c.w)};
+}
+// g <- tail_finish(g, E) in place on a (rows x C) matrix, channel = column: the stand-alone form for the products whose
+// epilogue cannot do it (BSR4, CSR, any-N).  One 16-byte piece per thread.
+__global__ __launch_bounds__(kWG) void tail_finish_k(float *__restrict__ g, int64_t ldg, const float *__restrict__ E, int64_t lde,
+                                                     const float *__restrict__ center, const float *__restrict__ B,
+                                                     const float *__restrict__ Cc, int64_t rows, int C4) {
+  const int64_t i = (int64_t)blockIdx.x * kWG + threadIdx.x;
+  if (i >= rows * C4) return;
+  const int64_t r = i / C4;
+  const int c = 4 * (int)(i - r * C4);
+  float *gp = g + r * ldg + c;
+  st4(gp, tail_finish4(ld4(gp), ld4_s(E + r * lde + c, kStreamNT), ld4(center + c), ld4(B + c), ld4(Cc + c)));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -442,6 +473,24 @@ __device__ __forceinline__ void spmm_q3_lds_body(const int *__restrict__ b_rowpt
   const int ke = b_rowptr[brc + 1 <= Mb ? brc + 1 : Mb];
   const int k0 = __builtin_amdgcn_readfirstlane(kb);
   const int k1 = (stays && r0 >= Mb) ? k0 : __builtin_amdgcn_readlane(ke, 63);   // (a wave past the end has no blocks)
+  // raw G (SpmmEpi::center / B / Cc): the three channel vectors go to this wave's own LDS copy by DMA, requested here, before
+  // the product loop, and read in the store path — no register is held across the loop and no workgroup barrier is needed
+  // (f4 index v·N + (N/4)·component + sub of vector v; the slots past 3·N take a second copy of Cc's)
+  constexpr bool TAILN = EPI && (N == 32 || N == 16);
+  constexpr int TAIL_LOADS = (3 * N + 63) / 64;
+  __shared__ f4 s_tail[TAILN ? WAVES : 1][TAILN ? 64 * TAIL_LOADS : 1];
+  bool tail = false;
+  if constexpr (TAILN) {
+    tail = epi.B != nullptr;                                  // (uniform)
+    if (tail) {
+#pragma unroll
+      for (int i = 0; i < TAIL_LOADS; ++i) {
+        const int idx = lane + 64 * i, vec = idx / N, pos = idx % N;
+        const float *src = (vec == 0 ? epi.center : (vec == 1 ? epi.B : epi.Cc)) + 4 * pos;
+        __builtin_amdgcn_global_load_lds(src, s_tail[wave] + 64 * i, 16, 0, 0);
+      }
+    }
+  }
   f4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0, acc2 = acc0, acc3 = acc0;
   for (int t0 = k0; t0 < k1; t0 += TILE) {
     const int nt = (k1 - t0) < TILE ? (k1 - t0) : TILE;
@@ -467,6 +516,10 @@ __device__ __forceinline__ void spmm_q3_lds_body(const int *__restrict__ b_rowpt
     __builtin_amdgcn_wave_barrier();            // all reads of this tile done before it is overwritten
   }
   if constexpr (EPI) {
+    if (tail) {                       // the channel vectors have landed (a wave without blocks has not waited for them yet)
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_wave_barrier();
+    }
     if (br < Mb) {
       const int64_t eq = (YG == 4) ? epi.lde : 4 * epi.lde, es = (YG == 4) ? (int64_t)N : epi.lde;
       const float *ep = epi.e + (int64_t)br * eq + sub * 4;
@@ -476,8 +529,18 @@ __device__ __forceinline__ void spmm_q3_lds_body(const int *__restrict__ b_rowpt
       if (epi.g) {
         const int64_t gq = (YG == 4) ? epi.ldg : 4 * epi.ldg, gs = (YG == 4) ? (int64_t)N : epi.ldg;
         const float *gp = epi.g + (int64_t)br * gq + sub * 4;
-        acc0 += ld4_s(gp, kStreamNT); acc1 += ld4_s(gp + gs, kStreamNT);
-        acc2 += ld4_s(gp + 2 * gs, kStreamNT); acc3 += ld4_s(gp + 3 * gs, kStreamNT);
+        f4 g0 = ld4_s(gp, kStreamNT), g1 = ld4_s(gp + gs, kStreamNT), g2 = ld4_s(gp + 2 * gs, kStreamNT),
+           g3 = ld4_s(gp + 3 * gs, kStreamNT);
+        if constexpr (TAILN) {
+          if (tail) {                 // raw gradient: finished here, E in registers (block rows without blocks included)
+            const f4 *tv = s_tail[wave] + sub;
+            g0 = tail_finish4(g0, e0, tv[0], tv[N], tv[2 * N]);
+            g1 = tail_finish4(g1, e1, tv[N / 4], tv[N + N / 4], tv[2 * N + N / 4]);
+            g2 = tail_finish4(g2, e2, tv[2 * (N / 4)], tv[N + 2 * (N / 4)], tv[2 * N + 2 * (N / 4)]);
+            g3 = tail_finish4(g3, e3, tv[3 * (N / 4)], tv[N + 3 * (N / 4)], tv[2 * N + 3 * (N / 4)]);
+          }
+        }
+        acc0 += g0; acc1 += g1; acc2 += g2; acc3 += g3;
       }
     }
   }
@@ -2452,6 +2515,11 @@ static int spmm_q3_launch(const int32_t *b_rowptr, const float *q_blk, int64_t M
     if (st) return st;
     if (!aligned16(epi.e) || epi.lde % 4 || (epi.g && (!aligned16(epi.g) || epi.ldg % 4))) return SN_E_ALIGN;
   }
+  if (epi.center || epi.B || epi.Cc) {          // a raw G: finished in the store, where the kernels can (sn_spmm_q3_tail_supported)
+    if (!epi.e || !epi.g || !epi.center || !epi.B || !epi.Cc) return SN_E_NULL;
+    if (!sn_spmm_q3_tail_supported(N, y_group)) return SN_E_UNSUPPORTED;
+    if (!aligned16(epi.center) || !aligned16(epi.B) || !aligned16(epi.Cc)) return SN_E_ALIGN;
+  }
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipEvent_t t_start, t_stop;
   timing_slot(1 | 8 | (epi.e ? 2 : 0) | (epi.g ? 4 : 0) | (stats_part ? 16 : 0), 4 * Mb, 4 * Kb, nblocks, N, &t_start, &t_stop);
@@ -2540,6 +2608,33 @@ int sn_spmm_q3_elubwd_absmax_f32(const int32_t *b_rowptr, const float *q_blk, in
   if (!E) return SN_E_NULL;
   return spmm_q3_launch(b_rowptr, q_blk, Mb, Kb, nblocks, X, ldx, x_group, N, Y, ldy, y_group, SpmmEpi{E, lde, G, ldg, y_absmax},
                         stream);
+}
+
+int32_t sn_spmm_q3_tail_supported(int32_t N, int32_t y_group) { return (N == 32 || N == 16) && y_group == 4; }
+
+int sn_spmm_q3_elubwd_tail_absmax_f32(const int32_t *b_rowptr, const float *q_blk, int64_t Mb, int64_t Kb, int64_t nblocks,
+                                      const float *X, int64_t ldx, int32_t x_group, int32_t N, const float *E, int64_t lde,
+                                      const float *G, int64_t ldg, const float *center, const float *B, const float *Cc, float *Y,
+                                      int64_t ldy, int32_t y_group, float *y_absmax, void *stream) {
+  if (!E || !G || !center || !B || !Cc) return SN_E_NULL;
+  SpmmEpi epi{E, lde, G, ldg, y_absmax};
+  epi.center = center;
+  epi.B = B;
+  epi.Cc = Cc;
+  return spmm_q3_launch(b_rowptr, q_blk, Mb, Kb, nblocks, X, ldx, x_group, N, Y, ldy, y_group, epi, stream);
+}
+
+int sn_elu_tail_finish_f32(float *g, int64_t ldg, const float *E, int64_t lde, const float *center, const float *B,
+                           const float *Cc, int64_t rows, int32_t C, void *stream) {
+  (void)hipGetLastError();      // a stale error left by an earlier runtime call of this thread is not ours to report
+  if (rows < 0 || C < 4 || (C & 3) || ldg < C || lde < C) return SN_E_SHAPE;
+  if (rows == 0) return SN_OK;
+  if (!g || !E || !center || !B || !Cc) return SN_E_NULL;
+  if (!aligned16(g) || !aligned16(E) || !aligned16(center) || !aligned16(B) || !aligned16(Cc) || (ldg & 3) || (lde & 3))
+    return SN_E_ALIGN;
+  hipLaunchKernelGGL(tail_finish_k, dim3(grid_for(rows * (C / 4), kWG)), dim3(kWG), 0, static_cast<hipStream_t>(stream), g, ldg, E,
+                     lde, center, B, Cc, rows, (int)(C / 4));
+  return launch_status();
 }
 
 int sn_bsr4_to_q3_f32(const int32_t *b_colind, const float *b_vals, int64_t nblocks, float *q_blk, int32_t *not_quaternion,

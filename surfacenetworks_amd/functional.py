@@ -185,7 +185,10 @@ def _launch(op: SparseOperator, x: torch.Tensor, y: torch.Tensor, group: int, ta
     """y <- op·x with the best resident format of `op` (product_form).  elubwd = (e, g): y <- (op·x) * elu'(e) + g fused into the
     store (the backward of an ELU-activated propagation stage; g may be None).  stats=True: where the kernel offers it (packed
     Dirac operators and Laplacian-type CSR operators, 128 channels) the launch also leaves the column statistics of y and
-    their partials are returned (kernels.spmm_q3_stats / spmm_csr_stats), else None."""
+    their partials are returned (kernels.spmm_q3_stats / spmm_csr_stats), else None.
+    elubwd = (e, g, tail): g is a RAW gradient (kernels.linear_dgrad_elu_raw) and tail = (center, B, Cc) finishes it — in the
+    store of the packed product where that kernel can, else by one finishing launch on g, in place, BEFORE the product: a raw
+    gradient never reaches a product unfinished."""
     M, K = op.shape
     timer = SpmmTimer.active
     rec = _lib_mod.recorder() if _lib_mod._recorder is not None else None
@@ -195,13 +198,24 @@ def _launch(op: SparseOperator, x: torch.Tensor, y: torch.Tensor, group: int, ta
             rec.tags.append((tag, known))                # (a launch plan replays its products' tags into an active timer)
         else:
             timer.tags.append((tag, op if known is None else known))
-    e, g = elubwd if elubwd is not None else (None, None)
+    e, g = elubwd[:2] if elubwd is not None else (None, None)
+    tail = elubwd[2] if elubwd is not None and len(elubwd) > 2 else None
     vec = (y.shape[1] // group) in (16, 32, 64, 128)
     kind, arr, _ = product_form(op, group, y.shape[1])
+    if tail is not None:
+        if g is None:
+            raise ValueError("_launch: a tail without the raw gradient it finishes")
+        if not (kind == "q3" and kernels.spmm_q3_tail_supported(y.shape[1] // group, group)):
+            kernels.elu_tail_finish(g, e, tail)
+            tail = None
     if kind == "q3":
         if stats and e is None and kernels.spmm_q3_stats_supported(y.shape[1] // group, group):
             return kernels.spmm_q3_stats(arr[0], arr[1], M // 4, K // 4, x, y, group)
-        am = kernels.spmm_q3(arr[0], arr[1], M // 4, K // 4, x, y, group, e, g, want_absmax=e is not None and kernels.absmax_wanted())
+        want_am = e is not None and kernels.absmax_wanted()
+        if tail is not None:
+            am = kernels.spmm_q3(arr[0], arr[1], M // 4, K // 4, x, y, group, e, g, want_absmax=want_am, tail=tail)
+        else:
+            am = kernels.spmm_q3(arr[0], arr[1], M // 4, K // 4, x, y, group, e, g, want_absmax=want_am)
         if am is not None:
             kernels.note_absmax(y, am)           # a fused ELU-backward product writes a gradient: the dy of the layer below
     elif kind == "bsr4":
@@ -582,14 +596,17 @@ def _wgrad_and_coeffs(dy, x, W, s, mean, invstd, beta, training, has_bias, rows_
     return dW, db, dgamma, dbeta, Bc, Cc
 
 
-def bnlin_backward(state, dy, need_dx=True, through_elu=None):
+def bnlin_backward(state, dy, need_dx=True, through_elu=None, raw_low=False):
     """Backward of bnlin_forward: G = dyᵀ·(x - mean) (split-K MFMA kernel) and colsum(dy) give every BatchNorm
     reduction algebraically (sum_r dz = colsum(dy)·W, sum_r dz∘(x-mean) = sum_j W∘G); dx = dy·(W·diag(s)) + (x-mean)∘B + C
     in ONE GEMM with the tail in its epilogue.  Returns (dx, dgamma, dbeta, dW, db).
 
     through_elu=(gadd,): x is a stage's concat buffer [e | P·e]; instead of dx the first element returned is the pair
     (dx[:, C/2:],  dx[:, :C/2] * elu'(e) + gadd) — the operand of the transposed propagation and the gradient that has
-    already passed the activation (gadd may be None), produced by the GEMM epilogue when the fused kernel applies."""
+    already passed the activation (gadd may be None), produced by the GEMM epilogue when the fused kernel applies.
+    raw_low (with through_elu=(None,), training, the fused kernel: the caller has checked): the second element of the pair is the
+    RAW product dy·Wf[:, :C/2] — x[:, :C/2] is not read — and a sixth value is returned, the tail (mean, B, Cc)[:C/2] its one
+    consumer finishes it with (kernels.note_tail)."""
     x, W, Wf, s, mean, invstd, beta, training, has_bias, rows_g = state
     dy = dy.contiguous()
     rows, C = x.shape
@@ -597,6 +614,11 @@ def bnlin_backward(state, dy, need_dx=True, through_elu=None):
     # centring inside the kernel leaves no fp32 cancellation against mean·colsum(dy)
     dW, db, dgamma, dbeta, Bc, Cc = _wgrad_and_coeffs(dy, x, W, s, mean, invstd, beta, training, has_bias, rows_g)
     dx = None
+    if raw_low:
+        if through_elu != (None,) or not training or not kernels.linear_dgrad_elu_supported(J, C):
+            raise RuntimeError("bnlin_backward: the raw low half exists only for the fused training-mode kernel without gadd")
+        h = C // 2
+        return kernels.linear_dgrad_elu_raw(dy, Wf, x, mean, Bc, Cc), dgamma, dbeta, dW, db, (mean[:h], Bc[:h], Cc[:h])
     if through_elu is not None and training and kernels.linear_dgrad_elu_supported(J, C):
         dx = kernels.linear_dgrad_elu(dy, Wf, x, mean, Bc, Cc, through_elu[0])
     elif need_dx or through_elu is not None:

@@ -261,9 +261,27 @@ def spmm_bsr4_elubwd(b_rowptr, b_colind, b_vals, Mb: int, Kb: int, x, e, g, y, g
               _p(x), ldx, group, N, _p(e), lde, _p(g), ldg, _p(y), ldy, group, _stream())
 
 
-def spmm_q3(b_rowptr, q_blk, Mb: int, Kb: int, x, y, group: int = 1, e=None, g=None, want_absmax: bool = False):
+def spmm_q3_tail_supported(N: int, group: int) -> bool:
+    """Whether the quaternion-packed product finishes a raw gradient in its store (spmm_q3(tail=...))."""
+    return bool(_lib.load().sn_spmm_q3_tail_supported(int(N), int(group)))
+
+
+def elu_tail_finish(g, e, tail) -> None:
+    """g <- the finished input gradient, in place, from the raw one linear_dgrad_elu_raw left (sn_elu_tail_finish_f32): for the
+    products whose store cannot do it.  tail = (center, B, Cc), one value per column of g."""
+    center, B, Cc = tail
+    _dev(g, e, center, B, Cc)
+    rows, C = g.shape
+    if e.shape != g.shape or any(t.shape != (C,) or not t.is_contiguous() for t in tail):
+        raise ValueError(f"elu_tail_finish: g {tuple(g.shape)}, e {tuple(e.shape)} and tail vectors of {C} do not match")
+    _lib.call("sn_elu_tail_finish_f32", _p(g), _ld(g), _p(e), _ld(e), _p(center), _p(B), _p(Cc), rows, C, _stream())
+
+
+def spmm_q3(b_rowptr, q_blk, Mb: int, Kb: int, x, y, group: int = 1, e=None, g=None, want_absmax: bool = False, tail=None):
     """y <- A·x for a quaternion-packed Dirac operator (sn_spmm_q3_f32); with e: (A·x) * elu'(e) + g (sn_spmm_q3_elubwd_f32).
-    want_absmax (with e): also returns the per-workgroup maxima of |y| (sn_spmm_q3_elubwd_absmax_f32), else None."""
+    want_absmax (with e): also returns the per-workgroup maxima of |y| (sn_spmm_q3_elubwd_absmax_f32), else None.
+    tail = (center, B, Cc): g is a raw gradient that the store finishes (sn_spmm_q3_elubwd_tail_absmax_f32; the caller has
+    asked spmm_q3_tail_supported)."""
     _dev(b_rowptr, q_blk, x, y, e, g)
     N = y.shape[1] // group
     ldx = _check_dense(x, 4 * Kb, group, N, "x")
@@ -274,6 +292,17 @@ def spmm_q3(b_rowptr, q_blk, Mb: int, Kb: int, x, y, group: int = 1, e=None, g=N
     else:
         lde = _check_dense(e, 4 * Mb, group, N, "e")
         ldg = _check_dense(g, 4 * Mb, group, N, "g") if g is not None else 0
+        if tail is not None:
+            center, B, Cc = tail
+            _dev(center, B, Cc)
+            if g is None or any(t.shape != (group * N,) or not t.is_contiguous() for t in tail):
+                raise ValueError("spmm_q3: a tail needs the raw gradient g and three contiguous vectors of one value per channel")
+            am = None
+            if want_absmax and Mb > 0:
+                am = torch.empty(int(_lib.load().sn_spmm_q3_absmax_blocks(Mb, N)), dtype=torch.float32, device=y.device)
+            _lib.call("sn_spmm_q3_elubwd_tail_absmax_f32", _p(b_rowptr), _p(q_blk), Mb, Kb, nblk, _p(x), ldx, group, N, _p(e), lde,
+                      _p(g), ldg, _p(center), _p(B), _p(Cc), _p(y), ldy, group, _p(am), _stream())
+            return am
         if want_absmax and Mb > 0:
             am = torch.empty(int(_lib.load().sn_spmm_q3_absmax_blocks(Mb, N)), dtype=torch.float32, device=y.device)
             _lib.call("sn_spmm_q3_elubwd_absmax_f32", _p(b_rowptr), _p(q_blk), Mb, Kb, nblk, _p(x), ldx, group, N, _p(e), lde, _p(g),
@@ -471,8 +500,54 @@ def note_absmax(t, maxima) -> None:
 def clear_absmax() -> None:
     """Drop every recorded bound (and with it the references to the gradient tensors they describe): called by the train steps
     once a backward pass has run — bounds nobody took (a gradient consumed only as an added term, the gradient into the first
-    layer) would otherwise keep up to _ABSMAX_KEEP gradient tensors alive across steps."""
+    layer) would otherwise keep up to _ABSMAX_KEEP gradient tensors alive across steps.  The tails of raw gradients go too."""
     _absmax_table.clear()
+    _tail_table.clear()
+
+
+# ---- raw face gradients (blocks.DEFER_FACE_TAIL) ----------------------------------------------------------------------------------
+# A Dirac block may return the gradient of its face input RAW (linear_dgrad_elu_raw: the bare GEMM product) for the previous
+# block's transposed product to finish.  What that product needs besides the gradient — the low halves of the stage's mean / B /
+# C vectors — travels like the maxima above: keyed by the gradient's data pointer, with a strong reference to the tensor and its
+# version counter, re-attached by a launch plan through `rec.tail_notes`.
+_tail_table = {}            # data_ptr -> (tensor, version, (center, B, Cc))
+
+
+def note_tail(t, tail) -> None:
+    """Record that t is a raw gradient and `tail` = (center, B, Cc) finishes it."""
+    if len(_tail_table) >= _ABSMAX_KEEP:
+        for k in list(_tail_table)[: len(_tail_table) - _ABSMAX_KEEP + 1]:
+            del _tail_table[k]
+    _tail_table.pop(t.data_ptr(), None)
+    _tail_table[t.data_ptr()] = (t, t._version if not t.is_inference() else None, tuple(tail))
+    rec = _lib.recorder() if _lib._recorder is not None else None
+    if rec is not None:
+        rec.tail_notes.append((t, tuple(tail)))
+
+
+def has_tail(t) -> bool:
+    """Whether take_tail(t) would succeed (nothing is taken)."""
+    ent = _tail_table.get(t.data_ptr())
+    if ent is None:
+        return False
+    src, version, _ = ent
+    return src.numel() == t.numel() and t.is_contiguous() and src.dtype == t.dtype and \
+        (version is None or src._version == version)
+
+
+def take_tail(t):
+    """The tail recorded for exactly this memory (same first element, element count and contents), or None."""
+    ent = _tail_table.pop(t.data_ptr(), None)
+    if ent is None:
+        return None
+    src, version, tail = ent
+    rec = _lib.recorder() if _lib._recorder is not None else None
+    if rec is not None:
+        rec.tail_notes[:] = [n for n in rec.tail_notes if n[1] is not tail]
+    if src.numel() != t.numel() or not t.is_contiguous() or src.dtype != t.dtype or \
+            (version is not None and src._version != version):
+        return None
+    return tail
 
 
 def take_absmax(t):
@@ -1152,6 +1227,21 @@ def linear_dgrad_elu(dy, W, x, center, B, Cc, gadd=None):
               _p(dx_hi), h, _p(gact), h, _p(gadd), _ld(gadd) if gadd is not None else 0, rows, J, C, _p(am), _stream())
     note_absmax(gact, am)                # gact is the dy operand of the layer below
     return dx_hi, gact
+
+
+def linear_dgrad_elu_raw(dy, W, x, center, B, Cc):
+    """As linear_dgrad_elu without gadd, but the low half leaves RAW (sn_linear_dgrad_elu_rawlow_f32): returns (dx_hi, graw),
+    graw = dy·W[:, :C/2], and x[:, :C/2] is not read.  The caller hands (center[:C/2], B[:C/2], Cc[:C/2]) to the consumer of
+    graw (note_tail); no maxima are left for it."""
+    _dev(dy, W, x, center, B, Cc)
+    rows, J = dy.shape
+    C = W.shape[1]
+    h = C // 2
+    dx_hi = torch.empty((rows, h), dtype=torch.float32, device=dy.device)
+    graw = torch.empty((rows, h), dtype=torch.float32, device=dy.device)
+    _lib.call("sn_linear_dgrad_elu_rawlow_f32", _p(dy), _ld(dy), _p(W), _ld(W), _p(x), _ld(x), _p(center), _p(B), _p(Cc),
+              _p(dx_hi), h, _p(graw), h, rows, J, C, _stream())
+    return dx_hi, graw
 
 
 def _new_dgrad_absmax(device):

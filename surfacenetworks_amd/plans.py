@@ -133,6 +133,7 @@ class _Recorder(TorchDispatchMode):
         self.allocs: List[torch.Tensor] = []  # kept alive until the layout is done: no address is handed out twice
         self.stray: List[str] = []
         self.notes: List[tuple] = []          # (tensor, maxima) recorded by kernels.note_absmax and not taken again
+        self.tail_notes: List[tuple] = []     # (tensor, (center, B, Cc)) recorded by kernels.note_tail and not taken again
         self.allow_cpu = _ALLOW_CPU
         self.tags: List[tuple] = []           # (tag, entry count | None) of every sparse product, in launch order (SpmmTimer)
 
@@ -267,6 +268,9 @@ class Plan:
                 self._add_copy(node[1], node[2], lay)
         self.result = _map_structure(result, lambda t: self._describe(t, lay, rec))
         self.effects = [(lay.describe(t, rec), lay.describe(m, rec)) for t, m in rec.notes]
+        # a raw gradient among the results and the three vectors that finish it: plan outputs like the maxima — the views built
+        # from these descriptions keep the arena they live in alive until the consuming block has run
+        self.tail_effects = [(lay.describe(t, rec), tuple(lay.describe(v, rec) for v in tl)) for t, tl in rec.tail_notes]
         # what a per-launch timer (functional.SpmmTimer) wants to know of this plan's sparse products; None: one of them has no
         # entry count on the host (the plan then steps aside while a timer runs)
         self.tags = list(rec.tags) if all(k is not None for _, k in rec.tags) else None
@@ -604,6 +608,10 @@ def _dry_run(impl, args, ext):
             ent = kernels._absmax_table.get(t.data_ptr())
             if ent is not None and ent[2] is m:
                 del kernels._absmax_table[t.data_ptr()]
+        for t, tl in rec.tail_notes:
+            ent = kernels._tail_table.get(t.data_ptr())
+            if ent is not None and ent[2] is tl:
+                del kernels._tail_table[t.data_ptr()]
         for t, before in keep:                      # attributes the dry run hung on (or took from) the operands: as they were
             t.__dict__.clear()
             t.__dict__.update(before)
@@ -624,12 +632,17 @@ def record(site: Site, key, impl, args, ext, device, alias_ok=()) -> Optional[Pl
     return plan
 
 
-def renote(grads, maxima) -> None:
+def renote(grads, maxima, tails=None) -> None:
     for g, m in zip(grads, maxima):
         if g is not None and m is not None:
             kernels.note_absmax(g, m)
+    for g, tl in zip(grads, tails or ()):
+        if g is not None and tl is not None:
+            kernels.note_tail(g, tl)
 
 
 def apply_effects(plan: Plan, build: _Builder) -> None:
     for dt, dm in plan.effects:
         kernels.note_absmax(build(dt), build(dm))
+    for dt, dtl in plan.tail_effects:
+        kernels.note_tail(build(dt), build(dtl))
