@@ -947,6 +947,62 @@ int sn_mesh_idt_laplacian_f32(const int32_t *Fp, const double *lp, int64_t nV, i
                               void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Sparse x sparse CSR products and the symmetric diagonal scaling: the operators of the 'amp' tower.
+ *
+ * Replaces: L = Dsq.dot(L).dot(Dsq); twice L = Dsq.dot(L).dot(Dsq), L = L.dot(L)     src/dense_correspondence/main.py:72-83
+ *           scipy's csr_matmat behind every one of those dots (the diagonal ones included).
+ *
+ * Definition of the product C = A B.  A is M x K, B is K x N, int32 CSR with fp32 values, columns strictly ascending inside a
+ *   row, explicit zeros allowed.  The structural pattern of row i is the union of the rows j of B over the stored (i, j) of A.
+ *   c_ik = fl(...fl(fl(0 + fl(a_ij1 b_j1k)) + fl(a_ij2 b_j2k))...),  j1 < j2 < ... the entries of A's row i in ascending column
+ *   order, only those j with (j, k) stored in B taking part.  Every product and every sum is rounded on its own (no fused
+ *   multiply-add, no fast-math), no floating-point atomics: two runs give identical bits.  Output columns ascend.  An entry whose
+ *   sum is exactly zero is dropped, as scipy drops it; the structural arrays (every entry kept) are a result of their own.
+ *   On an A with ascending columns this is scipy's csr_matmat value bit for bit; scipy's OUTPUT rows are unsorted, so a product
+ *   that takes an unsorted scipy result as its left operand sums in another order (LABNOTES.md#spgemm has the bound).
+ *
+ * sn_csr_spgemm_f32, three phases on one workspace (sn_csr_spgemm_workspace_bytes(M)); the caller owns every allocation:
+ *   phase 0 (structural count)  clears *status, writes s_rowptr[M + 1]; the caller reads s_rowptr[M] and allocates s_colind, s_vals.
+ *   phase 1 (fill + count)      writes s_colind, s_vals (the structural result) and rowptr[M + 1] of the entries != 0; the caller
+ *                               reads rowptr[M]: equal to s_rowptr[M], the structural arrays are the result, else it allocates.
+ *   phase 2 (compaction)        colind, vals: the entries != 0 in order.
+ *   One workgroup per result row: the candidate columns are marked as bits of an LDS bitmap over the row's column window
+ *   (atomicOr on bits is order-independent), a popcount prefix numbers them in ascending order, each thread then owns result
+ *   entries, walks A's row in order and finds k in B's row j by binary search.
+ *   *status bits: SN_SPGEMM_BAD_COLUMN  a column of A outside 0..K-1 or of B outside 0..N-1: it contributes nothing, nothing is
+ *                                       read out of bounds;
+ *                 SN_SPGEMM_TOO_WIDE    a result row whose candidates span more than sn_csr_spgemm_max_window() =
+ *                                       SN_SPGEMM_MAX_WINDOW columns (last - first + 1; the bitmap is 16 KiB of LDS);
+ *                 SN_SPGEMM_TOO_LARGE   the structural entries do not fit the int32 row pointers.
+ *   With one of the last two set the call is unsupported and NOTHING is written (s_rowptr included; later phases return at
+ *   once).  There is no host fallback.  No limit on the length of a row of A, B or C.
+ *
+ * sn_csr_inv_sqrt_degree_f32 : d[i] = (float)(1.0 / sqrt((double)(rowptr[i+1] - rowptr[i] - 1))), fp64 as numpy computes it.
+ *                              Clears *status; a row with fewer than two entries sets SN_CSR_NO_OFFDIAGONAL (the host divides
+ *                              by zero there; d[i] is then inf or nan).
+ * sn_csr_scale_sym_f32       : out_ij = fl(fl(d_i a_ij) d_j) of a square M x M matrix, what the two diagonal products of the
+ *                              reference give.  phase 0 clears *status, writes s_vals (on A's pattern) and rowptr[M + 1] of the
+ *                              results != 0; phase 1 compacts (a_rowptr, a_colind, s_vals) into (rowptr, colind, vals) — not
+ *                              needed when rowptr[M] == a_rowptr[M].  A column outside 0..M-1 gives 0 and sets
+ *                              SN_SPGEMM_BAD_COLUMN.  workspace: sn_csr_spgemm_workspace_bytes(M).
+ * ------------------------------------------------------------------------------------------ */
+#define SN_SPGEMM_MAX_WINDOW   131072
+#define SN_SPGEMM_BAD_COLUMN   1
+#define SN_SPGEMM_TOO_WIDE     2
+#define SN_SPGEMM_TOO_LARGE    4
+#define SN_CSR_NO_OFFDIAGONAL  8
+int64_t sn_csr_spgemm_max_window(void);
+size_t sn_csr_spgemm_workspace_bytes(int64_t M);
+int sn_csr_spgemm_f32(const int32_t *a_rowptr, const int32_t *a_colind, const float *a_vals, const int32_t *b_rowptr,
+                      const int32_t *b_colind, const float *b_vals, int64_t M, int64_t K, int64_t N, int32_t phase,
+                      int32_t *s_rowptr, int32_t *s_colind, float *s_vals, int32_t *rowptr, int32_t *colind, float *vals,
+                      int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+int sn_csr_inv_sqrt_degree_f32(const int32_t *rowptr, int64_t M, float *d, int32_t *status, void *stream);
+int sn_csr_scale_sym_f32(const int32_t *a_rowptr, const int32_t *a_colind, const float *a_vals, const float *d, int64_t M,
+                         int32_t phase, float *s_vals, int32_t *rowptr, int32_t *colind, float *vals, int32_t *status,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Row-streaming fp32 GEMMs of the per-node Linear layers with the weights held in registers
  * (v_mfma_f32_32x32x2_f32; the operands are tall-skinny: rows ~ 1e5..1e6, K and N in {128, 256}).
  *

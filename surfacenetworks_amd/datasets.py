@@ -192,11 +192,13 @@ def faust_frame_from_mesh(V, F, label=None, device="cuda", symmetric=True, geode
     }
 
 
-def faust_from_files(paths: Sequence[str], device="cuda", model="lap", pad_to=None, reorder="auto"):
-    """Resident FAUST dataset (dense_correspondence.FaustFrames) from reference .npz frames; `reorder` as FaustFrames."""
+def faust_from_files(paths: Sequence[str], device="cuda", model="lap", pad_to=None, reorder="auto", amplify="host"):
+    """Resident FAUST dataset (dense_correspondence.FaustFrames) from reference .npz frames; `reorder` and `amplify` as
+    FaustFrames."""
     from . import dense_correspondence as dc
 
-    return dc.FaustFrames([load_faust_frame(p, device) for p in paths], model=model, pad_to=pad_to, device=device, reorder=reorder)
+    return dc.FaustFrames([load_faust_frame(p, device) for p in paths], model=model, pad_to=pad_to, device=device, reorder=reorder,
+                          amplify=amplify)
 
 
 def write_faust_frame(path: str, V: np.ndarray, F: np.ndarray, label: np.ndarray, dist_mat: np.ndarray) -> None:

@@ -19,7 +19,8 @@ import torch.nn.functional as F
 from . import kernels, mesh_ops
 from . import utils_pt as utils
 from .arap import make_adam
-from .operators import OperatorPool, SparseOperator, geodesic_matrix_from_mesh, laplacian_operator_from_mesh
+from .operators import (OperatorPool, SparseOperator, amplify_sequence_operators, geodesic_matrix_from_mesh,
+                        laplacian_operator_from_mesh)
 
 
 
@@ -956,11 +957,17 @@ class FaustFrames:
     as a resident dataset with the TorusBodies interface: coordinates, label permutations and geodesic matrices as device
     tensors, the operators of the requested tower in OperatorPools; `sample(idx)` pads to `pad_to` vertices (main.py:193)."""
 
-    def __init__(self, frames, model="lap", pad_to=None, device="cuda", reorder="auto"):
-        """reorder ("auto" / True / False): scans arrive in whatever vertex order the scanner wrote (main.py:66-102 loads them as
+    def __init__(self, frames, model="lap", pad_to=None, device="cuda", reorder="auto", amplify="host"):
+        """amplify ("host" / "device", the 'amp' tower only): where the three operators of main.py:72-83 are built from a frame's
+        stored L — "host": amplify_sequence (scipy); "device": L is uploaded once and goes through
+        operators.amplify_sequence_operators (the first two matrices are the host's bit for bit, the third sums in ascending
+        column order: LABNOTES.md#spgemm).
+        reorder ("auto" / True / False): scans arrive in whatever vertex order the scanner wrote (main.py:66-102 loads them as
         stored); the frames are STORED in a locality numbering (mesh_ops.MeshOrder) — coordinates, operators, label permutations
         and the geodesic matrix renumbered once.  The loss (rows of the score matrix against targets from G, label, label_inv)
         is invariant to the numbering; `orders[i].vorder` maps stored positions back to the file's vertex ids."""
+        if amplify not in ("host", "device"):
+            raise ValueError(f'FaustFrames: amplify must be "host" or "device", got {amplify!r}')
         self.device = torch.device(device)
         self.kind = "dir" if "dir" in model else ("amp" if "amp" in model else "lap")      # dispatch order of main.py:72-95
         self.orders = [mesh_ops.MeshOrder.of_mesh(fr["F"].cpu().numpy(), int(fr["V"].shape[0]), reorder) for fr in frames]
@@ -975,7 +982,11 @@ class FaustFrames:
             self.pool_Di = OperatorPool([fr["Di"] for fr in frames], self.device, want_bsr4=True)
             self.pool_DiA = OperatorPool([fr["DiA"] for fr in frames], self.device, want_bsr4=True)
         elif self.kind == "amp":
-            seqs = [amplify_sequence(fr["L"]) for fr in frames]
+            if amplify == "device":
+                seqs = [[op.to_scipy() for op in amplify_sequence_operators(SparseOperator.from_scipy(fr["L"].astype("f"), self.device))]
+                        for fr in frames]
+            else:
+                seqs = [amplify_sequence(fr["L"]) for fr in frames]
             self.pool_Lseq = [OperatorPool([s[j] for s in seqs], self.device) for j in range(3)]
         else:
             self.pool_L = OperatorPool([fr["L"] for fr in frames], self.device)

@@ -760,6 +760,117 @@ def laplacian_from_mesh(V, F):
     return rowptr, colind, vals
 
 
+SPGEMM_BAD_COLUMN, SPGEMM_TOO_WIDE, SPGEMM_TOO_LARGE, CSR_NO_OFFDIAGONAL = 1, 2, 4, 8      # SN_SPGEMM_* / SN_CSR_* status bits
+
+
+def spgemm_max_window() -> int:
+    """The widest result row csr_spgemm takes: columns between its first and last candidate, one bit each in LDS."""
+    return int(_lib.load().sn_csr_spgemm_max_window())
+
+
+def _check_csr(who: str, arrays, rows: int):
+    rowptr, colind, vals = arrays
+    _dev(rowptr, colind, vals)
+    if rowptr.dtype != torch.int32 or colind.dtype != torch.int32 or vals.dtype != torch.float32:
+        raise TypeError(f"{who} wants int32 rowptr/colind and float32 vals")
+    if rowptr.dim() != 1 or rowptr.numel() != rows + 1 or colind.dim() != 1 or colind.shape != vals.shape:
+        raise ValueError(f"{who}: inconsistent CSR arrays for {rows} rows")
+    return rowptr.contiguous(), colind.contiguous(), vals.contiguous()
+
+
+def _raise_for_spgemm_status(who: str, st: int) -> None:
+    if st & SPGEMM_BAD_COLUMN:
+        raise ValueError(f"{who}: a column index is outside the operand's column range")
+    if st & CSR_NO_OFFDIAGONAL:
+        raise ValueError(f"{who}: a row holds fewer than two entries (no off-diagonal entry: D^-1/2 divides by zero)")
+    if st & SPGEMM_TOO_WIDE:
+        raise RuntimeError(f"{who}: a result row spans more than spgemm_max_window() = {spgemm_max_window()} columns; "
+                           "there is no other path")
+    if st & SPGEMM_TOO_LARGE:
+        raise RuntimeError(f"{who}: the result's structural entries do not fit int32 row pointers")
+
+
+def csr_spgemm(A_arrays, B_arrays, shape, keep_zeros: bool = False):
+    """C = A B of two CSR operands (sn_csr_spgemm_f32; the definition is in include/sn_spmm.h): A_arrays, B_arrays =
+    (rowptr, colind, vals) int32/int32/fp32 with columns ascending inside a row, shape = (M, K, N).  Returns (rowptr, colind,
+    vals), columns ascending, every sum sequential in fp32 over A's row, bit-reproducible.  An entry whose sum is exactly zero is
+    dropped as scipy drops it; keep_zeros=True returns the structural result.  Synchronises twice (reads the two sizes and the
+    status word).  ValueError for a column out of range, RuntimeError for a row wider than spgemm_max_window()."""
+    M, K, N = (int(s) for s in shape)
+    a_rp, a_ci, a_v = _check_csr("csr_spgemm (A)", A_arrays, M)
+    b_rp, b_ci, b_v = _check_csr("csr_spgemm (B)", B_arrays, K)
+    dev = a_rp.device
+    ws_bytes = int(_lib.load().sn_csr_spgemm_workspace_bytes(M))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    heads = torch.zeros(2, M + 1, dtype=torch.int32, device=dev)             # structural and final row pointers
+    s_rp, rp = heads[0], heads[1]
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ops = (_p(a_rp), _p(a_ci), _p(a_v), _p(b_rp), _p(b_ci), _p(b_v), M, K, N)
+    tail = (status.data_ptr(), _p(ws), ws_bytes, _stream())
+    _lib.call("sn_csr_spgemm_f32", *ops, 0, s_rp.data_ptr(), None, None, None, None, None, *tail)
+    st, nnz_s = int(status.item()), int(s_rp[-1].item())
+    _raise_for_spgemm_status("csr_spgemm", st)
+    s_ci = torch.empty(nnz_s, dtype=torch.int32, device=dev)
+    s_v = torch.empty(nnz_s, dtype=torch.float32, device=dev)
+    _lib.call("sn_csr_spgemm_f32", *ops, 1, s_rp.data_ptr(), _p(s_ci), _p(s_v), rp.data_ptr(), None, None, *tail)
+    if keep_zeros:
+        return s_rp, s_ci, s_v
+    nnz = int(rp[-1].item())
+    if nnz == nnz_s:                                                         # nothing cancelled: the structural arrays are the result
+        return s_rp, s_ci, s_v
+    ci = torch.empty(nnz, dtype=torch.int32, device=dev)
+    v = torch.empty(nnz, dtype=torch.float32, device=dev)
+    _lib.call("sn_csr_spgemm_f32", *ops, 2, s_rp.data_ptr(), _p(s_ci), _p(s_v), rp.data_ptr(), _p(ci), _p(v), *tail)
+    return rp, ci, v
+
+
+def csr_inv_sqrt_degree(rowptr, check: bool = True):
+    """d[i] = (float)(1 / sqrt(entries of row i - 1)) in fp64, numpy's value (sn_csr_inv_sqrt_degree_f32): the D^-1/2 of
+    src/dense_correspondence/main.py:77.  check: read the status word (one synchronisation) and raise ValueError for a row
+    with fewer than two entries, where the host divides by zero; else the 1-element status tensor is returned with d."""
+    _dev(rowptr)
+    if rowptr.dtype != torch.int32 or rowptr.dim() != 1 or rowptr.numel() < 1:
+        raise TypeError("csr_inv_sqrt_degree wants an int32 rowptr of M + 1 entries")
+    rowptr = rowptr.contiguous()
+    M = rowptr.numel() - 1
+    d = torch.empty(M, dtype=torch.float32, device=rowptr.device)
+    status = torch.empty(1, dtype=torch.int32, device=rowptr.device)
+    _lib.call("sn_csr_inv_sqrt_degree_f32", rowptr.data_ptr(), M, _p(d), status.data_ptr(), _stream())
+    if not check:
+        return d, status
+    _raise_for_spgemm_status("csr_inv_sqrt_degree", int(status.item()))
+    return d
+
+
+def csr_scale_sym(A_arrays, d, M: int):
+    """out_ij = fl(fl(d_i a_ij) d_j) of a square CSR matrix (sn_csr_scale_sym_f32): what `Dsq.dot(L).dot(Dsq)` gives
+    (main.py:78, 82), exact-zero results dropped as scipy's two diagonal products drop them.  Returns (rowptr, colind, vals);
+    colind is A's own tensor when nothing was dropped.  Synchronises once."""
+    M = int(M)
+    a_rp, a_ci, a_v = _check_csr("csr_scale_sym", A_arrays, M)
+    _dev(d)
+    if d.dtype != torch.float32 or d.dim() != 1 or d.numel() != M:
+        raise TypeError(f"csr_scale_sym wants d float32 of {M} entries")
+    d = d.contiguous()
+    dev = a_rp.device
+    ws_bytes = int(_lib.load().sn_csr_spgemm_workspace_bytes(M))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    rp = torch.empty(M + 1, dtype=torch.int32, device=dev)
+    s_v = torch.empty_like(a_v)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    args = (_p(a_rp), _p(a_ci), _p(a_v), _p(d), M)
+    tail = (status.data_ptr(), _p(ws), ws_bytes, _stream())
+    _lib.call("sn_csr_scale_sym_f32", *args, 0, _p(s_v), rp.data_ptr(), None, None, *tail)
+    st, nnz = int(status.item()), int(rp[-1].item())
+    _raise_for_spgemm_status("csr_scale_sym", st)
+    if nnz == a_ci.numel():
+        return rp, a_ci, s_v
+    ci = torch.empty(nnz, dtype=torch.int32, device=dev)
+    v = torch.empty(nnz, dtype=torch.float32, device=dev)
+    _lib.call("sn_csr_scale_sym_f32", *args, 1, _p(s_v), rp.data_ptr(), _p(ci), _p(v), *tail)
+    return rp, ci, v
+
+
 IDT_BAD_FACE, IDT_NOT_CONVERGED, IDT_DEGENERATE, IDT_NON_MANIFOLD, IDT_ORIENTATION = 1, 2, 4, 8, 16      # SN_IDT_* status bits
 IDT_CHUNK = 8                 # flip rounds enqueued between two reads of the counters
 

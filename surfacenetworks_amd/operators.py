@@ -25,7 +25,7 @@ import torch
 from . import kernels
 
 __all__ = ["SparseOperator", "OperatorPool", "PackedSegments", "as_operator", "dirac_operators_from_mesh",
-           "laplacian_operator_from_mesh", "geodesic_matrix_from_mesh"]
+           "laplacian_operator_from_mesh", "geodesic_matrix_from_mesh", "spgemm", "amplify_sequence_operators"]
 
 # A BSR4 copy is kept when zero-fill costs at most this much extra storage over CSR entries.
 _BSR4_MAX_FILL = 1.6
@@ -229,6 +229,15 @@ class SparseOperator:
 
     T = property(t)
 
+    def matmul(self, other) -> "SparseOperator":
+        """self · other between two SparseOperators (spgemm below); a dense right-hand side goes through functional.spmm."""
+        if not isinstance(other, SparseOperator):
+            raise TypeError("SparseOperator.matmul multiplies two SparseOperators; dense operands take functional.spmm")
+        return spgemm(self, other)
+
+    def __matmul__(self, other):
+        return spgemm(self, other) if isinstance(other, SparseOperator) else NotImplemented
+
     @classmethod
     def from_bsr4(cls, fwd, bwd, shape, batch: int = 1) -> "SparseOperator":
         """Operator and its transpose given directly as BSR4 triples (kernels.dirac_from_mesh)."""
@@ -428,6 +437,43 @@ def laplacian_operator_from_mesh(V: torch.Tensor, F: torch.Tensor, intrinsic: bo
     else:
         rowptr, colind, vals = kernels.laplacian_from_mesh(Vg.float(), Fg)
     return SparseOperator(rowptr, colind, vals, (B * nV, B * nV), batch=B)
+
+
+def spgemm(A: SparseOperator, B: SparseOperator, keep_zeros: bool = False) -> SparseOperator:
+    """C = A · B of two device operators in CSR (kernels.csr_spgemm; include/sn_spmm.h has the definition): every entry a
+    sequential fp32 sum over A's row in ascending column order, columns ascending, bit-reproducible, exact-zero sums dropped as
+    scipy's product drops them (keep_zeros=True keeps the structural pattern).  Two block-diagonal batches of the same count
+    multiply block by block: the result carries `batch`.  Raises ValueError for mismatched shapes or a column out of range and
+    RuntimeError for a result row wider than kernels.spgemm_max_window() columns — there is no host path."""
+    if not isinstance(A, SparseOperator) or not isinstance(B, SparseOperator):
+        raise TypeError("spgemm multiplies two SparseOperators")
+    (M, K), (K2, N) = A._shape, B._shape
+    if K != K2:
+        raise ValueError(f"spgemm: shapes {A._shape} and {B._shape} do not chain")
+    rp, ci, v = kernels.csr_spgemm((A.rowptr, A.colind, A.vals), (B.rowptr, B.colind, B.vals), (M, K, N), keep_zeros=keep_zeros)
+    return SparseOperator(rp, ci, v, (M, N), batch=A.batch if A.batch == B.batch else 1)
+
+
+def amplify_sequence_operators(L: SparseOperator):
+    """[L0, L1, L2]: the operator sequence of the 'amp' tower (src/dense_correspondence/main.py:72-83) from a device Laplacian,
+    in the reference's step order:  L0 = S(L);  L1 = S(L0)^2;  L2 = S(L1)^2,  S(X) = D^-1/2 X D^-1/2 (kernels.csr_scale_sym) and
+    D = entries per row of L - 1, taken ONCE from L's own row lengths (explicit zeros count, as they do on the host).  L0 and L1
+    are dense_correspondence.amplify_sequence's matrices bit for bit; L2 is the ascending-order sum where scipy sums its own
+    unsorted rows (LABNOTES.md#spgemm).  A block-diagonal batch gives the block-diagonal of the single meshes; `batch` is
+    carried over.  ValueError for a row holding only its diagonal."""
+    if not isinstance(L, SparseOperator):
+        raise TypeError("amplify_sequence_operators wants a SparseOperator")
+    M, K = L._shape
+    if M != K:
+        raise ValueError(f"amplify_sequence_operators wants a square operator, got {L._shape}")
+    d = kernels.csr_inv_sqrt_degree(L.rowptr)
+    cur = kernels.csr_scale_sym((L.rowptr, L.colind, L.vals), d, M)
+    out = [SparseOperator(*cur, (M, M), batch=L.batch)]
+    for _ in range(2):
+        cur = kernels.csr_scale_sym(cur, d, M)
+        cur = kernels.csr_spgemm(cur, cur, (M, M, M))
+        out.append(SparseOperator(*cur, (M, M), batch=L.batch))
+    return out
 
 
 def geodesic_matrix_from_mesh(V: torch.Tensor, F: torch.Tensor, symmetric: bool = True, require_connected: bool = True,
