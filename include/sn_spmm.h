@@ -947,6 +947,66 @@ int sn_mesh_idt_laplacian_f32(const int32_t *Fp, const double *lp, int64_t nV, i
                               void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Mesh clean-up: connected components, the largest one, and compaction of what is kept.
+ *
+ * Replaces: igl.facet_components + scipy.stats.mode + igl.slice + igl.remove_unreferenced
+ *           src/dense_correspondence/largest_component.py:28-47 (an off-line libigl script; nothing of it is on the device).
+ *
+ * Definition.  F int32 (nF, 3) over the vertices 0..nV-1.  A face is BAD when one of its indices lies outside 0..nV-1 or two
+ *   of its indices are equal: its flabel is -1, it joins nothing, it is never kept, and *status |= SN_CC_BAD_FACE.  Every
+ *   other face is good.  Non-manifold and inconsistently oriented input is welcome (unlike sn_mesh_glue_i32).
+ *   SN_CC_VERTEX: two vertices are joined when a good face holds both.  vlabel[v] = the smallest vertex id of v's class; a
+ *     vertex no good face uses is a class of its own, vlabel[v] = v.  flabel[f] = vlabel[F[f][0]].  Labels are vertex ids:
+ *     count has nV entries.
+ *   SN_CC_EDGE (igl.facet_components): two good faces are joined when each has a side on the same unordered vertex pair,
+ *     whatever the orientation and however many faces lie on that edge; faces that touch in one vertex only are not joined.
+ *     flabel[f] = the smallest face id of f's class.  Labels are face ids: count has nF entries.  vlabel may be NULL and is
+ *     not written.
+ *   count[l] = the number of good faces with label l (0 for an id that is no label).
+ *   summary[0..2] = {number of labels with at least one face, the winning label, its face count}: the winner has the largest
+ *     count, the smallest label on a tie — in edge mode the component that contains the lowest face index, scipy.stats.mode's
+ *     choice among the reference's first-face-ordered ids.  Without a good face summary = {0, -1, 0}.
+ *   All of it is a function of the partition alone: whatever order the threads run in, two runs are bit-identical.
+ * Method.  A concurrent union-find over parent[] (the label array itself): a link is one atomicCAS(&parent[hi], hi, lo) between
+ *   two roots, the larger under the smaller, so chains strictly decrease and a root is the minimum of its class; find halves
+ *   paths with plain stores (only non-roots are rewritten, only roots are CAS targets).  Lock-free: a pass is repeated only
+ *   because another thread's link succeeded.  Every loop is bounded by the node count (a chain has at most n nodes, a class is
+ *   linked at most n times); a bound that is hit — it cannot be, short of memory written from outside — sets SN_CC_INTERNAL
+ *   instead of spinning, and the labels are then not to be used.  Edge mode buckets every side under its lower vertex (count,
+ *   scan, fill, as the glue builder) and joins a side's face to the face of the first side of the bucket with the same upper
+ *   vertex; the bucket order picks the centre of that star, not the partition.  Every index read from F is range-checked
+ *   before it addresses anything.  Histogram: integer atomicAdd; winner: one 64-bit atomicMax per wave over
+ *   (count << 32) | (0x7fffffff - label).
+ *
+ * sn_mesh_components_i32 : vlabel[nV] (vertex mode), flabel[nF], count[nV or nF], summary[3] and *status (cleared first) as
+ *                          defined above.  workspace: sn_mesh_components_workspace_bytes(nV, nF, mode), else SN_E_WORKSPACE.
+ *                          Another mode: SN_E_SHAPE.  nV + 1 or 3 nF past int32: SN_E_RANGE.  Does not synchronise.
+ * sn_mesh_label_mask_i32 : keep[f] = (flabel[f] == *label && *label >= 0), label read on the device: the keep mask of the
+ *                          winner (label = summary + 1) without a round trip to the host.
+ * sn_mesh_compact_i32    : igl.slice + igl.remove_unreferenced.  Face f stays when keep[f] != 0 and f is good.  Outputs sized
+ *                          by the caller for the worst case, the used prefix as sizes[0..1] = {nV', nF'} says:
+ *                          I[nV] old -> new vertex id, -1 for a vertex no staying face uses;  J[nV'] new -> old, ascending
+ *                          (kept vertices keep their relative order);  Fsrc[nF'] the original index of every staying face,
+ *                          ascending;  Fnew[nF'][3] = I[F[Fsrc]];  Vnew[nV'][3] = V[J] bit for bit when V and Vnew are given
+ *                          (both or neither).  Marks are idempotent stores of 1, the positions two exclusive int32 scans
+ *                          (nF + 1 and nV + 1 entries, any number of scan tiles).  workspace:
+ *                          sn_mesh_compact_workspace_bytes(nV, nF), else SN_E_WORKSPACE.  Does not synchronise.
+ * ------------------------------------------------------------------------------------------ */
+#define SN_CC_EDGE      0
+#define SN_CC_VERTEX    1
+#define SN_CC_BAD_FACE  1
+#define SN_CC_INTERNAL  2
+size_t sn_mesh_components_workspace_bytes(int64_t nV, int64_t nF, int32_t mode);
+int sn_mesh_components_i32(const int32_t *F, int64_t nV, int64_t nF, int32_t mode, int32_t *vlabel, int32_t *flabel,
+                           int32_t *count, int32_t *summary, int32_t *status, void *workspace, size_t workspace_bytes,
+                           void *stream);
+int sn_mesh_label_mask_i32(const int32_t *flabel, int64_t nF, const int32_t *label, int32_t *keep, void *stream);
+size_t sn_mesh_compact_workspace_bytes(int64_t nV, int64_t nF);
+int sn_mesh_compact_i32(const float *V, const int32_t *F, const int32_t *keep, int64_t nV, int64_t nF, int32_t *I, int32_t *J,
+                        int32_t *Fsrc, int32_t *Fnew, float *Vnew, int32_t *sizes, void *workspace, size_t workspace_bytes,
+                        void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Sparse x sparse CSR products and the symmetric diagonal scaling: the operators of the 'amp' tower.
  *
  * Replaces: L = Dsq.dot(L).dot(Dsq); twice L = Dsq.dot(L).dot(Dsq), L = L.dot(L)     src/dense_correspondence/main.py:72-83

@@ -155,6 +155,11 @@ SIGNATURES = {
     "sn_mesh_idt_laplacian_items": (_i64, [_i64, _i64]),
     "sn_mesh_idt_laplacian_workspace_bytes": (_sz, [_i64, _i64]),
     "sn_mesh_idt_laplacian_f32": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sn_mesh_components_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "sn_mesh_components_i32": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sn_mesh_label_mask_i32": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    "sn_mesh_compact_workspace_bytes": (_sz, [_i64, _i64]),
+    "sn_mesh_compact_i32": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sn_csr_spgemm_max_window": (_i64, []),
     "sn_csr_spgemm_workspace_bytes": (_sz, [_i64]),
     "sn_csr_spgemm_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -871,6 +871,241 @@ inline size_t idt_lap_ws(int64_t nV, int64_t nF, char *w, IdtLapWs *out) {
 
 inline size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
 
+// ------------------------------------------------------------------------------------------------
+// Mesh clean-up: component labels by a concurrent union-find, and compaction by two scans (definition: sn_spmm.h).
+// A node is a vertex (SN_CC_VERTEX) or a face (SN_CC_EDGE).  parent[x] <= x always: a link is one CAS that turns a root into
+// the child of a smaller root, and path halving only replaces a parent by a grandparent.  So every chain strictly decreases,
+// the root of a class is its minimum, and nobody ever waits: a CAS fails only because another thread's link succeeded.
+// Loads and stores of parent[] are relaxed atomics of device scope, so that a retry reads what the winning CAS wrote.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int cc_load(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void cc_store(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// root of x.  A chain has at most n nodes; one step past that bound reports SN_CC_INTERNAL and returns -1.
+template <bool HALVE>
+__device__ __forceinline__ int cc_find(int *parent, int x, int n, int *status) {
+  for (int step = 0; step <= n; ++step) {
+    const int p = cc_load(parent + x);
+    if (p == x) return x;
+    if ((unsigned)p >= (unsigned)n) break;               // not a value this file writes
+    const int g = cc_load(parent + p);
+    if (g == p) return p;
+    if ((unsigned)g >= (unsigned)n) break;
+    if (HALVE) cc_store(parent + x, g);                  // x is no root and never becomes one again: no CAS targets it
+    x = g;
+  }
+  atomicOr(status, SN_CC_INTERNAL);
+  return -1;
+}
+
+// join the classes of a and b.  Every pass but the last follows a link made by somebody else, and a class is linked at most
+// once as the larger root: at most n passes.
+__device__ __forceinline__ void cc_unite(int *parent, int a, int b, int n, int *status) {
+  for (int pass = 0; pass <= n; ++pass) {
+    a = cc_find<true>(parent, a, n, status);
+    b = cc_find<true>(parent, b, n, status);
+    if (a < 0 || b < 0 || a == b) return;
+    const int hi = a > b ? a : b, lo = a > b ? b : a;
+    if (atomicCAS(parent + hi, hi, lo) == hi) return;
+  }
+  atomicOr(status, SN_CC_INTERNAL);
+}
+
+__global__ __launch_bounds__(kWG) void cc_init_k(int *__restrict__ parent, int *__restrict__ count, int64_t n) {
+  for (int64_t x = (int64_t)blockIdx.x * kWG + threadIdx.x; x < n; x += (int64_t)gridDim.x * kWG) {
+    parent[x] = (int)x;
+    count[x] = 0;
+  }
+}
+
+// vertex mode: the three vertices of a good face are one class
+__global__ __launch_bounds__(kWG) void cc_vertex_union_k(const int *__restrict__ F, int64_t nF, int64_t nV, int *parent,
+                                                         int *__restrict__ status) {
+  for (int64_t f = (int64_t)blockIdx.x * kWG + threadIdx.x; f < nF; f += (int64_t)gridDim.x * kWG) {
+    const int i = F[3 * f], j = F[3 * f + 1], k = F[3 * f + 2];
+    if (!face_ok(i, j, k, nV)) {
+      atomicOr(status, SN_CC_BAD_FACE);
+      continue;
+    }
+    cc_unite(parent, i, j, (int)nV, status);
+    cc_unite(parent, j, k, (int)nV, status);
+  }
+}
+
+// edge mode: the sides of the good faces, bucketed under the lower of their two vertices (orientation does not matter)
+__global__ __launch_bounds__(kWG) void cc_side_count_k(const int *__restrict__ F, int64_t nF, int64_t nV, int *__restrict__ ptr,
+                                                       int *__restrict__ status) {
+  for (int64_t f = (int64_t)blockIdx.x * kWG + threadIdx.x; f < nF; f += (int64_t)gridDim.x * kWG) {
+    const int i = F[3 * f], j = F[3 * f + 1], k = F[3 * f + 2];
+    if (!face_ok(i, j, k, nV)) {
+      atomicOr(status, SN_CC_BAD_FACE);
+      continue;
+    }
+    atomicAdd(&ptr[min(i, j)], 1);
+    atomicAdd(&ptr[min(j, k)], 1);
+    atomicAdd(&ptr[min(k, i)], 1);
+  }
+}
+
+__global__ __launch_bounds__(kWG) void cc_side_fill_k(const int *__restrict__ F, int64_t nF, int64_t nV, int *__restrict__ cursor,
+                                                      int *__restrict__ bucket) {
+  for (int64_t f = (int64_t)blockIdx.x * kWG + threadIdx.x; f < nF; f += (int64_t)gridDim.x * kWG) {
+    const int i = F[3 * f], j = F[3 * f + 1], k = F[3 * f + 2];
+    if (!face_ok(i, j, k, nV)) continue;
+    bucket[atomicAdd(&cursor[min(i, j)], 1)] = (int)(3 * f);
+    bucket[atomicAdd(&cursor[min(j, k)], 1)] = (int)(3 * f + 1);
+    bucket[atomicAdd(&cursor[min(k, i)], 1)] = (int)(3 * f + 2);
+  }
+}
+
+// A side joins its face to the face of the first side of its bucket on the same upper vertex: a star per edge, whatever the
+// number of faces on it.  The order inside a bucket (atomic cursor) picks the centre of the star, not the partition.
+__global__ __launch_bounds__(kWG) void cc_edge_union_k(const int *__restrict__ F, int64_t nF, int64_t nV, const int *__restrict__ ptr,
+                                                       const int *__restrict__ bucket, int *parent, int *__restrict__ status) {
+  for (int64_t c = (int64_t)blockIdx.x * kWG + threadIdx.x; c < 3 * nF; c += (int64_t)gridDim.x * kWG) {
+    const int64_t f = c / 3;
+    const int s = (int)(c - 3 * f);
+    const int i = F[3 * f], j = F[3 * f + 1], k = F[3 * f + 2];
+    if (!face_ok(i, j, k, nV)) continue;
+    const int a = s == 0 ? i : s == 1 ? j : k, b = s == 0 ? j : s == 1 ? k : i;
+    const int lo = min(a, b), hi = max(a, b);
+    for (int e = ptr[lo]; e < ptr[lo + 1]; ++e) {
+      const int d = bucket[e];
+      if ((unsigned)d >= (unsigned)(3 * nF)) continue;
+      const int g = d / 3, t = d - 3 * g;
+      if (max(F[d], F[3 * g + (t + 1) % 3]) != hi) continue;       // (a bucketed side belongs to a good face: its min is lo)
+      if (g != (int)f) cc_unite(parent, (int)f, g, (int)nF, status);
+      break;
+    }
+  }
+}
+
+// vlabel[v] = root of v, in place (a reader meets the old parent or the root: both are ancestors)
+__global__ __launch_bounds__(kWG) void cc_flatten_k(int *parent, int64_t n, int *__restrict__ status) {
+  for (int64_t x = (int64_t)blockIdx.x * kWG + threadIdx.x; x < n; x += (int64_t)gridDim.x * kWG) {
+    const int r = cc_find<false>(parent, (int)x, (int)n, status);
+    cc_store(parent + x, r < 0 ? (int)x : r);
+  }
+}
+
+// flabel and the histogram.  VERTEX: flabel[f] = vlabel[F[f][0]] (flattened by the launch before);  else flabel is the face
+// forest itself and f looks up its own root.
+template <bool VERTEX>
+__global__ __launch_bounds__(kWG) void cc_face_labels_k(const int *__restrict__ F, int64_t nF, int64_t nV, const int *vlabel,
+                                                        int *flabel, int *__restrict__ count, int *__restrict__ status) {
+  for (int64_t f = (int64_t)blockIdx.x * kWG + threadIdx.x; f < nF; f += (int64_t)gridDim.x * kWG) {
+    const int i = F[3 * f], j = F[3 * f + 1], k = F[3 * f + 2];
+    int r = -1;
+    if (face_ok(i, j, k, nV)) {
+      r = VERTEX ? vlabel[i] : cc_find<false>(flabel, (int)f, (int)nF, status);
+      if ((unsigned)r < (unsigned)(VERTEX ? nV : nF)) atomicAdd(&count[r], 1);
+      else r = (int)(VERTEX ? i : f);                             // only after SN_CC_INTERNAL
+    }
+    if (VERTEX) flabel[f] = r;
+    else if (r >= 0) cc_store(flabel + f, r);                     // a bad face stays its own root until cc_bad_labels_k
+  }
+}
+__global__ __launch_bounds__(kWG) void cc_bad_labels_k(const int *__restrict__ F, int64_t nF, int64_t nV, int *__restrict__ flabel) {
+  for (int64_t f = (int64_t)blockIdx.x * kWG + threadIdx.x; f < nF; f += (int64_t)gridDim.x * kWG)
+    if (!face_ok(F[3 * f], F[3 * f + 1], F[3 * f + 2], nV)) flabel[f] = -1;
+}
+
+// acc[0]: max over the labels of (count << 32) | (0x7fffffff - label) — the largest count, the smallest label on a tie;
+// acc[1]: the number of labels that have a face.  One pair of atomics per wave.
+typedef unsigned long long cc_word_t;
+__global__ __launch_bounds__(kWG) void cc_winner_k(const int *__restrict__ count, int64_t n, cc_word_t *__restrict__ acc) {
+  cc_word_t best = 0;
+  int used = 0;
+  for (int64_t l = (int64_t)blockIdx.x * kWG + threadIdx.x; l < n; l += (int64_t)gridDim.x * kWG) {
+    const int c = count[l];
+    if (c > 0) {
+      const cc_word_t w = ((cc_word_t)(unsigned)c << 32) | (cc_word_t)(0x7fffffffu - (unsigned)l);
+      best = w > best ? w : best;
+      ++used;
+    }
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    const cc_word_t o = __shfl_down(best, d, 64);
+    best = o > best ? o : best;
+    used += __shfl_down(used, d, 64);
+  }
+  if ((threadIdx.x & 63) == 0 && used > 0) {
+    atomicMax(&acc[0], best);
+    atomicAdd(&acc[1], (cc_word_t)used);
+  }
+}
+__global__ void cc_summary_k(const cc_word_t *__restrict__ acc, int *__restrict__ summary) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const cc_word_t w = acc[0];
+  summary[0] = (int)acc[1];
+  summary[1] = w ? (int)(0x7fffffffu - (unsigned)(w & 0xffffffffu)) : -1;
+  summary[2] = (int)(w >> 32);
+}
+
+// ---- compaction: fmark[f] = face f stays, vmark[v] = a staying face uses v (plain stores of 1), both with one slot past the
+// end so that the exclusive scans end in the totals ----
+__global__ __launch_bounds__(kWG) void compact_mark_k(const int *__restrict__ F, const int *__restrict__ keep, int64_t nF, int64_t nV,
+                                                      int *__restrict__ fmark, int *__restrict__ vmark) {
+  for (int64_t f = (int64_t)blockIdx.x * kWG + threadIdx.x; f <= nF; f += (int64_t)gridDim.x * kWG) {
+    if (f == nF) {
+      fmark[f] = 0;
+      break;
+    }
+    const int i = F[3 * f], j = F[3 * f + 1], k = F[3 * f + 2];
+    const bool stay = keep[f] != 0 && face_ok(i, j, k, nV);
+    fmark[f] = stay ? 1 : 0;
+    if (stay) vmark[i] = vmark[j] = vmark[k] = 1;
+  }
+}
+__global__ __launch_bounds__(kWG) void compact_vertices_k(const float *__restrict__ V, int64_t nV, const int *__restrict__ vpos,
+                                                          int *__restrict__ I, int *__restrict__ J, float *__restrict__ Vnew,
+                                                          const int *__restrict__ fpos, int64_t nF, int *__restrict__ sizes) {
+  for (int64_t v = (int64_t)blockIdx.x * kWG + threadIdx.x; v <= nV; v += (int64_t)gridDim.x * kWG) {
+    if (v == nV) {
+      sizes[0] = vpos[nV];
+      sizes[1] = fpos[nF];
+      break;
+    }
+    const int o = vpos[v];
+    const bool stay = vpos[v + 1] != o;
+    I[v] = stay ? o : -1;
+    if (!stay) continue;
+    J[o] = (int)v;
+    if (V) {
+      Vnew[3 * (int64_t)o] = V[3 * v];
+      Vnew[3 * (int64_t)o + 1] = V[3 * v + 1];
+      Vnew[3 * (int64_t)o + 2] = V[3 * v + 2];
+    }
+  }
+}
+__global__ __launch_bounds__(kWG) void compact_faces_k(const int *__restrict__ F, int64_t nF, const int *__restrict__ fpos,
+                                                       const int *__restrict__ vpos, int *__restrict__ Fsrc, int *__restrict__ Fnew) {
+  for (int64_t f = (int64_t)blockIdx.x * kWG + threadIdx.x; f < nF; f += (int64_t)gridDim.x * kWG) {
+    const int o = fpos[f];
+    if (fpos[f + 1] == o) continue;                      // a staying face passed face_ok: its indices address vpos
+    Fsrc[o] = (int)f;
+    Fnew[3 * (int64_t)o] = vpos[F[3 * f]];
+    Fnew[3 * (int64_t)o + 1] = vpos[F[3 * f + 1]];
+    Fnew[3 * (int64_t)o + 2] = vpos[F[3 * f + 2]];
+  }
+}
+__global__ __launch_bounds__(kWG) void label_mask_k(const int *__restrict__ flabel, int64_t nF, const int *__restrict__ label,
+                                                    int *__restrict__ keep) {
+  const int want = *label;
+  for (int64_t f = (int64_t)blockIdx.x * kWG + threadIdx.x; f < nF; f += (int64_t)gridDim.x * kWG)
+    keep[f] = (want >= 0 && flabel[f] == want) ? 1 : 0;
+}
+
+inline size_t scan_bytes(int64_t n) { return align16((size_t)((n + kScanTile - 1) / kScanTile + 1) * sizeof(int)); }
+// exclusive scan of a[0..n) in place on stream s
+inline void scan_in_place(int *a, int64_t n, int *sums, hipStream_t s) {
+  const int nblk = (int)((n + kScanTile - 1) / kScanTile);
+  hipLaunchKernelGGL(scan_sums_k, dim3(nblk), dim3(kWG), 0, s, a, n, sums);
+  hipLaunchKernelGGL(scan_top_k, dim3(1), dim3(kWG), 0, s, sums, nblk);
+  hipLaunchKernelGGL(scan_apply_k, dim3(nblk), dim3(kWG), 0, s, a, n, sums, a);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1193,6 +1428,103 @@ int sn_mesh_idt_laplacian_f32(const int32_t *Fp, const double *lp, int64_t nV, i
     hipLaunchKernelGGL((idt_entries_k<false>), dim3(grid_for(N)), dim3(kWG), 0, s, keys, order, N, nV, span, ws.hs, ws.cval, ws.A,
                        colind, vals);
   }
+  return launch_status();
+}
+
+size_t sn_mesh_components_workspace_bytes(int64_t nV, int64_t nF, int32_t mode) {
+  if (nV < 0) nV = 0;
+  if (nF < 0) nF = 0;
+  size_t b = 16;                                                           // the winner word and the label counter
+  if (mode == SN_CC_EDGE) b += 2 * align16((size_t)(nV + 1) * sizeof(int)) + align16((size_t)3 * nF * sizeof(int)) + scan_bytes(nV + 1);
+  return b;
+}
+
+int sn_mesh_components_i32(const int32_t *F, int64_t nV, int64_t nF, int32_t mode, int32_t *vlabel, int32_t *flabel,
+                           int32_t *count, int32_t *summary, int32_t *status, void *workspace, size_t workspace_bytes,
+                           void *stream) {
+  (void)hipGetLastError();
+  if (nV < 0 || nF < 0 || (mode != SN_CC_EDGE && mode != SN_CC_VERTEX)) return SN_E_SHAPE;
+  if (nV + 1 > INT_MAX || 3 * nF > INT_MAX) return SN_E_RANGE;
+  const bool vertex = mode == SN_CC_VERTEX;
+  const int64_t n = vertex ? nV : nF;
+  if (!summary || !status) return SN_E_NULL;
+  if (nF > 0 && (!F || !flabel)) return SN_E_NULL;
+  if (n > 0 && !count) return SN_E_NULL;
+  if (vertex && nV > 0 && !vlabel) return SN_E_NULL;
+  if (workspace_bytes < sn_mesh_components_workspace_bytes(nV, nF, mode) || !workspace) return SN_E_WORKSPACE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  char *w = static_cast<char *>(workspace);
+  cc_word_t *acc = reinterpret_cast<cc_word_t *>(w); w += 16;
+  hipError_t e = sn_internal_fill(acc, 0, 16, s);
+  if (e != hipSuccess) return (int)e;
+  e = sn_internal_fill(status, 0, sizeof(int), s);
+  if (e != hipSuccess) return (int)e;
+  int *parent = vertex ? vlabel : flabel;
+  if (n > 0) hipLaunchKernelGGL(cc_init_k, dim3(grid_for(n)), dim3(kWG), 0, s, parent, count, n);
+  if (vertex) {
+    if (nF > 0) hipLaunchKernelGGL(cc_vertex_union_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, nV, parent, status);
+    if (nV > 0) hipLaunchKernelGGL(cc_flatten_k, dim3(grid_for(nV)), dim3(kWG), 0, s, parent, nV, status);
+    if (nF > 0) hipLaunchKernelGGL((cc_face_labels_k<true>), dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, nV, vlabel, flabel, count, status);
+  } else if (nF > 0) {
+    int *ptr = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
+    int *cursor = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
+    int *bucket = reinterpret_cast<int *>(w); w += align16((size_t)3 * nF * sizeof(int));
+    int *sums = reinterpret_cast<int *>(w);
+    e = sn_internal_fill(ptr, 0, (size_t)(nV + 1) * sizeof(int), s);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(cc_side_count_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, nV, ptr, status);
+    scan_in_place(ptr, nV + 1, sums, s);
+    e = sn_internal_copy2d(cursor, 0, ptr, 0, (int64_t)((size_t)(nV + 1) * sizeof(int)), 1, s);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(cc_side_fill_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, nV, cursor, bucket);
+    hipLaunchKernelGGL(cc_edge_union_k, dim3(grid_for(3 * nF)), dim3(kWG), 0, s, F, nF, nV, ptr, bucket, parent, status);
+    hipLaunchKernelGGL((cc_face_labels_k<false>), dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, nV, (const int *)nullptr, flabel, count, status);
+    hipLaunchKernelGGL(cc_bad_labels_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, nV, flabel);
+  }
+  if (n > 0) hipLaunchKernelGGL(cc_winner_k, dim3(grid_for(n)), dim3(kWG), 0, s, count, n, acc);
+  hipLaunchKernelGGL(cc_summary_k, dim3(1), dim3(64), 0, s, acc, summary);
+  return launch_status();
+}
+
+int sn_mesh_label_mask_i32(const int32_t *flabel, int64_t nF, const int32_t *label, int32_t *keep, void *stream) {
+  (void)hipGetLastError();
+  if (nF < 0) return SN_E_SHAPE;
+  if (3 * nF > INT_MAX) return SN_E_RANGE;
+  if (nF == 0) return SN_OK;
+  if (!flabel || !label || !keep) return SN_E_NULL;
+  hipLaunchKernelGGL(label_mask_k, dim3(grid_for(nF)), dim3(kWG), 0, static_cast<hipStream_t>(stream), flabel, nF, label, keep);
+  return launch_status();
+}
+
+size_t sn_mesh_compact_workspace_bytes(int64_t nV, int64_t nF) {
+  if (nV < 0) nV = 0;
+  if (nF < 0) nF = 0;
+  return align16((size_t)(nV + 1) * sizeof(int)) + align16((size_t)(nF + 1) * sizeof(int)) + scan_bytes((nV > nF ? nV : nF) + 1);
+}
+
+int sn_mesh_compact_i32(const float *V, const int32_t *F, const int32_t *keep, int64_t nV, int64_t nF, int32_t *I, int32_t *J,
+                        int32_t *Fsrc, int32_t *Fnew, float *Vnew, int32_t *sizes, void *workspace, size_t workspace_bytes,
+                        void *stream) {
+  (void)hipGetLastError();
+  if (nV < 0 || nF < 0) return SN_E_SHAPE;
+  if (nV + 1 > INT_MAX || 3 * nF > INT_MAX) return SN_E_RANGE;
+  if (!sizes) return SN_E_NULL;
+  if (nF > 0 && (!F || !keep || !Fsrc || !Fnew)) return SN_E_NULL;
+  if (nV > 0 && (!I || !J)) return SN_E_NULL;
+  if (nV > 0 && !V != !Vnew) return SN_E_NULL;                     // the coordinates are copied when both are given
+  if (workspace_bytes < sn_mesh_compact_workspace_bytes(nV, nF) || !workspace) return SN_E_WORKSPACE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  char *w = static_cast<char *>(workspace);
+  int *vpos = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
+  int *fpos = reinterpret_cast<int *>(w); w += align16((size_t)(nF + 1) * sizeof(int));
+  int *sums = reinterpret_cast<int *>(w);
+  hipError_t e = sn_internal_fill(vpos, 0, (size_t)(nV + 1) * sizeof(int), s);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(compact_mark_k, dim3(grid_for(nF + 1)), dim3(kWG), 0, s, F, keep, nF, nV, fpos, vpos);
+  scan_in_place(fpos, nF + 1, sums, s);
+  scan_in_place(vpos, nV + 1, sums, s);
+  hipLaunchKernelGGL(compact_vertices_k, dim3(grid_for(nV + 1)), dim3(kWG), 0, s, V, nV, vpos, I, J, Vnew, fpos, nF, sizes);
+  if (nF > 0) hipLaunchKernelGGL(compact_faces_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, fpos, vpos, Fsrc, Fnew);
   return launch_status();
 }
 

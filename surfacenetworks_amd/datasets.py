@@ -159,7 +159,8 @@ def load_faust_frame(path: str, device="cuda") -> Dict:
     return fr
 
 
-def faust_frame_from_mesh(V, F, label=None, device="cuda", symmetric=True, geodesics="edges", laplacian="extrinsic") -> Dict:
+def faust_frame_from_mesh(V, F, label=None, device="cuda", symmetric=True, geodesics="edges", laplacian="extrinsic",
+                          component=None) -> Dict:
     """The frame dict of load_faust_frame from a raw triangle mesh: V (nV, 3), F (nF, 3) (numpy or tensors), host scipy
     L / Di / DiA from mesh_ops.mesh_operators, and G — the `dist_mat` the reference's files bring along — computed on the device
     by operators.geodesic_matrix_from_mesh (geodesics="edges": edge-path distances, "triangles": paths that cross the faces;
@@ -167,13 +168,27 @@ def faust_frame_from_mesh(V, F, label=None, device="cuda", symmetric=True, geode
     main.py:98-99 (vertex -> canonical id), None = identity.  A list of such frames is what FaustFrames takes.
     laplacian: "extrinsic" (default) keeps the host cotangent Laplacian; "intrinsic" takes L from the device builder on the
     intrinsic Delaunay triangulation (operators.laplacian_operator_from_mesh(intrinsic=True), fp32 scipy CSR) — the frame['L']
-    the reference builds with mesh.intrinsic_laplacian (main.py:87), in this project's scaling, not the unpublished one."""
-    from .operators import geodesic_matrix_from_mesh, laplacian_operator_from_mesh
+    the reference builds with mesh.intrinsic_laplacian (main.py:87), in this project's scaling, not the unpublished one.
+    component: None (default) takes the mesh as it is; "largest" first runs operators.clean_mesh — the largest edge-connected
+    component without bad faces and unused vertices, the reference's largest_component.py — builds the frame from the result
+    and adds frame["vertex_map"] (new -> original vertex id).  label must then be None: a permutation of the original ids
+    does not survive the removal, and the identity on the kept vertices is used."""
+    from .operators import clean_mesh, geodesic_matrix_from_mesh, laplacian_operator_from_mesh
 
     if geodesics not in ("edges", "triangles"):
         raise ValueError(f'faust_frame_from_mesh: geodesics must be "edges" or "triangles", got {geodesics!r}')
     if laplacian not in ("extrinsic", "intrinsic"):
         raise ValueError(f'faust_frame_from_mesh: laplacian must be "extrinsic" or "intrinsic", got {laplacian!r}')
+    if component not in (None, "largest"):
+        raise ValueError(f'faust_frame_from_mesh: component must be None or "largest", got {component!r}')
+    vertex_map = None
+    if component == "largest":
+        if label is not None:
+            raise ValueError('faust_frame_from_mesh: component="largest" renumbers the vertices; label must be None')
+        Vt = V if torch.is_tensor(V) else torch.from_numpy(np.array(V, dtype=np.float32))
+        Ft = F if torch.is_tensor(F) else torch.from_numpy(np.array(F))
+        cm = clean_mesh(Vt.to(device), Ft.to(device))
+        V, F, vertex_map = cm.V, cm.F, cm.vertex_map.to(torch.int64)
     Vn = np.asarray(V.detach().cpu() if torch.is_tensor(V) else V)
     Fn = np.asarray(F.detach().cpu() if torch.is_tensor(F) else F)
     nv = Vn.shape[0]
@@ -184,12 +199,15 @@ def faust_frame_from_mesh(V, F, label=None, device="cuda", symmetric=True, geode
     Vd = torch.from_numpy(Vn.astype("f")).to(device)
     Fd = torch.from_numpy(Fn.astype(np.int64)).to(device)
     L = laplacian_operator_from_mesh(Vd, Fd, intrinsic=True).to_scipy() if laplacian == "intrinsic" else ops["L"]
-    return {
+    frame = {
         "V": Vd, "F": Fd, "L": L, "Di": ops["Di"], "DiA": ops["DiA"],
         "label": torch.from_numpy(label.astype(np.int64)).to(device),
         "label_inv": torch.from_numpy(np.argsort(label).astype(np.int64)).to(device),
         "G": geodesic_matrix_from_mesh(Vd, Fd, symmetric=symmetric, method=geodesics),
     }
+    if vertex_map is not None:
+        frame["vertex_map"] = vertex_map
+    return frame
 
 
 def faust_from_files(paths: Sequence[str], device="cuda", model="lap", pad_to=None, reorder="auto", amplify="host"):

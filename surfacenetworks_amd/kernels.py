@@ -7,6 +7,8 @@ csr_to_bsr4 which must read one integer (the block count) back to size its outpu
 """
 from __future__ import annotations
 
+import collections
+
 import torch
 
 from . import _lib
@@ -984,6 +986,89 @@ def intrinsic_laplacian_from_mesh(V, F, max_rounds: int = 1024, state=None):
     _lib.call("sn_mesh_idt_laplacian_f32", *args, 2, _p(skeys), _p(order), rowptr.data_ptr(), _p(colind), _p(vals), None, _p(ws), ws_bytes,
               _stream())
     return rowptr, colind, vals
+
+
+CC_EDGE, CC_VERTEX = 0, 1                # SN_CC_EDGE / SN_CC_VERTEX
+CC_BAD_FACE, CC_INTERNAL = 1, 2          # status bits of mesh_components
+_CC_MODES = {"edge": CC_EDGE, "vertex": CC_VERTEX}
+
+MeshComponents = collections.namedtuple("MeshComponents", "vlabel flabel count summary status")
+MeshCompacted = collections.namedtuple("MeshCompacted", "I J Fsrc Fnew Vnew sizes")
+
+
+def mesh_components(F, num_vertices: int, mode: str = "edge") -> MeshComponents:
+    """Connected components of a triangle mesh on the device (sn_mesh_components_i32; the definition is in include/sn_spmm.h,
+    "Mesh clean-up", the host statement is mesh_ops.components).  F: (nF, 3) int32.  mode "edge": faces joined across shared
+    edges (igl.facet_components), labels are face ids; "vertex": vertices joined by faces, labels are vertex ids.
+    Returns MeshComponents(vlabel, flabel, count, summary, status), int32 device tensors: vlabel (nV,) in vertex mode, None in
+    edge mode; flabel (nF,), -1 for a bad face; count (nV,) or (nF,); summary (3,) = labels with a face, the winning label,
+    its face count; status (1,) with the CC_BAD_FACE / CC_INTERNAL bits.  Does not synchronise; two runs are bit-identical."""
+    _dev(F)
+    _check_mesh("mesh_components", None, F)
+    if mode not in _CC_MODES:
+        raise ValueError(f'mesh_components: mode must be "edge" or "vertex", got {mode!r}')
+    F = F.contiguous()
+    nV, nF = int(num_vertices), F.shape[0]
+    if nV < 0:
+        raise ValueError("mesh_components: num_vertices is negative")
+    dev = F.device
+    vertex = mode == "vertex"
+    vlabel = torch.empty(nV, dtype=torch.int32, device=dev) if vertex else None
+    flabel = torch.empty(nF, dtype=torch.int32, device=dev)
+    count = torch.empty(nV if vertex else nF, dtype=torch.int32, device=dev)
+    summary = torch.empty(3, dtype=torch.int32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ws_bytes = int(_lib.load().sn_mesh_components_workspace_bytes(nV, nF, _CC_MODES[mode]))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    _lib.call("sn_mesh_components_i32", _p(F), nV, nF, _CC_MODES[mode], _p(vlabel), _p(flabel), _p(count), summary.data_ptr(),
+              status.data_ptr(), _p(ws), ws_bytes, _stream())
+    return MeshComponents(vlabel, flabel, count, summary, status)
+
+
+def mesh_label_mask(flabel, label):
+    """keep (nF,) int32 = (flabel == label) with label a 1-element int32 DEVICE tensor (e.g. summary[1:2] of mesh_components:
+    the winner's faces without reading the label back); a negative label keeps nothing.  sn_mesh_label_mask_i32."""
+    _dev(flabel, label)
+    if flabel.dtype != torch.int32 or flabel.dim() != 1 or label.dtype != torch.int32 or label.numel() != 1:
+        raise TypeError("mesh_label_mask wants flabel (nF,) int32 and a 1-element int32 label tensor")
+    flabel = flabel.contiguous()
+    keep = torch.empty_like(flabel)
+    _lib.call("sn_mesh_label_mask_i32", _p(flabel), flabel.shape[0], label.data_ptr(), _p(keep), _stream())
+    return keep
+
+
+def mesh_compact(F, keep, num_vertices: int, V=None) -> MeshCompacted:
+    """Keep the good faces with keep[f] != 0 and the vertices they still use (igl.slice + igl.remove_unreferenced) on the device:
+    sn_mesh_compact_i32, host statement mesh_ops.compact.  F: (nF, 3) int32, keep: (nF,) int32, V: (nV, 3) fp32 or None.
+    Returns MeshCompacted(I, J, Fsrc, Fnew, Vnew, sizes), device tensors SIZED FOR THE WORST CASE: I (nV,) old -> new vertex id
+    or -1; J (nV,) new -> old, ascending; Fsrc (nF,) original index of each kept face, ascending; Fnew (nF, 3) renumbered;
+    Vnew (nV, 3) = V[J] (None without V); sizes (2,) int32 = (nV', nF'): the first nV' entries of J and Vnew and the first nF'
+    of Fsrc and Fnew are written.  Does not synchronise: the caller reads `sizes` when it needs the lengths."""
+    _dev(F, keep, V)
+    _check_mesh("mesh_compact", V, F)
+    if keep.dtype != torch.int32 or keep.dim() != 1:
+        raise TypeError("mesh_compact wants keep (nF,) int32")
+    nV, nF = int(num_vertices), F.shape[0]
+    if keep.shape[0] != nF:
+        raise ValueError(f"mesh_compact: keep has {keep.shape[0]} entries for {nF} faces")
+    if nV < 0 or (V is not None and V.shape[0] != nV):
+        raise ValueError(f"mesh_compact: V has {None if V is None else V.shape[0]} rows for {nV} vertices")
+    F, keep = F.contiguous(), keep.contiguous()
+    dev = F.device
+    I = torch.empty(nV, dtype=torch.int32, device=dev)
+    J = torch.empty(nV, dtype=torch.int32, device=dev)
+    Fsrc = torch.empty(nF, dtype=torch.int32, device=dev)
+    Fnew = torch.empty(nF, 3, dtype=torch.int32, device=dev)
+    Vnew = None
+    if V is not None:
+        V = V.contiguous()
+        Vnew = torch.empty(nV, 3, dtype=torch.float32, device=dev)
+    sizes = torch.empty(2, dtype=torch.int32, device=dev)
+    ws_bytes = int(_lib.load().sn_mesh_compact_workspace_bytes(nV, nF))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    _lib.call("sn_mesh_compact_i32", _p(V), _p(F), _p(keep), nV, nF, _p(I), _p(J), _p(Fsrc), _p(Fnew), _p(Vnew), sizes.data_ptr(),
+              _p(ws), ws_bytes, _stream())
+    return MeshCompacted(I, J, Fsrc, Fnew, Vnew, sizes)
 
 
 def _check_graph(who: str, rowptr, colind, n: int) -> None:

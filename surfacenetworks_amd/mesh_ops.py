@@ -19,6 +19,8 @@ Also here: the synthetic mesh generators SURVEY.md §8(d) prescribes for the ben
 """
 from __future__ import annotations
 
+import collections
+
 import numpy as np
 import scipy.sparse as sp
 
@@ -28,6 +30,7 @@ __all__ = [
     "locality_order", "edge_span", "MeshOrder", "permute_operator",
     "mesh_glue", "intrinsic_delaunay", "intrinsic_laplacian", "intrinsic_laplacian_from_lengths", "delaunay_margin",
     "IDT_THRESHOLD",
+    "good_faces", "components", "compact", "largest_component", "Components", "Compacted", "CC_BAD_FACE", "CC_INTERNAL",
 ]
 
 _PERMS = np.array([[0, 1, 2], [0, 2, 1], [1, 0, 2], [1, 2, 0], [2, 0, 1], [2, 1, 0]])  # itertools.permutations order
@@ -328,6 +331,113 @@ def intrinsic_laplacian(V: np.ndarray, F: np.ndarray, order: str = "fifo", seed:
     interior edge is >= 0 (the maximum principle the extrinsic operator lacks).  Host loops: slow at FAUST size."""
     Fp, l, _ = intrinsic_delaunay(V, F, order, seed)
     return intrinsic_laplacian_from_lengths(Fp, l, np.asarray(V).shape[0])
+
+
+# --------------------------------------------------------------------------------------------------
+# mesh clean-up: components, the largest one, compaction (definition: include/sn_spmm.h, "Mesh clean-up").  The host statement
+# of igl.facet_components + scipy.stats.mode + igl.slice + igl.remove_unreferenced as the reference's
+# src/dense_correspondence/largest_component.py:28-47 chains them; what the device kernels are compared to, bit for bit.
+# --------------------------------------------------------------------------------------------------
+CC_BAD_FACE = 1              # SN_CC_BAD_FACE: a face has an index outside 0..nV-1 or a repeated index
+CC_INTERNAL = 2              # SN_CC_INTERNAL: a device loop bound was hit (never set here)
+
+Components = collections.namedtuple("Components", "vlabel flabel count summary status")
+Compacted = collections.namedtuple("Compacted", "I J Fsrc Fnew Vnew sizes")
+
+
+def good_faces(F: np.ndarray, num_vertices: int) -> np.ndarray:
+    """(nF,) bool: all three indices inside 0..nV-1 and pairwise different."""
+    F = np.asarray(F, dtype=np.int64).reshape(-1, 3)
+    inside = ((F >= 0) & (F < num_vertices)).all(axis=1)
+    return inside & (F[:, 0] != F[:, 1]) & (F[:, 1] != F[:, 2]) & (F[:, 2] != F[:, 0])
+
+
+def _class_minima(n: int, a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """label[x] = the smallest node of x's class under the equivalence generated by a[i] ~ b[i].  Rounds of: every pair whose
+    ends carry different labels lowers the larger label's own label to the smaller (minimum over the pairs), then labels are
+    chased to their fixed point.  Labels only decrease and never leave the class; a round without such a pair ends it."""
+    label = np.arange(n, dtype=np.int64)
+    while a.size:
+        la, lb = label[a], label[b]
+        live = la != lb
+        if not live.any():
+            break
+        a, b, la, lb = a[live], b[live], la[live], lb[live]
+        np.minimum.at(label, np.maximum(la, lb), np.minimum(la, lb))
+        while True:
+            nxt = label[label]
+            if np.array_equal(nxt, label):
+                break
+            label = nxt
+    return label
+
+
+def components(F: np.ndarray, num_vertices: int, mode: str = "edge") -> Components:
+    """Connected components of a triangle mesh: Components(vlabel, flabel, count, summary, status), int32 arrays and a Python
+    int.  mode "vertex": vertices are joined by the good faces that hold them, a label is the smallest vertex id of a class,
+    flabel[f] = vlabel[F[f, 0]], count has nV entries.  mode "edge" (igl.facet_components): good faces are joined across a
+    shared unordered vertex pair — any number of faces on an edge, any orientation; a shared vertex alone joins nothing — a
+    label is the smallest face id, count has nF entries, vlabel is None.  A bad face has flabel -1 and sets CC_BAD_FACE.
+    summary = (labels with a face, the winner: largest count, smallest label on a tie, its count), (0, -1, 0) without faces."""
+    if mode not in ("edge", "vertex"):
+        raise ValueError(f'components: mode must be "edge" or "vertex", got {mode!r}')
+    F = np.asarray(F, dtype=np.int64).reshape(-1, 3)
+    nV, nF = int(num_vertices), F.shape[0]
+    good = good_faces(F, nV)
+    Fg, fid = F[good], np.nonzero(good)[0]
+    flabel = np.full(nF, -1, dtype=np.int64)
+    vlabel = None
+    if mode == "vertex":
+        vlabel = _class_minima(nV, np.concatenate([Fg[:, 0], Fg[:, 1]]), np.concatenate([Fg[:, 1], Fg[:, 2]]))
+        flabel[fid] = vlabel[Fg[:, 0]]
+        n = nV
+    else:
+        a = np.concatenate([Fg[:, 0], Fg[:, 1], Fg[:, 2]])
+        b = np.concatenate([Fg[:, 1], Fg[:, 2], Fg[:, 0]])
+        key = np.minimum(a, b) * max(nV, 1) + np.maximum(a, b)
+        face = np.concatenate([fid, fid, fid])
+        order = np.argsort(key, kind="stable")
+        same = key[order][1:] == key[order][:-1]                  # neighbours in the sorted list on one edge: a chain per edge
+        flabel[fid] = _class_minima(nF, face[order][:-1][same], face[order][1:][same])[fid]
+        n = nF
+    count = np.bincount(flabel[fid], minlength=n).astype(np.int32)
+    if fid.size:
+        win = int(np.argmax(count))                               # the first maximum: the smallest label among the largest
+        summary = np.array([np.count_nonzero(count), win, count[win]], dtype=np.int32)
+    else:
+        summary = np.array([0, -1, 0], dtype=np.int32)
+    return Components(None if vlabel is None else vlabel.astype(np.int32), flabel.astype(np.int32), count, summary,
+                      0 if good.all() else CC_BAD_FACE)
+
+
+def compact(V, F: np.ndarray, keep, num_vertices: int = None) -> Compacted:
+    """igl.slice + igl.remove_unreferenced: keep the good faces with keep[f] != 0 and the vertices they use.
+    Compacted(I, J, Fsrc, Fnew, Vnew, sizes): I (nV,) old -> new vertex id, -1 for a dropped vertex; J (nV',) new -> old,
+    ascending; Fsrc (nF',) the original index of every kept face, ascending; Fnew = I[F[Fsrc]]; Vnew = V[J] (None without V);
+    sizes = (nV', nF').  num_vertices is needed only when V is None."""
+    F = np.asarray(F, dtype=np.int64).reshape(-1, 3)
+    nV = int(np.asarray(V).shape[0] if V is not None else num_vertices)
+    stay = good_faces(F, nV) & (np.asarray(keep).reshape(-1) != 0)
+    Fsrc = np.nonzero(stay)[0]
+    used = np.zeros(nV, dtype=bool)
+    used[F[Fsrc].ravel()] = True
+    J = np.nonzero(used)[0]
+    I = np.full(nV, -1, dtype=np.int64)
+    I[J] = np.arange(J.size)
+    return Compacted(I.astype(np.int32), J.astype(np.int32), Fsrc.astype(np.int32), I[F[Fsrc]].astype(np.int32).reshape(-1, 3),
+                     None if V is None else np.asarray(V)[J], np.array([J.size, Fsrc.size], dtype=np.int32))
+
+
+def largest_component(V, F: np.ndarray, connectivity: str = "edge"):
+    """(V', F', J, Fsrc): the component with the most faces (on a tie the one with the smallest label) with its vertices
+    renumbered in ascending order, J its vertices' and Fsrc its faces' original indices — largest_component.py:28-47.
+    ValueError when no good face exists."""
+    V = np.asarray(V)
+    cc = components(F, V.shape[0], connectivity)
+    if cc.summary[1] < 0:
+        raise ValueError("largest_component: the mesh has no face with three distinct vertices of the mesh")
+    out = compact(V, F, cc.flabel == cc.summary[1])
+    return out.Vnew, out.Fnew, out.J, out.Fsrc
 
 
 # --------------------------------------------------------------------------------------------------

@@ -15,6 +15,7 @@ What this replaces in the reference (paths relative to the reference checkout):
 """
 from __future__ import annotations
 
+import collections
 import os
 import weakref
 from typing import Optional, Sequence
@@ -25,7 +26,8 @@ import torch
 from . import kernels
 
 __all__ = ["SparseOperator", "OperatorPool", "PackedSegments", "as_operator", "dirac_operators_from_mesh",
-           "laplacian_operator_from_mesh", "geodesic_matrix_from_mesh", "spgemm", "amplify_sequence_operators"]
+           "laplacian_operator_from_mesh", "geodesic_matrix_from_mesh", "spgemm", "amplify_sequence_operators",
+           "clean_mesh", "CleanMesh"]
 
 # A BSR4 copy is kept when zero-fill costs at most this much extra storage over CSR entries.
 _BSR4_MAX_FILL = 1.6
@@ -514,6 +516,68 @@ def geodesic_matrix_from_mesh(V: torch.Tensor, F: torch.Tensor, symmetric: bool 
         raise ValueError("geodesic_matrix_from_mesh: the mesh is disconnected (some vertex pairs have no edge path); pass "
                          "require_connected=False to keep +inf between components")
     return G
+
+
+CleanMesh = collections.namedtuple("CleanMesh", "V F vertex_map vertex_index face_map components faces_dropped vertices_dropped "
+                                                 "bad_faces")
+
+
+def clean_mesh(V, F, component="largest", connectivity: str = "edge") -> CleanMesh:
+    """A raw scan made into a mesh the builders here accept, on the device: the faces of one connected component (or of all),
+    without the faces that carry an index outside the mesh or a repeated index, and with the vertices nothing uses any more
+    removed and the rest renumbered in ascending order.  Replaces the reference's off-line libigl script
+    src/dense_correspondence/largest_component.py (igl.facet_components, scipy.stats.mode, igl.slice,
+    igl.remove_unreferenced); kernels.mesh_components / mesh_label_mask / mesh_compact do the work, include/sn_spmm.h ("Mesh
+    clean-up") has the definition and mesh_ops.largest_component the host statement.
+    V: (nV, 3), F: (nF, 3), device tensors or numpy (then moved to the current device).  connectivity: "edge" (the reference's:
+    faces are joined across shared edges) or "vertex".  component: "largest" — the most faces, on a tie the smallest label (in
+    edge mode the component holding the lowest face index, as stats.mode picks it); "all" — every good face stays; or an integer
+    label of kernels.mesh_components (the smallest face id of the component in edge mode, vertex id in vertex mode).
+    Returns CleanMesh: V (nV', 3) fp32 and F (nF', 3) int32 on the device, rows of V copied bit for bit; vertex_map (nV',) new
+    -> old vertex id, ascending; vertex_index (nV,) old -> new, -1 for a dropped vertex; face_map (nF',) the original index of
+    every kept face, ascending; and as Python ints: components (how many were found), faces_dropped, vertices_dropped,
+    bad_faces.  Synchronises once.  ValueError when the mesh has no good face or the label names no component."""
+    if connectivity not in ("edge", "vertex"):
+        raise ValueError(f'clean_mesh: connectivity must be "edge" or "vertex", got {connectivity!r}')
+    if isinstance(component, str):
+        if component not in ("largest", "all"):
+            raise ValueError(f'clean_mesh: component must be "largest", "all" or an integer label, got {component!r}')
+    elif isinstance(component, bool) or not isinstance(component, (int, np.integer)):
+        raise TypeError(f'clean_mesh: component must be "largest", "all" or an integer label, got {component!r}')
+    if not torch.is_tensor(V):
+        V = torch.from_numpy(np.array(V, dtype=np.float32)).to("cuda")
+    if not torch.is_tensor(F):
+        F = torch.from_numpy(np.array(F)).to(V.device)
+    if V.dim() != 2 or V.shape[1] != 3 or F.dim() != 2 or F.shape[1] != 3:
+        raise ValueError(f"clean_mesh wants V (nV, 3) and F (nF, 3), got {tuple(V.shape)} and {tuple(F.shape)}")
+    if F.dtype not in (torch.int32, torch.int64) or not V.is_floating_point():
+        raise TypeError("clean_mesh wants floating-point V and int32 or int64 F")
+    kernels._dev(V, F)
+    Vf, Fi = V.float().contiguous(), F.to(torch.int32).contiguous()
+    nV, nF = Vf.shape[0], Fi.shape[0]
+    cc = kernels.mesh_components(Fi, nV, connectivity)
+    if isinstance(component, str) and component == "all":
+        keep = torch.ones(nF, dtype=torch.int32, device=Fi.device)
+        picked = cc.summary[2:3]
+    elif isinstance(component, str):
+        keep = kernels.mesh_label_mask(cc.flabel, cc.summary[1:2])       # the winner's label never leaves the device
+        picked = cc.summary[2:3]
+    else:
+        lab = int(component)
+        if not 0 <= lab < cc.count.shape[0]:
+            raise ValueError(f"clean_mesh: label {lab} names no component")
+        keep = kernels.mesh_label_mask(cc.flabel, torch.full((1,), lab, dtype=torch.int32, device=Fi.device))
+        picked = cc.count[lab:lab + 1]
+    out = kernels.mesh_compact(Fi, keep, nV, Vf)
+    bad = (cc.flabel < 0).sum(dtype=torch.int32).view(1)
+    nVk, nFk, ncomp, _, _, st, nbad, npicked = torch.cat([out.sizes, cc.summary, cc.status, bad, picked]).tolist()   # the one read
+    if st & kernels.CC_INTERNAL:
+        raise RuntimeError("clean_mesh: the component kernels hit a loop bound (status SN_CC_INTERNAL)")
+    if ncomp == 0:
+        raise ValueError("clean_mesh: the mesh has no face with three distinct vertices of the mesh")
+    if npicked == 0:
+        raise ValueError(f"clean_mesh: label {component!r} names no component")
+    return CleanMesh(out.Vnew[:nVk], out.Fnew[:nFk], out.J[:nVk], out.I, out.Fsrc[:nFk], ncomp, nF - nFk, nV - nVk, nbad)
 
 
 class PackedSegments:
