@@ -1098,7 +1098,17 @@ int sn_csr_scale_sym_f32(const int32_t *a_rowptr, const int32_t *a_colind, const
  * buffers are safe; tests/test_dense_gpu.py::test_linear_kernels_stay_inside_their_views).
  * elu_stats_part holds sn_linear_fwd_stats_blocks(rows) blocks — the largest grid any forward kernel uses; a kernel with a
  * smaller grid writes zeros into the blocks past its own, so the merge may always read all of them.
+ * The launchers pick a kernel form by operand size; two read-only queries say which, so that tests straddle the real
+ * thresholds instead of repeating them:
+ * sn_linear_small_rows : operands of at most this many rows take the one-pass weight prologue (every Linear entry point).
+ * sn_linear_fwd_form   : the form sn_linear_fwd_tiles_f32 launches for these arguments (has_*: the pointer is non-NULL) —
+ *                     0 the fp32-MFMA A/B baseline (SN_GEMM_VARIANT=0), 1 split, small operand, 2 split, large operand
+ *                     (two-pass weight prologue), 3 the eight-wave forward kernel.  Arguments the launcher would refuse
+ *                     are not checked here.
  * ------------------------------------------------------------------------------------------ */
+int64_t sn_linear_small_rows(void);
+int32_t sn_linear_fwd_form(int64_t rows, int32_t K, int32_t J, int32_t has_residual, int32_t has_y, int32_t has_elu,
+                           int32_t has_tile_sums);
 int sn_linear_fwd_f32(const float *x, int64_t ldx, const float *W, int64_t ldw, const float *bias,
                       const float *residual, int64_t ldr, float *y, int64_t ldy, float *y_elu, int64_t lde,
                       int64_t rows, int32_t K, int32_t J, double *elu_stats_part /* NULL | [stats_blocks][2][128] */,

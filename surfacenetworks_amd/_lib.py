@@ -167,6 +167,8 @@ SIGNATURES = {
     "sn_csr_scale_sym_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sn_linear_fwd_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
     "sn_linear_fwd_stats_blocks": (_i32, [_i64]),
+    "sn_linear_small_rows": (_i64, []),
+    "sn_linear_fwd_form": (_i32, [_i64, _i32, _i32, _i32, _i32, _i32, _i32]),
     "sn_linear_fwd_tiles_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
     "sn_linear_fwd_segbias_tiles_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32,
                                                   _vp, _vp, _vp]),

@@ -1083,11 +1083,12 @@ inline int gemm_variant() {
 
 #define SN_UNPAREN(...) __VA_ARGS__
 constexpr int64_t kSmallRows = 131072;      // operands up to this many rows take the one-pass weight prologue (gemm_rows_split_k<…, SMALL>)
+inline bool small_operand(int64_t rows) { return rows <= kSmallRows; }
 // launch gemm_rows_split_k<2, TARGS...> (SMALL form for operands of at most kSmallRows rows); with the timing facility on
 // (sn_timing_enable: t_start / t_stop of the enclosing entry point) the kernel's own start / stop go into two events
 #define SN_SPLIT_LAUNCH(TARGS, ...)                                                                                    \
   do {                                                                                                                 \
-    if (rows <= kSmallRows) {                                                                                          \
+    if (small_operand(rows)) {                                                                                         \
       if (t_start) hipExtLaunchKernelGGL((gemm_rows_split_k<2, SN_UNPAREN TARGS, true>), dim3(grid), dim3(kWG), 0, s, t_start, t_stop, 0, __VA_ARGS__); \
       else hipLaunchKernelGGL((gemm_rows_split_k<2, SN_UNPAREN TARGS, true>), dim3(grid), dim3(kWG), 0, s, __VA_ARGS__); \
     } else {                                                                                                           \
@@ -1098,7 +1099,7 @@ constexpr int64_t kSmallRows = 131072;      // operands up to this many rows tak
 // the raw-low-half form of the input gradient through the activation (gemm_rows_split_k<…, RAWLOW>), NT_ output tiles per wave
 #define SN_SPLIT_LAUNCH_RAW(NT_, ...)                                                                                  \
   do {                                                                                                                 \
-    if (rows <= kSmallRows) {                                                                                          \
+    if (small_operand(rows)) {                                                                                         \
       if (t_start) hipExtLaunchKernelGGL((gemm_rows_split_k<2, 128, NT_, true, EPI_DGRAD_ELU, true, false, true, 4, true>), dim3(grid), dim3(kWG), 0, s, t_start, t_stop, 0, __VA_ARGS__); \
       else hipLaunchKernelGGL((gemm_rows_split_k<2, 128, NT_, true, EPI_DGRAD_ELU, true, false, true, 4, true>), dim3(grid), dim3(kWG), 0, s, __VA_ARGS__); \
     } else {                                                                                                           \
@@ -1107,6 +1108,18 @@ constexpr int64_t kSmallRows = 131072;      // operands up to this many rows tak
     }                                                                                                                  \
   } while (0)
 #define SN_SPLIT_LAUNCH_NT2(K_, EPI_, SIDE_, ...) SN_SPLIT_LAUNCH((K_, 2, true, EPI_, SIDE_, false), __VA_ARGS__)
+
+// Which kernel form a forward launch of sn_linear_fwd_tiles_f32 takes — the launcher and sn_linear_fwd_form both ask here:
+// 0 the fp32-MFMA A/B baseline, 1 gemm_rows_split_k<…, SMALL>, 2 gemm_rows_split_k with the two-pass weight prologue,
+// 3 gemm_fwd_w8_k (eight waves of 16 columns: large operands, the K = 256 launches that write only the activated copy — the
+// one shape it wins: one output stream — a wave's rows are 64-byte segments, and with a residual and two outputs the three
+// half-line streams cost more than the second wave per SIMD gains; LABNOTES r4w8)
+enum { FWD_FORM_BASELINE = 0, FWD_FORM_SMALL = 1, FWD_FORM_LARGE = 2, FWD_FORM_W8 = 3 };
+inline int linear_fwd_form(int64_t rows, int K, int J, bool residual, bool y, bool y_elu, bool tile_sums) {
+  if (gemm_variant() == 0) return FWD_FORM_BASELINE;
+  if (J == 128 && !small_operand(rows) && !tile_sums && K == 256 && !residual && y_elu && !y) return FWD_FORM_W8;
+  return small_operand(rows) ? FWD_FORM_SMALL : FWD_FORM_LARGE;
+}
 
 // Workgroups per CU.  One 4-wave workgroup per CU is a single wave per SIMD that owns the register file; the K = 128, one-tile
 // kernels of the fp16 form need <= 256 registers and run TWO per CU (2 waves per SIMD): -14 % on the plain forward, -10 % on
@@ -1130,6 +1143,13 @@ int32_t sn_gemm_variant(void) { return gemm_variant(); }
 
 // (the largest grid any forward kernel uses: a kernel with a smaller one zeroes the blocks past its own)
 int32_t sn_linear_fwd_stats_blocks(int64_t rows) { return rows > 0 ? (int32_t)gemm_grid(rows, 2) : 0; }
+
+int64_t sn_linear_small_rows(void) { return kSmallRows; }
+
+int32_t sn_linear_fwd_form(int64_t rows, int32_t K, int32_t J, int32_t has_residual, int32_t has_y, int32_t has_elu,
+                           int32_t has_tile_sums) {
+  return linear_fwd_form(rows, K, J, has_residual != 0, has_y != 0, has_elu != 0, has_tile_sums != 0);
+}
 
 int sn_linear_fwd_f32(const float *x, int64_t ldx, const float *W, int64_t ldw, const float *bias,
                       const float *residual, int64_t ldr, float *y, int64_t ldy, float *y_elu, int64_t lde,
@@ -1166,10 +1186,8 @@ int sn_linear_fwd_tiles_f32(const float *x, int64_t ldx, const float *W, int64_t
     if (t_start) hipExtLaunchKernelGGL((gemm_fwd_w8_k<KK, RES, EL>), dim3(grid8), dim3(512), 0, s, t_start, t_stop, 0, x, ldx, W, ldw, y, ldy, rows, ep); \
     else hipLaunchKernelGGL((gemm_fwd_w8_k<KK, RES, EL>), dim3(grid8), dim3(512), 0, s, x, ldx, W, ldw, y, ldy, rows, ep); \
   } while (0)
-  // eight waves of 16 columns (gemm_fwd_w8_k), large operands: the K = 256 launches that write only the activated copy (the one
-  // shape it wins: one output stream — a wave's rows are 64-byte segments, and with a residual and two outputs the three
-  // half-line streams cost more than the second wave per SIMD gains; LABNOTES r4w8)
-  if (gemm_variant() == 2 && J == 128 && rows > kSmallRows && !tile_sums && K == 256 && !residual && y_elu && !y) {
+  // (eight waves of 16 columns where linear_fwd_form says so; the split launches below pick SMALL / large by the same predicate)
+  if (linear_fwd_form(rows, K, J, residual != nullptr, y != nullptr, y_elu != nullptr, tile_sums != nullptr) == FWD_FORM_W8) {
     const unsigned grid8 = gemm_grid(rows, 1);
     SN_W8_FWD(256, false, true);
     return launch_status();

@@ -1276,6 +1276,19 @@ def new_tile_sums(rows: int, device):
     return torch.empty(((rows + 31) // 32, 128), dtype=torch.float32, device=device)
 
 
+def linear_small_rows() -> int:
+    """Operands of at most this many rows take the Linear kernels' one-pass weight prologue (sn_linear_small_rows)."""
+    return int(_lib.load().sn_linear_small_rows())
+
+
+def linear_fwd_form(rows: int, K: int, J: int, residual: bool = False, want_y: bool = True, y_elu: bool = False,
+                    tile_sums: bool = False) -> int:
+    """The kernel form linear_fwd launches for these arguments (sn_linear_fwd_form): 0 the fp32-MFMA A/B baseline, 1 split with
+    the one-pass weight prologue (small operand), 2 split with the two-pass prologue (large operand), 3 the eight-wave kernel."""
+    return int(_lib.load().sn_linear_fwd_form(rows, K, J, int(bool(residual)), int(bool(want_y)), int(bool(y_elu)),
+                                              int(bool(tile_sums))))
+
+
 def linear_fwd(x, W, bias, residual=None, y_elu=None, want_y: bool = True, elu_stats=None, tile_sums=None):
     """y = x·Wᵀ + bias (+ residual); optionally also writes elu(y) into the 2-D view `y_elu` (sn_linear_fwd_f32).
     want_y=False (with y_elu): only the activated copy is written and None is returned.

@@ -54,6 +54,29 @@ def random_csr(M, K, density, seed, empty_rows=()):
     return A
 
 
+# ---- the Linear kernels address their operands through raw buffer windows (sn_gemm.hip RowWindow, wgrad_u_k): tests place
+# every operand as a strided view inside an arena of NaNs, every output as a view inside an arena of canaries ---------------
+def _arena(rows, width, pad_rows=3, pad_cols=8, seed=0, fill=float("nan"), device="cuda", values=None):
+    """(arena, view): `view` = rows x width of random values (or of `values`, a rows x width tensor) inside a poisoned arena
+    (rows before / after, columns on both sides; the view's leading dimension is width + 2·pad_cols, 16-byte aligned)."""
+    import torch
+
+    a = torch.full((rows + 2 * pad_rows, width + 2 * pad_cols), fill, device=device)
+    v = a[pad_rows:pad_rows + rows, pad_cols:pad_cols + width]
+    if values is None:
+        values = torch.from_numpy(np.random.default_rng(seed).standard_normal((rows, width)).astype(np.float32))
+    v.copy_(values)
+    return a, v
+
+
+def _outside_untouched(arena, view_rows, width, canary, pad_rows=3, pad_cols=8):
+    import torch
+
+    m = torch.ones_like(arena, dtype=torch.bool)
+    m[pad_rows:pad_rows + view_rows, pad_cols:pad_cols + width] = False
+    return bool((arena[m] == canary).all())
+
+
 # ---- deterministic, library-independent parameter fill (golden fixtures store no weights) ------------------
 def _splitmix_uniform(n, seed):
     """n doubles in [0,1) from splitmix64 on (index, seed): exact integer arithmetic, identical everywhere."""

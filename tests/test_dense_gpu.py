@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import rel_err
+from helpers import _arena, _outside_untouched, rel_err
 from oracle import c_oracle
 
 pytestmark = pytest.mark.gpu
@@ -611,22 +611,7 @@ def test_split_fp16_row_and_column_scaling_covers_the_fp32_range():
 
 
 # ---- the Linear kernels address their operands through raw buffer windows (sn_gemm.hip RowWindow, wgrad_u_k): every
-# operand below is a strided view inside an arena of NaNs, every output a view inside an arena of canaries ---------------
-def _arena(rows, width, pad_rows=3, pad_cols=8, seed=0, fill=float("nan")):
-    """(arena, view): `view` = rows x width of random values inside a poisoned arena (rows before / after, columns on both
-    sides; the view's leading dimension is width + 2·pad_cols, 16-byte aligned)."""
-    a = torch.full((rows + 2 * pad_rows, width + 2 * pad_cols), fill, device=DEV)
-    v = a[pad_rows:pad_rows + rows, pad_cols:pad_cols + width]
-    v.copy_(torch.from_numpy(np.random.default_rng(seed).standard_normal((rows, width)).astype(np.float32)))
-    return a, v
-
-
-def _outside_untouched(arena, view_rows, width, canary, pad_rows=3, pad_cols=8):
-    m = torch.ones_like(arena, dtype=torch.bool)
-    m[pad_rows:pad_rows + view_rows, pad_cols:pad_cols + width] = False
-    return bool((arena[m] == canary).all())
-
-
+# operand below is a strided view inside an arena of NaNs, every output a view inside an arena of canaries (helpers._arena) ----
 @pytest.mark.parametrize("rows", [1, 31, 32, 33, 95, 1017, 8200])
 @pytest.mark.parametrize("K,J", [(128, 128), (256, 128), (128, 120), (256, 4), (128, 64)])
 def test_linear_kernels_stay_inside_their_views(rows, K, J):
