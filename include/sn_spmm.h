@@ -1007,6 +1007,73 @@ int sn_mesh_compact_i32(const float *V, const int32_t *F, const int32_t *keep, i
                         void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Mesh descriptors: per-vertex normals, mass, Gaussian and mean curvature, and the libigl-convention Laplacian M^-1 C.
+ *
+ * Replaces: compute_normals, area, laplacian_and_mass, compute_laplacian, gaussian_curvature, hacky_compute_laplacian
+ *           src/utils/geom_utils.py (all through pyigl), feeding src/normal_predict/sampler.py:21-91.
+ * These are this project's own definitions in libigl's conventions, not its bits.  Host statement: mesh_ops.vertex_descriptors,
+ * mesh_ops.libigl_laplacian.
+ *
+ * Arithmetic.  P = the fp32 coordinates widened to fp64.  Every product and sum is rounded on its own (no fused multiply-add);
+ *   a three-term sum is (x + y) + z;  u x w = (u_y w_z - u_z w_y, u_z w_x - u_x w_z, u_x w_y - u_y w_x);  u.w = (u_x w_x +
+ *   u_y w_y) + u_z w_z.  A sum "over the faces of a vertex" runs over its incident faces that are neither bad nor flat, in
+ *   ascending face index, from +0.0.  Outputs are rounded to fp32 at the end.
+ * Face f = (i, j, k).  BAD: an index outside 0..nV-1 or two equal indices; contributes nothing, SN_DESC_BAD_FACE, face outputs 0.
+ *   n_f = (P_j - P_i) x (P_k - P_i), dbl_f = sqrt(n_f.n_f), a_f = dbl_f / 2.  FLAT: !(dbl_f > 0) (zero or NaN); contributes
+ *   nothing to any vertex sum nor to the Laplacian's pattern, SN_DESC_FLAT_FACE, face outputs a_f = 0, nhat_f = 0.  Otherwise
+ *   nhat_f = n_f / dbl_f componentwise.  All three corners use the same n_f, dbl_f (from the first vertex).
+ * Corner (v; a, b), a and b the other two vertices in face order (the corner table of sn_mesh_corners_f32):
+ *   u = P_a - P_v, w = P_b - P_v, d_v = u.w, theta_v = atan2(dbl_f, d_v), cot_v = d_v / dbl_f.
+ *   The face is OBTUSE when d_i < 0 or d_j < 0 or d_k < 0.
+ * Vertex v:
+ *   N_area = sum n_f;  N_uniform = sum nhat_f;  N_angle = sum theta_v nhat_f (the scalar times each component).  Each is then
+ *     divided componentwise by sqrt(N.N); a length that is not > 0 gives (0, 0, 0) and SN_DESC_NO_NORMAL (an isolated vertex;
+ *     raised for the normals that were asked for).
+ *   M_bary = sum a_f / 3.
+ *   M_voronoi = sum of one term per corner (Meyer's mixed cells, libigl's MASSMATRIX_TYPE_VORONOI): obtuse face and d_v < 0:
+ *     a_f / 2;  obtuse face otherwise: a_f / 4;  else ((u.u) cot_b + (w.w) cot_a) / 8.
+ *   K = 2 pi - sum theta_v, the raw angle defect (at boundary vertices too, as igl.gaussian_curvature), 2 pi the fp64 constant.
+ *   dP = sum ((0.5 cot_b) u + (0.5 cot_a) w), componentwise: the cotangent Laplacian applied to the positions (the edge v-a lies
+ *     opposite b).
+ *   H = s sqrt(dP.dP) / (2 M_voronoi), s = -1 when dP.N_area > 0 (N_area before its division) and +1 otherwise; H = 0 when
+ *     M_voronoi is not > 0.  A sphere of radius r with outward faces has H = +1/r.
+ * Only + - * / sqrt and one atan2 per corner: everything but K and N_angle equals the host statement bit for bit.
+ *
+ * sn_mesh_descriptors_f32 : face_area[nF], face_normal[nF][3], n_area / n_uniform / n_angle [nV][3], mass_bary / mass_voronoi /
+ *     gauss (K) / mean (H) [nV].  Any output pointer may be NULL and is then not computed.  *status is cleared, then OR-ed.
+ *     No limit on the number of faces at a vertex: one thread per vertex streams over its incidence list (codes 3 f + c of the
+ *     good faces, counted, scanned, filled with an atomic cursor and sorted, so the order of the sums is fixed: two runs are
+ *     bit-identical).  workspace: sn_mesh_descriptors_workspace_bytes(nV, nF), else SN_E_WORKSPACE.  Negative nV or nF:
+ *     SN_E_SHAPE.  nV + 1 or 3 nF past int32: SN_E_RANGE.  Does not synchronise.
+ *
+ * sn_mesh_cot_laplacian_f32 : L = M^-1 C in CSR, libigl's igl.cotmatrix scaled by the inverse mass matrix.
+ *     C_vj = the sum of 0.5 cot at the corner opposite the edge v-j, over the faces of v that contain j, ascending face order.
+ *     Stored entry (v, j) = C_vj / M_v; diagonal = (0 - sum_j C_vj) / M_v, j ascending; M = M_bary (SN_DESC_MASS_BARYCENTRIC) or
+ *     M_voronoi (SN_DESC_MASS_VORONOI) in fp64, before any rounding.  Pattern: every distinct neighbour plus the diagonal, columns
+ *     ascending; an exactly zero C_vj is KEPT (sn_laplacian_csr_from_mesh drops it).  A vertex without mass has a NaN diagonal.
+ *     clamp != 0: an entry whose fp32 value is not finite or exceeds 1e10 in magnitude becomes (float) hack and SN_DESC_CLAMPED
+ *     is set (geom_utils.py:209-211).  -2 L(barycentric) is sn_laplacian_csr_from_mesh's A^-1 (D - W) without its two epsilons.
+ *     Two phases as sn_laplacian_csr_from_mesh (phase 0: rowptr and *status, cleared first; the caller reads rowptr[nV] and the
+ *     status, allocates, calls phase 1 with the same workspace, which ORs SN_DESC_CLAMPED into *status).  A vertex with more
+ *     than SN_LAP_MAX_DEGREE incident good faces sets SN_DESC_DEGREE in phase 0: the caller launches nothing further.
+ * ------------------------------------------------------------------------------------------ */
+#define SN_DESC_BAD_FACE   1
+#define SN_DESC_FLAT_FACE  2
+#define SN_DESC_NO_NORMAL  4
+#define SN_DESC_CLAMPED    8
+#define SN_DESC_DEGREE     16
+#define SN_DESC_MASS_BARYCENTRIC 0
+#define SN_DESC_MASS_VORONOI     1
+size_t sn_mesh_descriptors_workspace_bytes(int64_t nV, int64_t nF);
+int sn_mesh_descriptors_f32(const float *V, const int32_t *F, int64_t nV, int64_t nF, float *face_area, float *face_normal,
+                            float *n_area, float *n_uniform, float *n_angle, float *mass_bary, float *mass_voronoi,
+                            float *gauss, float *mean, int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+size_t sn_mesh_cot_laplacian_workspace_bytes(int64_t nV, int64_t nF);
+int sn_mesh_cot_laplacian_f32(const float *V, const int32_t *F, int64_t nV, int64_t nF, int32_t phase, int32_t mass, int32_t clamp,
+                              double hack, int32_t *rowptr, int32_t *colind, float *vals, int32_t *status, void *workspace,
+                              size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Sparse x sparse CSR products and the symmetric diagonal scaling: the operators of the 'amp' tower.
  *
  * Replaces: L = Dsq.dot(L).dot(Dsq); twice L = Dsq.dot(L).dot(Dsq), L = L.dot(L)     src/dense_correspondence/main.py:72-83

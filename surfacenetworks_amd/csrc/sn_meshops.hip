@@ -1106,6 +1106,236 @@ inline void scan_in_place(int *a, int64_t n, int *sums, hipStream_t s) {
   hipLaunchKernelGGL(scan_apply_k, dim3(nblk), dim3(kWG), 0, s, a, n, sums, a);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Per-vertex normals, mass and curvature, and the libigl-convention Laplacian (definition: sn_spmm.h, "Mesh descriptors").
+// Every per-face quantity is a function of the face alone, so a corner recomputes it from the three positions it has loaded
+// anyway instead of reading a 64-byte record another pass wrote: same bits, one gather less (LABNOTES.md#descriptors).
+// ------------------------------------------------------------------------------------------------
+struct FaceGeom {      // n_f and dbl_f from the first vertex, and the dot products d at the corners i, j, k
+  double nx, ny, nz, dbl, d0, d1, d2;
+};
+
+__device__ __forceinline__ double dot3(double ax, double ay, double az, double bx, double by, double bz) {
+  return (ax * bx + ay * by) + az * bz;
+}
+__device__ __forceinline__ double pick3(double x0, double x1, double x2, int c) { return c == 0 ? x0 : c == 1 ? x1 : x2; }
+__device__ __forceinline__ int pick3i(int x0, int x1, int x2, int c) { return c == 0 ? x0 : c == 1 ? x1 : x2; }
+
+// of a face that passed face_ok
+__device__ __forceinline__ FaceGeom face_geom(const float *__restrict__ V, int i, int j, int k) {
+  const double ix = V[3 * i], iy = V[3 * i + 1], iz = V[3 * i + 2];
+  const double jx = V[3 * j], jy = V[3 * j + 1], jz = V[3 * j + 2];
+  const double kx = V[3 * k], ky = V[3 * k + 1], kz = V[3 * k + 2];
+  const double ax = jx - ix, ay = jy - iy, az = jz - iz;       // P_j - P_i
+  const double bx = kx - ix, by = ky - iy, bz = kz - iz;       // P_k - P_i
+  FaceGeom g;
+  g.nx = ay * bz - az * by;
+  g.ny = az * bx - ax * bz;
+  g.nz = ax * by - ay * bx;
+  g.dbl = sqrt(dot3(g.nx, g.ny, g.nz, g.nx, g.ny, g.nz));
+  g.d0 = dot3(ax, ay, az, bx, by, bz);                                                  // (i; j, k)
+  g.d1 = dot3(kx - jx, ky - jy, kz - jz, ix - jx, iy - jy, iz - jz);                    // (j; k, i)
+  g.d2 = dot3(ix - kx, iy - ky, iz - kz, jx - kx, jy - ky, jz - kz);                    // (k; i, j)
+  return g;
+}
+
+// the corner (v; a, b) = corner c of a face that is neither bad nor flat
+struct CornerTerms {
+  double ux, uy, uz, wx, wy, wz;      // u = P_a - P_v, w = P_b - P_v
+  double dv, cota, cotb, af, vor;     // vor: the corner's term of M_voronoi
+};
+__device__ __forceinline__ CornerTerms corner_terms(const float *__restrict__ V, int v, int a, int b, const FaceGeom &g, int c) {
+  const double px = V[3 * v], py = V[3 * v + 1], pz = V[3 * v + 2];
+  CornerTerms t;
+  t.ux = (double)V[3 * a] - px; t.uy = (double)V[3 * a + 1] - py; t.uz = (double)V[3 * a + 2] - pz;
+  t.wx = (double)V[3 * b] - px; t.wy = (double)V[3 * b + 1] - py; t.wz = (double)V[3 * b + 2] - pz;
+  t.dv = pick3(g.d0, g.d1, g.d2, c);
+  t.cota = pick3(g.d1, g.d2, g.d0, c) / g.dbl;
+  t.cotb = pick3(g.d2, g.d0, g.d1, c) / g.dbl;
+  t.af = g.dbl / 2;
+  if (g.d0 < 0 || g.d1 < 0 || g.d2 < 0) {
+    t.vor = t.dv < 0 ? t.af / 2 : t.af / 4;
+  } else {
+    const double uu = dot3(t.ux, t.uy, t.uz, t.ux, t.uy, t.uz), ww = dot3(t.wx, t.wy, t.wz, t.wx, t.wy, t.wz);
+    t.vor = (uu * t.cotb + ww * t.cota) / 8;
+  }
+  return t;
+}
+
+// counts the corners of the good faces per vertex, raises the bad / flat bits, writes the face outputs that are wanted
+__global__ __launch_bounds__(kWG) void desc_face_k(const float *__restrict__ V, const int *__restrict__ F, int64_t nF, int64_t nV,
+                                                   int *__restrict__ count, float *__restrict__ face_area,
+                                                   float *__restrict__ face_normal, int *__restrict__ status) {
+  for (int64_t f = (int64_t)blockIdx.x * kWG + threadIdx.x; f < nF; f += (int64_t)gridDim.x * kWG) {
+    const int i = F[3 * f], j = F[3 * f + 1], k = F[3 * f + 2];
+    float a = 0.f, x = 0.f, y = 0.f, z = 0.f;
+    if (!face_ok(i, j, k, nV)) {
+      atomicOr(status, SN_DESC_BAD_FACE);
+    } else {
+      atomicAdd(&count[i], 1);
+      atomicAdd(&count[j], 1);
+      atomicAdd(&count[k], 1);
+      const FaceGeom g = face_geom(V, i, j, k);
+      if (!(g.dbl > 0)) {
+        atomicOr(status, SN_DESC_FLAT_FACE);
+      } else {
+        a = (float)(g.dbl / 2);
+        x = (float)(g.nx / g.dbl); y = (float)(g.ny / g.dbl); z = (float)(g.nz / g.dbl);
+      }
+    }
+    if (face_area) face_area[f] = a;
+    if (face_normal) { face_normal[3 * f] = x; face_normal[3 * f + 1] = y; face_normal[3 * f + 2] = z; }
+  }
+}
+
+// N / |N| componentwise, or zero and the flag
+__device__ __forceinline__ void desc_put_normal(float *__restrict__ out, int64_t v, double x, double y, double z, int *flags) {
+  const double len = sqrt(dot3(x, y, z, x, y, z));
+  const bool ok = len > 0;
+  if (!ok) *flags |= SN_DESC_NO_NORMAL;
+  out[3 * v] = ok ? (float)(x / len) : 0.f;
+  out[3 * v + 1] = ok ? (float)(y / len) : 0.f;
+  out[3 * v + 2] = ok ? (float)(z / len) : 0.f;
+}
+
+// one thread per vertex streams over its sorted incidence list (codes 3 f + c, ascending): no bound on the list's length
+__global__ __launch_bounds__(kWG) void desc_vertex_k(const float *__restrict__ V, const int *__restrict__ F, int64_t nV,
+                                                     const int *__restrict__ vptr, const int *__restrict__ inc,
+                                                     float *__restrict__ n_area, float *__restrict__ n_uniform,
+                                                     float *__restrict__ n_angle, float *__restrict__ mass_bary,
+                                                     float *__restrict__ mass_voronoi, float *__restrict__ gauss,
+                                                     float *__restrict__ mean, int *__restrict__ status) {
+  const bool want_angle = n_angle != nullptr || gauss != nullptr;
+  for (int64_t v = (int64_t)blockIdx.x * kWG + threadIdx.x; v < nV; v += (int64_t)gridDim.x * kWG) {
+    double nax = 0, nay = 0, naz = 0, nux = 0, nuy = 0, nuz = 0, ngx = 0, ngy = 0, ngz = 0;
+    double px = 0, py = 0, pz = 0, mb = 0, mv = 0, th = 0;
+    for (int o = vptr[v]; o < vptr[v + 1]; ++o) {
+      const int64_t f = inc[o] / 3;
+      const int c = inc[o] % 3;
+      const int idx[3] = {F[3 * f], F[3 * f + 1], F[3 * f + 2]};
+      const FaceGeom g = face_geom(V, idx[0], idx[1], idx[2]);
+      if (!(g.dbl > 0)) continue;
+      const CornerTerms t = corner_terms(V, (int)v, pick3i(idx[1], idx[2], idx[0], c), pick3i(idx[2], idx[0], idx[1], c), g, c);
+      const double hx = g.nx / g.dbl, hy = g.ny / g.dbl, hz = g.nz / g.dbl;
+      nax += g.nx; nay += g.ny; naz += g.nz;
+      nux += hx; nuy += hy; nuz += hz;
+      if (want_angle) {
+        const double a = atan2(g.dbl, t.dv);
+        th += a;
+        ngx += a * hx; ngy += a * hy; ngz += a * hz;
+      }
+      mb += t.af / 3;
+      mv += t.vor;
+      const double ha = 0.5 * t.cota, hb = 0.5 * t.cotb;
+      px += hb * t.ux + ha * t.wx;
+      py += hb * t.uy + ha * t.wy;
+      pz += hb * t.uz + ha * t.wz;
+    }
+    int flags = 0;
+    if (n_area) desc_put_normal(n_area, v, nax, nay, naz, &flags);
+    if (n_uniform) desc_put_normal(n_uniform, v, nux, nuy, nuz, &flags);
+    if (n_angle) desc_put_normal(n_angle, v, ngx, ngy, ngz, &flags);
+    if (mass_bary) mass_bary[v] = (float)mb;
+    if (mass_voronoi) mass_voronoi[v] = (float)mv;
+    if (gauss) gauss[v] = (float)(2 * 3.141592653589793 - th);
+    if (mean) {
+      const double len = sqrt(dot3(px, py, pz, px, py, pz));
+      const double s = dot3(px, py, pz, nax, nay, naz) > 0 ? -1.0 : 1.0;
+      mean[v] = mv > 0 ? (float)((s * len) / (2 * mv)) : 0.f;
+    }
+    if (flags) atomicOr(status, flags);
+  }
+}
+
+// an entry of the libigl-convention Laplacian rounded to fp32, with the reference's clamp when one is given
+__device__ __forceinline__ float cot_entry(double x, int clamp, float hack, int *flags) {
+  float v = (float)x;
+  if (clamp && !(fabsf(v) <= 1e10f)) {      // not finite, or past 1e10 either way
+    v = hack;
+    *flags |= SN_DESC_CLAMPED;
+  }
+  return v;
+}
+
+// L = M^-1 C by rows, the frame of laplacian_rows_k: neighbour lists in registers, hence its degree limit
+template <bool FILL>
+__global__ __launch_bounds__(kWG) void cot_laplacian_rows_k(const float *__restrict__ V, const int *__restrict__ F, int64_t nV,
+                                                            const int *__restrict__ vptr, const int *__restrict__ inc, int voronoi,
+                                                            int clamp, float hack, int *__restrict__ rowptr,
+                                                            int *__restrict__ colind, float *__restrict__ vals,
+                                                            int *__restrict__ status) {
+  for (int64_t i = (int64_t)blockIdx.x * kWG + threadIdx.x; i < nV; i += (int64_t)gridDim.x * kWG) {
+    const int b = vptr[i], e = vptr[i + 1];
+    if (e - b > kMaxDeg) {
+      atomicOr(status, SN_DESC_DEGREE);
+      if constexpr (!FILL) rowptr[i] = 1;
+      continue;
+    }
+    int nb[2 * kMaxDeg];          // neighbour ids (with duplicates), in face order
+    double cw[2 * kMaxDeg];       // contribution to C[i, nb]
+    int n = 0;
+    double M = 0;
+    for (int o = b; o < e; ++o) {
+      const int64_t f = inc[o] / 3;
+      const int c = inc[o] % 3;
+      const int idx[3] = {F[3 * f], F[3 * f + 1], F[3 * f + 2]};
+      const FaceGeom g = face_geom(V, idx[0], idx[1], idx[2]);
+      if (!(g.dbl > 0)) continue;
+      const int va = pick3i(idx[1], idx[2], idx[0], c), vb = pick3i(idx[2], idx[0], idx[1], c);
+      const CornerTerms t = corner_terms(V, (int)i, va, vb, g, c);
+      nb[n] = va; cw[n] = 0.5 * t.cotb; ++n;             // the edge i-a lies opposite b
+      nb[n] = vb; cw[n] = 0.5 * t.cota; ++n;
+      M += voronoi ? t.vor : t.af / 3;
+    }
+    for (int x = 1; x < n; ++x) {                        // stable insertion sort by neighbour id
+      const int kn = nb[x];
+      const double u = cw[x];
+      int y = x - 1;
+      while (y >= 0 && nb[y] > kn) {
+        nb[y + 1] = nb[y]; cw[y + 1] = cw[y];
+        --y;
+      }
+      nb[y + 1] = kn; cw[y + 1] = u;
+    }
+    if constexpr (!FILL) {
+      int cnt = 0;
+      for (int x = 0; x < n; ++x) cnt += (x == 0 || nb[x] != nb[x - 1]);
+      rowptr[i] = cnt + 1;
+    } else {
+      double S = 0;
+      int out = rowptr[i], dpos = -1, flags = 0;
+      for (int x = 0; x < n;) {
+        const int kn = nb[x];
+        double C = 0;
+        while (x < n && nb[x] == kn) C += cw[x++];
+        S += C;
+        if (dpos < 0 && kn > i) dpos = out++;            // the diagonal slot, filled below
+        colind[out] = kn;
+        vals[out] = cot_entry(C / M, clamp, hack, &flags);
+        ++out;
+      }
+      if (dpos < 0) dpos = out;
+      colind[dpos] = (int)i;
+      vals[dpos] = cot_entry((0 - S) / M, clamp, hack, &flags);
+      if (flags) atomicOr(status, flags);
+    }
+  }
+}
+
+inline size_t incidence_bytes(int64_t nV, int64_t nF) {
+  return align16((size_t)(nV + 1) * sizeof(int)) * 2 + align16((size_t)3 * nF * sizeof(int)) + scan_bytes(nV + 1);
+}
+
+// vptr / inc of the good faces (codes 3 f + c, ascending per vertex) after desc_face_k has counted into a zeroed vptr
+inline int incidence_build(const int *F, int64_t nV, int64_t nF, int *vptr, int *cursor, int *inc, int *sums, hipStream_t s) {
+  scan_in_place(vptr, nV + 1, sums, s);
+  const hipError_t e = sn_internal_copy2d(cursor, 0, vptr, 0, (int64_t)((size_t)(nV + 1) * sizeof(int)), 1, s);
+  if (e != hipSuccess) return (int)e;
+  if (nF > 0) hipLaunchKernelGGL(side_fill_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, nV, cursor, inc);
+  if (nV > 0) hipLaunchKernelGGL(vertex_sort_k, dim3(grid_for(nV)), dim3(kWG), 0, s, vptr, nV, inc);
+  return SN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1525,6 +1755,82 @@ int sn_mesh_compact_i32(const float *V, const int32_t *F, const int32_t *keep, i
   scan_in_place(vpos, nV + 1, sums, s);
   hipLaunchKernelGGL(compact_vertices_k, dim3(grid_for(nV + 1)), dim3(kWG), 0, s, V, nV, vpos, I, J, Vnew, fpos, nF, sizes);
   if (nF > 0) hipLaunchKernelGGL(compact_faces_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, fpos, vpos, Fsrc, Fnew);
+  return launch_status();
+}
+
+size_t sn_mesh_descriptors_workspace_bytes(int64_t nV, int64_t nF) {
+  return incidence_bytes(nV < 0 ? 0 : nV, nF < 0 ? 0 : nF);
+}
+
+int sn_mesh_descriptors_f32(const float *V, const int32_t *F, int64_t nV, int64_t nF, float *face_area, float *face_normal,
+                            float *n_area, float *n_uniform, float *n_angle, float *mass_bary, float *mass_voronoi,
+                            float *gauss, float *mean, int32_t *status, void *workspace, size_t workspace_bytes, void *stream) {
+  (void)hipGetLastError();
+  if (nV < 0 || nF < 0) return SN_E_SHAPE;
+  if (nV + 1 > INT_MAX || 3 * nF > INT_MAX) return SN_E_RANGE;
+  if (!status) return SN_E_NULL;
+  const bool per_vertex = n_area || n_uniform || n_angle || mass_bary || mass_voronoi || gauss || mean;
+  if ((nF > 0 && (!V || !F)) || (nV > 0 && per_vertex && !V)) return SN_E_NULL;
+  if (workspace_bytes < sn_mesh_descriptors_workspace_bytes(nV, nF) || !workspace) return SN_E_WORKSPACE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  char *w = static_cast<char *>(workspace);
+  int *vptr = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
+  int *cursor = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
+  int *inc = reinterpret_cast<int *>(w); w += align16((size_t)3 * nF * sizeof(int));
+  int *sums = reinterpret_cast<int *>(w);
+  hipError_t e = sn_internal_fill(vptr, 0, (size_t)(nV + 1) * sizeof(int), s);
+  if (e != hipSuccess) return (int)e;
+  e = sn_internal_fill(status, 0, sizeof(int), s);
+  if (e != hipSuccess) return (int)e;
+  if (nF > 0) hipLaunchKernelGGL(desc_face_k, dim3(grid_for(nF)), dim3(kWG), 0, s, V, F, nF, nV, vptr, face_area, face_normal, status);
+  if (per_vertex && nV > 0) {
+    const int st = incidence_build(F, nV, nF, vptr, cursor, inc, sums, s);
+    if (st != SN_OK) return st;
+    hipLaunchKernelGGL(desc_vertex_k, dim3(grid_for(nV)), dim3(kWG), 0, s, V, F, nV, vptr, inc, n_area, n_uniform, n_angle, mass_bary,
+                       mass_voronoi, gauss, mean, status);
+  }
+  return launch_status();
+}
+
+size_t sn_mesh_cot_laplacian_workspace_bytes(int64_t nV, int64_t nF) { return sn_mesh_descriptors_workspace_bytes(nV, nF); }
+
+int sn_mesh_cot_laplacian_f32(const float *V, const int32_t *F, int64_t nV, int64_t nF, int32_t phase, int32_t mass, int32_t clamp,
+                              double hack, int32_t *rowptr, int32_t *colind, float *vals, int32_t *status, void *workspace,
+                              size_t workspace_bytes, void *stream) {
+  (void)hipGetLastError();
+  if (nV < 0 || nF < 0 || (phase != 0 && phase != 1)) return SN_E_SHAPE;
+  if (mass != SN_DESC_MASS_BARYCENTRIC && mass != SN_DESC_MASS_VORONOI) return SN_E_SHAPE;
+  if (nV + 1 > INT_MAX || 3 * nF > INT_MAX) return SN_E_RANGE;
+  if (!rowptr || !status) return SN_E_NULL;
+  if ((nF > 0 || nV > 0) && (!V || (nF > 0 && !F))) return SN_E_NULL;
+  if (phase == 1 && nV > 0 && (!colind || !vals)) return SN_E_NULL;
+  if (workspace_bytes < sn_mesh_cot_laplacian_workspace_bytes(nV, nF) || !workspace) return SN_E_WORKSPACE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  char *w = static_cast<char *>(workspace);
+  int *vptr = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
+  int *cursor = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
+  int *inc = reinterpret_cast<int *>(w); w += align16((size_t)3 * nF * sizeof(int));
+  int *sums = reinterpret_cast<int *>(w);
+  const int voronoi = mass == SN_DESC_MASS_VORONOI;
+  if (phase == 0) {
+    hipError_t e = sn_internal_fill(vptr, 0, (size_t)(nV + 1) * sizeof(int), s);
+    if (e != hipSuccess) return (int)e;
+    e = sn_internal_fill(status, 0, sizeof(int), s);
+    if (e != hipSuccess) return (int)e;
+    if (nF > 0)
+      hipLaunchKernelGGL(desc_face_k, dim3(grid_for(nF)), dim3(kWG), 0, s, V, F, nF, nV, vptr, (float *)nullptr, (float *)nullptr, status);
+    const int st = incidence_build(F, nV, nF, vptr, cursor, inc, sums, s);
+    if (st != SN_OK) return st;
+    e = sn_internal_fill(rowptr + nV, 0, sizeof(int), s);
+    if (e != hipSuccess) return (int)e;
+    if (nV > 0)
+      hipLaunchKernelGGL((cot_laplacian_rows_k<false>), dim3(grid_for(nV)), dim3(kWG), 0, s, V, F, nV, vptr, inc, voronoi, 0, 0.f, rowptr,
+                         (int *)nullptr, (float *)nullptr, status);
+    scan_in_place(rowptr, nV + 1, sums, s);
+  } else if (nV > 0) {
+    hipLaunchKernelGGL((cot_laplacian_rows_k<true>), dim3(grid_for(nV)), dim3(kWG), 0, s, V, F, nV, vptr, inc, voronoi, clamp != 0,
+                       (float)hack, rowptr, colind, vals, status);
+  }
   return launch_status();
 }
 

@@ -24,7 +24,7 @@ from . import arap as _arap
 from . import mesh_ops
 from .operators import OperatorPool
 
-__all__ = ["load_arap_sequence", "arap_from_files", "load_mesh_mnist", "mnist_from_samples", "load_faust_frame", "faust_from_files", "faust_frame_from_mesh",
+__all__ = ["load_arap_sequence", "arap_from_files", "load_mesh_mnist", "mnist_from_samples", "load_faust_frame", "faust_from_files", "faust_frame_from_mesh", "normal_frame_from_mesh",
            "write_arap_sequence", "write_mesh_mnist", "write_faust_frame"]
 
 
@@ -207,6 +207,57 @@ def faust_frame_from_mesh(V, F, label=None, device="cuda", symmetric=True, geode
     }
     if vertex_map is not None:
         frame["vertex_map"] = vertex_map
+    return frame
+
+
+def normal_frame_from_mesh(V, F, model="lap", uniform_mesh=True, hack=1, target="area", name=None, device="cuda"):
+    """The frame dict of the reference's normal-prediction sampler (src/normal_predict/sampler.py:21-91, read_npz) from a raw
+    triangle mesh, built on the device: {'V' (nV, 3) fp32, 'F' (nF, 3) int64, 'input' (= V), 'target_dist' (nV, 3), 'name'} and
+    'L' (model="lap") or 'Di', 'DiA' (model="dir") as SparseOperators.
+    uniform_mesh: V -= V.min(0); V /= V.max() (sampler.py:48-50) in float64, rounded to fp32.  target_dist: the unit vertex
+    normals of the rescaled mesh, operators.vertex_normals(weighting=target) — the reference reads them from its OBJ files.
+    L: the libigl-convention Laplacian M^-1 C with the barycentric mass and the clamp `hack`
+    (operators.laplacian_operator_from_mesh(convention="libigl"); geom_utils.hacky_compute_laplacian).  Di / DiA: this project's
+    operators.dirac_operators_from_mesh — the reference's igl.dirac_operator belongs to an unpublished fork and is not reproduced.
+    Where read_npz gives up on a frame (non-finite target or operator values, sampler.py:31-33, 60-63, 75-77) this returns None
+    after a warnings.warn naming the reason.  Still missing of the reference's pipeline: principal curvatures, WKS inputs and
+    the geometric repair of fix_degenerate.py."""
+    import warnings
+
+    from .operators import dirac_operators_from_mesh, laplacian_operator_from_mesh, vertex_normals
+
+    if model not in ("lap", "dir"):
+        raise ValueError(f'normal_frame_from_mesh: model must be "lap" or "dir", got {model!r}')
+    Vn = np.array(V.detach().cpu() if torch.is_tensor(V) else V, dtype=np.float32).astype(np.float64)
+    Fn = np.asarray(F.detach().cpu() if torch.is_tensor(F) else F)
+    if Vn.ndim != 2 or Vn.shape[1] != 3 or Fn.ndim != 2 or Fn.shape[1] != 3:
+        raise ValueError(f"normal_frame_from_mesh wants V (nV, 3) and F (nF, 3), got {Vn.shape} and {Fn.shape}")
+    if uniform_mesh and Vn.size:
+        Vn = Vn - Vn.min(axis=0)
+        Vn = Vn / Vn.max()
+    Vd = torch.from_numpy(Vn.astype(np.float32)).to(device)
+    Fd = torch.from_numpy(Fn.astype(np.int64)).to(device)
+
+    def refuse(why):
+        warnings.warn(f"normal_frame_from_mesh: {name if name is not None else 'mesh'}: {why}; no frame")
+        return None
+
+    target_dist = vertex_normals(Vd, Fd, weighting=target)
+    if not bool(torch.isfinite(Vd).all()) or not bool(torch.isfinite(target_dist).all()):
+        return refuse("non-finite coordinates or target normals")
+    frame = {"V": Vd, "F": Fd, "input": Vd, "target_dist": target_dist, "name": name}
+    if model == "dir":
+        if not mesh_ops.good_faces(Fn, Vn.shape[0]).all():      # the Dirac builder takes clean meshes only
+            raise ValueError('normal_frame_from_mesh: model="dir" wants a mesh without bad faces (operators.clean_mesh makes one)')
+        Di, DiA = dirac_operators_from_mesh(Vd, Fd)
+        if not bool(torch.isfinite(Di._bsr4[2]).all()) or not bool(torch.isfinite(DiA._bsr4[2]).all()):
+            return refuse("non-finite Dirac operator values")
+        frame["Di"], frame["DiA"] = Di, DiA
+    else:
+        L = laplacian_operator_from_mesh(Vd, Fd, convention="libigl", mass="barycentric", hack=hack)
+        if not bool(torch.isfinite(L.vals).all()):
+            return refuse("non-finite Laplacian values")
+        frame["L"] = L
     return frame
 
 

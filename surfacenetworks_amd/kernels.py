@@ -1071,6 +1071,73 @@ def mesh_compact(F, keep, num_vertices: int, V=None) -> MeshCompacted:
     return MeshCompacted(I, J, Fsrc, Fnew, Vnew, sizes)
 
 
+DESC_BAD_FACE, DESC_FLAT_FACE, DESC_NO_NORMAL, DESC_CLAMPED, DESC_DEGREE = 1, 2, 4, 8, 16      # SN_DESC_* status bits
+# output name -> (per face?, trailing width) in the argument order of sn_mesh_descriptors_f32
+DESCRIPTOR_FIELDS = {"face_area": (True, 1), "face_normal": (True, 3), "n_area": (False, 3), "n_uniform": (False, 3),
+                     "n_angle": (False, 3), "mass_bary": (False, 1), "mass_voronoi": (False, 1), "gauss": (False, 1),
+                     "mean": (False, 1)}
+_DESC_MASS = {"barycentric": 0, "voronoi": 1}                 # SN_DESC_MASS_*
+
+
+def mesh_descriptors(V, F, want=None) -> dict:
+    """Per-face and per-vertex geometry of one triangle mesh (or a batch laid out as one disjoint mesh) on the device:
+    sn_mesh_descriptors_f32, definition in include/sn_spmm.h ("Mesh descriptors"), host statement mesh_ops.vertex_descriptors.
+    V: (nV, 3) fp32, F: (nF, 3) int32.  want: the names of DESCRIPTOR_FIELDS to compute, None = all.  Returns a dict with every
+    name of DESCRIPTOR_FIELDS — an fp32 device tensor (nF,), (nF, 3), (nV,) or (nV, 3), or None when it was not asked for — plus
+    "status": a 1-element int32 device tensor of DESC_* bits, not read here.  Any number of faces at a vertex.  Does not
+    synchronise; two runs are bit-identical."""
+    _dev(V, F)
+    _check_mesh("mesh_descriptors", V, F)
+    names = list(DESCRIPTOR_FIELDS) if want is None else list(want)
+    unknown = [n for n in names if n not in DESCRIPTOR_FIELDS]
+    if unknown:
+        raise ValueError(f"mesh_descriptors: unknown output {unknown[0]!r}; the outputs are {', '.join(DESCRIPTOR_FIELDS)}")
+    V, F = V.contiguous(), F.contiguous()
+    nV, nF = V.shape[0], F.shape[0]
+    dev = V.device
+    out = {}
+    for name, (per_face, width) in DESCRIPTOR_FIELDS.items():
+        rows = nF if per_face else nV
+        out[name] = torch.empty((rows,) if width == 1 else (rows, width), dtype=torch.float32, device=dev) if name in names else None
+    out["status"] = torch.empty(1, dtype=torch.int32, device=dev)
+    ws_bytes = int(_lib.load().sn_mesh_descriptors_workspace_bytes(nV, nF))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    _lib.call("sn_mesh_descriptors_f32", _p(V), _p(F), nV, nF, *[_p(out[n]) for n in DESCRIPTOR_FIELDS], out["status"].data_ptr(),
+              _p(ws), ws_bytes, _stream())
+    return out
+
+
+def cot_laplacian_from_mesh(V, F, mass: str = "barycentric", hack=None):
+    """The libigl-convention Laplacian L = M^-1 C of one mesh (or a batch laid out as one disjoint mesh) built on the device:
+    (rowptr, colind, vals, status) — CSR with ascending columns and explicit zeros kept, and the status word as a Python int
+    (DESC_BAD_FACE / DESC_FLAT_FACE / DESC_CLAMPED).  sn_mesh_cot_laplacian_f32; host statement mesh_ops.libigl_laplacian.
+    mass: "barycentric" | "voronoi".  hack: None, or the value put in place of every entry that is not finite or exceeds 1e10 in
+    magnitude.  Synchronises twice (nnz and the status after each phase).  Raises SnError when a vertex has more than
+    SN_LAP_MAX_DEGREE incident faces (DESC_DEGREE): nothing further is launched, there is no other path."""
+    _dev(V, F)
+    _check_mesh("cot_laplacian_from_mesh", V, F)
+    if mass not in _DESC_MASS:
+        raise ValueError(f'cot_laplacian_from_mesh: mass must be "barycentric" or "voronoi", got {mass!r}')
+    V, F = V.contiguous(), F.contiguous()
+    nV, nF = V.shape[0], F.shape[0]
+    dev = V.device
+    rowptr = torch.empty(nV + 1, dtype=torch.int32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ws_bytes = int(_lib.load().sn_mesh_cot_laplacian_workspace_bytes(nV, nF))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    head = (_p(V), _p(F), nV, nF)
+    tail = (_DESC_MASS[mass], int(hack is not None), float(0 if hack is None else hack))
+    _lib.call("sn_mesh_cot_laplacian_f32", *head, 0, *tail, _p(rowptr), None, None, status.data_ptr(), _p(ws), ws_bytes, _stream())
+    nnz, st = torch.cat([rowptr[-1:], status]).tolist()
+    if st & DESC_DEGREE:
+        raise _lib.SnError("cot_laplacian_from_mesh: a vertex has more incident faces than SN_LAP_MAX_DEGREE (status SN_DESC_DEGREE)")
+    colind = torch.empty(nnz, dtype=torch.int32, device=dev)
+    vals = torch.empty(nnz, dtype=torch.float32, device=dev)
+    _lib.call("sn_mesh_cot_laplacian_f32", *head, 1, *tail, _p(rowptr), _p(colind), _p(vals), status.data_ptr(), _p(ws), ws_bytes,
+              _stream())
+    return rowptr, colind, vals, int(status.item())
+
+
 def _check_graph(who: str, rowptr, colind, n: int) -> None:
     if rowptr.dtype != torch.int32 or colind.dtype != torch.int32:
         raise TypeError(f"{who} wants int32 rowptr and colind")

@@ -31,6 +31,8 @@ __all__ = [
     "mesh_glue", "intrinsic_delaunay", "intrinsic_laplacian", "intrinsic_laplacian_from_lengths", "delaunay_margin",
     "IDT_THRESHOLD",
     "good_faces", "components", "compact", "largest_component", "Components", "Compacted", "CC_BAD_FACE", "CC_INTERNAL",
+    "descriptor_sums", "vertex_descriptors", "libigl_laplacian", "Descriptors", "LAP_MAX_DEGREE",
+    "DESC_BAD_FACE", "DESC_FLAT_FACE", "DESC_NO_NORMAL", "DESC_CLAMPED", "DESC_DEGREE",
 ]
 
 _PERMS = np.array([[0, 1, 2], [0, 2, 1], [1, 0, 2], [1, 2, 0], [2, 0, 1], [2, 1, 0]])  # itertools.permutations order
@@ -438,6 +440,142 @@ def largest_component(V, F: np.ndarray, connectivity: str = "edge"):
         raise ValueError("largest_component: the mesh has no face with three distinct vertices of the mesh")
     out = compact(V, F, cc.flabel == cc.summary[1])
     return out.Vnew, out.Fnew, out.J, out.Fsrc
+
+
+# --------------------------------------------------------------------------------------------------
+# mesh descriptors: normals, mass, curvature and the libigl-convention Laplacian (definition: include/sn_spmm.h, "Mesh
+# descriptors").  The host statement of what src/utils/geom_utils.py takes from pyigl, in numpy float64 with the operation
+# order of the header: elementwise ufuncs only (each rounds on its own), np.add.at for the ordered sums, no np.sum, no np.cross.
+# --------------------------------------------------------------------------------------------------
+DESC_BAD_FACE, DESC_FLAT_FACE, DESC_NO_NORMAL, DESC_CLAMPED, DESC_DEGREE = 1, 2, 4, 8, 16      # SN_DESC_* status bits
+LAP_MAX_DEGREE = 24          # SN_LAP_MAX_DEGREE: the device row kernels keep a vertex's neighbours in registers
+
+Descriptors = collections.namedtuple("Descriptors", "face_area face_normal n_area n_uniform n_angle mass_bary mass_voronoi gauss "
+                                                    "mean status")
+
+
+def _dot3(u, w):
+    return (u[:, 0] * w[:, 0] + u[:, 1] * w[:, 1]) + u[:, 2] * w[:, 2]
+
+
+def _cross3(u, w):
+    return np.stack([u[:, 1] * w[:, 2] - u[:, 2] * w[:, 1], u[:, 2] * w[:, 0] - u[:, 0] * w[:, 2],
+                     u[:, 0] * w[:, 1] - u[:, 1] * w[:, 0]], axis=1)
+
+
+def descriptor_sums(V: np.ndarray, F: np.ndarray) -> dict:
+    """Everything the header defines per face and per vertex, in float64 BEFORE the rounding to fp32: a dict with
+    n (nF, 3), dbl, area, nhat (nF, 3), valid (nF,) bool (neither bad nor flat), good (nF,) bool (not bad), the vertex sums
+    N_area, N_uniform, N_angle (nV, 3), M_bary, M_voronoi, theta (the angle sum), dP (nV, 3), degree (valid faces per vertex),
+    and the per-corner lists of the valid faces in (face, corner) order: corner_v, corner_a, corner_b, corner_cot_a,
+    corner_cot_b."""
+    P = np.asarray(V, dtype=np.float32).astype(np.float64).reshape(-1, 3)
+    F = np.asarray(F, dtype=np.int64).reshape(-1, 3)
+    nV, nF = P.shape[0], F.shape[0]
+    good = good_faces(F, nV)
+    Fs = np.where(good[:, None], F, 0) if nV else np.zeros_like(F)
+    Pc = [P[Fs[:, c]] if nV else np.zeros((nF, 3)) for c in range(3)]
+    with np.errstate(all="ignore"):
+        n = _cross3(Pc[1] - Pc[0], Pc[2] - Pc[0])
+        dbl = np.sqrt(_dot3(n, n))
+        valid = good & (dbl > 0)
+        area = np.where(valid, dbl / 2, 0.0)
+        nhat = np.where(valid[:, None], n / dbl[:, None], 0.0)
+        d = np.stack([_dot3(Pc[(c + 1) % 3] - Pc[c], Pc[(c + 2) % 3] - Pc[c]) for c in range(3)], axis=1)
+        obtuse = (d[:, 0] < 0) | (d[:, 1] < 0) | (d[:, 2] < 0)
+        # per corner, face-major and corner-minor, valid faces only: a vertex meets its faces in ascending order
+        fid = np.repeat(np.nonzero(valid)[0], 3)
+        cid = np.tile(np.arange(3), int(valid.sum()))
+        v, a, b = Fs[fid, cid], Fs[fid, (cid + 1) % 3], Fs[fid, (cid + 2) % 3]
+        u, w = P[a] - P[v], P[b] - P[v]
+        dv, da, db = d[fid, cid], d[fid, (cid + 1) % 3], d[fid, (cid + 2) % 3]
+        dblc, af = dbl[fid], dbl[fid] / 2
+        theta = np.arctan2(dblc, dv)
+        cota, cotb = da / dblc, db / dblc
+        vor = np.where(obtuse[fid], np.where(dv < 0, af / 2, af / 4), (_dot3(u, u) * cotb + _dot3(w, w) * cota) / 8)
+        lap = (0.5 * cotb)[:, None] * u + (0.5 * cota)[:, None] * w
+        out = {"n": n, "dbl": dbl, "area": area, "nhat": nhat, "valid": valid, "good": good,
+               "N_area": np.zeros((nV, 3)), "N_uniform": np.zeros((nV, 3)), "N_angle": np.zeros((nV, 3)), "M_bary": np.zeros(nV),
+               "M_voronoi": np.zeros(nV), "theta": np.zeros(nV), "dP": np.zeros((nV, 3)), "degree": np.zeros(nV, dtype=np.int64),
+               "corner_v": v, "corner_a": a, "corner_b": b, "corner_cot_a": cota, "corner_cot_b": cotb}
+        np.add.at(out["N_area"], v, n[fid])
+        np.add.at(out["N_uniform"], v, nhat[fid])
+        np.add.at(out["N_angle"], v, theta[:, None] * nhat[fid])
+        np.add.at(out["M_bary"], v, af / 3)
+        np.add.at(out["M_voronoi"], v, vor)
+        np.add.at(out["theta"], v, theta)
+        np.add.at(out["dP"], v, lap)
+        np.add.at(out["degree"], v, 1)
+    return out
+
+
+def vertex_descriptors(V: np.ndarray, F: np.ndarray) -> Descriptors:
+    """Descriptors(face_area, face_normal, n_area, n_uniform, n_angle, mass_bary, mass_voronoi, gauss, mean, status): the fp32
+    arrays of sn_mesh_descriptors_f32 and its status word as a Python int (DESC_BAD_FACE | DESC_FLAT_FACE | DESC_NO_NORMAL).
+    Replaces geom_utils.compute_normals / area / laplacian_and_mass / gaussian_curvature (all pyigl) in this project's own
+    definition: area-, uniform- and angle-weighted unit normals, barycentric and Voronoi (Meyer mixed) mass, the raw angle
+    defect K, and the mean curvature H from the cotangent Laplacian of the positions, positive on an outward sphere."""
+    s = descriptor_sums(V, F)
+    status = 0
+    if not s["good"].all():
+        status |= DESC_BAD_FACE
+    if (s["good"] & ~s["valid"]).any():
+        status |= DESC_FLAT_FACE
+    normals = []
+    with np.errstate(all="ignore"):
+        for key in ("N_area", "N_uniform", "N_angle"):
+            N = s[key]
+            length = np.sqrt(_dot3(N, N))
+            ok = length > 0
+            if not ok.all():
+                status |= DESC_NO_NORMAL
+            normals.append(np.where(ok[:, None], N / length[:, None], 0.0).astype(np.float32))
+        K = 2 * np.pi - s["theta"]
+        dP, Mv = s["dP"], s["M_voronoi"]
+        sign = np.where(_dot3(dP, s["N_area"]) > 0, -1.0, 1.0)
+        H = np.where(Mv > 0, (sign * np.sqrt(_dot3(dP, dP))) / (2 * Mv), 0.0)
+        f32 = lambda x: np.asarray(x).astype(np.float32)
+        return Descriptors(f32(s["area"]), f32(s["nhat"]), *normals, f32(s["M_bary"]), f32(Mv), f32(K), f32(H), status)
+
+
+def libigl_laplacian(V: np.ndarray, F: np.ndarray, mass: str = "barycentric", hack=None):
+    """(L, status): L = M^-1 C, igl.cotmatrix scaled by the inverse of igl.massmatrix, as fp32 scipy CSR with columns ascending
+    and explicit zeros kept (sn_mesh_cot_laplacian_f32; geom_utils.hacky_compute_laplacian and compute_laplacian).  mass:
+    "barycentric" | "voronoi".  hack: None, or the value that replaces every entry whose fp32 value is not finite or exceeds
+    1e10 in magnitude (DESC_CLAMPED is then set in status, next to DESC_BAD_FACE / DESC_FLAT_FACE).  A vertex without mass has
+    a NaN diagonal when no hack is given.  No degree limit here: the device builder refuses past LAP_MAX_DEGREE."""
+    if mass not in ("barycentric", "voronoi"):
+        raise ValueError(f'libigl_laplacian: mass must be "barycentric" or "voronoi", got {mass!r}')
+    s = descriptor_sums(V, F)
+    nV = s["M_bary"].shape[0]
+    M = s["M_bary"] if mass == "barycentric" else s["M_voronoi"]
+    v, a, b = s["corner_v"], s["corner_a"], s["corner_b"]
+    # per valid face and corner: (v, a) gets 0.5 cot_b, (v, b) gets 0.5 cot_a; still face-major, so add.at sums in face order
+    rows = np.stack([v, v], axis=1).ravel()
+    cols = np.stack([a, b], axis=1).ravel()
+    cw = np.stack([0.5 * s["corner_cot_b"], 0.5 * s["corner_cot_a"]], axis=1).ravel()
+    keys, inv = np.unique(rows * max(nV, 1) + cols, return_inverse=True)          # ascending (row, col)
+    krow, kcol = keys // max(nV, 1), keys % max(nV, 1)
+    Cv = np.zeros(keys.size)
+    S = np.zeros(nV)
+    with np.errstate(all="ignore"):
+        np.add.at(Cv, inv.ravel(), cw)
+        np.add.at(S, krow, Cv)                                                     # j ascending inside every row
+        vals = np.concatenate([Cv / M[krow], (0 - S) / M]).astype(np.float32)
+    r = np.concatenate([krow, np.arange(nV)])
+    c = np.concatenate([kcol, np.arange(nV)])
+    o = np.lexsort((c, r))
+    vals, c = vals[o], c[o]
+    status = (0 if s["good"].all() else DESC_BAD_FACE) | (DESC_FLAT_FACE if (s["good"] & ~s["valid"]).any() else 0)
+    if hack is not None:
+        with np.errstate(all="ignore"):
+            bad = ~(np.abs(vals) <= np.float32(1e10))
+        if bad.any():
+            vals[bad] = np.float32(hack)
+            status |= DESC_CLAMPED
+    rowptr = np.zeros(nV + 1, dtype=np.int32)
+    np.cumsum(np.bincount(r, minlength=nV), out=rowptr[1:])
+    return sp.csr_matrix((vals, c.astype(np.int32), rowptr), shape=(nV, nV)), status
 
 
 # --------------------------------------------------------------------------------------------------

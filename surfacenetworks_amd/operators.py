@@ -16,6 +16,7 @@ What this replaces in the reference (paths relative to the reference checkout):
 from __future__ import annotations
 
 import collections
+import dataclasses
 import os
 import weakref
 from typing import Optional, Sequence
@@ -27,7 +28,8 @@ from . import kernels
 
 __all__ = ["SparseOperator", "OperatorPool", "PackedSegments", "as_operator", "dirac_operators_from_mesh",
            "laplacian_operator_from_mesh", "geodesic_matrix_from_mesh", "spgemm", "amplify_sequence_operators",
-           "clean_mesh", "CleanMesh"]
+           "clean_mesh", "CleanMesh", "vertex_descriptors", "MeshDescriptors", "vertex_normals", "face_areas", "vertex_mass",
+           "gaussian_curvature"]
 
 # A BSR4 copy is kept when zero-fill costs at most this much extra storage over CSR entries.
 _BSR4_MAX_FILL = 1.6
@@ -415,8 +417,93 @@ def dirac_operators_from_mesh(V: torch.Tensor, F: torch.Tensor):
     return Di, DiA
 
 
-def laplacian_operator_from_mesh(V: torch.Tensor, F: torch.Tensor, intrinsic: bool = False, max_rounds: int = 1024) -> SparseOperator:
-    """L = A^-1 (D - W) built on the device (sn_laplacian_csr_from_mesh) — replaces the host pipeline
+def _offset_batch(who: str, V: torch.Tensor, F: torch.Tensor):
+    """(Vg, Fg, B, nV, nF): a batch (B, nV, 3) with shared (nF, 3) or per-mesh (B, nF, 3) faces laid out as one disjoint mesh."""
+    if V.dim() == 3:
+        if V.shape[2] != 3 or F.dim() not in (2, 3) or F.shape[-1] != 3 or (F.dim() == 3 and F.shape[0] != V.shape[0]):
+            raise ValueError(f"{who} wants V (B, nV, 3) with F (nF, 3) or (B, nF, 3), got {tuple(V.shape)} and {tuple(F.shape)}")
+        B, nV = V.shape[0], V.shape[1]
+        Fb = F if F.dim() == 3 else F.unsqueeze(0).expand(B, -1, -1)
+        off = (torch.arange(B, device=V.device, dtype=torch.int32) * nV).view(B, 1, 1)
+        Fi = Fb.to(torch.int32)
+        # an index outside its own mesh stays outside the batch (it must not land in a neighbour's block)
+        Fg = torch.where((Fi >= 0) & (Fi < nV), Fi + off, torch.full_like(Fi, -1)).reshape(-1, 3)
+        return V.reshape(B * nV, 3).float(), Fg, B, nV, Fb.shape[1]
+    if V.dim() != 2 or V.shape[1] != 3 or F.dim() != 2 or F.shape[1] != 3:
+        raise ValueError(f"{who} wants V (nV, 3) and F (nF, 3), got {tuple(V.shape)} and {tuple(F.shape)}")
+    return V.float(), F.to(torch.int32), 1, V.shape[0], F.shape[0]
+
+
+@dataclasses.dataclass
+class MeshDescriptors:
+    """What operators.vertex_descriptors returns: fp32 device tensors, None for an output that was not asked for.  Face outputs
+    are (nF,) / (nF, 3), vertex outputs (nV,) / (nV, 3), with a leading batch axis for a batch; status is a 1-element int32
+    device tensor of kernels.DESC_* bits (of the whole batch)."""
+    face_area: Optional[torch.Tensor] = None
+    face_normal: Optional[torch.Tensor] = None
+    n_area: Optional[torch.Tensor] = None
+    n_uniform: Optional[torch.Tensor] = None
+    n_angle: Optional[torch.Tensor] = None
+    mass_bary: Optional[torch.Tensor] = None
+    mass_voronoi: Optional[torch.Tensor] = None
+    gauss: Optional[torch.Tensor] = None
+    mean: Optional[torch.Tensor] = None
+    status: Optional[torch.Tensor] = None
+
+
+def vertex_descriptors(V: torch.Tensor, F: torch.Tensor, want=None) -> MeshDescriptors:
+    """Normals, mass and curvature of a triangle mesh on the device (kernels.mesh_descriptors; include/sn_spmm.h, "Mesh
+    descriptors", has the definition and mesh_ops.vertex_descriptors the host statement) — what the reference's
+    src/utils/geom_utils.py takes from pyigl: compute_normals, area, laplacian_and_mass, gaussian_curvature.
+    V: (nV, 3), F: (nF, 3), or a batch V: (B, nV, 3) with F shared or (B, nF, 3): one launch sequence over the offset faces,
+    bit-identical to the per-mesh calls.  want: names of the MeshDescriptors fields to compute (None: all of them).
+    Bad faces (an index outside the mesh, a repeated index) and flat faces contribute nothing and are reported in `status`
+    together with vertices that have no normal.  Does not synchronise."""
+    kernels._dev(V, F)
+    Vg, Fg, B, nV, nF = _offset_batch("vertex_descriptors", V, F)
+    out = kernels.mesh_descriptors(Vg, Fg, want)
+    if V.dim() == 3:
+        for name, (per_face, width) in kernels.DESCRIPTOR_FIELDS.items():
+            if out[name] is not None:
+                out[name] = out[name].view((B, nF if per_face else nV) + ((width,) if width > 1 else ()))
+    return MeshDescriptors(**out)
+
+
+def vertex_normals(V: torch.Tensor, F: torch.Tensor, weighting: str = "area") -> torch.Tensor:
+    """(nV, 3) unit vertex normals, "area"-, "uniform"- or "angle"-weighted (igl.per_vertex_normals' three weightings; a vertex
+    without a normal gets zeros) — geom_utils.compute_normals and the OBJ normals of sampler.py:23."""
+    if weighting not in ("area", "uniform", "angle"):
+        raise ValueError(f'vertex_normals: weighting must be "area", "uniform" or "angle", got {weighting!r}')
+    return getattr(vertex_descriptors(V, F, want=["n_" + weighting]), "n_" + weighting)
+
+
+def face_areas(V: torch.Tensor, F: torch.Tensor) -> torch.Tensor:
+    """(nF,) face areas, 0 for a bad or flat face — geom_utils.area."""
+    return vertex_descriptors(V, F, want=["face_area"]).face_area
+
+
+def vertex_mass(V: torch.Tensor, F: torch.Tensor, kind: str = "voronoi") -> torch.Tensor:
+    """(nV,) diagonal of the mass matrix: "voronoi" (Meyer's mixed cells) or "barycentric" — igl.massmatrix."""
+    if kind not in ("voronoi", "barycentric"):
+        raise ValueError(f'vertex_mass: kind must be "voronoi" or "barycentric", got {kind!r}')
+    name = "mass_voronoi" if kind == "voronoi" else "mass_bary"
+    return getattr(vertex_descriptors(V, F, want=[name]), name)
+
+
+def gaussian_curvature(V: torch.Tensor, F: torch.Tensor, area_avg: bool = False) -> torch.Tensor:
+    """(nV,) angle defect 2 pi - sum of the incident angles (igl.gaussian_curvature); area_avg: divided by the Voronoi mass, as
+    geom_utils.gaussian_curvature does."""
+    d = vertex_descriptors(V, F, want=["gauss", "mass_voronoi"] if area_avg else ["gauss"])
+    return d.gauss / d.mass_voronoi if area_avg else d.gauss
+
+
+def laplacian_operator_from_mesh(V: torch.Tensor, F: torch.Tensor, intrinsic: bool = False, max_rounds: int = 1024,
+                                 convention: str = "reference", mass: str = "barycentric", hack=None) -> SparseOperator:
+    """convention="libigl": L = M^-1 C, igl.cotmatrix scaled by the inverse mass matrix (kernels.cot_laplacian_from_mesh;
+    geom_utils.hacky_compute_laplacian), mass "barycentric" | "voronoi", hack: None or the value that replaces entries that are
+    not finite or exceed 1e10 in magnitude; explicit zeros kept; intrinsic=True is refused with it.  `status` (DESC_* bits, a
+    Python int) is set on the returned operator.  convention="reference" (default), everything below:
+    L = A^-1 (D - W) built on the device (sn_laplacian_csr_from_mesh) — replaces the host pipeline
     mesh.cotangent_weights + graph.laplacian (src/mesh_mnist/add_laplacian.py:43-48).  V: (nV,3) or (B,nV,3) for a batch
     of equally sized meshes (block-diagonal result); F: (nF,3) shared or (B,nF,3).
     intrinsic=True: the same operator on the intrinsic Delaunay triangulation of the mesh (edge flips on the device,
@@ -425,6 +512,19 @@ def laplacian_operator_from_mesh(V: torch.Tensor, F: torch.Tensor, intrinsic: bo
     Every interior edge then has a non-negative weight.  A batch is one launch sequence over the offset faces.  Limits: the
     mesh must be manifold and consistently oriented (ValueError names what it is not), at most max_rounds parallel flip
     rounds (RuntimeError), explicit zeros are kept, no vertex-degree limit."""
+    if convention not in ("reference", "libigl"):
+        raise ValueError(f'laplacian_operator_from_mesh: convention must be "reference" or "libigl", got {convention!r}')
+    if convention == "libigl":
+        if intrinsic:
+            raise ValueError('laplacian_operator_from_mesh: intrinsic=True has no convention="libigl" form')
+        kernels._dev(V, F)
+        Vg, Fg, B, nV, _ = _offset_batch("laplacian_operator_from_mesh", V, F)
+        rowptr, colind, vals, st = kernels.cot_laplacian_from_mesh(Vg, Fg, mass, hack)
+        L = SparseOperator(rowptr, colind, vals, (B * nV, B * nV), batch=B)
+        L.status = st
+        return L
+    if mass != "barycentric" or hack is not None:
+        raise ValueError('laplacian_operator_from_mesh: mass and hack belong to convention="libigl"')
     if V.dim() == 3:
         B, nV = V.shape[0], V.shape[1]
         Fb = F if F.dim() == 3 else F.unsqueeze(0).expand(B, -1, -1)
