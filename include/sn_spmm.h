@@ -1007,6 +1007,86 @@ int sn_mesh_compact_i32(const float *V, const int32_t *F, const int32_t *keep, i
                         void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Mesh repair: weld duplicate vertices, drop duplicate faces, orient every component consistently.
+ *
+ * Replaces: igl.remove_duplicate_vertices, igl.bfs_orient and the face filter of fix_degen
+ *           src/normal_predict/fix_degenerate.py (pyigl on the host; nothing of it is on the device).
+ * This is the project's own definition in libigl's conventions, not libigl's bits.  Host statement: mesh_ops.repair_mesh
+ * (weld_vertices, unique_faces, orient_faces), vectorised numpy that is not the device algorithm; the device is compared to it
+ * bit for bit.  V fp32 (nV, 3), F int32 (nF, 3).
+ *
+ * Definition.
+ *   1. Weld key.  tol == 0: the key of a vertex is its three fp32 coordinates compared AS VALUES, so -0.0 and +0.0 are one key.
+ *      tol > 0: the key is rint((double)x / tol) per coordinate — fp64 division, round-half-even — as int64.  A vertex is
+ *      UNWELDABLE when a coordinate is not finite or, with tol > 0, a quotient lies outside +-2^62 (an infinite quotient
+ *      included).  An unweldable vertex is welded to nothing, and every face that uses one is a bad face
+ *      (SN_REPAIR_NONFINITE).  tol > 0 IS A GRID, NOT A BALL: the cells are the cubes [(k - 1/2) tol, (k + 1/2) tol] around the
+ *      lattice points k tol.  Two points 0.2 tol apart on either side of a cell border stay apart; two points 0.9 tol apart
+ *      inside one cell weld.  No vertex moves: a tolerance only decides who is one class.
+ *   2. Weld.  Vertices with equal keys are a class, its representative rep[v] is the smallest vertex id of the class
+ *      (rep[v] = v for an unweldable vertex).  F is rewritten through rep; in the rewritten F an unweldable vertex is written
+ *      as -1, so that every later step sees its faces as bad, and an index outside 0..nV-1 stays what it is.  The coordinates
+ *      of a representative are kept bit for bit (a -0.0 stays -0.0).  With weld == 0 rep[v] = v, and only a non-finite
+ *      coordinate makes a vertex unweldable.
+ *   3. Bad and duplicate faces.  A face is BAD when it has an index outside 0..nV-1, an unweldable vertex or, after welding, a
+ *      repeated index (SN_REPAIR_BAD_FACE); it is never kept.  Two good faces over the same UNORDERED vertex triple are
+ *      duplicates, whatever their winding: the smallest face id stays (keep = 1), the others are dropped.  With unique == 0
+ *      every good face stays.  counts = {bad faces, duplicate faces, degenerate faces}: a kept face is DEGENERATE when the fp64
+ *      squared double-area |(b - a) x (c - a)|^2 — differences of the fp32 coordinates widened to fp64, cross product
+ *      (uy wz - uz wy, uz wx - ux wz, ux wy - uy wx), (cx cx + cy cy) + cz cz, no contraction — is exactly 0: a cap or a needle
+ *      on three distinct vertices.  Such a face is COUNTED AND KEPT: flipping it away (fix_degen_face_with_flip) changes
+ *      connectivity in an order-dependent way and is not done here, nor is orient_outward.
+ *   4. Orientation.  Among the kept faces an edge (unordered vertex pair) carried by exactly two faces is a LINK; an edge with
+ *      one face, or with three and more, links nothing, and the edges with three and more are counted (nonmanifold edges,
+ *      SN_REPAIR_NONMANIFOLD).  The classes of faces under links are the orientation classes; label[f] = the smallest face id
+ *      of f's class, -1 for a face that is not kept.  In each class the smallest face id keeps its winding and every other
+ *      face gets the winding that makes each link traversed in opposite directions by its two faces: flip[f] = 1 turns
+ *      (a, b, c) into (a, c, b).  When no such winding exists (a Moebius band) every face of the class is left as it came
+ *      (flip = 0), the class is counted and SN_REPAIR_NONORIENTABLE is set.  counts = {nonmanifold edges, classes without a
+ *      consistent winding, classes}.
+ *   5. Compaction: sn_mesh_compact_i32 on the oriented faces with the keep mask of step 3.
+ *   All of it is a function of the input alone: whatever order the threads run in, two runs are bit-identical.
+ * Method.  Steps 2 and 3 use one scheme: an open-addressing table of ids with at least 2 n slots.  A slot is claimed by
+ *   atomicCAS(empty -> id) and holds ids of one key from then on; a probe compares its key with the key of the id in the slot,
+ *   moves on when they differ and does atomicMin(slot, id) when they agree.  Slots are never emptied, so a class meets in one
+ *   slot and a second launch reads its minimum from there: k coincident vertices cost k atomics, not k^2 comparisons.  Step 4
+ *   is the union-find of the clean-up section over the faces with the parity to the parent in bit 0 of the word: a link is
+ *   atomicCAS(&w[hi], hi << 1, (lo << 1) | p) between two roots, larger under smaller; path halving stores (grandparent,
+ *   composed parity) with a plain 32-bit store, and since the parity between a node and an ancestor is fixed by the links made,
+ *   every word a reader meets is a valid pair.  Two faces of one link that reach one root with the wrong relative parity flag
+ *   that root; a later launch carries the flag to the final root.  The root is the smallest face id and parity 0 means "as it
+ *   came", which is the definition.  Lock-free, every loop bounded as in the clean-up section (SN_REPAIR_INTERNAL, results then
+ *   not to be used); the packed parity needs nF < 2^30.  Links are found in the side buckets of SN_CC_EDGE built over the kept
+ *   faces: a side walks the bucket of its lower vertex, so the cost grows with the square of the number of kept sides that
+ *   share one lower vertex (6 on a regular mesh).  Shared words are read and written with relaxed device-scope atomics.
+ *
+ * sn_mesh_weld_f32         : rep[nV], Fw[nF][3], counts[1] = {vertices with rep[v] != v}, *status (cleared first).  tol < 0 or
+ *                            not finite: SN_E_SHAPE.  nV > 2^30 or 3 nF past int32: SN_E_RANGE.  workspace:
+ *                            sn_mesh_weld_workspace_bytes(nV), else SN_E_WORKSPACE.  Does not synchronise.
+ * sn_mesh_unique_faces_i32 : keep[nF], counts[3], *status (cleared first) of step 3 for the welded F.  V may be NULL: the
+ *                            degenerate count is then 0.  workspace: sn_mesh_unique_faces_workspace_bytes(nF).
+ * sn_mesh_orient_i32       : flip[nF], label[nF], counts[3], *status (cleared first) of step 4 for the faces with keep[f] != 0
+ *                            (a bad face among them is skipped and sets SN_REPAIR_BAD_FACE);  Fout[nF][3] (may be NULL, must
+ *                            not be F) = F with the flagged faces turned.  nF >= 2^30: SN_E_RANGE.  workspace:
+ *                            sn_mesh_orient_workspace_bytes(nV, nF).  Does not synchronise.
+ * None of the three allocates; every fill and copy is a kernel of this library.
+ * ------------------------------------------------------------------------------------------ */
+#define SN_REPAIR_BAD_FACE       1
+#define SN_REPAIR_NONFINITE      2
+#define SN_REPAIR_NONORIENTABLE  4
+#define SN_REPAIR_NONMANIFOLD    8
+#define SN_REPAIR_INTERNAL       16
+size_t sn_mesh_weld_workspace_bytes(int64_t nV);
+int sn_mesh_weld_f32(const float *V, const int32_t *F, int64_t nV, int64_t nF, double tol, int32_t weld, int32_t *rep, int32_t *Fw,
+                     int32_t *counts, int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+size_t sn_mesh_unique_faces_workspace_bytes(int64_t nF);
+int sn_mesh_unique_faces_i32(const float *V, const int32_t *F, int64_t nV, int64_t nF, int32_t unique, int32_t *keep,
+                             int32_t *counts, int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+size_t sn_mesh_orient_workspace_bytes(int64_t nV, int64_t nF);
+int sn_mesh_orient_i32(const int32_t *F, const int32_t *keep, int64_t nV, int64_t nF, int32_t *flip, int32_t *label, int32_t *Fout,
+                       int32_t *counts, int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Mesh descriptors: per-vertex normals, mass, Gaussian and mean curvature, and the libigl-convention Laplacian M^-1 C.
  *
  * Replaces: compute_normals, area, laplacian_and_mass, compute_laplacian, gaussian_curvature, hacky_compute_laplacian

@@ -160,6 +160,12 @@ SIGNATURES = {
     "sn_mesh_label_mask_i32": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
     "sn_mesh_compact_workspace_bytes": (_sz, [_i64, _i64]),
     "sn_mesh_compact_i32": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sn_mesh_weld_workspace_bytes": (_sz, [_i64]),
+    "sn_mesh_weld_f32": (C.c_int, [_vp, _vp, _i64, _i64, C.c_double, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sn_mesh_unique_faces_workspace_bytes": (_sz, [_i64]),
+    "sn_mesh_unique_faces_i32": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sn_mesh_orient_workspace_bytes": (_sz, [_i64, _i64]),
+    "sn_mesh_orient_i32": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sn_mesh_descriptors_workspace_bytes": (_sz, [_i64, _i64]),
     "sn_mesh_descriptors_f32": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sn_mesh_cot_laplacian_workspace_bytes": (_sz, [_i64, _i64]),

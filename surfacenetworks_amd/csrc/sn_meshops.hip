@@ -933,9 +933,11 @@ __global__ __launch_bounds__(kWG) void cc_vertex_union_k(const int *__restrict__
 }
 
 // edge mode: the sides of the good faces, bucketed under the lower of their two vertices (orientation does not matter)
-__global__ __launch_bounds__(kWG) void cc_side_count_k(const int *__restrict__ F, int64_t nF, int64_t nV, int *__restrict__ ptr,
-                                                       int *__restrict__ status) {
+// (keep: only the faces with keep[f] != 0 take part — the orientation of the repair section; nullptr: every good face)
+__global__ __launch_bounds__(kWG) void cc_side_count_k(const int *__restrict__ F, const int *__restrict__ keep, int64_t nF, int64_t nV,
+                                                       int *__restrict__ ptr, int *__restrict__ status) {
   for (int64_t f = (int64_t)blockIdx.x * kWG + threadIdx.x; f < nF; f += (int64_t)gridDim.x * kWG) {
+    if (keep && keep[f] == 0) continue;
     const int i = F[3 * f], j = F[3 * f + 1], k = F[3 * f + 2];
     if (!face_ok(i, j, k, nV)) {
       atomicOr(status, SN_CC_BAD_FACE);
@@ -947,9 +949,10 @@ __global__ __launch_bounds__(kWG) void cc_side_count_k(const int *__restrict__ F
   }
 }
 
-__global__ __launch_bounds__(kWG) void cc_side_fill_k(const int *__restrict__ F, int64_t nF, int64_t nV, int *__restrict__ cursor,
-                                                      int *__restrict__ bucket) {
+__global__ __launch_bounds__(kWG) void cc_side_fill_k(const int *__restrict__ F, const int *__restrict__ keep, int64_t nF, int64_t nV,
+                                                      int *__restrict__ cursor, int *__restrict__ bucket) {
   for (int64_t f = (int64_t)blockIdx.x * kWG + threadIdx.x; f < nF; f += (int64_t)gridDim.x * kWG) {
+    if (keep && keep[f] == 0) continue;
     const int i = F[3 * f], j = F[3 * f + 1], k = F[3 * f + 2];
     if (!face_ok(i, j, k, nV)) continue;
     bucket[atomicAdd(&cursor[min(i, j)], 1)] = (int)(3 * f);
@@ -1104,6 +1107,313 @@ inline void scan_in_place(int *a, int64_t n, int *sums, hipStream_t s) {
   hipLaunchKernelGGL(scan_sums_k, dim3(nblk), dim3(kWG), 0, s, a, n, sums);
   hipLaunchKernelGGL(scan_top_k, dim3(1), dim3(kWG), 0, s, sums, nblk);
   hipLaunchKernelGGL(scan_apply_k, dim3(nblk), dim3(kWG), 0, s, a, n, sums, a);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Mesh repair: weld, duplicate faces, orientation (definition: sn_spmm.h, "Mesh repair").
+// Weld and duplicate faces share one scheme: an open-addressing table of ids at load factor <= 0.5.  A slot is claimed by one
+// atomicCAS(empty -> id) and from then on holds ids of ONE key only: a probe compares its own key with the key of the id it
+// finds, moves on when they differ and does atomicMin(slot, id) when they agree.  Slots are never emptied, so every member of a
+// class stops at the same slot, whatever the order, and after the launch that slot holds the smallest id of the class.  Which
+// slot a class sits in depends on the order; what is read from it does not.  A class of k coincident members costs k atomics
+// on one word, not k^2 comparisons.
+// ------------------------------------------------------------------------------------------------
+constexpr int kRepairEmpty = -1;
+constexpr int64_t kRepairMaxNodes = (int64_t)1 << 30;      // table of at most 2^31 slots; the parity bit of the orientation forest
+
+struct RepairKey { int64_t a, b, c; };
+__device__ __forceinline__ bool key_eq(const RepairKey &x, const RepairKey &y) { return x.a == y.a && x.b == y.b && x.c == y.c; }
+__device__ __forceinline__ uint32_t key_slot(const RepairKey &k, uint32_t mask) {
+  uint64_t h = (uint64_t)k.a * 0x9E3779B97F4A7C15ull;
+  h = (h ^ (h >> 29)) + (uint64_t)k.b;
+  h *= 0xBF58476D1CE4E5B9ull;
+  h = (h ^ (h >> 31)) + (uint64_t)k.c;
+  h *= 0x94D049BB133111EBull;
+  return (uint32_t)(h >> 32) & mask;
+}
+
+// weld key of vertex v; false: v is unweldable.  tol == 0: the fp32 values themselves, -0.0 as +0.0 (one bit pattern per value);
+// tol > 0: rint((double)x / tol), round-half-even, as int64, quotients outside +-2^62 (an infinite one among them) refused.
+// weld == 0: nothing is welded and only a non-finite coordinate refuses.
+__device__ __forceinline__ bool weld_key(const float *__restrict__ V, int64_t v, double tol, int weld, RepairKey *key) {
+  int64_t q[3];
+  bool ok = true;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float x = V[3 * v + c];
+    q[c] = 0;
+    if (!isfinite(x)) ok = false;
+    else if (!weld) continue;
+    else if (tol > 0) {
+      const double r = rint((double)x / tol);
+      if (!(fabs(r) <= 0x1p62)) ok = false;
+      else q[c] = (int64_t)r;
+    } else {
+      q[c] = (int64_t)__float_as_uint(x == 0.0f ? 0.0f : x);
+    }
+  }
+  key->a = q[0], key->b = q[1], key->c = q[2];
+  return ok;
+}
+// key of face f: its three vertex ids in ascending order; false: f is bad
+__device__ __forceinline__ bool face_key(const int *__restrict__ F, int64_t f, int64_t nV, RepairKey *key) {
+  int i = F[3 * f], j = F[3 * f + 1], k = F[3 * f + 2];
+  if (!face_ok(i, j, k, nV)) return false;
+  int t;
+  if (i > j) t = i, i = j, j = t;
+  if (j > k) t = j, j = k, k = t;
+  if (i > j) t = i, i = j, j = t;
+  key->a = i, key->b = j, key->c = k;
+  return true;
+}
+
+// one wave64 sum, then one atomicAdd per wave
+__device__ __forceinline__ void wave_count(int v, int *dst) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
+  if ((threadIdx.x & 63) == 0 && v) atomicAdd(dst, v);
+}
+
+// FACES: the ids are faces of F and the key is face_key; else vertices of V and weld_key.  The probe loops are bounded by the
+// table size (the table has at least twice as many slots as ids, so an empty slot is always met first): SN_REPAIR_INTERNAL.
+template <bool FACES>
+__device__ __forceinline__ bool repair_key(const float *__restrict__ V, const int *__restrict__ F, int64_t x, int64_t nV, double tol,
+                                           RepairKey *key) {
+  return FACES ? face_key(F, x, nV, key) : weld_key(V, x, tol, 1, key);
+}
+template <bool FACES>
+__global__ __launch_bounds__(kWG) void repair_insert_k(const float *__restrict__ V, const int *__restrict__ F, int64_t n, int64_t nV,
+                                                       double tol, int *table, uint32_t mask, int *__restrict__ status) {
+  for (int64_t x = (int64_t)blockIdx.x * kWG + threadIdx.x; x < n; x += (int64_t)gridDim.x * kWG) {
+    RepairKey mine, other;
+    if (!repair_key<FACES>(V, F, x, nV, tol, &mine)) continue;
+    uint32_t h = key_slot(mine, mask);
+    bool done = false;
+    for (uint32_t probe = 0; probe <= mask && !done; ++probe, h = (h + 1) & mask) {
+      int cur = cc_load(table + h);
+      if (cur == kRepairEmpty) {
+        cur = atomicCAS(table + h, kRepairEmpty, (int)x);
+        if (cur == kRepairEmpty) {
+          done = true;
+          break;
+        }
+      }
+      if ((unsigned)cur >= (unsigned)n || !repair_key<FACES>(V, F, cur, nV, tol, &other)) break;       // not a value this file writes
+      if (key_eq(mine, other)) {
+        atomicMin(table + h, (int)x);
+        done = true;
+      }
+    }
+    if (!done) atomicOr(status, SN_REPAIR_INTERNAL);
+  }
+}
+// the slot of x's class, read after repair_insert_k has finished: the smallest id of the class (x itself after SN_REPAIR_INTERNAL)
+template <bool FACES>
+__device__ __forceinline__ int repair_lookup(const float *__restrict__ V, const int *__restrict__ F, int64_t x, int64_t n, int64_t nV,
+                                             double tol, const RepairKey &mine, const int *__restrict__ table, uint32_t mask,
+                                             int *__restrict__ status) {
+  uint32_t h = key_slot(mine, mask);
+  for (uint32_t probe = 0; probe <= mask; ++probe, h = (h + 1) & mask) {
+    const int cur = table[h];
+    RepairKey other;
+    if ((unsigned)cur >= (unsigned)n || !repair_key<FACES>(V, F, cur, nV, tol, &other)) break;
+    if (key_eq(mine, other)) return cur;
+  }
+  atomicOr(status, SN_REPAIR_INTERNAL);
+  return (int)x;
+}
+
+__global__ __launch_bounds__(kWG) void weld_rep_k(const float *__restrict__ V, int64_t nV, double tol, int weld,
+                                                  const int *__restrict__ table, uint32_t mask, int *__restrict__ rep,
+                                                  int *__restrict__ counts, int *__restrict__ status) {
+  int welded = 0;
+  for (int64_t v = (int64_t)blockIdx.x * kWG + threadIdx.x; v < nV; v += (int64_t)gridDim.x * kWG) {
+    RepairKey mine;
+    int r = (int)v;
+    if (weld && weld_key(V, v, tol, 1, &mine)) r = repair_lookup<false>(V, nullptr, v, nV, nV, tol, mine, table, mask, status);
+    rep[v] = r;
+    welded += r != (int)v;
+  }
+  wave_count(welded, counts);
+}
+// F through the representative; an unweldable vertex is written as -1, so that every later step sees its faces as bad; an index
+// outside 0..nV-1 stays what it is
+__global__ __launch_bounds__(kWG) void weld_faces_k(const float *__restrict__ V, const int *__restrict__ F, int64_t nF, int64_t nV,
+                                                    double tol, int weld, const int *__restrict__ rep, int *__restrict__ Fw,
+                                                    int *__restrict__ status) {
+  for (int64_t e = (int64_t)blockIdx.x * kWG + threadIdx.x; e < 3 * nF; e += (int64_t)gridDim.x * kWG) {
+    const int v = F[e];
+    int out = v;
+    if ((unsigned)v < (unsigned)nV) {
+      RepairKey key;
+      if (weld_key(V, v, tol, weld, &key)) out = rep[v];
+      else {
+        out = -1;
+        atomicOr(status, SN_REPAIR_NONFINITE);
+      }
+    }
+    Fw[e] = out;
+  }
+}
+
+// keep[f] = f is good and (with unique) the smallest face id on its unordered vertex triple.  counts = {bad faces, duplicate
+// faces, kept faces whose fp64 squared double-area is exactly 0}
+__global__ __launch_bounds__(kWG) void unique_keep_k(const float *__restrict__ V, const int *__restrict__ F, int64_t nF, int64_t nV,
+                                                     int unique, const int *__restrict__ table, uint32_t mask, int *__restrict__ keep,
+                                                     int *__restrict__ counts, int *__restrict__ status) {
+  int bad = 0, dup = 0, flat = 0;
+  for (int64_t f = (int64_t)blockIdx.x * kWG + threadIdx.x; f < nF; f += (int64_t)gridDim.x * kWG) {
+    RepairKey mine;
+    int stay = 0;
+    if (!face_key(F, f, nV, &mine)) {
+      ++bad;
+    } else {
+      stay = !unique || repair_lookup<true>(nullptr, F, f, nF, nV, 0.0, mine, table, mask, status) == (int)f;
+      dup += !stay;
+      if (stay && V) {
+        const int a = F[3 * f], b = F[3 * f + 1], c = F[3 * f + 2];
+        const double ux = (double)V[3 * b] - (double)V[3 * a], uy = (double)V[3 * b + 1] - (double)V[3 * a + 1],
+                     uz = (double)V[3 * b + 2] - (double)V[3 * a + 2];
+        const double wx = (double)V[3 * c] - (double)V[3 * a], wy = (double)V[3 * c + 1] - (double)V[3 * a + 1],
+                     wz = (double)V[3 * c + 2] - (double)V[3 * a + 2];
+        const double cx = uy * wz - uz * wy, cy = uz * wx - ux * wz, cz = ux * wy - uy * wx;
+        flat += ((cx * cx + cy * cy) + cz * cz) == 0.0;
+      }
+    }
+    keep[f] = stay;
+  }
+  if (bad) atomicOr(status, SN_REPAIR_BAD_FACE);
+  wave_count(bad, counts);
+  wave_count(dup, counts + 1);
+  wave_count(flat, counts + 2);
+}
+
+// ---- orientation: the union-find of cc_unite with the parity to the parent in bit 0, w[x] = (parent << 1) | parity ----
+// A root is w[x] == x << 1.  A link is one CAS on a root, the larger under the smaller; halving stores (grandparent, parity
+// to it) into a non-root.  The parity between a node and any of its ancestors is fixed by the links once made, so every word
+// a reader meets is a valid (ancestor, parity to it) pair.  Returns the root, *par = parity of x to it; -1 past the bound.
+template <bool HALVE>
+__device__ __forceinline__ int or_find(int *w, int x, int n, int *par, int *status) {
+  int acc = 0;
+  for (int step = 0; step <= n; ++step) {
+    const int wx = cc_load(w + x), p = wx >> 1;
+    if (wx == x << 1) {
+      *par = acc;
+      return x;
+    }
+    if ((unsigned)p >= (unsigned)n) break;
+    const int wp = cc_load(w + p), g = wp >> 1;
+    if (wp == p << 1) {
+      *par = acc ^ (wx & 1);
+      return p;
+    }
+    if ((unsigned)g >= (unsigned)n) break;
+    const int q = (wx ^ wp) & 1;
+    if (HALVE) cc_store(w + x, (g << 1) | q);
+    acc ^= q;
+    x = g;
+  }
+  atomicOr(status, SN_REPAIR_INTERNAL);
+  return -1;
+}
+// faces a and b must end with flip[a] ^ flip[b] == p.  In one class already: a disagreement flags the root met (or_resolve_k
+// carries the flag to the final root).
+__device__ __forceinline__ void or_unite(int *w, int *conflict, int a, int b, int p, int n, int *status) {
+  for (int pass = 0; pass <= n; ++pass) {
+    int pa, pb;
+    a = or_find<true>(w, a, n, &pa, status);
+    b = or_find<true>(w, b, n, &pb, status);
+    if (a < 0 || b < 0) return;
+    p ^= pa ^ pb;                                                  // now between the two roots
+    if (a == b) {
+      if (p) cc_store(conflict + a, 1);
+      return;
+    }
+    const int hi = a > b ? a : b, lo = a > b ? b : a;
+    if (atomicCAS(w + hi, hi << 1, (lo << 1) | p) == hi << 1) return;
+  }
+  atomicOr(status, SN_REPAIR_INTERNAL);
+}
+__global__ __launch_bounds__(kWG) void or_init_k(int *__restrict__ w, int *__restrict__ conflict, int64_t n) {
+  for (int64_t x = (int64_t)blockIdx.x * kWG + threadIdx.x; x < n; x += (int64_t)gridDim.x * kWG) {
+    w[x] = (int)x << 1;
+    conflict[x] = 0;
+  }
+}
+// One thread per side of a kept face.  It counts the sides of its bucket on its own edge, itself included: exactly two is a
+// link, made by the side with the lower code; three and more link nothing and the lowest code counts the edge.
+__global__ __launch_bounds__(kWG) void or_link_k(const int *__restrict__ F, const int *__restrict__ keep, int64_t nF, int64_t nV,
+                                                 const int *__restrict__ ptr, const int *__restrict__ bucket, int *w, int *conflict,
+                                                 int *__restrict__ counts, int *__restrict__ status) {
+  int edges = 0;
+  for (int64_t c = (int64_t)blockIdx.x * kWG + threadIdx.x; c < 3 * nF; c += (int64_t)gridDim.x * kWG) {
+    const int64_t f = c / 3;
+    const int s = (int)(c - 3 * f);
+    if (keep[f] == 0) continue;
+    const int i = F[3 * f], j = F[3 * f + 1], k = F[3 * f + 2];
+    if (!face_ok(i, j, k, nV)) continue;
+    const int a = s == 0 ? i : s == 1 ? j : k, b = s == 0 ? j : s == 1 ? k : i;
+    const int lo = min(a, b), hi = max(a, b);
+    int m = 0, other = -1, other_from = -1, first = INT_MAX;
+    for (int e = ptr[lo]; e < ptr[lo + 1]; ++e) {
+      const int d = bucket[e];
+      if ((unsigned)d >= (unsigned)(3 * nF)) continue;
+      const int g = d / 3, t = d - 3 * g;
+      const int from = F[d], to = F[3 * g + (t + 1) % 3];
+      if (max(from, to) != hi) continue;                           // (a bucketed side belongs to a good face: its min is lo)
+      ++m;
+      first = min(first, d);
+      if (d != (int)c) other = d, other_from = from;
+    }
+    if (m == 2 && (int)c < other) or_unite(w, conflict, (int)f, other / 3, other_from == a ? 1 : 0, (int)nF, status);
+    else if (m > 2 && first == (int)c) ++edges;
+  }
+  if (edges) atomicOr(status, SN_REPAIR_NONMANIFOLD);
+  wave_count(edges, counts);
+}
+// w[f] = (root << 1) | parity in place (still a valid pair), and a flagged face flags its root
+__global__ __launch_bounds__(kWG) void or_resolve_k(int *w, int *conflict, int64_t nF, int *__restrict__ status) {
+  for (int64_t f = (int64_t)blockIdx.x * kWG + threadIdx.x; f < nF; f += (int64_t)gridDim.x * kWG) {
+    int par;
+    const int r = or_find<false>(w, (int)f, (int)nF, &par, status);
+    if (r < 0) continue;
+    cc_store(w + f, (r << 1) | par);
+    if (r != (int)f && cc_load(conflict + f)) cc_store(conflict + r, 1);
+  }
+}
+// label, flip and the oriented faces; counts[1..2] = {classes without a consistent winding, classes}
+__global__ __launch_bounds__(kWG) void or_finish_k(const int *__restrict__ F, const int *__restrict__ keep, int64_t nF, int64_t nV,
+                                                   int *label, const int *__restrict__ conflict, int *__restrict__ flip,
+                                                   int *__restrict__ Fout, int *__restrict__ counts, int *__restrict__ status) {
+  int classes = 0, twisted = 0;
+  for (int64_t f = (int64_t)blockIdx.x * kWG + threadIdx.x; f < nF; f += (int64_t)gridDim.x * kWG) {
+    const int i = F[3 * f], j = F[3 * f + 1], k = F[3 * f + 2];
+    const bool in = keep[f] != 0 && face_ok(i, j, k, nV);
+    const int wf = label[f], r = wf >> 1;
+    int turn = 0;
+    if (in && (unsigned)r < (unsigned)nF) {
+      const int bad = conflict[r];
+      turn = bad ? 0 : (wf & 1);
+      classes += r == (int)f;
+      twisted += r == (int)f && bad;
+    }
+    label[f] = in ? r : -1;
+    flip[f] = turn;
+    if (Fout) {
+      Fout[3 * f] = i;
+      Fout[3 * f + 1] = turn ? k : j;
+      Fout[3 * f + 2] = turn ? j : k;
+    }
+  }
+  if (twisted) atomicOr(status, SN_REPAIR_NONORIENTABLE);
+  wave_count(twisted, counts + 1);
+  wave_count(classes, counts + 2);
+}
+
+inline uint32_t repair_table_slots(int64_t n) {      // a power of two >= 2 n, n <= 2^30
+  uint32_t t = 2;
+  while ((int64_t)t < 2 * n) t <<= 1;
+  return t;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1702,11 +2012,11 @@ int sn_mesh_components_i32(const int32_t *F, int64_t nV, int64_t nF, int32_t mod
     int *sums = reinterpret_cast<int *>(w);
     e = sn_internal_fill(ptr, 0, (size_t)(nV + 1) * sizeof(int), s);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(cc_side_count_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, nV, ptr, status);
+    hipLaunchKernelGGL(cc_side_count_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, (const int *)nullptr, nF, nV, ptr, status);
     scan_in_place(ptr, nV + 1, sums, s);
     e = sn_internal_copy2d(cursor, 0, ptr, 0, (int64_t)((size_t)(nV + 1) * sizeof(int)), 1, s);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(cc_side_fill_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, nV, cursor, bucket);
+    hipLaunchKernelGGL(cc_side_fill_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, (const int *)nullptr, nF, nV, cursor, bucket);
     hipLaunchKernelGGL(cc_edge_union_k, dim3(grid_for(3 * nF)), dim3(kWG), 0, s, F, nF, nV, ptr, bucket, parent, status);
     hipLaunchKernelGGL((cc_face_labels_k<false>), dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, nV, (const int *)nullptr, flabel, count, status);
     hipLaunchKernelGGL(cc_bad_labels_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, nV, flabel);
@@ -1831,6 +2141,113 @@ int sn_mesh_cot_laplacian_f32(const float *V, const int32_t *F, int64_t nV, int6
     hipLaunchKernelGGL((cot_laplacian_rows_k<true>), dim3(grid_for(nV)), dim3(kWG), 0, s, V, F, nV, vptr, inc, voronoi, clamp != 0,
                        (float)hack, rowptr, colind, vals, status);
   }
+  return launch_status();
+}
+
+size_t sn_mesh_weld_workspace_bytes(int64_t nV) {
+  if (nV < 0 || nV > kRepairMaxNodes) nV = 0;
+  return align16((size_t)repair_table_slots(nV) * sizeof(int));
+}
+
+int sn_mesh_weld_f32(const float *V, const int32_t *F, int64_t nV, int64_t nF, double tol, int32_t weld, int32_t *rep, int32_t *Fw,
+                     int32_t *counts, int32_t *status, void *workspace, size_t workspace_bytes, void *stream) {
+  (void)hipGetLastError();
+  if (nV < 0 || nF < 0 || !(tol >= 0) || !(tol <= 1.7976931348623157e308)) return SN_E_SHAPE;
+  if (nV > kRepairMaxNodes || 3 * nF > INT_MAX) return SN_E_RANGE;
+  if (!counts || !status) return SN_E_NULL;
+  if (nV > 0 && (!V || !rep)) return SN_E_NULL;
+  if (nF > 0 && (!F || !Fw)) return SN_E_NULL;
+  if (workspace_bytes < sn_mesh_weld_workspace_bytes(nV) || !workspace) return SN_E_WORKSPACE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int *table = static_cast<int *>(workspace);
+  const uint32_t slots = repair_table_slots(nV);
+  hipError_t e = sn_internal_fill(counts, 0, sizeof(int), s);
+  if (e != hipSuccess) return (int)e;
+  e = sn_internal_fill(status, 0, sizeof(int), s);
+  if (e != hipSuccess) return (int)e;
+  if (nV > 0) {
+    if (weld) {
+      e = sn_internal_fill(table, 0xff, (size_t)slots * sizeof(int), s);                    // kRepairEmpty in every slot
+      if (e != hipSuccess) return (int)e;
+      hipLaunchKernelGGL((repair_insert_k<false>), dim3(grid_for(nV)), dim3(kWG), 0, s, V, (const int *)nullptr, nV, nV, tol, table,
+                         slots - 1, status);
+    }
+    hipLaunchKernelGGL(weld_rep_k, dim3(grid_for(nV)), dim3(kWG), 0, s, V, nV, tol, (int)weld, table, slots - 1, rep, counts, status);
+  }
+  if (nF > 0) hipLaunchKernelGGL(weld_faces_k, dim3(grid_for(3 * nF)), dim3(kWG), 0, s, V, F, nF, nV, tol, (int)weld, rep, Fw, status);
+  return launch_status();
+}
+
+size_t sn_mesh_unique_faces_workspace_bytes(int64_t nF) {
+  if (nF < 0 || nF > kRepairMaxNodes) nF = 0;
+  return align16((size_t)repair_table_slots(nF) * sizeof(int));
+}
+
+int sn_mesh_unique_faces_i32(const float *V, const int32_t *F, int64_t nV, int64_t nF, int32_t unique, int32_t *keep,
+                             int32_t *counts, int32_t *status, void *workspace, size_t workspace_bytes, void *stream) {
+  (void)hipGetLastError();
+  if (nV < 0 || nF < 0) return SN_E_SHAPE;
+  if (nV + 1 > INT_MAX || 3 * nF > INT_MAX) return SN_E_RANGE;
+  if (!counts || !status) return SN_E_NULL;
+  if (nF > 0 && (!F || !keep)) return SN_E_NULL;
+  if (workspace_bytes < sn_mesh_unique_faces_workspace_bytes(nF) || !workspace) return SN_E_WORKSPACE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int *table = static_cast<int *>(workspace);
+  const uint32_t slots = repair_table_slots(nF);
+  hipError_t e = sn_internal_fill(counts, 0, 3 * sizeof(int), s);
+  if (e != hipSuccess) return (int)e;
+  e = sn_internal_fill(status, 0, sizeof(int), s);
+  if (e != hipSuccess) return (int)e;
+  if (nF == 0) return launch_status();
+  if (unique) {
+    e = sn_internal_fill(table, 0xff, (size_t)slots * sizeof(int), s);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL((repair_insert_k<true>), dim3(grid_for(nF)), dim3(kWG), 0, s, (const float *)nullptr, F, nF, nV, 0.0, table,
+                       slots - 1, status);
+  }
+  hipLaunchKernelGGL(unique_keep_k, dim3(grid_for(nF)), dim3(kWG), 0, s, V, F, nF, nV, (int)unique, table, slots - 1, keep, counts,
+                     status);
+  return launch_status();
+}
+
+size_t sn_mesh_orient_workspace_bytes(int64_t nV, int64_t nF) {
+  if (nV < 0) nV = 0;
+  if (nF < 0) nF = 0;
+  return 2 * align16((size_t)(nV + 1) * sizeof(int)) + align16((size_t)3 * nF * sizeof(int)) + align16((size_t)nF * sizeof(int)) +
+         scan_bytes(nV + 1);
+}
+
+int sn_mesh_orient_i32(const int32_t *F, const int32_t *keep, int64_t nV, int64_t nF, int32_t *flip, int32_t *label, int32_t *Fout,
+                       int32_t *counts, int32_t *status, void *workspace, size_t workspace_bytes, void *stream) {
+  (void)hipGetLastError();
+  if (nV < 0 || nF < 0) return SN_E_SHAPE;
+  if (nV + 1 > INT_MAX || nF >= kRepairMaxNodes) return SN_E_RANGE;        // a face id and its parity bit share one int32
+  if (!counts || !status) return SN_E_NULL;
+  if (nF > 0 && (!F || !keep || !flip || !label)) return SN_E_NULL;
+  if (workspace_bytes < sn_mesh_orient_workspace_bytes(nV, nF) || !workspace) return SN_E_WORKSPACE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  char *w = static_cast<char *>(workspace);
+  int *ptr = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
+  int *cursor = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
+  int *bucket = reinterpret_cast<int *>(w); w += align16((size_t)3 * nF * sizeof(int));
+  int *conflict = reinterpret_cast<int *>(w); w += align16((size_t)nF * sizeof(int));
+  int *sums = reinterpret_cast<int *>(w);
+  hipError_t e = sn_internal_fill(counts, 0, 3 * sizeof(int), s);
+  if (e != hipSuccess) return (int)e;
+  e = sn_internal_fill(status, 0, sizeof(int), s);
+  if (e != hipSuccess) return (int)e;
+  if (nF == 0) return launch_status();
+  e = sn_internal_fill(ptr, 0, (size_t)(nV + 1) * sizeof(int), s);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(or_init_k, dim3(grid_for(nF)), dim3(kWG), 0, s, label, conflict, nF);
+  hipLaunchKernelGGL(cc_side_count_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, keep, nF, nV, ptr, status);
+  scan_in_place(ptr, nV + 1, sums, s);
+  e = sn_internal_copy2d(cursor, 0, ptr, 0, (int64_t)((size_t)(nV + 1) * sizeof(int)), 1, s);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(cc_side_fill_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, keep, nF, nV, cursor, bucket);
+  hipLaunchKernelGGL(or_link_k, dim3(grid_for(3 * nF)), dim3(kWG), 0, s, F, keep, nF, nV, ptr, bucket, label, conflict, counts, status);
+  hipLaunchKernelGGL(or_resolve_k, dim3(grid_for(nF)), dim3(kWG), 0, s, label, conflict, nF, status);
+  hipLaunchKernelGGL(or_finish_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, keep, nF, nV, label, conflict, flip, Fout, counts, status);
   return launch_status();
 }
 

@@ -160,7 +160,7 @@ def load_faust_frame(path: str, device="cuda") -> Dict:
 
 
 def faust_frame_from_mesh(V, F, label=None, device="cuda", symmetric=True, geodesics="edges", laplacian="extrinsic",
-                          component=None) -> Dict:
+                          component=None, repair=False) -> Dict:
     """The frame dict of load_faust_frame from a raw triangle mesh: V (nV, 3), F (nF, 3) (numpy or tensors), host scipy
     L / Di / DiA from mesh_ops.mesh_operators, and G — the `dist_mat` the reference's files bring along — computed on the device
     by operators.geodesic_matrix_from_mesh (geodesics="edges": edge-path distances, "triangles": paths that cross the faces;
@@ -172,8 +172,11 @@ def faust_frame_from_mesh(V, F, label=None, device="cuda", symmetric=True, geode
     component: None (default) takes the mesh as it is; "largest" first runs operators.clean_mesh — the largest edge-connected
     component without bad faces and unused vertices, the reference's largest_component.py — builds the frame from the result
     and adds frame["vertex_map"] (new -> original vertex id).  label must then be None: a permutation of the original ids
-    does not survive the removal, and the identity on the kept vertices is used."""
-    from .operators import clean_mesh, geodesic_matrix_from_mesh, laplacian_operator_from_mesh
+    does not survive the removal, and the identity on the kept vertices is used.
+    repair: True first runs operators.repair_mesh (duplicate vertices welded, duplicate faces dropped, every component wound
+    consistently) — before component= and the builders — and adds frame["repair"], the RepairedMesh; frame["vertex_map"] then
+    leads from the frame's vertices to the original ids through both steps.  label must be None here too."""
+    from .operators import clean_mesh, geodesic_matrix_from_mesh, laplacian_operator_from_mesh, repair_mesh
 
     if geodesics not in ("edges", "triangles"):
         raise ValueError(f'faust_frame_from_mesh: geodesics must be "edges" or "triangles", got {geodesics!r}')
@@ -181,14 +184,22 @@ def faust_frame_from_mesh(V, F, label=None, device="cuda", symmetric=True, geode
         raise ValueError(f'faust_frame_from_mesh: laplacian must be "extrinsic" or "intrinsic", got {laplacian!r}')
     if component not in (None, "largest"):
         raise ValueError(f'faust_frame_from_mesh: component must be None or "largest", got {component!r}')
-    vertex_map = None
+    vertex_map = repaired = None
+    if repair:
+        if label is not None:
+            raise ValueError("faust_frame_from_mesh: repair=True renumbers the vertices; label must be None")
+        Vt = V if torch.is_tensor(V) else torch.from_numpy(np.array(V, dtype=np.float32))
+        Ft = F if torch.is_tensor(F) else torch.from_numpy(np.array(F))
+        repaired = repair_mesh(Vt.to(device), Ft.to(device))
+        V, F, vertex_map = repaired.V, repaired.F, repaired.vertex_map.to(torch.int64)
     if component == "largest":
         if label is not None:
             raise ValueError('faust_frame_from_mesh: component="largest" renumbers the vertices; label must be None')
         Vt = V if torch.is_tensor(V) else torch.from_numpy(np.array(V, dtype=np.float32))
         Ft = F if torch.is_tensor(F) else torch.from_numpy(np.array(F))
         cm = clean_mesh(Vt.to(device), Ft.to(device))
-        V, F, vertex_map = cm.V, cm.F, cm.vertex_map.to(torch.int64)
+        kept = cm.vertex_map.to(torch.int64)
+        V, F, vertex_map = cm.V, cm.F, kept if vertex_map is None else vertex_map[kept]
     Vn = np.asarray(V.detach().cpu() if torch.is_tensor(V) else V)
     Fn = np.asarray(F.detach().cpu() if torch.is_tensor(F) else F)
     nv = Vn.shape[0]
@@ -207,10 +218,12 @@ def faust_frame_from_mesh(V, F, label=None, device="cuda", symmetric=True, geode
     }
     if vertex_map is not None:
         frame["vertex_map"] = vertex_map
+    if repaired is not None:
+        frame["repair"] = repaired
     return frame
 
 
-def normal_frame_from_mesh(V, F, model="lap", uniform_mesh=True, hack=1, target="area", name=None, device="cuda"):
+def normal_frame_from_mesh(V, F, model="lap", uniform_mesh=True, hack=1, target="area", name=None, device="cuda", repair=False):
     """The frame dict of the reference's normal-prediction sampler (src/normal_predict/sampler.py:21-91, read_npz) from a raw
     triangle mesh, built on the device: {'V' (nV, 3) fp32, 'F' (nF, 3) int64, 'input' (= V), 'target_dist' (nV, 3), 'name'} and
     'L' (model="lap") or 'Di', 'DiA' (model="dir") as SparseOperators.
@@ -220,14 +233,23 @@ def normal_frame_from_mesh(V, F, model="lap", uniform_mesh=True, hack=1, target=
     (operators.laplacian_operator_from_mesh(convention="libigl"); geom_utils.hacky_compute_laplacian).  Di / DiA: this project's
     operators.dirac_operators_from_mesh — the reference's igl.dirac_operator belongs to an unpublished fork and is not reproduced.
     Where read_npz gives up on a frame (non-finite target or operator values, sampler.py:31-33, 60-63, 75-77) this returns None
-    after a warnings.warn naming the reason.  Still missing of the reference's pipeline: principal curvatures, WKS inputs and
-    the geometric repair of fix_degenerate.py."""
+    after a warnings.warn naming the reason.
+    repair: True first runs operators.repair_mesh on the mesh as given (welding, duplicate faces, one winding per component:
+    what keeps the target normals from cancelling) and builds the frame from its result; the frame gains 'repair', the
+    RepairedMesh with the maps back to the input.  Still missing of the reference's pipeline: principal curvatures, WKS inputs
+    and the edge flips that fix_degenerate.py applies to zero-area faces (repair only counts those)."""
     import warnings
 
-    from .operators import dirac_operators_from_mesh, laplacian_operator_from_mesh, vertex_normals
+    from .operators import dirac_operators_from_mesh, laplacian_operator_from_mesh, repair_mesh, vertex_normals
 
     if model not in ("lap", "dir"):
         raise ValueError(f'normal_frame_from_mesh: model must be "lap" or "dir", got {model!r}')
+    repaired = None
+    if repair:
+        Vt = V if torch.is_tensor(V) else torch.from_numpy(np.array(V, dtype=np.float32))
+        Ft = F if torch.is_tensor(F) else torch.from_numpy(np.array(F))
+        repaired = repair_mesh(Vt.to(device), Ft.to(device))
+        V, F = repaired.V, repaired.F
     Vn = np.array(V.detach().cpu() if torch.is_tensor(V) else V, dtype=np.float32).astype(np.float64)
     Fn = np.asarray(F.detach().cpu() if torch.is_tensor(F) else F)
     if Vn.ndim != 2 or Vn.shape[1] != 3 or Fn.ndim != 2 or Fn.shape[1] != 3:
@@ -246,6 +268,8 @@ def normal_frame_from_mesh(V, F, model="lap", uniform_mesh=True, hack=1, target=
     if not bool(torch.isfinite(Vd).all()) or not bool(torch.isfinite(target_dist).all()):
         return refuse("non-finite coordinates or target normals")
     frame = {"V": Vd, "F": Fd, "input": Vd, "target_dist": target_dist, "name": name}
+    if repaired is not None:
+        frame["repair"] = repaired
     if model == "dir":
         if not mesh_ops.good_faces(Fn, Vn.shape[0]).all():      # the Dirac builder takes clean meshes only
             raise ValueError('normal_frame_from_mesh: model="dir" wants a mesh without bad faces (operators.clean_mesh makes one)')

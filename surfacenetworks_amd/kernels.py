@@ -1071,6 +1071,92 @@ def mesh_compact(F, keep, num_vertices: int, V=None) -> MeshCompacted:
     return MeshCompacted(I, J, Fsrc, Fnew, Vnew, sizes)
 
 
+# SN_REPAIR_* status bits
+REPAIR_BAD_FACE, REPAIR_NONFINITE, REPAIR_NONORIENTABLE, REPAIR_NONMANIFOLD, REPAIR_INTERNAL = 1, 2, 4, 8, 16
+
+MeshWeld = collections.namedtuple("MeshWeld", "rep F counts status")
+MeshUniqueFaces = collections.namedtuple("MeshUniqueFaces", "keep counts status")
+MeshOrient = collections.namedtuple("MeshOrient", "flip label F counts status")
+
+
+def mesh_weld(V, F, tol: float = 0.0, weld: bool = True) -> MeshWeld:
+    """Weld the vertices with equal keys on the device (sn_mesh_weld_f32; the definition is in include/sn_spmm.h, "Mesh
+    repair", the host statement is mesh_ops.weld_vertices).  V: (nV, 3) fp32, F: (nF, 3) int32.  tol == 0: equal coordinates
+    (-0.0 == +0.0); tol > 0: equal cells of the grid rint(x / tol).  weld=False welds nothing and only marks the vertices with a
+    non-finite coordinate.  Returns MeshWeld(rep, F, counts, status), int32 device tensors: rep (nV,) the smallest vertex id of
+    each vertex's class; F (nF, 3) rewritten through rep, -1 for an unweldable vertex; counts (1,) = vertices with rep != id;
+    status (1,) with the REPAIR_* bits.  Does not synchronise; two runs are bit-identical."""
+    _dev(V, F)
+    _check_mesh("mesh_weld", V, F)
+    tol = float(tol)
+    if not 0.0 <= tol < float("inf"):
+        raise ValueError(f"mesh_weld: tol must be finite and >= 0, got {tol!r}")
+    V, F = V.contiguous(), F.contiguous()
+    nV, nF = V.shape[0], F.shape[0]
+    dev = V.device
+    rep = torch.empty(nV, dtype=torch.int32, device=dev)
+    Fw = torch.empty(nF, 3, dtype=torch.int32, device=dev)
+    counts = torch.empty(1, dtype=torch.int32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ws_bytes = int(_lib.load().sn_mesh_weld_workspace_bytes(nV))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    _lib.call("sn_mesh_weld_f32", _p(V), _p(F), nV, nF, tol, 1 if weld else 0, _p(rep), _p(Fw), counts.data_ptr(), status.data_ptr(),
+              _p(ws), ws_bytes, _stream())
+    return MeshWeld(rep, Fw, counts, status)
+
+
+def mesh_unique_faces(F, num_vertices: int, V=None, unique: bool = True) -> MeshUniqueFaces:
+    """The faces that stay (sn_mesh_unique_faces_i32, host statement mesh_ops.unique_faces): keep (nF,) int32 = 1 for a good face
+    that has the smallest face id on its unordered vertex triple (unique=False: for every good face); counts (3,) int32 = bad
+    faces, duplicate faces, kept faces of fp64 double-area exactly 0 (0 without V); status (1,).  F: (nF, 3) int32, as a rule
+    the F of mesh_weld; V: (nV, 3) fp32 or None.  Does not synchronise; two runs are bit-identical."""
+    _dev(F, V)
+    _check_mesh("mesh_unique_faces", V, F)
+    nV, nF = int(num_vertices), F.shape[0]
+    if nV < 0 or (V is not None and V.shape[0] != nV):
+        raise ValueError(f"mesh_unique_faces: V has {None if V is None else V.shape[0]} rows for {nV} vertices")
+    F = F.contiguous()
+    V = None if V is None else V.contiguous()
+    dev = F.device
+    keep = torch.empty(nF, dtype=torch.int32, device=dev)
+    counts = torch.empty(3, dtype=torch.int32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ws_bytes = int(_lib.load().sn_mesh_unique_faces_workspace_bytes(nF))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    _lib.call("sn_mesh_unique_faces_i32", _p(V), _p(F), nV, nF, 1 if unique else 0, _p(keep), counts.data_ptr(), status.data_ptr(),
+              _p(ws), ws_bytes, _stream())
+    return MeshUniqueFaces(keep, counts, status)
+
+
+def mesh_orient(F, keep, num_vertices: int) -> MeshOrient:
+    """A consistent winding for every orientation class of the kept faces (sn_mesh_orient_i32, host statement
+    mesh_ops.orient_faces).  F: (nF, 3) int32, keep: (nF,) int32.  Returns MeshOrient(flip, label, F, counts, status), int32
+    device tensors: flip (nF,) 1 where (a, b, c) became (a, c, b); label (nF,) the smallest face id of the face's class, -1 for
+    a face that is not kept; F (nF, 3) the faces after the turns; counts (3,) = edges with three and more faces, classes without
+    a consistent winding (left as they came), classes; status (1,).  Does not synchronise; two runs are bit-identical."""
+    _dev(F, keep)
+    _check_mesh("mesh_orient", None, F)
+    if keep.dtype != torch.int32 or keep.dim() != 1:
+        raise TypeError("mesh_orient wants keep (nF,) int32")
+    nV, nF = int(num_vertices), F.shape[0]
+    if keep.shape[0] != nF:
+        raise ValueError(f"mesh_orient: keep has {keep.shape[0]} entries for {nF} faces")
+    if nV < 0:
+        raise ValueError("mesh_orient: num_vertices is negative")
+    F, keep = F.contiguous(), keep.contiguous()
+    dev = F.device
+    flip = torch.empty(nF, dtype=torch.int32, device=dev)
+    label = torch.empty(nF, dtype=torch.int32, device=dev)
+    Fout = torch.empty(nF, 3, dtype=torch.int32, device=dev)
+    counts = torch.empty(3, dtype=torch.int32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ws_bytes = int(_lib.load().sn_mesh_orient_workspace_bytes(nV, nF))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    _lib.call("sn_mesh_orient_i32", _p(F), _p(keep), nV, nF, _p(flip), _p(label), _p(Fout), counts.data_ptr(), status.data_ptr(),
+              _p(ws), ws_bytes, _stream())
+    return MeshOrient(flip, label, Fout, counts, status)
+
+
 DESC_BAD_FACE, DESC_FLAT_FACE, DESC_NO_NORMAL, DESC_CLAMPED, DESC_DEGREE = 1, 2, 4, 8, 16      # SN_DESC_* status bits
 # output name -> (per face?, trailing width) in the argument order of sn_mesh_descriptors_f32
 DESCRIPTOR_FIELDS = {"face_area": (True, 1), "face_normal": (True, 3), "n_area": (False, 3), "n_uniform": (False, 3),

@@ -31,6 +31,8 @@ __all__ = [
     "mesh_glue", "intrinsic_delaunay", "intrinsic_laplacian", "intrinsic_laplacian_from_lengths", "delaunay_margin",
     "IDT_THRESHOLD",
     "good_faces", "components", "compact", "largest_component", "Components", "Compacted", "CC_BAD_FACE", "CC_INTERNAL",
+    "weld_vertices", "unique_faces", "orient_faces", "repair_mesh", "Welded", "UniqueFaces", "Oriented", "Repaired",
+    "REPAIR_BAD_FACE", "REPAIR_NONFINITE", "REPAIR_NONORIENTABLE", "REPAIR_NONMANIFOLD", "REPAIR_INTERNAL",
     "descriptor_sums", "vertex_descriptors", "libigl_laplacian", "Descriptors", "LAP_MAX_DEGREE",
     "DESC_BAD_FACE", "DESC_FLAT_FACE", "DESC_NO_NORMAL", "DESC_CLAMPED", "DESC_DEGREE",
 ]
@@ -440,6 +442,164 @@ def largest_component(V, F: np.ndarray, connectivity: str = "edge"):
         raise ValueError("largest_component: the mesh has no face with three distinct vertices of the mesh")
     out = compact(V, F, cc.flabel == cc.summary[1])
     return out.Vnew, out.Fnew, out.J, out.Fsrc
+
+
+# --------------------------------------------------------------------------------------------------
+# mesh repair: weld, duplicate faces, orientation (definition: include/sn_spmm.h, "Mesh repair").  The host statement of
+# igl.remove_duplicate_vertices + igl.bfs_orient and the face filter of src/normal_predict/fix_degenerate.py, by sorting and
+# frontier sweeps; what the device's hash tables and parity union-find are compared to, bit for bit.
+# --------------------------------------------------------------------------------------------------
+REPAIR_BAD_FACE, REPAIR_NONFINITE, REPAIR_NONORIENTABLE, REPAIR_NONMANIFOLD, REPAIR_INTERNAL = 1, 2, 4, 8, 16   # SN_REPAIR_*
+
+Welded = collections.namedtuple("Welded", "rep F counts status")
+UniqueFaces = collections.namedtuple("UniqueFaces", "keep counts status")
+Oriented = collections.namedtuple("Oriented", "flip label F counts status")
+Repaired = collections.namedtuple("Repaired", "V F vertex_map vertex_index face_map flipped welded_vertices bad_faces "
+                                              "duplicate_faces degenerate_faces nonmanifold_edges nonorientable_classes classes")
+
+
+def _group_minima(cols, ids: np.ndarray) -> np.ndarray:
+    """For rows given as equally long key columns: the smallest id among the rows equal to each row, in the order of ids."""
+    if ids.size == 0:
+        return ids.copy()
+    order = np.lexsort(tuple(cols[::-1]))
+    new = np.zeros(ids.size, dtype=bool)
+    new[0] = True
+    for c in cols:
+        s = c[order]
+        new[1:] |= s[1:] != s[:-1]
+    start = np.nonzero(new)[0]
+    low = np.minimum.reduceat(ids[order], start)
+    out = np.empty_like(ids)
+    out[order] = np.repeat(low, np.diff(np.append(start, ids.size)))
+    return out
+
+
+def weld_vertices(V: np.ndarray, F: np.ndarray, tol: float = 0.0, weld: bool = True) -> Welded:
+    """Steps 1 and 2: Welded(rep, F, counts, status).  rep (nV,) int32 the smallest vertex id with v's key (v itself for an
+    unweldable vertex); F (nF, 3) int32 through rep, -1 for an unweldable vertex, an index outside 0..nV-1 unchanged; counts
+    (1,) = vertices with rep != id.  tol == 0: fp32 values (-0.0 == +0.0); tol > 0: the grid rint(float64(x) / tol), a quotient
+    outside +-2**62 unweldable.  weld=False: rep is the identity and only non-finite coordinates are unweldable."""
+    tol = float(tol)
+    if not 0.0 <= tol < np.inf:
+        raise ValueError(f"weld_vertices: tol must be finite and >= 0, got {tol!r}")
+    V = np.asarray(V, dtype=np.float32).reshape(-1, 3)
+    F = np.asarray(F, dtype=np.int64).reshape(-1, 3)
+    nV = V.shape[0]
+    ok = np.isfinite(V).all(axis=1)
+    rep = np.arange(nV, dtype=np.int64)
+    if weld:
+        if tol > 0:
+            with np.errstate(all="ignore"):
+                q = np.rint(V.astype(np.float64) / tol)
+                ok &= (np.abs(q) <= 2.0 ** 62).all(axis=1)
+            key = q[ok].astype(np.int64)
+        else:
+            key = V[ok]                                             # sorted and compared as values: -0.0 == +0.0
+        ids = np.nonzero(ok)[0]
+        rep[ids] = _group_minima([key[:, 0], key[:, 1], key[:, 2]], ids)
+    inside = (F >= 0) & (F < nV)
+    Fc = np.where(inside, F, 0)
+    Fw = np.where(inside, np.where(ok[Fc], rep[Fc], -1), F)
+    status = REPAIR_NONFINITE if (inside & ~ok[Fc]).any() else 0
+    return Welded(rep.astype(np.int32), Fw.astype(np.int32), np.array([np.count_nonzero(rep != np.arange(nV))], dtype=np.int32),
+                  status)
+
+
+def unique_faces(F: np.ndarray, num_vertices: int, V=None, unique: bool = True) -> UniqueFaces:
+    """Step 3: UniqueFaces(keep, counts, status).  keep (nF,) int32 = 1 for a good face with the smallest face id on its
+    unordered vertex triple (unique=False: every good face); counts (3,) = bad faces, duplicate faces, kept faces whose fp64
+    squared double-area is exactly 0 (0 without V)."""
+    F = np.asarray(F, dtype=np.int64).reshape(-1, 3)
+    nV = int(num_vertices)
+    good = good_faces(F, nV)
+    fid = np.nonzero(good)[0]
+    keep = good.copy()
+    if unique:
+        T = np.sort(F[fid], axis=1)
+        keep[fid] = _group_minima([T[:, 0], T[:, 1], T[:, 2]], fid) == fid
+    flat = 0
+    if V is not None:
+        P = np.asarray(V, dtype=np.float32).astype(np.float64)
+        K = F[keep]
+        u, w = P[K[:, 1]] - P[K[:, 0]], P[K[:, 2]] - P[K[:, 0]]
+        with np.errstate(all="ignore"):
+            c = _cross3(u, w)
+            flat = np.count_nonzero(((c[:, 0] * c[:, 0] + c[:, 1] * c[:, 1]) + c[:, 2] * c[:, 2]) == 0.0)
+    counts = np.array([F.shape[0] - fid.size, fid.size - np.count_nonzero(keep), flat], dtype=np.int32)
+    return UniqueFaces(keep.astype(np.int32), counts, 0 if good.all() else REPAIR_BAD_FACE)
+
+
+def orient_faces(F: np.ndarray, keep, num_vertices: int) -> Oriented:
+    """Step 4: Oriented(flip, label, F, counts, status) for the good faces with keep[f] != 0.  An edge with exactly two of them
+    is a link; label (nF,) int32 = the smallest face id of the class under links, -1 for a face that takes no part; flip (nF,)
+    int32 = 1 where (a, b, c) becomes (a, c, b) so that every link is traversed in opposite directions, the smallest face of a
+    class keeping its winding; a class that has no such winding is left as it came.  counts (3,) = edges with three and more
+    faces, classes without a consistent winding, classes.  The parities spread from the class minima, a frontier at a time."""
+    F = np.asarray(F, dtype=np.int64).reshape(-1, 3)
+    nV, nF = int(num_vertices), F.shape[0]
+    good = good_faces(F, nV)
+    part = good & (np.asarray(keep).reshape(-1) != 0)
+    fid = np.nonzero(part)[0]
+    Fk = F[fid]
+    a = np.concatenate([Fk[:, 0], Fk[:, 1], Fk[:, 2]])
+    b = np.concatenate([Fk[:, 1], Fk[:, 2], Fk[:, 0]])
+    face = np.concatenate([fid, fid, fid])
+    key = np.minimum(a, b) * max(nV, 1) + np.maximum(a, b)
+    order = np.argsort(key, kind="stable")
+    ks = key[order]
+    start = np.nonzero(np.append(True, ks[1:] != ks[:-1]))[0] if ks.size else np.zeros(0, dtype=np.int64)
+    size = np.diff(np.append(start, ks.size))
+    two = start[size == 2]
+    s0, s1 = order[two], order[two + 1]
+    lf, lg, lp = face[s0], face[s1], (a[s0] == a[s1]).astype(np.int64)      # the same direction twice: one of the two turns
+    label = np.full(nF, -1, dtype=np.int64)
+    label[fid] = _class_minima(nF, lf, lg)[fid]
+    # the neighbours of every face over its links, as a CSR list
+    src, dst, par = np.concatenate([lf, lg]), np.concatenate([lg, lf]), np.concatenate([lp, lp])
+    o = np.argsort(src, kind="stable")
+    src, dst, par = src[o], dst[o], par[o]
+    ptr = np.zeros(nF + 1, dtype=np.int64)
+    np.cumsum(np.bincount(src, minlength=nF), out=ptr[1:])
+    flip = np.full(nF, -1, dtype=np.int64)
+    front = fid[label[fid] == fid]
+    flip[front] = 0
+    while front.size:
+        n = ptr[front + 1] - ptr[front]
+        e = np.repeat(ptr[front] - np.cumsum(n) + n, n) + np.arange(int(n.sum()))
+        nxt, val = dst[e], flip[np.repeat(front, n)] ^ par[e]
+        new = flip[nxt] < 0
+        flip[nxt[new]] = val[new]                                   # (two frontier faces may reach one face: a clash shows below)
+        front = np.unique(nxt[new])
+    twisted = np.zeros(nF, dtype=bool)
+    twisted[label[lf[(flip[lf] ^ flip[lg]) != lp]]] = True
+    flip[~part] = 0
+    flip[part & twisted[np.where(part, label, 0)]] = 0
+    Fo = F.copy()
+    t = flip == 1
+    Fo[t, 1], Fo[t, 2] = F[t, 2], F[t, 1]
+    counts = np.array([np.count_nonzero(size > 2), np.count_nonzero(twisted), np.count_nonzero(label[fid] == fid)], dtype=np.int32)
+    status = (0 if (good | (np.asarray(keep).reshape(-1) == 0)).all() else REPAIR_BAD_FACE) | \
+             (REPAIR_NONMANIFOLD if counts[0] else 0) | (REPAIR_NONORIENTABLE if counts[1] else 0)
+    return Oriented(flip.astype(np.int32), label.astype(np.int32), Fo.astype(np.int32), counts, int(status))
+
+
+def repair_mesh(V, F, tol: float = 0.0, weld: bool = True, unique: bool = True, orient: bool = True) -> Repaired:
+    """The five steps chained: what operators.repair_mesh computes on the device, field by field (numpy arrays and Python
+    ints).  orient=False leaves every winding and reports -1 for nonmanifold_edges, nonorientable_classes and classes."""
+    V = np.asarray(V, dtype=np.float32).reshape(-1, 3)
+    nV = V.shape[0]
+    w = weld_vertices(V, F, tol, weld)
+    u = unique_faces(w.F, nV, V, unique)
+    if orient:
+        o = orient_faces(w.F, u.keep, nV)
+        Fo, flip, oc = o.F, o.flip, [int(c) for c in o.counts]
+    else:
+        Fo, flip, oc = w.F, np.zeros(w.F.shape[0], dtype=np.int32), [-1, -1, -1]
+    c = compact(V, Fo, u.keep)
+    vertex_index = c.I[w.rep]
+    return Repaired(c.Vnew, c.Fnew, c.J, vertex_index, c.Fsrc, flip[c.Fsrc], int(w.counts[0]), int(u.counts[0]), int(u.counts[1]),
+                    int(u.counts[2]), oc[0], oc[1], oc[2])
 
 
 # --------------------------------------------------------------------------------------------------

@@ -28,7 +28,7 @@ from . import kernels
 
 __all__ = ["SparseOperator", "OperatorPool", "PackedSegments", "as_operator", "dirac_operators_from_mesh",
            "laplacian_operator_from_mesh", "geodesic_matrix_from_mesh", "spgemm", "amplify_sequence_operators",
-           "clean_mesh", "CleanMesh", "vertex_descriptors", "MeshDescriptors", "vertex_normals", "face_areas", "vertex_mass",
+           "clean_mesh", "CleanMesh", "repair_mesh", "RepairedMesh", "vertex_descriptors", "MeshDescriptors", "vertex_normals", "face_areas", "vertex_mass",
            "gaussian_curvature"]
 
 # A BSR4 copy is kept when zero-fill costs at most this much extra storage over CSR entries.
@@ -678,6 +678,64 @@ def clean_mesh(V, F, component="largest", connectivity: str = "edge") -> CleanMe
     if npicked == 0:
         raise ValueError(f"clean_mesh: label {component!r} names no component")
     return CleanMesh(out.Vnew[:nVk], out.Fnew[:nFk], out.J[:nVk], out.I, out.Fsrc[:nFk], ncomp, nF - nFk, nV - nVk, nbad)
+
+
+RepairedMesh = collections.namedtuple("RepairedMesh", "V F vertex_map vertex_index face_map flipped welded_vertices bad_faces "
+                                                      "duplicate_faces degenerate_faces nonmanifold_edges nonorientable_classes "
+                                                      "classes")
+
+
+def repair_mesh(V, F, tol: float = 0.0, weld: bool = True, unique: bool = True, orient: bool = True) -> RepairedMesh:
+    """A triangle soup or an inconsistently wound scan made into a mesh the builders here accept, on the device: duplicate
+    vertices welded, bad and duplicate faces dropped, every component wound consistently, unused vertices removed.  The first
+    step of the pipeline, before clean_mesh; replaces the reference's host-side pyigl calls (igl.remove_duplicate_vertices,
+    igl.bfs_orient, the face filter of src/normal_predict/fix_degenerate.py).  kernels.mesh_weld / mesh_unique_faces /
+    mesh_orient / mesh_compact do the work, include/sn_spmm.h ("Mesh repair") has the definition and mesh_ops.repair_mesh the
+    host statement, which this equals bit for bit.
+    V: (nV, 3), F: (nF, 3), device tensors or numpy (then moved to the current device).  tol == 0 welds vertices with equal
+    coordinates (-0.0 == +0.0); tol > 0 welds the vertices in one cell of the grid rint(x / tol) — a grid, not a ball: points on
+    either side of a cell border stay apart.  weld / unique / orient switch the steps off one at a time: without weld only the
+    vertices with a non-finite coordinate are marked, without unique every good face stays, without orient every winding stays
+    and the three orientation counts are -1.
+    Returns RepairedMesh: V (nV', 3) fp32 and F (nF', 3) int32 on the device, rows of V copied bit for bit; vertex_map (nV',)
+    new -> the smallest old vertex id of its class, ascending; vertex_index (nV,) old -> new, a welded vertex mapping to its
+    class, -1 only for a dropped one; face_map (nF',) the original index of every kept face, ascending; flipped (nF',) int32, 1
+    where the face was turned from (a, b, c) to (a, c, b); and as Python ints: welded_vertices, bad_faces (an index outside the
+    mesh, a non-finite vertex or, after welding, a repeated index), duplicate_faces, degenerate_faces (kept faces of zero area on
+    three distinct vertices: counted, never repaired), nonmanifold_edges (three and more faces: they link nothing),
+    nonorientable_classes (left as they came) and classes.  Synchronises once."""
+    tol = float(tol)
+    if not 0.0 <= tol < float("inf"):
+        raise ValueError(f"repair_mesh: tol must be finite and >= 0, got {tol!r}")
+    if not torch.is_tensor(V):
+        V = torch.from_numpy(np.array(V, dtype=np.float32)).to("cuda")
+    if not torch.is_tensor(F):
+        F = torch.from_numpy(np.array(F)).to(V.device)
+    if V.dim() != 2 or V.shape[1] != 3 or F.dim() != 2 or F.shape[1] != 3:
+        raise ValueError(f"repair_mesh wants V (nV, 3) and F (nF, 3), got {tuple(V.shape)} and {tuple(F.shape)}")
+    if F.dtype not in (torch.int32, torch.int64) or not V.is_floating_point():
+        raise TypeError("repair_mesh wants floating-point V and int32 or int64 F")
+    kernels._dev(V, F)
+    Vf, Fi = V.float().contiguous(), F.to(torch.int32).contiguous()
+    nV = Vf.shape[0]
+    w = kernels.mesh_weld(Vf, Fi, tol, weld)
+    u = kernels.mesh_unique_faces(w.F, nV, Vf, unique)
+    words = [w.counts, u.counts, w.status, u.status]
+    if orient:
+        o = kernels.mesh_orient(w.F, u.keep, nV)
+        Fo, flip = o.F, o.flip
+        words += [o.counts, o.status]
+    else:
+        Fo, flip = w.F, torch.zeros(Fi.shape[0], dtype=torch.int32, device=Fi.device)
+    out = kernels.mesh_compact(Fo, u.keep, nV, Vf)
+    got = torch.cat([out.sizes] + words).tolist()                                         # the one read
+    nVk, nFk, welded, bad, dup, flat, st_w, st_u = got[:8]
+    nonman, twisted, classes, st_o = got[8:] if orient else (-1, -1, -1, 0)
+    if (st_w | st_u | st_o) & kernels.REPAIR_INTERNAL:
+        raise RuntimeError("repair_mesh: the repair kernels hit a loop bound (status SN_REPAIR_INTERNAL)")
+    face_map = out.Fsrc[:nFk]
+    return RepairedMesh(out.Vnew[:nVk], out.Fnew[:nFk], out.J[:nVk], out.I[w.rep.long()], face_map, flip[face_map.long()], welded, bad,
+                        dup, flat, nonman, twisted, classes)
 
 
 class PackedSegments:
