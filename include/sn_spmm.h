@@ -485,6 +485,19 @@ int sn_masked_smooth_l1_fwd_f32(const float *out, int64_t ldo, const float *targ
 int sn_masked_smooth_l1_bwd_f32(const float *out, int64_t ldo, const float *target, int64_t ldt, const float *rowmask,
                                 int64_t rows, int32_t C, double scale, const float *gloss, float *gout, int64_t ldg,
                                 void *stream);
+/* Loss and gradient in one pass over out and target (a training step reads them once instead of twice):
+ *   sn_masked_smooth_l1_fwdg_f32 : the loss of sn_masked_smooth_l1_fwd_f32 — the same grid, items and order of the sum, so the
+ *                   same bits — and gout as sn_masked_smooth_l1_bwd_f32 writes it for gloss[0] == 1 (the same expression, so the
+ *                   same bits).  Where out and target allow 16-byte items, gout must too (SN_E_ALIGN otherwise).
+ *   sn_masked_smooth_l1_bwdg_f32 : sn_masked_smooth_l1_bwd_f32 over a gout that sn_masked_smooth_l1_fwdg_f32 filled for the same
+ *                   operands: gout is kept when gloss[0] == 1 — tested on the device, gloss may be written by a captured graph —
+ *                   and recomputed from out and target otherwise.  Same result as sn_masked_smooth_l1_bwd_f32 for every gloss. */
+int sn_masked_smooth_l1_fwdg_f32(const float *out, int64_t ldo, const float *target, int64_t ldt, const float *rowmask,
+                                 int64_t rows, int32_t C, double scale, float *loss, float *gout, int64_t ldg, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+int sn_masked_smooth_l1_bwdg_f32(const float *out, int64_t ldo, const float *target, int64_t ldt, const float *rowmask,
+                                 int64_t rows, int32_t C, double scale, const float *gloss, float *gout, int64_t ldg,
+                                 void *stream);
 /* sn_gather_segments_f32: batch assembly of dense per-sample windows (the ARAP sampler's inputs / targets,
  * src/as_rigid_as_possible/main.py:126-152): out[(i*rows_per_item + r)*len + c] = src[base[i] + r*row_stride + c],
  * i < nitems, r < rows_per_item, c < len; base is a DEVICE array of element offsets into the resident dataset. */
@@ -1302,6 +1315,17 @@ int sn_linear_dgrad_eluseg_f32(const float *dy, int64_t lddy, const float *W, in
 int sn_linear_fwd_tiles_f32(const float *x, int64_t ldx, const float *W, int64_t ldw, const float *bias, const float *residual,
                             int64_t ldr, float *y, int64_t ldy, float *y_elu, int64_t lde, int64_t rows, int32_t K, int32_t J,
                             double *elu_stats_part, float *tile_sums, void *stream);
+/* sn_linear_fwd_frame_f32: the plain forward launch (y only) of a layer whose J outputs are J/3 frames of 3 coordinates — the ARAP
+ * models' last layer, 40 predicted frames (src/as_rigid_as_possible/models.py:105,152: `x + inputs[:, :, -3:].repeat(1, 1, 40)`):
+ *   y[r][3t + c] = (x·Wᵀ + bias)[r][3t + c] + frame[r·ldf + c],   c < 3, t < J/3
+ * with the product and bias formed exactly as sn_linear_fwd_tiles_f32 forms them and the frame value added by one further fp32
+ * addition: the same bits as that launch followed by a broadcast add over its result, without the second pass over y.  J a
+ * multiple of 12 (J <= 128), K in {128, 256}; frame needs 4-byte alignment only (ldf >= 3: e.g. the last three columns of the
+ * (rows, 6) input); only its three addressed columns of rows < `rows` are read.  16-bit matrix-pipe kernels only:
+ * sn_linear_fwd_frame_supported says whether this process has them for a K -> J layer (SN_E_UNSUPPORTED otherwise). */
+int32_t sn_linear_fwd_frame_supported(int32_t K, int32_t J);
+int sn_linear_fwd_frame_f32(const float *x, int64_t ldx, const float *W, int64_t ldw, const float *bias, const float *frame,
+                            int64_t ldf, float *y, int64_t ldy, int64_t rows, int32_t K, int32_t J, void *stream);
 int sn_linear_fwd_segbias_tiles_f32(const float *x, int64_t ldx, const float *W, int64_t ldw, const float *segbias,
                                     int64_t rows_per_seg, const float *residual, int64_t ldr, float *y, int64_t ldy, float *y_elu,
                                     int64_t lde, int64_t rows, int32_t K, int32_t J, double *elu_stats_part, float *tile_sums,

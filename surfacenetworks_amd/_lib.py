@@ -98,6 +98,8 @@ SIGNATURES = {
     "sn_masked_smooth_l1_workspace_bytes": (_sz, [_i64, _i32]),
     "sn_masked_smooth_l1_fwd_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, C.c_double, _vp, _vp, _sz, _vp]),
     "sn_masked_smooth_l1_bwd_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, C.c_double, _vp, _vp, _i64, _vp]),
+    "sn_masked_smooth_l1_fwdg_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, C.c_double, _vp, _vp, _i64, _vp, _sz, _vp]),
+    "sn_masked_smooth_l1_bwdg_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, C.c_double, _vp, _vp, _i64, _vp]),
     "sn_pair_argmin_f32": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
     "sn_pair_ce_fwd_f32": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
     "sn_pair_ce_bwd_f32": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp]),
@@ -180,6 +182,8 @@ SIGNATURES = {
     "sn_linear_small_rows": (_i64, []),
     "sn_linear_fwd_form": (_i32, [_i64, _i32, _i32, _i32, _i32, _i32, _i32]),
     "sn_linear_fwd_tiles_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "sn_linear_fwd_frame_supported": (_i32, [_i32, _i32]),
+    "sn_linear_fwd_frame_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp]),
     "sn_linear_fwd_segbias_tiles_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32,
                                                   _vp, _vp, _vp]),
     "sn_avg_stats_from_tiles_ragged_f32": (C.c_int, [_vp, _vp, _i32, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),

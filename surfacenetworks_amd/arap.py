@@ -25,6 +25,11 @@ from .operators import OperatorPool, PackedSegments, h2d_async
 INPUT_FRAMES = 2       # main.py:105
 OUTPUT_FRAMES = 40     # main.py:106
 
+# The output end of the step without the passes its result does not need (LABNOTES.md#steptail): the last-frame residual added
+# in the last GEMM's store, the loss gradient written by the loss pass, and the last Dirac block's pre-activation vertex output —
+# which only its activated copy's consumer, conv2, would read — not written.  False: the unfused composition, same bits.
+FUSED_TAIL = True
+
 
 def _num_faces(Di, DiA, batch_size):
     """models.py:133-136 — works for 3-D batched and 2-D block-diagonal operators."""
@@ -37,6 +42,16 @@ def _add_last_frame(x, inputs, frames):
     tensor is never written."""
     B, V, _ = x.shape
     return (x.reshape(B, V, frames, 3) + inputs[:, :, None, -3:]).reshape(B, V, 3 * frames)
+
+
+def _predict(conv2, x, inputs):
+    """_add_last_frame(elu_conv1x1(conv2, x), inputs, OUTPUT_FRAMES) — how the BatchNorm models leave (models.py:148-152).
+    FUSED_TAIL: the last input frame is added in the last GEMM's own store (same bits, no second pass over the 120-column
+    output) where the layer and the operands are covered; inputs that want a gradient keep the torch add, which carries it."""
+    frame = inputs[:, :, -3:]
+    if FUSED_TAIL and utils.elu_conv1x1_frame_ok(conv2, x, frame):
+        return utils.elu_conv1x1(conv2, x, frame)
+    return _add_last_frame(utils.elu_conv1x1(conv2, x), inputs, OUTPUT_FRAMES)
 
 
 class Model(nn.Module):
@@ -62,8 +77,7 @@ class Model(nn.Module):
                 x = blk(L, mask, x, avg_next=i + 1 < self.layer)      # (a global-average block follows: hand it the tile sums)
             else:
                 x = blk(L, mask, x)
-        x = utils.elu_conv1x1(self.conv2, x)
-        return _add_last_frame(x, inputs, OUTPUT_FRAMES)
+        return _predict(self.conv2, x, inputs)
 
 
 class AvgModel(nn.Module):
@@ -80,8 +94,7 @@ class AvgModel(nn.Module):
         x = self.conv1(inputs)
         for i in range(15):
             x = self._modules["rn{}".format(i)](L, mask, x)
-        x = utils.elu_conv1x1(self.conv2, x)
-        return _add_last_frame(x, inputs, OUTPUT_FRAMES)
+        return _predict(self.conv2, x, inputs)
 
 
 class MlpModel(nn.Module):
@@ -119,31 +132,43 @@ class DirModel(nn.Module):
         v = self.conv1(inputs)
         f = None                                                   # f = zeros(batch, faces, 128) (models.py:138), not materialised
         nf = _num_faces(Di, DiA, batch_size)
+        # the last block's pre-activation output feeds conv2 alone, which reads its activated copy: not written (FUSED_TAIL)
+        last_v = not (FUSED_TAIL and utils.USE_WHOLE_BLOCKS and utils.snB.elu_conv_ok(self.conv2, v))
         for i in range(15):
             blk = self._modules["rn{}".format(i)]
             if i % 2 == 0:
                 v, f = blk(Di, DiA, v, f, f_out_needed=False, num_faces=nf,   # f only feeds the next Dirac block (models.py:139-147)
-                           avg_next=i + 1 < 15)                                # (a global-average block follows: hand it the tile sums)
+                           avg_next=i + 1 < 15,                                # (a global-average block follows: hand it the tile sums)
+                           v_out_needed=i + 1 < 15 or last_v)
             else:
                 v = blk(None, mask, v)
-        x = utils.elu_conv1x1(self.conv2, v)
-        return _add_last_frame(x, inputs, OUTPUT_FRAMES)
+        return _predict(self.conv2, v, inputs)
 
 
 class _MaskedSmoothL1(torch.autograd.Function):
     """sum smooth_l1(outputs * mask, targets) / batch_size as one pass forward (fp64 sums) and one pass backward
-    (kernels.masked_smooth_l1_*) instead of five elementwise passes over the (B, V, 120) tensors."""
+    (kernels.masked_smooth_l1_*) instead of five elementwise passes over the (B, V, 120) tensors.  FUSED_TAIL, when a gradient
+    will be asked for: ONE pass — the forward also writes the gradient for gloss = 1 (what every driver's loss.backward()
+    passes), and the backward launch returns at once unless gloss is something else (kernels.masked_smooth_l1_fwdg / _bwdg).
+    That buffer, (rows, C) floats, then lives from the loss to the backward instead of being allocated by the backward."""
 
     @staticmethod
-    def forward(ctx, out2d, tgt2d, rowmask, scale):
+    def forward(ctx, out2d, tgt2d, rowmask, scale, with_grad=False):
         ctx.save_for_backward(out2d, tgt2d, rowmask)
         ctx.scale = scale
+        ctx.g = None
+        if with_grad:                          # (loss_fn: a backward can follow; no_grad / evaluation allocate nothing)
+            loss, ctx.g = kernels.masked_smooth_l1_fwdg(out2d, tgt2d, rowmask, scale)
+            return loss
         return kernels.masked_smooth_l1_fwd(out2d, tgt2d, rowmask, scale)
 
     @staticmethod
     def backward(ctx, gloss):
         out2d, tgt2d, rowmask = ctx.saved_tensors
-        return kernels.masked_smooth_l1_bwd(out2d, tgt2d, rowmask, ctx.scale, gloss.contiguous()), None, None, None
+        g, ctx.g = ctx.g, None                                            # (a second backward recomputes it whole)
+        if g is not None:
+            return kernels.masked_smooth_l1_bwdg(out2d, tgt2d, rowmask, ctx.scale, gloss.contiguous(), g), None, None, None, None
+        return kernels.masked_smooth_l1_bwd(out2d, tgt2d, rowmask, ctx.scale, gloss.contiguous()), None, None, None, None
 
 
 def loss_fn(outputs, targets, mask, batch_size):
@@ -154,8 +179,10 @@ def loss_fn(outputs, targets, mask, batch_size):
     if outputs.dim() == 3 and outputs.dtype == torch.float32 and targets.dtype == torch.float32 and \
             not targets.requires_grad and mask.numel() == outputs.shape[0] * outputs.shape[1]:
         C = outputs.shape[2]
+        # (inside the node grad mode is always off: whether a backward can follow is decided here)
+        with_grad = bool(FUSED_TAIL and outputs.is_cuda and outputs.requires_grad and torch.is_grad_enabled())
         out = _MaskedSmoothL1.apply(outputs.reshape(-1, C), targets.reshape(-1, C).contiguous(),
-                                    mask.reshape(-1).to(torch.float32).contiguous(), 1.0 / batch_size)
+                                    mask.reshape(-1).to(torch.float32).contiguous(), 1.0 / batch_size, with_grad)
         return out
     outputs = outputs * mask.expand_as(outputs)
     return F.smooth_l1_loss(outputs, targets, reduction="sum") / batch_size

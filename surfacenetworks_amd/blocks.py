@@ -30,7 +30,8 @@ from .functional import (SpmmTimer, _launch, _rows2d, product_form, avg_stage_ba
 from .graphs import active_capture
 from .operators import as_operator
 
-__all__ = ["lap_block", "dirac_block", "avg_block", "avg_block_ragged", "avg_block_ragged_ok", "take_activated", "attach_activated", "zero_faces_ok", "elu_conv", "elu_conv_ok"]
+__all__ = ["lap_block", "dirac_block", "avg_block", "avg_block_ragged", "avg_block_ragged_ok", "take_activated", "attach_activated", "zero_faces_ok", "elu_conv", "elu_conv_ok",
+           "elu_conv_frame_ok"]
 
 
 # A Dirac block whose face input is the activated hand-off of a block that ran with need_f=False returns the gradient of that
@@ -313,11 +314,12 @@ def _nan_placeholder(device):
     return t
 
 
-def _dirac_fwd(v, f, pre_v, pre_f, g0, b0, W0, c0, rm0, rv0, g1, b1, W1, c1, rm1, rv1, opDi, opDiA, need_f, avg_next, tr0, mo0,
-               ep0, tr1, mo1, ep1):
+def _dirac_fwd(v, f, pre_v, pre_f, g0, b0, W0, c0, rm0, rv0, g1, b1, W1, c1, rm1, rv1, opDi, opDiA, need_f, need_v, avg_next, tr0,
+               mo0, ep0, tr1, mo1, ep1):
     """DirResNet2 (utils_pt.py:191-220):
          cat0 = [elu(f), Di·elu(v)]  -> f_out = Lin(BN(cat0));   cat1 = [elu(v), DiA·elu(f_out)] -> v + Lin(BN(cat1)).
-    Returns ((v_new, f_out | None, nxt_v, nxt_f), saved)."""
+    Returns ((v_new | None, f_out | None, nxt_v, nxt_f), saved); need_v=False: only the activated copy of v_new (nxt_v's first
+    half) is written, where the fused GEMM offers that."""
     rv, C = v.shape
     rf = opDi.shape[0] // 4
     cat1 = _activated(v, pre_v)
@@ -338,7 +340,8 @@ def _dirac_fwd(v, f, pre_v, pre_f, g0, b0, W0, c0, rm0, rv0, g1, b1, W1, c1, rm1
     nxt_v = _new_cat(rv, C, v.device)
     pv = _new_part(rv, C, v.device, narrow=True)
     tv = _new_tiles(rv, C, v.device, pv, avg_next)
-    v_new, st1 = bnlin_forward(cat1, g1, b1, W1, c1, rm1, rv1, tr1, mo1, ep1, v, nxt_v[:, :C], elu_stats=pv, tile_sums=tv)
+    v_new, st1 = bnlin_forward(cat1, g1, b1, W1, c1, rm1, rv1, tr1, mo1, ep1, v, nxt_v[:, :C], want_y=need_v, elu_stats=pv,
+                               tile_sums=tv)
     _attach_part(nxt_v, pv, tv)
     return (v_new, f_out, nxt_v, nxt_f), ((cat0, cat1, nxt_f), st0, st1)
 
@@ -397,8 +400,8 @@ class _DiracBlock(torch.autograd.Function):
     """DirResNet2 as one autograd node (_dirac_fwd / _dirac_bwd), through a launch plan when the block is plannable."""
 
     @staticmethod
-    def forward(ctx, v, f, opDi, opDiA, pre_v, pre_f, need_f, avg_next, g0, b0, W0, c0, rm0, rv0, tr0, mo0, ep0, g1, b1, W1, c1,
-                rm1, rv1, tr1, mo1, ep1):
+    def forward(ctx, v, f, opDi, opDiA, pre_v, pre_f, need_f, need_v, avg_next, g0, b0, W0, c0, rm0, rv0, tr0, mo0, ep0, g1, b1, W1,
+                c1, rm1, rv1, tr1, mo1, ep1):
         v = _rows2d(v)
         if f is not None and pre_f is None:
             f = _rows2d(f)                     # (with a hand-off f is only a carrier — possibly the zero-stride NaN placeholder of
@@ -414,7 +417,7 @@ class _DiracBlock(torch.autograd.Function):
             box[0] = True
         ctx.rawbox = [False] if not need_f else None
         tensors = (v, f, pre_v, pre_f, g0, b0, W0, c0, rm0, rv0, g1, b1, W1, c1, rm1, rv1)
-        consts = (need_f, avg_next, tr0, mo0, ep0, tr1, mo1, ep1)
+        consts = (need_f, need_v, avg_next, tr0, mo0, ep0, tr1, mo1, ep1)
         outs = None
         ctx._sn_plan = None
         if plans.usable(v):
@@ -433,6 +436,10 @@ class _DiracBlock(torch.autograd.Function):
             f_out = _nan_placeholder(v.device).expand(nxt_f.shape[0], v.shape[1])
             if ctx.rawbox is not None:
                 nxt_f._sn_rawbox = ctx.rawbox
+        if v_new is None:
+            # need_v=False: the caller hands v to elu_conv only, which reads the activated hand-off (165 MB of stores at the ARAP
+            # batch); the gradient of the pre-activation output arrives from there as ever
+            v_new = _nan_placeholder(v.device).expand(v.shape[0], v.shape[1])
         ctx.mark_non_differentiable(nxt_v, nxt_f)
         ctx.set_materialize_grads(False)
         return v_new, f_out, nxt_v, nxt_f
@@ -440,7 +447,7 @@ class _DiracBlock(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_vnew, g_fout, _gv, _gf):
         if g_vnew is None and g_fout is None:
-            return (None,) * 26
+            return (None,) * 27
         opDi, opDiA = ctx.ops
         g_vnew = g_vnew.contiguous() if g_vnew is not None else None
         g_fout = g_fout.contiguous() if g_fout is not None else None
@@ -455,7 +462,7 @@ class _DiracBlock(torch.autograd.Function):
         else:
             r = _dirac_bwd(unstash(ctx), opDi, opDiA, g_vnew, g_fout, *consts)
         none5 = (None,) * 5
-        return (r[0], r[1], None, None, None, None, None, None) + r[2:6] + none5 + r[6:10] + none5
+        return (r[0], r[1], None, None, None, None, None, None, None) + r[2:6] + none5 + r[6:10] + none5
 
 
 def _drop_counters(*running_means) -> None:
@@ -467,12 +474,14 @@ def _drop_counters(*running_means) -> None:
             d.pop("_sn_nbt", None)
 
 
-def dirac_block(mod, Di, DiA, v, f, need_f=True, num_faces=None, avg_next=None):
+def dirac_block(mod, Di, DiA, v, f, need_f=True, num_faces=None, avg_next=None, need_v=True):
     """DirResNet2.forward on (B, V, C) / (B, F, C) tensors; `mod` supplies bn_fc0 / bn_fc1.  need_f=False: the returned
     face features are only a carrier of the activated hand-off for the next Dirac block (see _DiracBlock.forward).
     f=None (with num_faces): all-zero face features, never materialised (zero_faces_ok says when).
     avg_next: the vertex output feeds a global-average block next: the GEMM that writes its activated copy also leaves the
-    per-tile column sums that block needs (no statistics pass over its operand)."""
+    per-tile column sums that block needs (no statistics pass over its operand).
+    need_v=False: the returned vertex features are only a carrier of the activated hand-off for elu_conv — the models' last layer —
+    and come back as the NaN placeholder where the fused GEMM can leave them unwritten."""
     B, V, C = v.shape
     F_ = f.shape[1] if f is not None else int(num_faces)
     rv, rf = B * V, B * F_
@@ -481,7 +490,7 @@ def dirac_block(mod, Di, DiA, v, f, need_f=True, num_faces=None, avg_next=None):
         raise ValueError(f"DirResNet2: Di {tuple(opDi.shape)} / DiA {tuple(opDiA.shape)} do not match v rows {rv}, f rows {rf}")
     v_new, f_out, nxt_v, nxt_f = _DiracBlock.apply(v.reshape(rv, C), f.reshape(rf, C) if f is not None else None, opDi, opDiA,
                                                   take_activated(v, rv, C),
-                                                  take_activated(f, rf, C) if f is not None else None, bool(need_f),
+                                                  take_activated(f, rf, C) if f is not None else None, bool(need_f), bool(need_v),
                                                   _wants_tiles(mod, avg_next), *_bn_args(mod._modules["bn_fc0"]), *_bn_args(mod._modules["bn_fc1"]))
     _mark_producer(nxt_v, mod, avg_next)
     return attach_activated(v_new.view(B, V, C), nxt_v), attach_activated(f_out.view(B, F_, C), nxt_f)
@@ -775,12 +784,12 @@ def avg_block_ragged(mod, seg, inputs):
     return attach_activated(out.view(B, V, C), nxt)
 
 
-def _elu_conv_fwd(v, pre, g0, b0, W0, c0, rm0, rv0, tr0, mo0, ep0):
+def _elu_conv_fwd(v, pre, frame, g0, b0, W0, c0, rm0, rv0, tr0, mo0, ep0):
     C = v.shape[1]
     cat = _activated(v, pre)
     part = getattr(cat, "_sn_part", None)        # statistics of elu(v) left by the GEMM that wrote it
     pre_stats = kernels.colstats_from_part(part, v.shape[0]) if (part is not None and tr0 and C == 128) else None
-    y, st = bnlin_forward(cat[:, :C], g0, b0, W0, c0, rm0, rv0, tr0, mo0, ep0, pre_stats=pre_stats)
+    y, st = bnlin_forward(cat[:, :C], g0, b0, W0, c0, rm0, rv0, tr0, mo0, ep0, pre_stats=pre_stats, frame=frame)
     return (y,), (st,)
 
 
@@ -793,17 +802,19 @@ def _elu_conv_bwd(saved, dy, need_gv):
 class _EluConv(torch.autograd.Function):
     """GraphConv1x1("pre")(F.elu(v)) — the models' last layer (src/as_rigid_as_possible/models.py:148-150) — as one node:
     elu(v) is the activated hand-off of the preceding block when there is one (no ELU pass), and the backward runs the
-    BatchNorm tail and the activation derivative as one pass."""
+    BatchNorm tail and the activation derivative as one pass.  frame ((rows, 3) view, optional; no gradient): added to every group
+    of three outputs in the GEMM's store (elu_conv_frame_ok)."""
 
     @staticmethod
-    def forward(ctx, v, pre, g0, b0, W0, c0, rm0, rv0, tr0, mo0, ep0):
-        v = _rows2d(v)
-        tensors = (v, pre, g0, b0, W0, c0, rm0, rv0)
+    def forward(ctx, v, pre, frame, g0, b0, W0, c0, rm0, rv0, tr0, mo0, ep0):
+        if pre is None:
+            v = _rows2d(v)                     # (with a hand-off v is only a carrier — possibly the NaN placeholder of need_v=False)
+        tensors = (v, pre, frame, g0, b0, W0, c0, rm0, rv0)
         consts = (tr0, mo0, ep0)
         ctx._sn_plan = None
         outs = None
         if plans.usable(v):
-            outs = _plan_forward(ctx, _SITES["elu_conv_fwd"], _elu_conv_fwd, tensors, (), consts, v.shape[1], 2, (1, 6))
+            outs = _plan_forward(ctx, _SITES["elu_conv_fwd"], _elu_conv_fwd, tensors, (), consts, v.shape[1], 3, (1, 7))
             if outs is not None:
                 _drop_counters(rm0)
         ctx._sn_planned = outs is not None
@@ -820,15 +831,41 @@ class _EluConv(torch.autograd.Function):
             r = _plan_backward(ctx, _SITES["elu_conv_bwd"], _elu_conv_bwd, (dy,), (need,))
         else:
             r = _elu_conv_bwd(unstash(ctx), dy, need)
-        return (r[0], None) + r[1:5] + (None,) * 5
+        return (r[0], None, None) + r[1:5] + (None,) * 5
 
 
-def elu_conv(conv, v):
-    """conv(F.elu(v)) for a GraphConv1x1 with batch_norm="pre" on a (B, N, C) tensor, as one autograd node."""
+def _unwritten(t: torch.Tensor) -> bool:
+    """The zero-stride NaN stand-in a block returns for an output it was told not to write (_nan_placeholder)."""
+    return t.numel() > 1 and not any(t.stride())
+
+
+def elu_conv(conv, v, frame=None):
+    """conv(F.elu(v)) for a GraphConv1x1 with batch_norm="pre" on a (B, N, C) tensor, as one autograd node.
+    frame ((B, N, 3), elu_conv_frame_ok): y[..., 3t + c] += frame[..., c] in the GEMM's store."""
     B, N, C = v.shape
     rows = B * N
-    y = _EluConv.apply(v.reshape(rows, C), take_activated(v, rows, C), *_bn_args(conv))
+    pre = take_activated(v, rows, C)
+    if pre is None and _unwritten(v):
+        raise RuntimeError("elu_conv: the vertex features are the placeholder of a block that ran with v_out_needed=False, and the "
+                           "activated hand-off that stands for them is gone (taken by another consumer, or the tensor was copied)")
+    if frame is not None:
+        frame = frame.detach().reshape(rows, 3)
+    y = _EluConv.apply(v.reshape(rows, C), pre, frame, *_bn_args(conv))
     return y.view(B, N, conv.num_outputs)
+
+
+def elu_conv_frame_ok(conv, v, frame) -> bool:
+    """elu_conv can add `frame` — (B, N, 3) float32, e.g. the last three columns of the (B, N, 6) input, nothing that wants a
+    gradient — in the GEMM's store: on the device, outputs in whole groups of twelve, rows that one 2-D view addresses."""
+    B, N, C = v.shape
+    J = conv.num_outputs
+    if not (v.is_cuda and frame.is_cuda and frame.dtype == torch.float32 and tuple(frame.shape) == (B, N, 3)) or \
+            (frame.requires_grad and torch.is_grad_enabled()):
+        return False
+    if not (kernels.linear_fwd_supported(C, J) and kernels.linear_fwd_frame_supported(C, J)):
+        return False
+    s = frame.stride()
+    return s[2] == 1 and s[1] >= 3 and (B == 1 or s[0] == N * s[1]) and frame.data_ptr() % 4 == 0
 
 
 def elu_conv_ok(conv, v) -> bool:

@@ -17,6 +17,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "sn_dense_common.h"
 
 namespace {
@@ -743,7 +745,9 @@ __global__ __launch_bounds__(kWG) void masked_sl1_final_k(const double *__restri
 
 __device__ __forceinline__ float sl1_grad(float d) { return d < -1.f ? -1.f : (d > 1.f ? 1.f : d); }
 
-template <bool VEC>
+// SKIP1: g already holds the gradient for gloss == 1 (masked_sl1_fwdg_k wrote it with this kernel's own expression): the
+// launch is then over after one uniform load; any other gloss recomputes g from out and target as always, over the same buffer.
+template <bool VEC, bool SKIP1 = false>
 __global__ __launch_bounds__(kWG) void masked_sl1_bwd_k(const float *__restrict__ o, int64_t ldo,
                                                         const float *__restrict__ t, int64_t ldt,
                                                         const float *__restrict__ mask, int64_t rows, int C, float scale,
@@ -752,6 +756,8 @@ __global__ __launch_bounds__(kWG) void masked_sl1_bwd_k(const float *__restrict_
   constexpr int W = VEC ? 4 : 1;
   const int cw = C / W;
   const int64_t total = rows * cw;
+  if constexpr (SKIP1)
+    if (gloss[0] == 1.0f) return;
   const float gs = gloss[0] * scale;
   for (int64_t i = (int64_t)blockIdx.x * kWG + threadIdx.x; i < total; i += (int64_t)gridDim.x * kWG) {
     const int64_t r = i / cw;
@@ -766,6 +772,85 @@ __global__ __launch_bounds__(kWG) void masked_sl1_bwd_k(const float *__restrict_
       g[r * ldg + c] = gm * sl1_grad(o[r * ldo + c] * m - t[r * ldt + c]);
     }
   }
+}
+
+// Loss and its gradient in ONE pass: masked_sl1_fwd_k's sum — same grid, same items per thread, added in the same order, so the
+// loss has the same bits — and, from the same difference, g = (1·scale)·m·sl1_grad(d): masked_sl1_bwd_k's expression for
+// gloss == 1.  Four items of a thread are requested before the first is consumed (the forward kernel has one 16-byte load pair in
+// flight per thread), and (row, column) of an item walk with the grid stride instead of a 64-bit division per item.
+template <bool VEC>
+__global__ __launch_bounds__(kWG) void masked_sl1_fwdg_k(const float *__restrict__ o, int64_t ldo,
+                                                         const float *__restrict__ t, int64_t ldt,
+                                                         const float *__restrict__ mask, int64_t rows, int C, float scale,
+                                                         double *__restrict__ partial, float *__restrict__ g, int64_t ldg) {
+  __shared__ double red[kWG];
+  constexpr int W = VEC ? 4 : 1;
+  constexpr int U = 4;
+  typedef typename std::conditional<VEC, f4, float>::type item_t;
+  const int cw = C / W;
+  const int64_t total = rows * cw;
+  const int64_t stride = (int64_t)gridDim.x * kWG;
+  const int64_t dr = stride / cw;                 // an item `stride` further on lies dr rows and dc items to the right (+ a carry)
+  const int dc = (int)(stride - dr * cw);
+  const float gs = 1.0f * scale;
+  int64_t i = (int64_t)blockIdx.x * kWG + threadIdx.x;
+  int64_t r = i / cw;
+  int ci = (int)(i - r * cw);
+  auto load = [&](const float *p) {
+    if constexpr (VEC) return ld4_s(p, 1);
+    else return *p;
+  };
+  auto consume = [&](const item_t &ov, const item_t &tv, float m, float *gp, double &acc) {
+    const float gm = gs * m;
+    if constexpr (VEC) {
+      const float dx = ov.x * m - tv.x, dy = ov.y * m - tv.y, dz = ov.z * m - tv.z, dw = ov.w * m - tv.w;
+      acc += sl1(dx) + sl1(dy) + sl1(dz) + sl1(dw);
+      st4_s(gp, f4{gm * sl1_grad(dx), gm * sl1_grad(dy), gm * sl1_grad(dz), gm * sl1_grad(dw)}, 1);
+    } else {
+      const float d = ov * m - tv;
+      acc += sl1(d);
+      *gp = gm * sl1_grad(d);
+    }
+  };
+  double acc = 0;
+  for (; i + (U - 1) * stride < total; i += U * stride) {
+    item_t ov[U], tv[U];
+    float m[U];
+    float *gp[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int c = ci * W;
+      m[u] = mask ? mask[r] : 1.f;
+      ov[u] = load(o + r * ldo + c);
+      tv[u] = load(t + r * ldt + c);
+      gp[u] = g + r * ldg + c;
+      r += dr;
+      ci += dc;
+      if (ci >= cw) {
+        ci -= cw;
+        ++r;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) consume(ov[u], tv[u], m[u], gp[u], acc);
+  }
+  for (; i < total; i += stride) {
+    const int c = ci * W;
+    consume(load(o + r * ldo + c), load(t + r * ldt + c), mask ? mask[r] : 1.f, g + r * ldg + c, acc);
+    r += dr;
+    ci += dc;
+    if (ci >= cw) {
+      ci -= cw;
+      ++r;
+    }
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = kWG / 2; s > 0; s >>= 1) {
+    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2751,9 +2836,38 @@ int sn_masked_smooth_l1_fwd_f32(const float *out, int64_t ldo, const float *targ
   return launch_status();
 }
 
-int sn_masked_smooth_l1_bwd_f32(const float *out, int64_t ldo, const float *target, int64_t ldt, const float *rowmask,
-                                int64_t rows, int32_t C, double scale, const float *gloss, float *gout, int64_t ldg,
-                                void *stream) {
+int sn_masked_smooth_l1_fwdg_f32(const float *out, int64_t ldo, const float *target, int64_t ldt, const float *rowmask,
+                                 int64_t rows, int32_t C, double scale, float *loss, float *gout, int64_t ldg, void *workspace,
+                                 size_t workspace_bytes, void *stream) {
+  (void)hipGetLastError();      // a stale error left by an earlier runtime call of this thread is not ours to report
+  if (rows < 0 || C < 1 || ldo < C || ldt < C || ldg < C) return SN_E_SHAPE;
+  if (!loss) return SN_E_NULL;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (rows == 0) {
+    const hipError_t e = sn_internal_fill(loss, 0, sizeof(float), s);
+    return e == hipSuccess ? SN_OK : (int)e;
+  }
+  if (!out || !target || !gout || !workspace) return SN_E_NULL;
+  if (workspace_bytes < (size_t)kLossBlocks * sizeof(double)) return SN_E_WORKSPACE;
+  // the forward's own predicate decides the items (hence the order of the sum); a gradient buffer that cannot take 16-byte stores
+  // is refused, not served by another order
+  const bool vec = (C % 4 == 0) && (ldo % 4 == 0) && (ldt % 4 == 0) && aligned16(out) && aligned16(target);
+  if (vec && ((ldg % 4) || !aligned16(gout))) return SN_E_ALIGN;
+  const int nblk = loss_blocks(rows * (vec ? C / 4 : C));
+  double *partial = static_cast<double *>(workspace);
+  if (vec)
+    hipLaunchKernelGGL((masked_sl1_fwdg_k<true>), dim3(nblk), dim3(kWG), 0, s, out, ldo, target, ldt, rowmask, rows, (int)C,
+                       (float)scale, partial, gout, ldg);
+  else
+    hipLaunchKernelGGL((masked_sl1_fwdg_k<false>), dim3(nblk), dim3(kWG), 0, s, out, ldo, target, ldt, rowmask, rows, (int)C,
+                       (float)scale, partial, gout, ldg);
+  hipLaunchKernelGGL(masked_sl1_final_k, dim3(1), dim3(kWG), 0, s, partial, nblk, scale, loss);
+  return launch_status();
+}
+
+static int masked_sl1_bwd_launch(const float *out, int64_t ldo, const float *target, int64_t ldt, const float *rowmask,
+                                 int64_t rows, int32_t C, double scale, const float *gloss, float *gout, int64_t ldg,
+                                 bool skip1, void *stream) {
   (void)hipGetLastError();      // a stale error left by an earlier runtime call of this thread is not ours to report
   if (rows < 0 || C < 1 || ldo < C || ldt < C || ldg < C) return SN_E_SHAPE;
   if (rows == 0) return SN_OK;
@@ -2764,13 +2878,32 @@ int sn_masked_smooth_l1_bwd_f32(const float *out, int64_t ldo, const float *targ
   const int64_t items = rows * (vec ? C / 4 : C);
   int64_t blocks = (items + kWG - 1) / kWG;
   if (blocks > 16 * 1024) blocks = 16 * 1024;
-  if (vec)
-    hipLaunchKernelGGL((masked_sl1_bwd_k<true>), dim3((unsigned)blocks), dim3(kWG), 0, s, out, ldo, target, ldt, rowmask, rows, (int)C,
-                       (float)scale, gloss, gout, ldg);
-  else
-    hipLaunchKernelGGL((masked_sl1_bwd_k<false>), dim3((unsigned)blocks), dim3(kWG), 0, s, out, ldo, target, ldt, rowmask, rows, (int)C,
-                       (float)scale, gloss, gout, ldg);
+#define SN_SL1_BWD(VEC_, SKIP_)                                                                                          \
+  hipLaunchKernelGGL((masked_sl1_bwd_k<VEC_, SKIP_>), dim3((unsigned)blocks), dim3(kWG), 0, s, out, ldo, target, ldt, rowmask, rows, \
+                     (int)C, (float)scale, gloss, gout, ldg)
+  if (skip1) {
+    if (vec) SN_SL1_BWD(true, true);
+    else SN_SL1_BWD(false, true);
+  } else {
+    if (vec) SN_SL1_BWD(true, false);
+    else SN_SL1_BWD(false, false);
+  }
+#undef SN_SL1_BWD
   return launch_status();
+}
+
+int sn_masked_smooth_l1_bwd_f32(const float *out, int64_t ldo, const float *target, int64_t ldt, const float *rowmask,
+                                int64_t rows, int32_t C, double scale, const float *gloss, float *gout, int64_t ldg,
+                                void *stream) {
+  return masked_sl1_bwd_launch(out, ldo, target, ldt, rowmask, rows, C, scale, gloss, gout, ldg, false, stream);
+}
+
+// gout holds what sn_masked_smooth_l1_fwdg_f32 left for the same operands: kept when gloss[0] == 1 (tested on the device: gloss
+// may be a captured graph's scalar), recomputed as sn_masked_smooth_l1_bwd_f32 otherwise
+int sn_masked_smooth_l1_bwdg_f32(const float *out, int64_t ldo, const float *target, int64_t ldt, const float *rowmask,
+                                 int64_t rows, int32_t C, double scale, const float *gloss, float *gout, int64_t ldg,
+                                 void *stream) {
+  return masked_sl1_bwd_launch(out, ldo, target, ldt, rowmask, rows, C, scale, gloss, gout, ldg, true, stream);
 }
 
 int sn_gather_segments_f32(const float *src, const int64_t *base, int64_t nitems, int64_t rows_per_item, int64_t row_stride,

@@ -91,6 +91,11 @@ struct EpiArgs {
   // the BatchNorm sums: per-mesh column sums follow from the tiles inside a mesh (sn_avg_stats_from_tiles_f32), so the
   // statistics pass over the operand (segstats_k: 165 MB per stage at the ARAP batch) disappears.  NULL: not wanted.
   float *tile_sums;
+  // forward, plain (no residual, no ELU copy), jv a multiple of 12 — the ARAP models' last layer, 40 predicted frames of 3
+  // coordinates: frame[r·ldf + c] is added to output columns 3t + c of row r AFTER the product and bias are complete (one separate
+  // fp32 add: the same bits as a broadcast add over the stored result).  frame rows are only 4-byte aligned (ldf >= 3).
+  const float *frame;
+  int64_t ldf;
 };
 constexpr int kAbsmaxBlocks = 512;      // >= the largest grid of any input-gradient launch (2 workgroups per CU)
 
@@ -367,7 +372,8 @@ __device__ __forceinline__ void bst4(rsrc_t r, int voff, const f4 &v) {         
 // RAWLOW (dgrad+elu only): the low half leaves as the BARE product — no BatchNorm tail, no activation derivative, no maximum —
 // and its side operand is never read: the transposed product that consumes it holds elu(.) in registers already and finishes
 // the gradient in its store (sn_spmm_q3_elubwd_tail_absmax_f32).  ep.v0 then points at column `half` of x.
-template <int PC, int K, int NT, bool TRANSW, int EPI, bool SIDE, bool ELU, bool SMALL = false, int WV = 4, bool RAWLOW = false>
+template <int PC, int K, int NT, bool TRANSW, int EPI, bool SIDE, bool ELU, bool SMALL = false, int WV = 4, bool RAWLOW = false,
+          bool FRAME = false>
 __global__ __launch_bounds__(64 * WV, (PC == 2 && K == 128 && NT == 1 && WV == 4) ? 2 : 1) void gemm_rows_split_k(const float *__restrict__ In, int64_t ldi,
                                                          const float *__restrict__ W, int64_t ldw,
                                                          float *__restrict__ Out, int64_t ldo, int64_t rows, EpiArgs ep) {
@@ -477,6 +483,7 @@ __global__ __launch_bounds__(64 * WV, (PC == 2 && K == 128 && NT == 1 && WV == 4
   constexpr bool DGE = (EPI == EPI_DGRAD_ELU);
   static_assert(!DGE || SIDE, "the ELU variant needs the BatchNorm tail operand");
   static_assert(!RAWLOW || DGE, "the raw low half is a form of the input gradient through the activation");
+  static_assert(!FRAME || (EPI == EPI_FWD && !SIDE && !ELU && NT == 1), "the frame epilogue is a form of the plain forward");
   const bool lowhalf = DGE && 32 * NT * wave < ep.half;          // a wave's 32·NT columns lie on one side (scalar condition)
   const bool colv = EPI != EPI_FWD || ecol < ep.jv;          // my 4 output columns exist
   if constexpr (EPI == EPI_FWD) {
@@ -504,7 +511,12 @@ __global__ __launch_bounds__(64 * WV, (PC == 2 && K == 128 && NT == 1 && WV == 4
   const int vo_out = colv ? 4 * (erow * (int)ldo + ecol) : kOob, js_out = 4 * RPI * (int)ldo;
   const int vo_o2 = colv ? 4 * (erow * (int)ep.ld2 + ecol) : kOob, js_o2 = 4 * RPI * (int)ep.ld2;
   const int vo_ga = 4 * (erow * (int)ep.ld3 + ecol), js_ga = 4 * RPI * (int)ep.ld3;
-  RowWindow w_in, w_side, w_out, w_o2, w_ga;
+  // FRAME: my columns ecol .. ecol + 3 take frame values (ecol + i) % 3, i.e. three dwords of the row in MY rotation (the
+  // fourth repeats the first): the rotation goes into the load offsets, once per kernel
+  const int fph = ecol % 3;
+  const int vo_fr = FRAME ? 4 * erow * (int)ep.ldf : 0, js_fr = FRAME ? 4 * RPI * (int)ep.ldf : 0;
+  const int fo0 = 4 * fph, fo1 = 4 * ((fph + 1) % 3), fo2 = 4 * ((fph + 2) % 3);
+  RowWindow w_in, w_side, w_out, w_o2, w_ga, w_fr;
   const int64_t row0 = tile * 32;
   // valid rows of a tile: 32 except in the matrix's last tile
   const int last_nrt = (int)(rows - (ntiles - 1) * 32);
@@ -522,6 +534,10 @@ __global__ __launch_bounds__(64 * WV, (PC == 2 && K == 128 && NT == 1 && WV == 4
   if constexpr (DGE) {
     if (has_ga) w_ga.init(ep.v4, ep.ld3, row0, last_nrt, ep.half);
     else w_ga.init_empty();
+  }
+  if constexpr (FRAME) {
+    w_fr.init(ep.frame, ep.ldf, row0, last_nrt, 3);
+    if (G > 1) w_fr.stride(G);
   }
   if (G > 1) {
     w_in.stride(G);
@@ -638,6 +654,18 @@ __global__ __launch_bounds__(64 * WV, (PC == 2 && K == 128 && NT == 1 && WV == 4
         }
       }
     }
+    // FRAME: the three values of each of my rows, REQUESTED here like the side operand and combined after the k loop (rows past
+    // the end lie beyond the window's extent: they read 0 and are not stored)
+    float fr[FRAME ? NST : 1][3];
+    if constexpr (FRAME) {
+      const rsrc_t r_fr = w_fr.rsrc(to_last);
+#pragma unroll
+      for (int j = 0; j < NST; ++j) {
+        fr[j][0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r_fr, vo_fr + j * js_fr + fo0, 0, 0));
+        fr[j][1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r_fr, vo_fr + j * js_fr + fo1, 0, 0));
+        fr[j][2] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r_fr, vo_fr + j * js_fr + fo2, 0, 0));
+      }
+    }
     f4 ga[NST];                        // dgrad+elu, low half: the gradient added after the activation derivative
     if constexpr (DGE && !RAWLOW) {
       if (lowhalf) {                   // (without the operand: an empty window — the loads return zeros, no traffic)
@@ -701,6 +729,7 @@ __global__ __launch_bounds__(64 * WV, (PC == 2 && K == 128 && NT == 1 && WV == 4
         if (useseg) v += (erow + RPI * j < nb ? sg0 : sg1);          // (scalar condition: a branch, not a select)
         else v += k0;
         if constexpr (SIDE) v += sd[j];
+        if constexpr (FRAME) v += f4{fr[j][0], fr[j][1], fr[j][2], fr[j][0]};      // (the GEMM's value is final: one more add)
       } else if constexpr (SIDE) {            // dgrad (both forms): BatchNorm tail
         const f4 xv = sd[j] - k0;
         v.x += __builtin_fmaf(xv.x, k1.x, k2.x);
@@ -784,6 +813,7 @@ __global__ __launch_bounds__(64 * WV, (PC == 2 && K == 128 && NT == 1 && WV == 4
     w_out.next();
     if constexpr (DGE || (EPI == EPI_FWD && ELU)) w_o2.next();
     if constexpr (DGE) w_ga.next();
+    if constexpr (FRAME) w_fr.next();
   };
   while (true) {
     do_tile(IC<0>{}, tile);
@@ -1209,6 +1239,44 @@ int sn_linear_fwd_tiles_f32(const float *x, int64_t ldx, const float *W, int64_t
     hipLaunchKernelGGL((gemm_rows_k<256, 1, false, EPI_FWD>), dim3(grid), dim3(kWG), 0, s, x, ldx, W, ldw, y, ldy, rows, ep);
   else
     hipLaunchKernelGGL((gemm_rows_k<128, 1, false, EPI_FWD>), dim3(grid), dim3(kWG), 0, s, x, ldx, W, ldw, y, ldy, rows, ep);
+  return launch_status();
+}
+
+// 1: sn_linear_fwd_frame_f32 covers a K -> J layer in this process (the 16-bit matrix-pipe kernels; J a multiple of 12)
+int32_t sn_linear_fwd_frame_supported(int32_t K, int32_t J) {
+  return gemm_variant() != 0 && (K == 128 || K == 256) && J >= 12 && J <= 128 && J % 12 == 0;
+}
+
+int sn_linear_fwd_frame_f32(const float *x, int64_t ldx, const float *W, int64_t ldw, const float *bias, const float *frame,
+                            int64_t ldf, float *y, int64_t ldy, int64_t rows, int32_t K, int32_t J, void *stream) {
+  (void)hipGetLastError();      // a stale error left by an earlier runtime call of this thread is not ours to report
+  if (rows < 0 || K < 1 || J < 1 || ldx < K || ldw < K || ldy < J || ldf < 3) return SN_E_SHAPE;
+  if (!sn_linear_fwd_frame_supported(K, J) || !ld32(ldx, ldy, ldf)) return SN_E_UNSUPPORTED;
+  if (rows == 0) return SN_OK;
+  if (!x || !W || !bias || !frame || !y) return SN_E_NULL;
+  if (!aligned16(x) || !aligned16(W) || !aligned16(bias) || !aligned16(y) || (ldy % 4) || (ldx % 4) || (ldw % 4) ||
+      (reinterpret_cast<uintptr_t>(frame) & 3u))
+    return SN_E_ALIGN;
+  EpiArgs ep{bias, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, 0, nullptr, 0, 0, nullptr, nullptr,
+             sn_linear_fwd_stats_blocks(rows), (int)J, nullptr, 0, nullptr, 1, nullptr, frame, ldf};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const unsigned grid = gemm_grid(rows, gemm_wgs(K, 1));
+  hipEvent_t t_start = nullptr, t_stop = nullptr;
+  sn_internal_timing_slot(0x100 | 4, rows, K, rows * 4 * ((int64_t)K + J + 3), J, &t_start, &t_stop);
+  // the forward launches of sn_linear_fwd_tiles_f32 for a plain output (same grid, same SMALL / large choice) with the frame add
+#define SN_FRAME_FWD(KK, SM)                                                                                           \
+  do {                                                                                                                 \
+    if (t_start) hipExtLaunchKernelGGL((gemm_rows_split_k<2, KK, 1, false, EPI_FWD, false, false, SM, 4, false, true>), dim3(grid), dim3(kWG), 0, s, t_start, t_stop, 0, x, ldx, W, ldw, y, ldy, rows, ep); \
+    else hipLaunchKernelGGL((gemm_rows_split_k<2, KK, 1, false, EPI_FWD, false, false, SM, 4, false, true>), dim3(grid), dim3(kWG), 0, s, x, ldx, W, ldw, y, ldy, rows, ep); \
+  } while (0)
+  if (K == 256) {
+    if (small_operand(rows)) SN_FRAME_FWD(256, true);
+    else SN_FRAME_FWD(256, false);
+  } else {
+    if (small_operand(rows)) SN_FRAME_FWD(128, true);
+    else SN_FRAME_FWD(128, false);
+  }
+#undef SN_FRAME_FWD
   return launch_status();
 }
 

@@ -498,10 +498,12 @@ def _take_counter(running_mean):
 
 
 def bnlin_forward(x, gamma, beta, W, b, running_mean, running_var, training, momentum, eps, residual=None, elu_out=None,
-                  want_y=True, elu_stats=None, pre_stats=None, tile_sums=None):
+                  want_y=True, elu_stats=None, pre_stats=None, tile_sums=None, frame=None):
     """Forward of the folded BatchNorm1d("pre") + Linear on a (rows, C) operand (no autograd): statistics in one pass
     (fp64 accumulation), BN folded into the weights  y = x·(W·diag(s))ᵀ + (b + W·t),  s = gamma*invstd, t = beta - mean*s,
-    optional residual add and ELU copy in the GEMM epilogue.  Returns (y, state) with `state` for bnlin_backward."""
+    optional residual add and ELU copy in the GEMM epilogue.  Returns (y, state) with `state` for bnlin_backward.
+    frame ((rows, 3) view; the caller has asked kernels.linear_fwd_frame_supported): added to every group of three outputs in the
+    GEMM's store (kernels.linear_fwd_frame) — a constant of the layer, nothing of it reaches the backward."""
     # x may carry `_sn_part`: the column statistics of its first half, left by the GEMM that wrote it (blocks.py) — the
     # statistics pass then reads only the propagated half
     part, part_hi = getattr(x, "_sn_part", None), getattr(x, "_sn_part_hi", None)   # (hi: left by the SpMM that wrote P·e)
@@ -524,7 +526,11 @@ def bnlin_forward(x, gamma, beta, W, b, running_mean, running_var, training, mom
                                                  running_var, nbt)
     if residual is not None:
         residual = _rows2d(residual)
-    if kernels.linear_fwd_supported(x.shape[1], W.shape[0]):
+    if frame is not None:
+        if residual is not None or elu_out is not None or not want_y:
+            raise ValueError("bnlin_forward: the frame epilogue belongs to the plain forward")
+        y = kernels.linear_fwd_frame(x, Wf, bf, frame)
+    elif kernels.linear_fwd_supported(x.shape[1], W.shape[0]):
         y = kernels.linear_fwd(x, Wf, bf, residual, elu_out, want_y, elu_stats, tile_sums)   # row-streaming GEMM, weights in registers
     else:
         if elu_stats is not None:

@@ -1459,6 +1459,25 @@ def linear_fwd(x, W, bias, residual=None, y_elu=None, want_y: bool = True, elu_s
     return y if keep else None
 
 
+def linear_fwd_frame_supported(K: int, J: int) -> bool:
+    """linear_fwd_frame covers a K -> J layer: J/3 frames of 3 coordinates, J a multiple of 12 (split kernels only)."""
+    return bool(_lib.load().sn_linear_fwd_frame_supported(int(K), int(J)))
+
+
+def linear_fwd_frame(x, W, bias, frame):
+    """y[r, 3t + c] = (x·Wᵀ + bias)[r, 3t + c] + frame[r, c]: linear_fwd's plain launch with the per-row frame (a (rows, 3) view of
+    any row stride, 4-byte aligned) added in the store — the bits of linear_fwd followed by the broadcast add
+    (sn_linear_fwd_frame_f32)."""
+    _dev(x, W, bias, frame)
+    rows, K = x.shape
+    J = W.shape[0]
+    if frame.shape != (rows, 3) or frame.dtype != torch.float32:
+        raise ValueError(f"linear_fwd_frame: frame must be a ({rows}, 3) float32 view, got {tuple(frame.shape)} {frame.dtype}")
+    y = torch.empty((rows, J), dtype=torch.float32, device=x.device)
+    _lib.call("sn_linear_fwd_frame_f32", _p(x), _ld(x), _p(W), _ld(W), _p(bias), _p(frame), _ld(frame), _p(y), J, rows, K, J, _stream())
+    return y
+
+
 def avg_stats_from_tiles(tile_sums, part, e, mask, inv_count, rows_per_seg: int, nseg: int):
     """(m, stats) of avg_stats WITHOUT a pass over e: from the per-tile column sums and the statistics partials the GEMM that
     wrote e left (sn_avg_stats_from_tiles_f32)."""
@@ -2076,6 +2095,32 @@ def masked_smooth_l1_bwd(out2d, target2d, rowmask, scale: float, gloss):
     rows, C = out2d.shape
     g = torch.empty((rows, C), dtype=torch.float32, device=out2d.device)
     _lib.call("sn_masked_smooth_l1_bwd_f32", _p(out2d), _ld(out2d), _p(target2d), _ld(target2d), _p(rowmask), rows, C,
+              float(scale), _p(gloss), _p(g), C, _stream())
+    return g
+
+
+def masked_smooth_l1_fwdg(out2d, target2d, rowmask, scale: float):
+    """(loss, g): masked_smooth_l1_fwd's loss — same bits — and, from the same pass over out2d and target2d, the gradient
+    masked_smooth_l1_bwd returns for gloss == 1 (sn_masked_smooth_l1_fwdg_f32).  masked_smooth_l1_bwdg finishes g for any gloss."""
+    _dev(out2d, target2d, rowmask)
+    rows, C = out2d.shape
+    loss = torch.empty((), dtype=torch.float32, device=out2d.device)
+    g = torch.empty((rows, C), dtype=torch.float32, device=out2d.device)
+    ws_bytes = int(_lib.load().sn_masked_smooth_l1_workspace_bytes(rows, C))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=out2d.device)
+    _lib.call("sn_masked_smooth_l1_fwdg_f32", _p(out2d), _ld(out2d), _p(target2d), _ld(target2d), _p(rowmask), rows, C,
+              float(scale), _p(loss), _p(g), C, _p(ws), ws_bytes, _stream())
+    return loss, g
+
+
+def masked_smooth_l1_bwdg(out2d, target2d, rowmask, scale: float, gloss, g):
+    """masked_smooth_l1_bwd into the buffer masked_smooth_l1_fwdg left for the same operands: the launch returns at once when
+    the device scalar gloss is 1 and recomputes g otherwise — the same bits either way (sn_masked_smooth_l1_bwdg_f32)."""
+    _dev(out2d, target2d, rowmask, gloss, g)
+    rows, C = out2d.shape
+    if g.shape != (rows, C) or g.dtype != torch.float32 or not g.is_contiguous():
+        raise ValueError("masked_smooth_l1_bwdg: g must be the contiguous (rows, C) float32 buffer of masked_smooth_l1_fwdg")
+    _lib.call("sn_masked_smooth_l1_bwdg_f32", _p(out2d), _ld(out2d), _p(target2d), _ld(target2d), _p(rowmask), rows, C,
               float(scale), _p(gloss), _p(g), C, _stream())
     return g
 

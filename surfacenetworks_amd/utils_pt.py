@@ -136,12 +136,23 @@ class GraphConv1x1(nn.Module):
         return y if cat is None else snB.attach_activated(y, cat)
 
 
-def elu_conv1x1(conv: GraphConv1x1, x: torch.Tensor) -> torch.Tensor:
+def elu_conv1x1(conv: GraphConv1x1, x: torch.Tensor, frame=None) -> torch.Tensor:
     """conv(F.elu(x)) — how every model of the reference enters its last GraphConv1x1 (as_rigid_as_possible/models.py:148-150,
-    dense_correspondence/models.py:177-179) — as one fused node where the shapes allow, else literally that."""
+    dense_correspondence/models.py:177-179) — as one fused node where the shapes allow, else literally that.
+    frame ((B, N, 3), only where elu_conv1x1_frame_ok says so): also `+ frame.repeat(1, 1, J/3)` — the ARAP models' last-frame
+    residual (as_rigid_as_possible/models.py:105,152) — added in the GEMM's store instead of a pass over the output."""
+    if frame is not None:
+        if not elu_conv1x1_frame_ok(conv, x, frame):
+            raise ValueError("elu_conv1x1: this layer / frame is not covered by the fused store (ask elu_conv1x1_frame_ok first)")
+        return snB.elu_conv(conv, x, frame)
     if USE_WHOLE_BLOCKS and snB.elu_conv_ok(conv, x):
         return snB.elu_conv(conv, x)
     return conv(F.elu(x))
+
+
+def elu_conv1x1_frame_ok(conv: GraphConv1x1, x: torch.Tensor, frame: torch.Tensor) -> bool:
+    """elu_conv1x1 takes `frame` for this layer and these operands (blocks.elu_conv_frame_ok); else the caller adds it itself."""
+    return bool(USE_WHOLE_BLOCKS and snB.elu_conv_ok(conv, x) and snB.elu_conv_frame_ok(conv, x, frame))
 
 
 class GraphBatchNorm(nn.Module):
@@ -225,7 +236,7 @@ class DirResNet2(_TwoStage):
         super().__init__(num_outputs)
         self.res_f = res_f          # accepted and unused, as in the reference (utils_pt.py:189)
 
-    def forward(self, Di, DiA, v, f, f_out_needed=True, num_faces=None, avg_next=None):
+    def forward(self, Di, DiA, v, f, f_out_needed=True, num_faces=None, avg_next=None, v_out_needed=True):
         """f_out_needed=False (not in the reference's signature): the caller promises to use the returned face features ONLY
         as the `f` argument of the next DirResNet2 — the block then skips writing them (the next block reads the activated
         copy handed over internally) and returns a NaN placeholder of the right shape in their place.
@@ -233,17 +244,21 @@ class DirResNet2(_TwoStage):
         model of the reference feeds its first Dirac block (as_rigid_as_possible/models.py:138) — and are not materialised:
         the face stage runs over the propagated half only (same values).
         avg_next (not in the reference's signature; True / False / None = not said): the vertex output feeds an AvgResNet2 next:
-        see LapResNet2.forward (None: learnt from the block that consumes the hand-off)."""
+        see LapResNet2.forward (None: learnt from the block that consumes the hand-off).
+        v_out_needed=False (not in the reference's signature): the caller promises to hand the returned vertex features ONLY to
+        elu_conv1x1 — a model's last block —, which reads the activated copy handed over internally: the block then skips writing
+        them where its fused kernels can and returns a NaN placeholder of the right shape (elu_conv1x1 refuses the placeholder
+        without its hand-off; anything else computes NaN)."""
         batch_size, num_nodes, num_inputs = v.size()
         if f is None:
             if num_faces is None:
                 raise ValueError("DirResNet2: f=None needs num_faces")
             if _blocks_ok(self, v) and snB.zero_faces_ok(self, num_inputs):
-                return snB.dirac_block(self, Di, DiA, v, None, f_out_needed, num_faces, avg_next)
+                return snB.dirac_block(self, Di, DiA, v, None, f_out_needed, num_faces, avg_next, v_out_needed)
             f = torch.zeros(batch_size, int(num_faces), num_inputs, dtype=v.dtype, device=v.device)
         _, num_faces, _ = f.size()
         if _blocks_ok(self, v):
-            return snB.dirac_block(self, Di, DiA, v, f, f_out_needed, None, avg_next)   # the whole block as one autograd node
+            return snB.dirac_block(self, Di, DiA, v, f, f_out_needed, None, avg_next, v_out_needed)   # the whole block as one autograd node
         v2d = v.reshape(batch_size * num_nodes, num_inputs)
         cat0, e_v = snF.dirac_face_stage(as_operator(Di), v2d, f.reshape(batch_size * num_faces, num_inputs))
         f_out = self.bn_fc0.forward2d(cat0)
