@@ -1100,6 +1100,102 @@ int sn_mesh_orient_i32(const int32_t *F, const int32_t *keep, int64_t nV, int64_
                        int32_t *counts, int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Lattice Delaunay and the Mesh-MNIST maker: images to triangle meshes on the device.
+ *
+ * Replaces: run()                   src/mesh_mnist/create_data.py:62-99 (a multiprocessing.Pool over 70 000 images)
+ *           bilinear_interpolation  src/mesh_mnist/create_data.py:28-36
+ *           Grid.poisson            src/mesh_mnist/poisson_disc.py (Bridson's sampling with Python's random)
+ *           scipy.spatial.Delaunay  (Qhull on the host)
+ * This is the project's own definition on an INTEGER LATTICE, not a reproduction of Python's random stream nor of Qhull's choice
+ * among cocircular diagonals.  Host statements: mesh_ops.delaunay_2d, poisson_disc, lattice_intensity, mesh_digits — Python-int
+ * arithmetic that is not the device algorithm; the device is compared to them bit for bit.  No transcendental function and no
+ * floating-point predicate anywhere.
+ *
+ * Lattice.  A point is a pair of int32 coordinates with |x|, |y| < 2^24.  orient(a, b, c) = (bx - ax)(cy - ay) - (by - ay)(cx - ax)
+ *   fits int64.  incircle(a, b, c, d) = the 3 x 3 determinant of the rows (px - dx, py - dy, (px - dx)^2 + (py - dy)^2), p = a, b,
+ *   c; it needs at most 104 bits and is evaluated in __int128.  It is > 0 iff d lies strictly inside the circle through the
+ *   counter-clockwise a, b, c.  Float input is snapped by the caller with rint(P / quantum).
+ *
+ * Delaunay (sn_delaunay2d_i32).  The result is a triangulation of the convex hull of the set: every triangle counter-clockwise
+ *   with orient > 0; a point on a hull edge is a boundary vertex (no zero-area triangle exists); no point lies strictly inside the
+ *   circle of any triangle.  nF = 2 n - 2 - b, b the number of boundary vertices.  Faces are CANONICAL: each rotated so that its
+ *   smallest input index comes first, the faces sorted lexicographically; rows nF .. 2 Nmax - 1 of F are -1.  cocircular = the
+ *   number of interior edges of the result whose incircle value is exactly 0: with 0 the triangulation is unique; otherwise the
+ *   result is one of the valid ones, a function of the input alone (two runs are bit-identical).
+ *   Refusals, per set (nF = 0, the other sets are not affected), the first that applies:
+ *     count > SN_DELAUNAY_MAX_POINTS or count > Nmax  SN_DT_TOO_LARGE;   a coordinate with |c| >= 2^24  SN_DT_RANGE;
+ *     count < 3  SN_DT_DEGENERATE;   two equal points  SN_DT_DUPLICATE;   all points on one line  SN_DT_DEGENERATE;
+ *     a bad edge is left after max_rounds flip rounds  SN_DT_NOT_CONVERGED.  SN_DT_INTERNAL: a loop bound of the sweep was hit
+ *     (never for a valid input).
+ *   Method.  One workgroup per set, everything in LDS (50 KiB: 1024 points as 64-bit sort keys, 2048 faces and their adjacency as
+ *   int16, one claim word per face; a batch with Nmax <= 512 runs the same code at half the capacity and half the LDS).  Bitonic sort by (x, y).  One lane sweeps: the collinear prefix p0 .. p(k-1) is fanned from
+ *   the first point pk off their line, then each later point — strictly outside the hull so far, since it is the largest — walks
+ *   the hull ring from its predecessor in both directions while orient(a, b, p) < 0 and caps every edge it sees with a triangle
+ *   (at most hull-size steps).  Then Lawson flips in claim-then-flip rounds: an interior edge with incircle > 0 does atomicMin of
+ *   its id 3 f + s on the claim words of its two faces and their four outer neighbours, and flips in the second half of the round
+ *   iff it holds all six, so the flips of one round touch disjoint faces and the smallest bad edge always flips; every flip
+ *   strictly improves the triangulation, so the rounds end, and the schedule does not depend on thread timing.  The canonical
+ *   keys (three 10-bit indices) are sorted and stored with vector stores.  counts[b] = {flips, cocircular, rounds, boundary}.
+ *
+ * Poisson-disc sampling (sn_poisson_disc_i32).  Q = 2^16 lattice units per pixel.  The domain is the open rectangle
+ *   (0, W Q) x (0, H Q); R = round(r Q) (the caller's); cell = isqrt(R^2 / 2), so a cell holds at most one sample and a sample
+ *   closer than R lies within +-2 cells; gw = ceil(W Q / cell), gh = ceil(H Q / cell), gw gh <= SN_DELAUNAY_MAX_POINTS (else
+ *   SN_E_UNSUPPORTED); W Q, H Q < 2^24 and 4 <= R, 4 R < 2^31 (else SN_E_RANGE / SN_E_SHAPE).
+ *   Random numbers are counter-based: draw(step, cand, retry, purpose) = h4, where h0 = seed and
+ *   h(i+1) = mix64(h(i) + 0x9E3779B97F4A7C15 + w(i)) modulo 2^64 for w = (image index, attempt, step, cand << 16 | retry << 8 |
+ *   purpose), mix64 the splitmix64 finaliser (z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27, z *= 0x94D049BB133111EB,
+ *   z ^= z >> 31).  An integer below m is ((draw >> 32) m) >> 32; the bias of multiply-shift is part of the definition.
+ *   Step 0: the first sample is (1 + below(W Q - 1), 1 + below(H Q - 1)) from purposes 0 and 1 (cand = retry = 0).
+ *   Step s >= 1, while the active list is not empty: j = below(active count) from purpose 2 picks the active sample a.  Candidate
+ *   c = 0 .. 29: for retry t = 0 .. 31, dx = below(4 R) - 2 R (purpose 3), dy likewise (purpose 4), until R^2 <= dx^2 + dy^2 <
+ *   4 R^2; a candidate whose 32 draws all fail is invalid.  A candidate a + (dx, dy) is valid when it lies inside the open
+ *   rectangle and its squared distance to every sample in the 5 x 5 cells around its own is >= R^2.  The valid candidate with the
+ *   LOWEST index becomes the next sample and joins the active list at its end (so lanes test the 30 in parallel and give the
+ *   sequential result); with none, a is retired: active[j] = the last active sample, the list shrinks by one.
+ *   At most one sample per cell and one retirement per sample: the loop runs at most 2 gw gh steps.  P holds the samples in the
+ *   order they were made (rows past count are 0), steps[b] the number of steps taken.
+ *
+ * Maker (sn_mesh_digits_u8).  images (B, rows, cols) uint8; the domain is W = cols - 1 by H = rows - 1 pixels.  For attempt = 0,
+ *   1, .. max_attempts - 1 (max_attempts <= SN_MESHDIGITS_MAX_ATTEMPTS): sample image image_base + b with that attempt number,
+ *   refuse the sample when it has fewer than min_points points (101 is the reference's "> 100"; at least 3), triangulate, refuse
+ *   it when the triangulation has a status or when any triangle has orient <= min_det.  SN_MESHDIGITS_MIN_DET = floor(0.02 2^32)
+ *   states the reference's flat-area test, area <= 1e-2 pixel^2 (orient = 2 area Q^2).  The reference also tests the area of the
+ *   triangle in 3-D; a triangle is never smaller than its projection, so the flat test implies it and the 3-D area is not
+ *   computed.  The first sample that is not refused is the mesh and attempts[b] its attempt number; when all are refused the
+ *   image gets SN_DT_REJECTED, count = nF = 0 and attempts[b] = max_attempts.
+ *   Intensity at (x, y), bilinear with the reference's indexing (create_data.py:28-36; the first coordinate runs along the
+ *   columns, the second up the rows): iu = x >> 16, fu = x & 0xFFFF, iv = y >> 16, fv = y & 0xFFFF, f00 = I[rows-1-iv][iu], f01 =
+ *   I[rows-1-iv][iu+1], f10 = I[rows-2-iv][iu], f11 = I[rows-2-iv][iu+1]; sum = f00 (Q-fv)(Q-fu) + f01 (Q-fv) fu + f10 fv (Q-fu)
+ *   + f11 fv fu in int64; z = (float)((double)sum / (255 2^32)).  V = ((float)x 2^-16, (float)y 2^-16, z), exact in fp32.
+ *   Outputs, padded to Nmax >= gw gh: P (B, Nmax, 2), count, V (B, Nmax, 3) (rows past count are 0), F (B, 2 Nmax, 3), nF,
+ *   status, attempts, counts (B, 4) as sn_delaunay2d_i32's.  One workgroup per image.  Samples are at least R apart, so discs
+ *   of radius R / 2 around them are disjoint inside the domain grown by R / 2: n <= 4 (W Q + R)(H Q + R) / (3 R^2) (pi > 3).  When
+ *   that bound is at most 512 — it is 481 for MNIST's 27 x 27 pixels at r = 1.5 — the image's state is sized for 512 points and
+ *   takes 32 KiB of LDS, otherwise for 1024 points and 62 KiB; the results do not depend on which.
+ * None of the three allocates or synchronises; every loop is bounded by the input size.
+ * ------------------------------------------------------------------------------------------ */
+#define SN_DELAUNAY_MAX_POINTS      1024
+#define SN_MESHDIGITS_MAX_ATTEMPTS  8
+#define SN_MESHDIGITS_MIN_DET       85899345
+#define SN_DT_DEGENERATE     1
+#define SN_DT_DUPLICATE      2
+#define SN_DT_RANGE          4
+#define SN_DT_TOO_LARGE      8
+#define SN_DT_NOT_CONVERGED  16
+#define SN_DT_REJECTED       32
+#define SN_DT_INTERNAL       64
+int64_t sn_delaunay2d_max_points(void);
+int sn_delaunay2d_i32(const int32_t *P, const int32_t *count, int64_t B, int64_t Nmax, int32_t max_rounds, int32_t *F, int32_t *nF,
+                      int32_t *status, int32_t *counts, void *stream);
+int64_t sn_poisson_disc_cells(int64_t W, int64_t H, int64_t R);     /* gw gh, or a negative SN_E_* */
+int sn_poisson_disc_i32(uint64_t seed, int64_t image_base, int32_t attempt, int64_t W, int64_t H, int64_t R, int64_t B, int64_t Nmax,
+                        int32_t *P, int32_t *count, int32_t *steps, void *stream);
+int sn_mesh_digits_u8(const uint8_t *images, int64_t B, int32_t rows, int32_t cols, uint64_t seed, int64_t image_base, int64_t R,
+                      int32_t min_points, int64_t min_det, int32_t max_attempts, int32_t max_rounds, int64_t Nmax, int32_t *P,
+                      int32_t *count, float *V, int32_t *F, int32_t *nF, int32_t *status, int32_t *attempts, int32_t *counts,
+                      void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Mesh descriptors: per-vertex normals, mass, Gaussian and mean curvature, and the libigl-convention Laplacian M^-1 C.
  *
  * Replaces: compute_normals, area, laplacian_and_mass, compute_laplacian, gaussian_curvature, hacky_compute_laplacian

@@ -168,6 +168,12 @@ SIGNATURES = {
     "sn_mesh_unique_faces_i32": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sn_mesh_orient_workspace_bytes": (_sz, [_i64, _i64]),
     "sn_mesh_orient_i32": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sn_delaunay2d_max_points": (_i64, []),
+    "sn_delaunay2d_i32": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "sn_poisson_disc_cells": (_i64, [_i64, _i64, _i64]),
+    "sn_poisson_disc_i32": (C.c_int, [C.c_uint64, _i64, _i32, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "sn_mesh_digits_u8": (C.c_int, [_vp, _i64, _i32, _i32, C.c_uint64, _i64, _i64, _i32, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp,
+                                    _vp, _vp, _vp, _vp, _vp]),
     "sn_mesh_descriptors_workspace_bytes": (_sz, [_i64, _i64]),
     "sn_mesh_descriptors_f32": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sn_mesh_cot_laplacian_workspace_bytes": (_sz, [_i64, _i64]),

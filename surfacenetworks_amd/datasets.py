@@ -24,7 +24,7 @@ from . import arap as _arap
 from . import mesh_ops
 from .operators import OperatorPool
 
-__all__ = ["load_arap_sequence", "arap_from_files", "load_mesh_mnist", "mnist_from_samples", "load_faust_frame", "faust_from_files", "faust_frame_from_mesh", "normal_frame_from_mesh",
+__all__ = ["load_arap_sequence", "arap_from_files", "load_mesh_mnist", "mnist_from_samples", "mesh_mnist_from_images", "mesh_digit_samples", "load_faust_frame", "faust_from_files", "faust_frame_from_mesh", "normal_frame_from_mesh",
            "write_arap_sequence", "write_mesh_mnist", "write_faust_frame"]
 
 
@@ -122,6 +122,136 @@ def mnist_from_samples(samples: Sequence[Dict], device="cuda", model="dir", reor
     else:
         ds.pool_L = OperatorPool([op(i, "L", "vorder", "vorder", 1) for i in range(ds.n)], ds.device)
     ds.orders = orders
+    ds.run_nv = ds.run_nf = 0
+    return ds
+
+
+_DIGITS_CHUNK = 4096      # images per launch of the maker (its padded outputs take 30 KiB per image)
+
+
+def _digit_meshes(images, seed, r, device, min_points=101, min_det=None):
+    """kernels.mesh_digits over `images`, _DIGITS_CHUNK at a time (image_base keeps the random stream keyed by the image's index
+    in the whole array) -> (status, attempts, V list, F list): host arrays per image, V (n, 3) fp32 and F (nF, 3) int32 views
+    cut to their sizes, empty for a rejected image."""
+    from . import kernels
+
+    img = images if torch.is_tensor(images) else torch.from_numpy(np.ascontiguousarray(images))
+    if img.dim() != 3 or img.dtype != torch.uint8:
+        raise ValueError(f"images must be (B, rows, cols) uint8, got {tuple(img.shape)} {img.dtype}")
+    R = int(round(float(r) * mesh_ops.MESHDIGITS_Q))
+    status, attempts, Vs, Fs = [], [], [], []
+    for s in range(0, img.shape[0], _DIGITS_CHUNK):
+        out = kernels.mesh_digits(img[s: s + _DIGITS_CHUNK].to(device), seed=seed, R=R, min_points=min_points, image_base=s,
+                                  min_det=kernels.MESHDIGITS_MIN_DET if min_det is None else min_det)
+        count, nF, V, F = (getattr(out, k).cpu().numpy() for k in ("count", "nF", "V", "F"))
+        status.append(out.status.cpu().numpy())
+        attempts.append(out.attempts.cpu().numpy())
+        Vs += [V[b, : count[b]] for b in range(V.shape[0])]
+        Fs += [F[b, : nF[b]] for b in range(F.shape[0])]
+    cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0, np.int32)
+    return cat(status), cat(attempts), Vs, Fs
+
+
+def _warn_rejected(who, status):
+    import warnings
+
+    rejected = np.flatnonzero(status != 0)
+    if rejected.size:
+        warnings.warn(f"{who}: {rejected.size} image(s) found no mesh that passes the quality test in "
+                      f"{mesh_ops.MESHDIGITS_MAX_ATTEMPTS} attempts and are left out: {rejected.tolist()}")
+    return rejected
+
+
+def _labels_for(who, labels, count):
+    lab = np.asarray(labels.cpu() if torch.is_tensor(labels) else labels).reshape(-1)
+    if lab.shape[0] != count:
+        raise ValueError(f"{who}: {lab.shape[0]} labels for {count} images")
+    return lab
+
+
+def mesh_digit_samples(images, labels, seed=0, r=1.5, device="cuda") -> List[Dict]:
+    """The reference's first Mesh-MNIST stage (src/mesh_mnist/create_data.py:62-105) on the device: a list of {'V' (n, 3) float32,
+    'F' (nF, 3) int32, 'label'} dicts in create_data.py's own layout — unscaled pixel coordinates with the bilinear intensity as z
+    — that the reference's add_laplacian.py or write_mesh_mnist take.  images: (B, rows, cols) uint8 (numpy or tensor).  Images
+    that stay rejected after the retries are left out (warnings.warn names them)."""
+    lab = _labels_for("mesh_digit_samples", labels, images.shape[0])
+    status, _, Vs, Fs = _digit_meshes(images, seed, r, device)
+    _warn_rejected("mesh_digit_samples", status)
+    return [{"V": Vs[b].copy(), "F": Fs[b].copy(), "label": int(lab[b])} for b in range(len(Vs)) if status[b] == 0]
+
+
+def _csr_block(A, r0, r1, c0, c1):
+    """Rows r0..r1, columns c0..c1 of a block-diagonal scipy CSR whose rows r0..r1 have no entry outside those columns."""
+    import scipy.sparse as sp
+
+    ip = A.indptr[r0: r1 + 1]
+    sl = slice(int(ip[0]), int(ip[-1]))
+    return sp.csr_matrix((A.data[sl], A.indices[sl] - c0, ip - ip[0]), shape=(r1 - r0, c1 - c0))
+
+
+def mesh_mnist_from_images(images, labels, seed=0, r=1.5, device="cuda", model="dir", reorder="auto", scale=True):
+    """Images to a trainable Mesh-MNIST dataset on the device: the whole of src/mesh_mnist/create_data.py (Poisson-disc points,
+    bilinear intensity, Delaunay, the area test with its retries: kernels.mesh_digits, one launch per 4096 images) and of
+    add_laplacian.py (the operators, from the existing device builders on V / 27 - (0.5, 0.5, 0), add_laplacian.py:40-41).
+    images: (B, rows, cols) uint8, 28 x 28 for MNIST; any size whose (cols - 1) x (rows - 1) pixel domain the sampler's grid takes
+    (the divisor is then max(rows, cols) - 1).  labels: (B,).  r: the Poisson-disc radius in pixels.  scale=False keeps pixel
+    coordinates.  Returns a dataset with the MeshDigits interface (pools, sample_batch, orders) for mesh_mnist.train_step and
+    graphed_train_step.  Images that stay rejected after the retries are left out: `rejected` holds their indices (also named by
+    a warnings.warn), `source` the image index of every mesh, `attempts` the attempt each mesh came from, `V` / `F` the stored
+    (scaled, reordered) meshes as numpy arrays."""
+    from . import mesh_mnist as mm
+    from .operators import dirac_operators_from_mesh, laplacian_operator_from_mesh
+
+    if model not in ("dir", "lap"):
+        raise ValueError(f'mesh_mnist_from_images: model must be "dir" or "lap", got {model!r}')
+    lab = _labels_for("mesh_mnist_from_images", labels, images.shape[0])
+    status, attempts, Vs, Fs = _digit_meshes(images, seed, r, device)
+    rejected = _warn_rejected("mesh_mnist_from_images", status)
+    keep = np.flatnonzero(status == 0)
+    if keep.size == 0:
+        raise ValueError("mesh_mnist_from_images: no image gave a mesh")
+    side = np.float32(max(images.shape[1], images.shape[2]) - 1)
+    ds = mm.MeshDigits.__new__(mm.MeshDigits)
+    ds.device, ds.kind, ds.n = torch.device(device), model, int(keep.size)
+    ds.rejected, ds.source, ds.attempts = rejected, keep, attempts[keep]
+    ds.orders, ds.V, ds.F = [], [], []
+    for b in keep:
+        Vb, Fb = Vs[b], Fs[b].astype(np.int64)
+        if scale:                                   # fp32 division and subtraction, each rounded once
+            Vb = Vb / side - np.array([0.5, 0.5, 0.0], np.float32)
+        order = mesh_ops.MeshOrder.of_mesh(Fb, Vb.shape[0], reorder)
+        Vb, Fb = order.mesh(Vb, Fb)
+        ds.orders.append(order)
+        ds.V.append(np.ascontiguousarray(Vb, dtype=np.float32))
+        ds.F.append(np.ascontiguousarray(Fb, dtype=np.int32))
+    ds.nv = np.array([v.shape[0] for v in ds.V])
+    ds.nf = np.array([f.shape[0] for f in ds.F])
+    # _DIGITS_CHUNK meshes at a time as ONE disjoint mesh: one run of the device builders, cut into per-mesh blocks for the pools
+    mats = {"Di": [], "DiA": [], "L": []}
+    for s in range(0, ds.n, _DIGITS_CHUNK):
+        e = min(s + _DIGITS_CHUNK, ds.n)
+        voff = np.concatenate([[0], np.cumsum(ds.nv[s:e])])
+        foff = np.concatenate([[0], np.cumsum(ds.nf[s:e])])
+        Vg = torch.from_numpy(np.concatenate(ds.V[s:e])).to(ds.device)
+        Fg = torch.from_numpy(np.concatenate([f + np.int32(o) for f, o in zip(ds.F[s:e], voff[:-1])])).to(ds.device)
+        if model == "dir":
+            Di, DiA = (op.to_scipy() for op in dirac_operators_from_mesh(Vg, Fg))
+            mats["Di"] += [_csr_block(Di, 4 * foff[i], 4 * foff[i + 1], 4 * voff[i], 4 * voff[i + 1]) for i in range(e - s)]
+            mats["DiA"] += [_csr_block(DiA, 4 * voff[i], 4 * voff[i + 1], 4 * foff[i], 4 * foff[i + 1]) for i in range(e - s)]
+        else:
+            L = laplacian_operator_from_mesh(Vg, Fg).to_scipy()
+            mats["L"] += [_csr_block(L, voff[i], voff[i + 1], voff[i], voff[i + 1]) for i in range(e - s)]
+    if model == "dir":
+        ds.pool_Di = OperatorPool(mats["Di"], ds.device, want_bsr4=True)
+        ds.pool_DiA = OperatorPool(mats["DiA"], ds.device, want_bsr4=True)
+    else:
+        ds.pool_L = OperatorPool(mats["L"], ds.device)
+    xyz = np.zeros((ds.n, int(ds.nv.max()), 3), np.float32)
+    for i, v in enumerate(ds.V):
+        xyz[i, : v.shape[0]] = v
+    ds.xyz = torch.from_numpy(xyz).to(ds.device)
+    ds.vcount = torch.from_numpy(ds.nv).to(ds.device)
+    ds.labels = torch.from_numpy(lab[keep].astype(np.int64)).to(ds.device)
     ds.run_nv = ds.run_nf = 0
     return ds
 

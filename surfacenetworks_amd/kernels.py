@@ -2152,3 +2152,91 @@ def linear_dgrad_eluseg(dy, W, x, center, B, Cc, segvec, rows_per_seg: int, rowm
               _p(am), _stream())
     note_absmax(gact, am)
     return gact
+
+
+# ---- lattice Delaunay, Poisson-disc sampling, the Mesh-MNIST maker (csrc/sn_delaunay.hip) -------------------------------------
+DT_DEGENERATE, DT_DUPLICATE, DT_RANGE, DT_TOO_LARGE, DT_NOT_CONVERGED, DT_REJECTED, DT_INTERNAL = 1, 2, 4, 8, 16, 32, 64   # SN_DT_*
+MESHDIGITS_MAX_ATTEMPTS = 8                      # SN_MESHDIGITS_MAX_ATTEMPTS
+MESHDIGITS_MIN_DET = 85899345                    # SN_MESHDIGITS_MIN_DET
+DT_MAX_ROUNDS = 4096                             # default flip-round budget (210 random points take about 50 rounds)
+
+Delaunay2D = collections.namedtuple("Delaunay2D", "F nF status counts")
+PoissonDisc = collections.namedtuple("PoissonDisc", "P count steps")
+MeshDigitsOut = collections.namedtuple("MeshDigitsOut", "P count V F nF status attempts counts")
+
+
+def delaunay_max_points() -> int:
+    return int(_lib.load().sn_delaunay2d_max_points())
+
+
+def delaunay_2d(P, count=None, max_rounds: int = DT_MAX_ROUNDS) -> Delaunay2D:
+    """Delaunay triangulations of a padded batch of lattice point sets on the device (sn_delaunay2d_i32; definition in
+    include/sn_spmm.h, "Lattice Delaunay and the Mesh-MNIST maker"; host statement mesh_ops.delaunay_2d).  P: (B, Nmax, 2) int32,
+    count: (B,) int32 or None (every set has Nmax points).  Returns Delaunay2D of int32 device tensors: F (B, 2 Nmax, 3) canonical
+    faces with -1 past nF, nF (B,), status (B,) of DT_* bits, counts (B, 4) = flips, cocircular, rounds, boundary vertices.  A
+    refused set has nF = 0 and does not disturb the others.  Does not synchronise; two runs are bit-identical."""
+    _dev(P, count)
+    if P.dtype != torch.int32 or P.dim() != 3 or P.shape[2] != 2:
+        raise TypeError("delaunay_2d wants P (B, Nmax, 2) int32")
+    B, nmax = P.shape[0], P.shape[1]
+    if count is not None and (count.dtype != torch.int32 or count.shape != (B,)):
+        raise TypeError("delaunay_2d wants count (B,) int32")
+    P = P.contiguous()
+    count = None if count is None else count.contiguous()
+    dev = P.device
+    F = torch.empty(B, 2 * nmax, 3, dtype=torch.int32, device=dev)
+    nF = torch.empty(B, dtype=torch.int32, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    counts = torch.empty(B, 4, dtype=torch.int32, device=dev)
+    _lib.call("sn_delaunay2d_i32", _p(P), _p(count), B, nmax, int(max_rounds), _p(F), _p(nF), _p(status), _p(counts), _stream())
+    return Delaunay2D(F, nF, status, counts)
+
+
+def poisson_disc_cells(width: int, height: int, R: int) -> int:
+    """Cells of the sampler's grid for a width x height pixel domain and radius R lattice units: the most samples one image can
+    get.  ValueError for parameters outside the lattice or with more cells than SN_DELAUNAY_MAX_POINTS."""
+    cells = int(_lib.load().sn_poisson_disc_cells(int(width), int(height), int(R)))
+    if cells < 0:
+        raise ValueError(f"poisson_disc: domain {width} x {height} with R = {R} is refused "
+                         f"({_lib.load().sn_status_string(cells).decode()}; at most {delaunay_max_points()} cells)")
+    return cells
+
+
+def poisson_disc(batch: int, seed: int = 0, image_base: int = 0, attempt: int = 0, R: int = 98304, width: int = 27, height: int = 27,
+                 device="cuda") -> PoissonDisc:
+    """Bridson Poisson-disc samples in integers for images image_base .. image_base + batch - 1 (sn_poisson_disc_i32, host
+    statement mesh_ops.poisson_disc).  R: the radius in lattice units (2^16 per pixel).  Returns PoissonDisc(P (B, cells, 2) int32
+    in the order the samples were made, count (B,), steps (B,)) on the device.  Does not synchronise."""
+    cells = poisson_disc_cells(width, height, R)
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("surfacenetworks_amd kernels run on the MI355X only: there is no CPU/eager fallback in this package")
+    P = torch.empty(batch, cells, 2, dtype=torch.int32, device=dev)
+    count = torch.empty(batch, dtype=torch.int32, device=dev)
+    steps = torch.empty(batch, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call("sn_poisson_disc_i32", int(seed) & (2 ** 64 - 1), int(image_base), int(attempt), int(width), int(height), int(R),
+                  int(batch), cells, _p(P), _p(count), _p(steps), _stream())
+    return PoissonDisc(P, count, steps)
+
+
+def mesh_digits(images, seed: int = 0, R: int = 98304, min_points: int = 101, min_det: int = MESHDIGITS_MIN_DET, image_base: int = 0,
+                max_attempts: int = MESHDIGITS_MAX_ATTEMPTS, max_rounds: int = DT_MAX_ROUNDS) -> MeshDigitsOut:
+    """Images to meshes in one launch: sampler, Delaunay, quality test, retries and intensity (sn_mesh_digits_u8, host statement
+    mesh_ops.mesh_digits).  images: (B, rows, cols) uint8 on the device.  Returns MeshDigitsOut of device tensors padded to the
+    sampler's cell count Nmax: P (B, Nmax, 2) int32, count (B,), V (B, Nmax, 3) fp32, F (B, 2 Nmax, 3) int32 (-1 past nF), nF,
+    status (0 or DT_REJECTED), attempts, counts (B, 4).  Does not synchronise; two runs are bit-identical."""
+    _dev(images)
+    if images.dtype != torch.uint8 or images.dim() != 3:
+        raise TypeError("mesh_digits wants images (B, rows, cols) uint8")
+    B, rows, cols = images.shape
+    cells = poisson_disc_cells(cols - 1, rows - 1, R)
+    images = images.contiguous()
+    dev = images.device
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    out = MeshDigitsOut(i32(B, cells, 2), i32(B), torch.empty(B, cells, 3, dtype=torch.float32, device=dev), i32(B, 2 * cells, 3),
+                        i32(B), i32(B), i32(B), i32(B, 4))
+    _lib.call("sn_mesh_digits_u8", _p(images), B, rows, cols, int(seed) & (2 ** 64 - 1), int(image_base), int(R), int(min_points),
+              int(min_det), int(max_attempts), int(max_rounds), cells, _p(out.P), _p(out.count), _p(out.V), _p(out.F), _p(out.nF),
+              _p(out.status), _p(out.attempts), _p(out.counts), _stream())
+    return out

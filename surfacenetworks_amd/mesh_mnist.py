@@ -160,6 +160,15 @@ class MeshDigits:
         # the reference keeps a running maximum of the padded sizes across steps (main.py:83-84,119-120)
         self.run_nv = self.run_nf = 0
 
+    @classmethod
+    def from_images(cls, images, labels, seed=0, r=1.5, device="cuda", model="dir", reorder="auto", scale=True):
+        """The dataset of real images instead of the stand-in: Poisson-disc points, bilinear intensity, Delaunay, the quality test
+        and the operators, all on the device (datasets.mesh_mnist_from_images; src/mesh_mnist/create_data.py + add_laplacian.py).
+        images: (B, 28, 28) uint8, labels: (B,)."""
+        from .datasets import mesh_mnist_from_images
+
+        return mesh_mnist_from_images(images, labels, seed=seed, r=r, device=device, model=model, reorder=reorder, scale=scale)
+
     def sample_batch(self, batch_size, rng, ids=None) -> Batch:
         ids = rng.integers(0, self.n, size=batch_size) if ids is None else np.asarray(ids)
         self.run_nv = max(self.run_nv, int(self.nv[ids].max()))

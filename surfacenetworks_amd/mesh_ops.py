@@ -35,6 +35,10 @@ __all__ = [
     "REPAIR_BAD_FACE", "REPAIR_NONFINITE", "REPAIR_NONORIENTABLE", "REPAIR_NONMANIFOLD", "REPAIR_INTERNAL",
     "descriptor_sums", "vertex_descriptors", "libigl_laplacian", "Descriptors", "LAP_MAX_DEGREE",
     "DESC_BAD_FACE", "DESC_FLAT_FACE", "DESC_NO_NORMAL", "DESC_CLAMPED", "DESC_DEGREE",
+    "delaunay_2d", "poisson_disc", "poisson_grid", "mesh_digits", "lattice_orient", "lattice_incircle", "lattice_intensity",
+    "lattice_draw", "canonical_faces", "snap_to_lattice", "Delaunay2D", "PoissonDisc", "MeshDigitsResult",
+    "DT_DEGENERATE", "DT_DUPLICATE", "DT_RANGE", "DT_TOO_LARGE", "DT_NOT_CONVERGED", "DT_REJECTED", "DT_INTERNAL",
+    "DELAUNAY_MAX_POINTS", "DELAUNAY_COORD_LIMIT", "MESHDIGITS_MAX_ATTEMPTS", "MESHDIGITS_Q", "MESHDIGITS_MIN_DET",
 ]
 
 _PERMS = np.array([[0, 1, 2], [0, 2, 1], [1, 0, 2], [1, 2, 0], [2, 0, 1], [2, 1, 0]])  # itertools.permutations order
@@ -916,3 +920,304 @@ def read_ply_ascii(path: str):
     V = np.array([[float(t) for t in lines[k + i].split()[:3]] for i in range(nv)])
     F = np.array([[int(t) for t in lines[k + nv + i].split()[1:4]] for i in range(nf)], dtype=np.int64)
     return V, F
+
+
+# ---- Mesh-MNIST from images: lattice Delaunay, Poisson-disc sampling, intensity, quality test ---------------------------------
+# Definition: include/sn_spmm.h ("Lattice Delaunay and the Mesh-MNIST maker").  Everything below is Python-int arithmetic — no
+# floating-point predicate, no transcendental function — and is NOT the device algorithm: a scan over the whole hull instead of a
+# walk, one flip at a time from a stack instead of claim-then-flip rounds.  The device is compared to it bit for bit.
+DT_DEGENERATE, DT_DUPLICATE, DT_RANGE, DT_TOO_LARGE, DT_NOT_CONVERGED, DT_REJECTED, DT_INTERNAL = 1, 2, 4, 8, 16, 32, 64   # SN_DT_*
+DELAUNAY_MAX_POINTS = 1024           # SN_DELAUNAY_MAX_POINTS
+DELAUNAY_COORD_LIMIT = 1 << 24       # |x|, |y| < 2^24
+MESHDIGITS_MAX_ATTEMPTS = 8          # SN_MESHDIGITS_MAX_ATTEMPTS
+MESHDIGITS_Q = 1 << 16               # lattice units per pixel
+MESHDIGITS_MIN_DET = 85899345        # SN_MESHDIGITS_MIN_DET = floor(0.02 * 2^32): area <= 1e-2 pixel^2  <=>  det <= this
+POISSON_CANDIDATES, POISSON_RETRIES = 30, 32
+
+Delaunay2D = collections.namedtuple("Delaunay2D", "F nF status flips cocircular boundary")
+PoissonDisc = collections.namedtuple("PoissonDisc", "P count steps")
+MeshDigitsResult = collections.namedtuple("MeshDigitsResult", "P count V F nF status attempts")
+
+_M64 = (1 << 64) - 1
+_GOLDEN = 0x9E3779B97F4A7C15
+
+
+def lattice_orient(a, b, c) -> int:
+    """Twice the signed area of (a, b, c), exact: > 0 counter-clockwise."""
+    return (int(b[0]) - int(a[0])) * (int(c[1]) - int(a[1])) - (int(b[1]) - int(a[1])) * (int(c[0]) - int(a[0]))
+
+
+def lattice_incircle(a, b, c, d) -> int:
+    """The in-circle determinant of differences, exact: > 0 iff d lies strictly inside the circle through the counter-clockwise
+    a, b, c."""
+    adx, ady = int(a[0]) - int(d[0]), int(a[1]) - int(d[1])
+    bdx, bdy = int(b[0]) - int(d[0]), int(b[1]) - int(d[1])
+    cdx, cdy = int(c[0]) - int(d[0]), int(c[1]) - int(d[1])
+    ad, bd, cd = adx * adx + ady * ady, bdx * bdx + bdy * bdy, cdx * cdx + cdy * cdy
+    return ad * (bdx * cdy - bdy * cdx) - bd * (adx * cdy - ady * cdx) + cd * (adx * bdy - ady * bdx)
+
+
+def canonical_faces(F) -> np.ndarray:
+    """Each face rotated so that its smallest index comes first, faces sorted lexicographically."""
+    F = np.asarray(F, dtype=np.int64).reshape(-1, 3)
+    if F.shape[0] == 0:
+        return np.zeros((0, 3), np.int32)
+    k = np.argmin(F, axis=1)
+    R = np.stack([F[np.arange(F.shape[0]), (k + j) % 3] for j in range(3)], axis=1)
+    return R[np.lexsort((R[:, 2], R[:, 1], R[:, 0]))].astype(np.int32)
+
+
+def snap_to_lattice(P, quantum: float) -> np.ndarray:
+    """rint(P / quantum) in float64, as int64 (the caller's range check follows)."""
+    return np.rint(np.asarray(P, dtype=np.float64) / float(quantum)).astype(np.int64)
+
+
+def _delaunay_one(pts, max_flips=None):
+    n = len(pts)
+    none = np.zeros((0, 3), np.int32)
+    if n > DELAUNAY_MAX_POINTS:
+        return Delaunay2D(none, 0, DT_TOO_LARGE, 0, 0, 0)
+    if any(abs(x) >= DELAUNAY_COORD_LIMIT or abs(y) >= DELAUNAY_COORD_LIMIT for x, y in pts):
+        return Delaunay2D(none, 0, DT_RANGE, 0, 0, 0)
+    if n < 3:
+        return Delaunay2D(none, 0, DT_DEGENERATE, 0, 0, 0)
+    order = sorted(range(n), key=lambda i: pts[i])
+    p = [pts[i] for i in order]
+    if any(p[i] == p[i + 1] for i in range(n - 1)):
+        return Delaunay2D(none, 0, DT_DUPLICATE, 0, 0, 0)
+    k = next((i for i in range(2, n) if lattice_orient(p[0], p[1], p[i]) != 0), None)
+    if k is None:
+        return Delaunay2D(none, 0, DT_DEGENERATE, 0, 0, 0)
+    # sweep: the first k points are a collinear chain in sort order, p[k] fans it; every later point lies strictly outside the
+    # hull so far and gets one triangle per hull edge it sees strictly (an edge it is collinear with is not seen)
+    faces = []
+    if lattice_orient(p[0], p[1], p[k]) > 0:
+        faces += [[i, i + 1, k] for i in range(k - 1)]
+        hull = list(range(k)) + [k]
+    else:
+        faces += [[i + 1, i, k] for i in range(k - 1)]
+        hull = list(range(k - 1, -1, -1)) + [k]
+    for i in range(k + 1, n):
+        h = len(hull)
+        vis = [lattice_orient(p[hull[j]], p[hull[(j + 1) % h]], p[i]) < 0 for j in range(h)]
+        start = next(j for j in range(h) if vis[j] and not vis[j - 1])
+        m = 0
+        while vis[(start + m) % h]:
+            a, b = hull[(start + m) % h], hull[(start + m + 1) % h]
+            faces.append([b, a, i])
+            m += 1
+        chain = [hull[(start + j) % h] for j in range(m + 1)]
+        rest = [hull[(start + m + 1 + j) % h] for j in range(h - m - 1)]
+        hull = [chain[0], i, chain[-1]] + rest
+    # Lawson flips, one at a time, only where the exact in-circle value is > 0
+    edge = {}
+    for f, (a, b, c) in enumerate(faces):
+        for u, v in ((a, b), (b, c), (c, a)):
+            edge.setdefault((min(u, v), max(u, v)), []).append(f)
+    stack = [e for e, fs in edge.items() if len(fs) == 2]
+    flips = 0
+    limit = n * n if max_flips is None else int(max_flips)
+    status = 0
+
+    def opposite(f, u, v):
+        """face f rotated to (u', v', w) with {u', v'} = {u, v}"""
+        a, b, c = faces[f]
+        for x, y, z in ((a, b, c), (b, c, a), (c, a, b)):
+            if {x, y} == {u, v}:
+                return x, y, z
+        raise AssertionError("edge not in face")
+
+    while stack:
+        e = stack.pop()
+        fs = edge.get(e)
+        if fs is None or len(fs) != 2:
+            continue
+        f, g = fs
+        u, v, w = opposite(f, *e)
+        _, _, z = opposite(g, *e)
+        if lattice_incircle(p[u], p[v], p[w], p[z]) <= 0:
+            continue
+        if flips >= limit:
+            status = DT_NOT_CONVERGED
+            break
+        flips += 1
+        faces[f], faces[g] = [u, z, w], [z, v, w]
+        del edge[e]
+        edge[(min(w, z), max(w, z))] = [f, g]
+        for (x, y), old, new in (((u, z), g, f), ((v, w), f, g)):
+            fl = edge[(min(x, y), max(x, y))]
+            fl[fl.index(old)] = new
+        stack += [(min(x, y), max(x, y)) for x, y in ((u, z), (z, v), (v, w), (w, u))]
+    if status:
+        return Delaunay2D(none, 0, status, flips, 0, 0)
+    cocircular = 0
+    for e, fs in edge.items():
+        if len(fs) == 2:
+            u, v, w = opposite(fs[0], *e)
+            z = opposite(fs[1], *e)[2]
+            cocircular += lattice_incircle(p[u], p[v], p[w], p[z]) == 0
+    F = canonical_faces([[order[a], order[b], order[c]] for a, b, c in faces])
+    return Delaunay2D(F, F.shape[0], 0, flips, int(cocircular), 2 * n - 2 - F.shape[0])
+
+
+def delaunay_2d(P, count=None, quantum=None, max_flips=None) -> Delaunay2D:
+    """The Delaunay triangulation of lattice point sets, host statement of operators.delaunay_2d / sn_delaunay2d_i32.
+    P: (n, 2) one set, or (B, Nmax, 2) a padded batch with count (B,) (None: every set has Nmax points).  Integer input is taken as
+    lattice coordinates; with quantum the input is snapped, rint(P / quantum).  One set returns Delaunay2D(F (nF, 3) int32 in
+    canonical form, nF, status (DT_* bits), flips, cocircular, boundary vertices) as Python ints; a batch returns the same fields
+    as arrays, F (B, 2 Nmax, 3) with -1 in the rows past nF.  A refused set has nF = 0.  With cocircular == 0 the result is THE
+    Delaunay triangulation; otherwise it is one of them."""
+    P = np.asarray(P)
+    L = snap_to_lattice(P, quantum) if quantum is not None else P
+    if L.ndim == 2:
+        return _delaunay_one([(int(x), int(y)) for x, y in L[: (L.shape[0] if count is None else int(count))]], max_flips)
+    B, nmax = L.shape[0], L.shape[1]
+    count = np.full(B, nmax) if count is None else np.asarray(count).reshape(-1)
+    F = np.full((B, 2 * nmax, 3), -1, np.int32)
+    out = np.zeros((5, B), np.int32)
+    for b in range(B):
+        c = int(count[b])
+        if c > nmax:
+            r = Delaunay2D(None, 0, DT_TOO_LARGE, 0, 0, 0)
+        else:
+            r = _delaunay_one([(int(x), int(y)) for x, y in L[b, : max(c, 0)]], max_flips)
+        F[b, : r.nF] = r.F if r.nF else 0
+        out[:, b] = (r.nF, r.status, r.flips, r.cocircular, r.boundary)
+    return Delaunay2D(F, out[0], out[1], out[2], out[3], out[4])
+
+
+def _mix64(z: int) -> int:
+    z &= _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def lattice_draw(seed: int, image: int, attempt: int, step: int, cand: int, retry: int, purpose: int) -> int:
+    """The counter-based 64-bit draw: h = seed; for w in (image, attempt, step, cand << 16 | retry << 8 | purpose):
+    h = mix64(h + 0x9E3779B97F4A7C15 + w), all modulo 2^64, mix64 the splitmix64 finaliser."""
+    h = int(seed) & _M64
+    for w in (int(image), int(attempt), int(step), (int(cand) << 16) | (int(retry) << 8) | int(purpose)):
+        h = _mix64((h + _GOLDEN + w) & _M64)
+    return h
+
+
+def _below(draw: int, m: int) -> int:
+    return ((draw >> 32) * m) >> 32
+
+
+def poisson_grid(r: float, width: int, height: int):
+    """(R, cell, gw, gh) of the sampler's grid: R = round(r Q), cell = isqrt(R^2 / 2), gw x gh cells cover the domain."""
+    import math
+
+    R = int(round(float(r) * MESHDIGITS_Q))
+    cell = math.isqrt(R * R // 2)
+    if R < 4 or width < 1 or height < 1 or max(width, height) * MESHDIGITS_Q >= DELAUNAY_COORD_LIMIT or 4 * R >= (1 << 31):
+        raise ValueError(f"poisson_disc: r = {r}, domain {width} x {height} is outside the lattice")
+    gw, gh = -(-width * MESHDIGITS_Q // cell), -(-height * MESHDIGITS_Q // cell)
+    if gw * gh > DELAUNAY_MAX_POINTS:
+        raise ValueError(f"poisson_disc: {gw} x {gh} cells exceed DELAUNAY_MAX_POINTS = {DELAUNAY_MAX_POINTS}")
+    return R, cell, gw, gh
+
+
+def poisson_disc(seed: int, image: int, attempt: int = 0, r: float = 1.5, width: int = 27, height: int = 27) -> PoissonDisc:
+    """Bridson's Poisson-disc sampling of the open rectangle (0, width Q) x (0, height Q) in integers (host statement of
+    sn_poisson_disc_i32; poisson_disc.py's Grid.poisson restated, not its random stream).  Returns PoissonDisc(P (n, 2) int32 in
+    the order the samples were made, n, steps)."""
+    R, cell, gw, gh = poisson_grid(r, width, height)
+    WQ, HQ, R2 = width * MESHDIGITS_Q, height * MESHDIGITS_Q, R * R
+    draw = lambda step, cand, retry, purpose: lattice_draw(seed, image, attempt, step, cand, retry, purpose)
+    grid = {}
+    pts = [(1 + _below(draw(0, 0, 0, 0), WQ - 1), 1 + _below(draw(0, 0, 0, 1), HQ - 1))]
+    grid[(pts[0][0] // cell, pts[0][1] // cell)] = 0
+    active = [0]
+    steps = 0
+    for step in range(1, 2 * gw * gh + 1):
+        if not active:
+            break
+        steps = step
+        j = _below(draw(step, 0, 0, 2), len(active))
+        ax, ay = pts[active[j]]
+        won = None
+        for c in range(POISSON_CANDIDATES):
+            for t in range(POISSON_RETRIES):
+                dx = _below(draw(step, c, t, 3), 4 * R) - 2 * R
+                dy = _below(draw(step, c, t, 4), 4 * R) - 2 * R
+                if R2 <= dx * dx + dy * dy < 4 * R2:
+                    break
+            else:
+                continue
+            x, y = ax + dx, ay + dy
+            if not (0 < x < WQ and 0 < y < HQ):
+                continue
+            gx, gy = x // cell, y // cell
+            if all((x - pts[i][0]) ** 2 + (y - pts[i][1]) ** 2 >= R2
+                   for i in (grid.get((gx + u, gy + v)) for u in range(-2, 3) for v in range(-2, 3)) if i is not None):
+                won = (x, y)
+                break
+        if won is None:
+            active[j] = active[-1]
+            active.pop()
+        else:
+            grid[(won[0] // cell, won[1] // cell)] = len(pts)
+            active.append(len(pts))
+            pts.append(won)
+    return PoissonDisc(np.array(pts, dtype=np.int32).reshape(-1, 2), len(pts), steps)
+
+
+def lattice_intensity(image: np.ndarray, P) -> np.ndarray:
+    """Bilinear intensity of a uint8 image at lattice points (x, y), 16 fraction bits, with the reference's indexing
+    (create_data.py:28-36: rows rows-1 - int(y) and rows-1 - int(y + 1), columns int(x) and int(x + 1)), exact in integers, then
+    fp32(double(sum) / (255 2^32)).  Points with 0 <= x < (cols - 1) Q and 0 <= y < (rows - 1) Q."""
+    image = np.asarray(image)
+    top = image.shape[0] - 1
+    Q = MESHDIGITS_Q
+    out = np.zeros(len(P), np.float32)
+    for i, (x, y) in enumerate(np.asarray(P).reshape(-1, 2).tolist()):
+        iu, fu, iv, fv = x >> 16, x & (Q - 1), y >> 16, y & (Q - 1)
+        f00, f01 = int(image[top - iv, iu]), int(image[top - iv, iu + 1])
+        f10, f11 = int(image[top - iv - 1, iu]), int(image[top - iv - 1, iu + 1])
+        s = f00 * (Q - fv) * (Q - fu) + f01 * (Q - fv) * fu + f10 * fv * (Q - fu) + f11 * fv * fu
+        out[i] = np.float32(np.float64(s) / np.float64(255 * (1 << 32)))
+    return out
+
+
+def mesh_digits(images, seed: int = 0, r: float = 1.5, min_points: int = 101, min_det: int = MESHDIGITS_MIN_DET,
+                image_base: int = 0, max_attempts: int = MESHDIGITS_MAX_ATTEMPTS) -> MeshDigitsResult:
+    """Images to meshes (host statement of sn_mesh_digits_u8; create_data.py:62-99 restated): per image, attempt 0, 1, ...:
+    Poisson-disc points, Delaunay, and the sample is taken when it has at least min_points points and every triangle's
+    orientation determinant exceeds min_det (flat area > 1e-2 pixel^2 by default); after max_attempts refusals the image is
+    DT_REJECTED.  images: (B, rows, cols) uint8; the domain is (cols - 1) x (rows - 1) pixels.  Returns MeshDigitsResult of
+    padded arrays, Nmax = the sampler's cell count: P (B, Nmax, 2) int32, count (B,), V (B, Nmax, 3) fp32 = (x / Q, y / Q,
+    intensity), F (B, 2 Nmax, 3) int32 canonical with -1 past nF, nF, status, attempts (the attempt taken; max_attempts when
+    rejected).  Rows past count are 0."""
+    images = np.asarray(images)
+    if images.ndim != 3 or images.dtype != np.uint8:
+        raise ValueError("mesh_digits wants images (B, rows, cols) uint8")
+    B, rows, cols = images.shape
+    _, _, gw, gh = poisson_grid(r, cols - 1, rows - 1)
+    nmax = gw * gh
+    min_points = max(int(min_points), 3)
+    P = np.zeros((B, nmax, 2), np.int32)
+    V = np.zeros((B, nmax, 3), np.float32)
+    F = np.full((B, 2 * nmax, 3), -1, np.int32)
+    count, nF, status, attempts = (np.zeros(B, np.int32) for _ in range(4))
+    for b in range(B):
+        attempts[b], status[b] = max_attempts, DT_REJECTED
+        for attempt in range(max_attempts):
+            s = poisson_disc(seed, image_base + b, attempt, r, cols - 1, rows - 1)
+            if s.count < min_points:
+                continue
+            d = delaunay_2d(s.P)
+            if d.status:
+                continue
+            pts = s.P.tolist()
+            if min(lattice_orient(pts[i], pts[j], pts[k]) for i, j, k in d.F.tolist()) <= min_det:
+                continue
+            n = s.count
+            P[b, :n], count[b], F[b, : d.nF], nF[b], status[b], attempts[b] = s.P, n, d.F, d.nF, 0, attempt
+            V[b, :n, 0] = (s.P[:, 0].astype(np.float64) / MESHDIGITS_Q).astype(np.float32)
+            V[b, :n, 1] = (s.P[:, 1].astype(np.float64) / MESHDIGITS_Q).astype(np.float32)
+            V[b, :n, 2] = lattice_intensity(images[b], s.P)
+            break
+    return MeshDigitsResult(P, count, V, F, nF, status, attempts)

@@ -29,7 +29,7 @@ from . import kernels
 __all__ = ["SparseOperator", "OperatorPool", "PackedSegments", "as_operator", "dirac_operators_from_mesh",
            "laplacian_operator_from_mesh", "geodesic_matrix_from_mesh", "spgemm", "amplify_sequence_operators",
            "clean_mesh", "CleanMesh", "repair_mesh", "RepairedMesh", "vertex_descriptors", "MeshDescriptors", "vertex_normals", "face_areas", "vertex_mass",
-           "gaussian_curvature"]
+           "gaussian_curvature", "delaunay_2d", "Delaunay2D"]
 
 # A BSR4 copy is kept when zero-fill costs at most this much extra storage over CSR entries.
 _BSR4_MAX_FILL = 1.6
@@ -736,6 +736,59 @@ def repair_mesh(V, F, tol: float = 0.0, weld: bool = True, unique: bool = True, 
     face_map = out.Fsrc[:nFk]
     return RepairedMesh(out.Vnew[:nVk], out.Fnew[:nFk], out.J[:nVk], out.I[w.rep.long()], face_map, flip[face_map.long()], welded, bad,
                         dup, flat, nonman, twisted, classes)
+
+
+@dataclasses.dataclass
+class Delaunay2D:
+    """What operators.delaunay_2d returns, int32 device tensors; one set: F (2 n, 3) and 0-d fields, a batch: F (B, 2 Nmax, 3)
+    and (B,) fields.  F is canonical with -1 in the rows past nF; status holds kernels.DT_* bits (0: triangulated)."""
+    F: torch.Tensor
+    nF: torch.Tensor
+    status: torch.Tensor
+    flips: torch.Tensor
+    cocircular: torch.Tensor
+    rounds: torch.Tensor
+    boundary: torch.Tensor
+
+    def faces(self, b: Optional[int] = None) -> torch.Tensor:
+        """The (nF, 3) faces of the set (of set b of a batch).  Reads nF: synchronises."""
+        F, nF = (self.F, self.nF) if b is None else (self.F[b], self.nF[b])
+        return F[: int(nF)]
+
+
+def delaunay_2d(P, count=None, quantum=None, max_rounds: int = kernels.DT_MAX_ROUNDS, device="cuda") -> Delaunay2D:
+    """Delaunay triangulation of 2-D point sets on the device, exact on an integer lattice (kernels.delaunay_2d; the definition
+    is in include/sn_spmm.h, "Lattice Delaunay and the Mesh-MNIST maker", the host statement is mesh_ops.delaunay_2d) — the
+    batched replacement of scipy.spatial.Delaunay in src/mesh_mnist/create_data.py:81.
+    P: tensor or numpy, (n, 2) one set or (B, Nmax, 2) a padded batch with count (B,) (None: every set has Nmax points).  Integer
+    P are lattice coordinates, |x|, |y| < 2^24.  quantum: the input (any dtype) is snapped first, rint(P / quantum) in float64;
+    floating-point P needs it.  At most kernels.delaunay_max_points() points per set.  Each set gets its own status
+    (kernels.DT_*): a refused set has nF = 0 and leaves its neighbours alone.  Nothing synchronises unless the caller reads."""
+    Pt = P if torch.is_tensor(P) else torch.from_numpy(np.ascontiguousarray(P))
+    Pt = Pt.to(device) if not Pt.is_cuda else Pt
+    if Pt.dim() not in (2, 3) or Pt.shape[-1] != 2:
+        raise ValueError(f"delaunay_2d wants P (n, 2) or (B, Nmax, 2), got {tuple(Pt.shape)}")
+    if quantum is not None:
+        q = float(quantum)
+        if not (q > 0.0 and q < float("inf")):
+            raise ValueError(f"delaunay_2d: quantum must be finite and > 0, got {quantum!r}")
+        Pt = torch.round(Pt.to(torch.float64) / q)
+        Pt = torch.where(torch.isfinite(Pt), Pt, torch.full_like(Pt, float(1 << 24)))
+    elif Pt.is_floating_point():
+        raise TypeError("delaunay_2d: floating-point P needs quantum= (the lattice spacing); integer P are lattice coordinates")
+    lim = 1 << 24                                  # a coordinate at +-2^24 is out of range: the kernel reports DT_RANGE
+    Pi = Pt.clamp(-lim, lim).to(torch.int32)
+    single = Pi.dim() == 2
+    if single:
+        Pi = Pi.unsqueeze(0)
+        count = None if count is None else torch.as_tensor([int(count)])
+    if count is not None:
+        count = (count if torch.is_tensor(count) else torch.from_numpy(np.asarray(count))).to(Pi.device).to(torch.int32).reshape(-1)
+        if count.shape[0] != Pi.shape[0]:
+            raise ValueError(f"delaunay_2d: count has {count.shape[0]} entries for {Pi.shape[0]} sets")
+    r = kernels.delaunay_2d(Pi, count, max_rounds)
+    f = (lambda t: t[0]) if single else (lambda t: t)
+    return Delaunay2D(f(r.F), f(r.nF), f(r.status), f(r.counts[:, 0]), f(r.counts[:, 1]), f(r.counts[:, 2]), f(r.counts[:, 3]))
 
 
 class PackedSegments:
