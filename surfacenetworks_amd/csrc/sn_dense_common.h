@@ -4,13 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sn_internal.h"
 #include "sn_spmm.h"
-
-// per-launch timing shared with sn_kernels.hip (the facility behind sn_timing_*)
-int sn_internal_cu_count();
-hipError_t sn_internal_fill(void *dst, int value, size_t bytes, hipStream_t s);
-hipError_t sn_internal_copy2d(void *dst, int64_t dpitch, const void *src, int64_t spitch, int64_t width, int64_t rows, hipStream_t s);
-bool sn_internal_timing_slot(int kind, int64_t rows, int64_t width, int64_t bytes, int outw, hipEvent_t *s, hipEvent_t *e);
 
 namespace {
 

@@ -24,11 +24,8 @@
 #include <mutex>
 #include <vector>
 
+#include "sn_internal.h"
 #include "sn_spmm.h"
-
-int sn_internal_cu_count();
-hipError_t sn_internal_fill(void *dst, int value, size_t bytes, hipStream_t s);
-hipError_t sn_internal_copy2d(void *dst, int64_t dpitch, const void *src, int64_t spitch, int64_t width, int64_t rows, hipStream_t s);
 
 namespace {
 
@@ -759,31 +756,28 @@ __global__ __launch_bounds__(kWG) void coo_to_csr_k(const int64_t *__restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------------
-// int32 exclusive scan, 3 launches (block sums -> scan of sums -> rescan with offsets).
+// int32 exclusive scan, 3 launches (block sums -> scan of sums -> rescan with offsets): the one scan of the library, reached
+// from the other translation units as sn_internal_scan_i32 (sn_internal.h).
 // ------------------------------------------------------------------------------------------------
 constexpr int kScanItems = 8;
 constexpr int kScanTile = kWG * kScanItems;
 
-__device__ __forceinline__ int wave_incl_scan(int v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int t = __shfl_up(v, d, 64);
-    if (lane >= d) v += t;
-  }
-  return v;
-}
-
 // exclusive scan of one value per thread across the 256-thread workgroup; returns the prefix,
 // *total receives the workgroup sum.
-__device__ __forceinline__ int block_excl_scan(int v, int *total) {
-  __shared__ int wsum[kWG / 64];
-  const int incl = wave_incl_scan(v);
+template <class T>
+__device__ __forceinline__ T block_excl_scan(T v, T *total) {
+  __shared__ T wsum[kWG / 64];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  T incl = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const T t = __shfl_up(incl, d, 64);
+    if (lane >= d) incl += t;
+  }
   __syncthreads();
   if (lane == 63) wsum[wave] = incl;
   __syncthreads();
-  int off = 0, tot = 0;
+  T off = 0, tot = 0;
 #pragma unroll
   for (int i = 0; i < kWG / 64; ++i) {
     if (i < wave) off += wsum[i];
@@ -801,25 +795,32 @@ __global__ __launch_bounds__(kWG) void scan_block_sums(const int *__restrict__ i
   for (int i = 0; i < kScanItems; ++i)
     if (base + i < n) s += in[base + i];
   int tot;
-  block_excl_scan(s, &tot);
+  block_excl_scan<int>(s, &tot);
   if (threadIdx.x == 0) sums[blockIdx.x] = tot;
 }
 
-__global__ __launch_bounds__(kWG) void scan_sums_inplace(int *__restrict__ sums, int nblk) {
-  int carry = 0;
+// one workgroup over the block sums, 256 per pass, added up in int64: without an overflow the int32 values of a 32-bit
+// sum; a total past INT_MAX raises too_large in *status (when there is one)
+__global__ __launch_bounds__(kWG) void scan_sums_inplace(int *__restrict__ sums, int nblk, int *__restrict__ status,
+                                                         int too_large) {
+  long long carry = 0;
   for (int b0 = 0; b0 < nblk; b0 += kWG) {
     const int i = b0 + threadIdx.x;
-    const int v = (i < nblk) ? sums[i] : 0;
-    int tot;
-    const int ex = block_excl_scan(v, &tot);
-    if (i < nblk) sums[i] = carry + ex;
+    const long long v = (i < nblk) ? sums[i] : 0;
+    long long tot;
+    const long long ex = block_excl_scan<long long>(v, &tot);
+    if (i < nblk) sums[i] = (int)(carry + ex);
     carry += tot;
     __syncthreads();
   }
+  if (threadIdx.x == 0 && carry > INT_MAX && status) atomicOr(status, too_large);
 }
 
+// out = exclusive scan; nothing is written once *status holds a bit of skip_mask
 __global__ __launch_bounds__(kWG) void scan_apply(const int *__restrict__ in, int64_t n,
-                                                  const int *__restrict__ sums, int *__restrict__ out) {
+                                                  const int *__restrict__ sums, int *__restrict__ out,
+                                                  const int *__restrict__ status, int skip_mask) {
+  if (status && (*status & skip_mask)) return;
   const int64_t base = (int64_t)blockIdx.x * kScanTile + threadIdx.x * kScanItems;
   int v[kScanItems];
   int s = 0;
@@ -829,7 +830,7 @@ __global__ __launch_bounds__(kWG) void scan_apply(const int *__restrict__ in, in
     s += v[i];
   }
   int tot;
-  int run = block_excl_scan(s, &tot) + sums[blockIdx.x];
+  int run = block_excl_scan<int>(s, &tot) + sums[blockIdx.x];
 #pragma unroll
   for (int i = 0; i < kScanItems; ++i) {
     if (base + i < n) out[base + i] = run;
@@ -1887,11 +1888,7 @@ inline int check_dense(const float *P, int64_t ld, int group, int N) {
 int exclusive_scan_i32(const int *in, int64_t n, int *out, void *ws, size_t ws_bytes, hipStream_t s) {
   const int64_t nblk = (n + kScanTile - 1) / kScanTile;
   if (ws_bytes < (size_t)nblk * sizeof(int)) return SN_E_WORKSPACE;
-  if (n <= 0) return SN_OK;
-  int *sums = static_cast<int *>(ws);
-  hipLaunchKernelGGL(scan_block_sums, dim3((unsigned)nblk), dim3(kWG), 0, s, in, n, sums);
-  hipLaunchKernelGGL(scan_sums_inplace, dim3(1), dim3(kWG), 0, s, sums, (int)nblk);
-  hipLaunchKernelGGL(scan_apply, dim3((unsigned)nblk), dim3(kWG), 0, s, in, n, sums, out);
+  sn_internal_scan_i32(in, n, out, static_cast<int *>(ws), nullptr, 0, 0, s);
   return launch_status();
 }
 
@@ -2025,6 +2022,14 @@ hipError_t sn_internal_copy2d(void *dst, int64_t dpitch, const void *src, int64_
 
 hipError_t sn_internal_fill(void *dst, int value, size_t bytes, hipStream_t s) {
   return bytes ? sn_internal_fill2d(dst, 0, value, (int64_t)bytes, 1, s) : hipSuccess;
+}
+
+void sn_internal_scan_i32(const int *in, int64_t n, int *out, int *sums, int *status, int too_large, int skip_mask, hipStream_t s) {
+  if (n <= 0) return;
+  const int nblk = (int)((n + kScanTile - 1) / kScanTile);
+  hipLaunchKernelGGL(scan_block_sums, dim3((unsigned)nblk), dim3(kWG), 0, s, in, n, sums);
+  hipLaunchKernelGGL(scan_sums_inplace, dim3(1), dim3(kWG), 0, s, sums, nblk, status, too_large);
+  hipLaunchKernelGGL(scan_apply, dim3((unsigned)nblk), dim3(kWG), 0, s, in, n, (const int *)sums, out, (const int *)status, skip_mask);
 }
 
 // The same timing slot for the Linear-layer launchers of the other translation units (sn_gemm.hip, sn_dense.hip): kind

@@ -7,17 +7,12 @@
 #include <limits.h>
 #include <stdint.h>
 
+#include "sn_internal.h"
 #include "sn_spmm.h"
-
-// fills / device copies as kernels of this library (sn_kernels.hip says why not hipMemsetAsync)
-hipError_t sn_internal_fill(void *dst, int value, size_t bytes, hipStream_t s);
-hipError_t sn_internal_copy2d(void *dst, int64_t dpitch, const void *src, int64_t spitch, int64_t width, int64_t rows, hipStream_t s);
 
 namespace {
 
 constexpr int kWG = 256;
-constexpr int kScanItems = 8;
-constexpr int kScanTile = kWG * kScanItems;
 
 inline int launch_status() {
   const hipError_t e = hipGetLastError();
@@ -53,74 +48,84 @@ __global__ __launch_bounds__(kWG) void face_area_k(const float *__restrict__ V, 
   }
 }
 
-// ---- int32 exclusive scan (same 3-launch scheme as sn_kernels.hip) ---------------------------------------
-__device__ __forceinline__ int block_excl_scan(int v, int *total) {
-  __shared__ int wsum[kWG / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int t = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += t;
-  }
-  __syncthreads();
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  int off = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < kWG / 64; ++i) {
-    if (i < wave) off += wsum[i];
-    tot += wsum[i];
-  }
-  *total = tot;
-  return off + incl - v;
+// a face contributes its three corners only when its indices are three distinct vertices of the mesh
+__device__ __forceinline__ bool face_ok(int i, int j, int k, int64_t nV) {
+  return (unsigned)i < (unsigned)nV && (unsigned)j < (unsigned)nV && (unsigned)k < (unsigned)nV && i != j && j != k && k != i;
 }
-__global__ __launch_bounds__(kWG) void scan_sums_k(const int *__restrict__ in, int64_t n, int *__restrict__ sums) {
-  const int64_t base = (int64_t)blockIdx.x * kScanTile + threadIdx.x * kScanItems;
-  int s = 0;
-#pragma unroll
-  for (int i = 0; i < kScanItems; ++i)
-    if (base + i < n) s += in[base + i];
-  int tot;
-  block_excl_scan(s, &tot);
-  if (threadIdx.x == 0) sums[blockIdx.x] = tot;
+
+// ---- buckets by vertex: count into a zeroed ptr[0..nV], bucket_offsets, fill through the atomic cursor ------------------------
+// A bucket holds codes CODE * face + corner.  KEY: the bucket of corner c is its own vertex (kCornerVertex: the side that starts
+// there) or the lower end of the side c -> c + 1 (kLowerEnd).  FILTER: which faces take part.  The order inside a bucket is the
+// order of the atomics: a reader that depends on it sorts the bucket (sort_run), the others say why they do not.
+enum BucketKey { kCornerVertex, kLowerEnd };
+enum BucketFilter { kEveryFace, kGoodFaces, kGoodKeptFaces };      // kGoodKeptFaces: face_ok and keep[f] != 0
+
+template <BucketKey KEY>
+__device__ __forceinline__ int bucket_of(const int (&v)[3], int c) {
+  return KEY == kCornerVertex ? v[c] : min(v[c], v[(c + 1) % 3]);
 }
-__global__ __launch_bounds__(kWG) void scan_top_k(int *__restrict__ sums, int nblk) {
-  int carry = 0;
-  for (int b0 = 0; b0 < nblk; b0 += kWG) {
-    const int i = b0 + threadIdx.x;
-    const int v = (i < nblk) ? sums[i] : 0;
-    int tot;
-    const int ex = block_excl_scan(v, &tot);
-    if (i < nblk) sums[i] = carry + ex;
-    carry += tot;
-    __syncthreads();
+// false: the face takes no part; *bad: because it failed face_ok (a face that is not kept is not looked at)
+template <BucketFilter FILTER>
+__device__ __forceinline__ bool bucket_takes(const int (&v)[3], const int *__restrict__ keep, int64_t f, int64_t nV, bool *bad) {
+  *bad = false;
+  if (FILTER == kEveryFace) return true;
+  if (FILTER == kGoodKeptFaces && keep[f] == 0) return false;
+  *bad = !face_ok(v[0], v[1], v[2], nV);
+  return !*bad;
+}
+
+// STATUS_BIT is raised in *status (when there is one) for a face that fails face_ok
+template <BucketKey KEY, BucketFilter FILTER, int STATUS_BIT>
+__global__ __launch_bounds__(kWG) void bucket_count_k(const int *__restrict__ F, const int *__restrict__ keep, int64_t nF, int64_t nV,
+                                                      int *__restrict__ count, int *__restrict__ status) {
+  for (int64_t f = (int64_t)blockIdx.x * kWG + threadIdx.x; f < nF; f += (int64_t)gridDim.x * kWG) {
+    const int v[3] = {F[3 * f], F[3 * f + 1], F[3 * f + 2]};
+    bool bad;
+    if (!bucket_takes<FILTER>(v, keep, f, nV, &bad)) {
+      if (bad && status) atomicOr(status, STATUS_BIT);
+      continue;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) atomicAdd(&count[bucket_of<KEY>(v, c)], 1);
   }
 }
-__global__ __launch_bounds__(kWG) void scan_apply_k(const int *__restrict__ in, int64_t n, const int *__restrict__ sums,
-                                                    int *__restrict__ out) {
-  const int64_t base = (int64_t)blockIdx.x * kScanTile + threadIdx.x * kScanItems;
-  int v[kScanItems], s = 0;
+template <BucketKey KEY, BucketFilter FILTER, int CODE>
+__global__ __launch_bounds__(kWG) void bucket_fill_k(const int *__restrict__ F, const int *__restrict__ keep, int64_t nF, int64_t nV,
+                                                     int *__restrict__ cursor, int *__restrict__ bucket) {
+  for (int64_t f = (int64_t)blockIdx.x * kWG + threadIdx.x; f < nF; f += (int64_t)gridDim.x * kWG) {
+    const int v[3] = {F[3 * f], F[3 * f + 1], F[3 * f + 2]};
+    bool bad;
+    if (!bucket_takes<FILTER>(v, keep, f, nV, &bad)) continue;
 #pragma unroll
-  for (int i = 0; i < kScanItems; ++i) {
-    v[i] = (base + i < n) ? in[base + i] : 0;
-    s += v[i];
-  }
-  int tot;
-  int run = block_excl_scan(s, &tot) + sums[blockIdx.x];
-#pragma unroll
-  for (int i = 0; i < kScanItems; ++i) {
-    if (base + i < n) out[base + i] = run;
-    run += v[i];
+    for (int c = 0; c < 3; ++c) bucket[atomicAdd(&cursor[bucket_of<KEY>(v, c)], 1)] = (int)(CODE * f + c);
   }
 }
 
-// incidence lists: entry = 4*face + corner, scattered with an atomic cursor then sorted per vertex (= by face)
-__global__ __launch_bounds__(kWG) void incidence_scatter_k(const int *__restrict__ F, int64_t nF, int *__restrict__ cursor,
-                                                           int *__restrict__ inc) {
-  for (int64_t f = (int64_t)blockIdx.x * kWG + threadIdx.x; f < nF; f += (int64_t)gridDim.x * kWG)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) inc[atomicAdd(&cursor[F[3 * f + c]], 1)] = (int)(4 * f + c);
+// counts in ptr[0..nV) and a zero at nV -> the buckets' offsets, in place, and the cursor the fill advances (a copy)
+inline int bucket_offsets(int *ptr, int *cursor, int *sums, int64_t nV, hipStream_t s) {
+  sn_internal_scan_i32(ptr, nV + 1, ptr, sums, nullptr, 0, 0, s);
+  const hipError_t e = sn_internal_copy2d(cursor, 0, ptr, 0, (int64_t)((size_t)(nV + 1) * sizeof(int)), 1, s);
+  return e == hipSuccess ? SN_OK : (int)e;
+}
+
+// stable insertion sort of key[b..e), ascending, that carries up to two payload arrays along
+template <class A = char, class B = char>
+__device__ __forceinline__ void sort_run(int *key, int b, int e, A *pa = nullptr, B *pb = nullptr) {
+  for (int i = b + 1; i < e; ++i) {
+    const int k = key[i];
+    const A va = pa ? pa[i] : A();
+    const B vb = pb ? pb[i] : B();
+    int j = i - 1;
+    while (j >= b && key[j] > k) {
+      key[j + 1] = key[j];
+      if (pa) pa[j + 1] = pa[j];
+      if (pb) pb[j + 1] = pb[j];
+      --j;
+    }
+    key[j + 1] = k;
+    if (pa) pa[j + 1] = va;
+    if (pb) pb[j + 1] = vb;
+  }
 }
 
 // sort each vertex's list, write DiA's block columns, and Av_j = sum_{incident faces, ascending} Af/3 (mesh.py:43-45)
@@ -129,15 +134,7 @@ __global__ __launch_bounds__(kWG) void vertex_lists_k(const int *__restrict__ vp
                                                       int *__restrict__ dia_colind) {
   for (int64_t v = (int64_t)blockIdx.x * kWG + threadIdx.x; v < nV; v += (int64_t)gridDim.x * kWG) {
     const int b = vptr[v], e = vptr[v + 1];
-    for (int i = b + 1; i < e; ++i) {
-      const int key = inc[i];
-      int j = i - 1;
-      while (j >= b && inc[j] > key) {
-        inc[j + 1] = inc[j];
-        --j;
-      }
-      inc[j + 1] = key;
-    }
+    sort_run(inc, b, e);
     double a = 0;
     for (int i = b; i < e; ++i) {
       a += Af[inc[i] >> 2] / 3;
@@ -148,18 +145,7 @@ __global__ __launch_bounds__(kWG) void vertex_lists_k(const int *__restrict__ vp
 }
 
 __global__ __launch_bounds__(kWG) void vertex_sort_k(const int *__restrict__ vptr, int64_t nV, int *__restrict__ inc) {
-  for (int64_t v = (int64_t)blockIdx.x * kWG + threadIdx.x; v < nV; v += (int64_t)gridDim.x * kWG) {
-    const int b = vptr[v], e = vptr[v + 1];
-    for (int i = b + 1; i < e; ++i) {
-      const int key = inc[i];
-      int j = i - 1;
-      while (j >= b && inc[j] > key) {
-        inc[j + 1] = inc[j];
-        --j;
-      }
-      inc[j + 1] = key;
-    }
-  }
+  for (int64_t v = (int64_t)blockIdx.x * kWG + threadIdx.x; v < nV; v += (int64_t)gridDim.x * kWG) sort_run(inc, vptr[v], vptr[v + 1]);
 }
 
 // the 4x4 block  -Q(0,e)/(2Af)  (mesh.py:28-33,55-58), row-major, as doubles
@@ -275,17 +261,7 @@ __global__ __launch_bounds__(kWG) void laplacian_rows_k(const float *__restrict_
       A += t;
       A += t;
     }
-    // stable insertion sort by neighbour id (keeps face order among duplicates)
-    for (int x = 1; x < n; ++x) {
-      const int kn = nb[x];
-      const double u = wij[x], v = wji[x];
-      int y = x - 1;
-      while (y >= 0 && nb[y] > kn) {
-        nb[y + 1] = nb[y]; wij[y + 1] = wij[y]; wji[y + 1] = wji[y];
-        --y;
-      }
-      nb[y + 1] = kn; wij[y + 1] = u; wji[y + 1] = v;
-    }
+    sort_run(nb, 0, n, wij, wji);      // by neighbour id; stable: keeps face order among duplicates
     // merge duplicates; d_i = sum over neighbours (ascending) of W[nb, i]; entries with W[i,nb] == 0 are dropped
     const double ainv = 1 / (A + 1e-9);
     double d = 0;
@@ -459,25 +435,7 @@ struct MeshCorner {      // (v; a, b): the record of the header, 40 bytes
 };
 static_assert(sizeof(MeshCorner) == SN_MESH_CORNER_BYTES, "corner record layout");
 
-// a face contributes its three corners only when its indices are three distinct vertices of the mesh
-__device__ __forceinline__ bool face_ok(int i, int j, int k, int64_t nV) {
-  return (unsigned)i < (unsigned)nV && (unsigned)j < (unsigned)nV && (unsigned)k < (unsigned)nV && i != j && j != k && k != i;
-}
-
-__global__ __launch_bounds__(kWG) void corner_count_k(const int *__restrict__ F, int64_t nF, int64_t nV, int *__restrict__ count,
-                                                      int *__restrict__ status_flag) {
-  for (int64_t f = (int64_t)blockIdx.x * kWG + threadIdx.x; f < nF; f += (int64_t)gridDim.x * kWG) {
-    const int i = F[3 * f], j = F[3 * f + 1], k = F[3 * f + 2];
-    if (!face_ok(i, j, k, nV)) {
-      if (status_flag) atomicExch(status_flag, 1);
-      continue;
-    }
-    atomicAdd(&count[i], 1);
-    atomicAdd(&count[j], 1);
-    atomicAdd(&count[k], 1);
-  }
-}
-
+// the records of the good faces, scattered through the cursor of their corner-vertex buckets
 __global__ __launch_bounds__(kWG) void corner_fill_k(const float *__restrict__ V, const int *__restrict__ F, int64_t nF, int64_t nV,
                                                      int *__restrict__ cursor, MeshCorner *__restrict__ rec) {
   for (int64_t f = (int64_t)blockIdx.x * kWG + threadIdx.x; f < nF; f += (int64_t)gridDim.x * kWG) {
@@ -597,18 +555,7 @@ int mesh_geodesics_launch(const int *cptr, const MeshCorner *rec, int n, int src
 constexpr int kIdtRefused = SN_IDT_BAD_FACE | SN_IDT_NON_MANIFOLD | SN_IDT_ORIENTATION;
 typedef unsigned long long idt_claim_t;
 
-// sides bucketed by the vertex they start at (counted by corner_count_k: one side starts at every corner of a valid face)
-__global__ __launch_bounds__(kWG) void side_fill_k(const int *__restrict__ F, int64_t nF, int64_t nV, int *__restrict__ cursor,
-                                                   int *__restrict__ bucket) {
-  for (int64_t f = (int64_t)blockIdx.x * kWG + threadIdx.x; f < nF; f += (int64_t)gridDim.x * kWG) {
-    const int i = F[3 * f], j = F[3 * f + 1], k = F[3 * f + 2];
-    if (!face_ok(i, j, k, nV)) continue;
-    bucket[atomicAdd(&cursor[i], 1)] = (int)(3 * f);
-    bucket[atomicAdd(&cursor[j], 1)] = (int)(3 * f + 1);
-    bucket[atomicAdd(&cursor[k], 1)] = (int)(3 * f + 2);
-  }
-}
-
+// The sides are bucketed by the vertex they start at (kCornerVertex over the good faces).
 // twin of the side a -> b: the one side b -> a in b's bucket.  The order inside a bucket (atomic cursor) does not matter: a
 // twin is stored only when it is the only candidate.
 __global__ __launch_bounds__(kWG) void glue_twin_k(const float *__restrict__ V, const int *__restrict__ F, int64_t nF, int64_t nV,
@@ -850,26 +797,65 @@ __global__ __launch_bounds__(kWG) void idt_entries_k(const int64_t *__restrict__
   }
 }
 
+// ---- workspace layouts: one description each (SnCarver), run by the *_workspace_bytes query without a workspace and by the
+// entry point with it.  nV, nF >= 0. ----
+struct BucketWs {      // ptr[nV + 1], cursor[nV + 1], bucket[3 nF], the scan's scratch
+  int *ptr = nullptr, *cursor = nullptr, *bucket = nullptr, *sums = nullptr;
+  BucketWs() = default;
+  BucketWs(SnCarver &c, int64_t nV, int64_t nF)
+      : ptr(c.take<int>(nV + 1)), cursor(c.take<int>(nV + 1)), bucket(c.take<int>(3 * nF)), sums(c.take_scan(nV + 1)) {}
+};
+struct DiracWs {       // the Dirac builder's; the Laplacian builder shares it and leaves Av alone
+  SnCarver c;
+  double *Af, *Av;
+  BucketWs b;
+  DiracWs(void *w, int64_t nV, int64_t nF) : c(w), Af(c.take<double>(nF)), Av(c.take<double>(nV)), b(c, nV, nF) {}
+};
+struct CornersWs {
+  SnCarver c;
+  int *cursor, *sums;
+  CornersWs(void *w, int64_t nV) : c(w), cursor(c.take<int>(nV + 1)), sums(c.take_scan(nV + 1)) {}
+};
+struct MeshBucketWs {  // glue, descriptors, cot Laplacian
+  SnCarver c;
+  BucketWs b;
+  MeshBucketWs(void *w, int64_t nV, int64_t nF) : c(w), b(c, nV, nF) {}
+};
 struct IdtLapWs {
+  SnCarver c;
   double *cval, *cmass, *A;
   int *hs, *sums;
+  IdtLapWs(void *w, int64_t nV, int64_t nF)
+      : c(w), cval(c.take<double>(12 * nF + nV)), cmass(c.take<double>(12 * nF + nV)), A(c.take<double>(nV)),
+        hs(c.take<int>(12 * nF + nV + 1)), sums(c.take_scan(12 * nF + nV + 1)) {}
 };
-inline size_t idt_lap_ws(int64_t nV, int64_t nF, char *w, IdtLapWs *out) {
-  const int64_t N = 12 * nF + nV;
-  const size_t scan = (size_t)((N + 1 + kScanTile - 1) / kScanTile + 1) * sizeof(int);
-  const size_t b0 = ((size_t)N * sizeof(double) + 15) & ~(size_t)15, b1 = ((size_t)nV * sizeof(double) + 15) & ~(size_t)15,
-               b2 = ((size_t)(N + 1) * sizeof(int) + 15) & ~(size_t)15;
-  if (out) {
-    out->cval = reinterpret_cast<double *>(w);
-    out->cmass = reinterpret_cast<double *>(w + b0);
-    out->A = reinterpret_cast<double *>(w + 2 * b0);
-    out->hs = reinterpret_cast<int *>(w + 2 * b0 + b1);
-    out->sums = reinterpret_cast<int *>(w + 2 * b0 + b1 + b2);
+struct ComponentsWs {  // the winner word and the label counter; edge mode: the sides' buckets
+  SnCarver c;
+  unsigned long long *acc;
+  BucketWs b;
+  ComponentsWs(void *w, int64_t nV, int64_t nF, bool edge) : c(w), acc(c.take<unsigned long long>(2)) {
+    if (edge) b = BucketWs(c, nV, nF);
   }
-  return 2 * b0 + b1 + b2 + ((scan + 15) & ~(size_t)15);
+};
+struct CompactWs {     // one scratch for both scans
+  SnCarver c;
+  int *vpos, *fpos, *sums;
+  CompactWs(void *w, int64_t nV, int64_t nF)
+      : c(w), vpos(c.take<int>(nV + 1)), fpos(c.take<int>(nF + 1)), sums(c.take_scan((nV > nF ? nV : nF) + 1)) {}
+};
+struct OrientWs {
+  SnCarver c;
+  BucketWs b;
+  int *conflict;
+  OrientWs(void *w, int64_t nV, int64_t nF) : c(w), b(c, nV, nF), conflict(c.take<int>(nF)) {}
+};
+template <class T>
+inline size_t one_slice_bytes(int64_t count) {      // a workspace that is one array: the entry point takes it as it comes
+  SnCarver c(nullptr);
+  c.take<T>(count);
+  return c.bytes;
 }
-
-inline size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
+inline int64_t at_least_0(int64_t n) { return n < 0 ? 0 : n; }
 
 // ------------------------------------------------------------------------------------------------
 // Mesh clean-up: component labels by a concurrent union-find, and compaction by two scans (definition: sn_spmm.h).
@@ -932,35 +918,8 @@ __global__ __launch_bounds__(kWG) void cc_vertex_union_k(const int *__restrict__
   }
 }
 
-// edge mode: the sides of the good faces, bucketed under the lower of their two vertices (orientation does not matter)
-// (keep: only the faces with keep[f] != 0 take part — the orientation of the repair section; nullptr: every good face)
-__global__ __launch_bounds__(kWG) void cc_side_count_k(const int *__restrict__ F, const int *__restrict__ keep, int64_t nF, int64_t nV,
-                                                       int *__restrict__ ptr, int *__restrict__ status) {
-  for (int64_t f = (int64_t)blockIdx.x * kWG + threadIdx.x; f < nF; f += (int64_t)gridDim.x * kWG) {
-    if (keep && keep[f] == 0) continue;
-    const int i = F[3 * f], j = F[3 * f + 1], k = F[3 * f + 2];
-    if (!face_ok(i, j, k, nV)) {
-      atomicOr(status, SN_CC_BAD_FACE);
-      continue;
-    }
-    atomicAdd(&ptr[min(i, j)], 1);
-    atomicAdd(&ptr[min(j, k)], 1);
-    atomicAdd(&ptr[min(k, i)], 1);
-  }
-}
-
-__global__ __launch_bounds__(kWG) void cc_side_fill_k(const int *__restrict__ F, const int *__restrict__ keep, int64_t nF, int64_t nV,
-                                                      int *__restrict__ cursor, int *__restrict__ bucket) {
-  for (int64_t f = (int64_t)blockIdx.x * kWG + threadIdx.x; f < nF; f += (int64_t)gridDim.x * kWG) {
-    if (keep && keep[f] == 0) continue;
-    const int i = F[3 * f], j = F[3 * f + 1], k = F[3 * f + 2];
-    if (!face_ok(i, j, k, nV)) continue;
-    bucket[atomicAdd(&cursor[min(i, j)], 1)] = (int)(3 * f);
-    bucket[atomicAdd(&cursor[min(j, k)], 1)] = (int)(3 * f + 1);
-    bucket[atomicAdd(&cursor[min(k, i)], 1)] = (int)(3 * f + 2);
-  }
-}
-
+// edge mode: the sides of the good faces, bucketed under the lower of their two vertices (kLowerEnd: orientation does not
+// matter; the orientation of the repair section buckets only the kept faces).
 // A side joins its face to the face of the first side of its bucket on the same upper vertex: a star per edge, whatever the
 // number of faces on it.  The order inside a bucket (atomic cursor) picks the centre of the star, not the partition.
 __global__ __launch_bounds__(kWG) void cc_edge_union_k(const int *__restrict__ F, int64_t nF, int64_t nV, const int *__restrict__ ptr,
@@ -1100,14 +1059,8 @@ __global__ __launch_bounds__(kWG) void label_mask_k(const int *__restrict__ flab
     keep[f] = (want >= 0 && flabel[f] == want) ? 1 : 0;
 }
 
-inline size_t scan_bytes(int64_t n) { return align16((size_t)((n + kScanTile - 1) / kScanTile + 1) * sizeof(int)); }
 // exclusive scan of a[0..n) in place on stream s
-inline void scan_in_place(int *a, int64_t n, int *sums, hipStream_t s) {
-  const int nblk = (int)((n + kScanTile - 1) / kScanTile);
-  hipLaunchKernelGGL(scan_sums_k, dim3(nblk), dim3(kWG), 0, s, a, n, sums);
-  hipLaunchKernelGGL(scan_top_k, dim3(1), dim3(kWG), 0, s, sums, nblk);
-  hipLaunchKernelGGL(scan_apply_k, dim3(nblk), dim3(kWG), 0, s, a, n, sums, a);
-}
+inline void scan_in_place(int *a, int64_t n, int *sums, hipStream_t s) { sn_internal_scan_i32(a, n, a, sums, nullptr, 0, 0, s); }
 
 // ------------------------------------------------------------------------------------------------
 // Mesh repair: weld, duplicate faces, orientation (definition: sn_spmm.h, "Mesh repair").
@@ -1597,16 +1550,7 @@ __global__ __launch_bounds__(kWG) void cot_laplacian_rows_k(const float *__restr
       nb[n] = vb; cw[n] = 0.5 * t.cota; ++n;
       M += voronoi ? t.vor : t.af / 3;
     }
-    for (int x = 1; x < n; ++x) {                        // stable insertion sort by neighbour id
-      const int kn = nb[x];
-      const double u = cw[x];
-      int y = x - 1;
-      while (y >= 0 && nb[y] > kn) {
-        nb[y + 1] = nb[y]; cw[y + 1] = cw[y];
-        --y;
-      }
-      nb[y + 1] = kn; cw[y + 1] = u;
-    }
+    sort_run(nb, 0, n, cw);                              // by neighbour id, stable
     if constexpr (!FILL) {
       int cnt = 0;
       for (int x = 0; x < n; ++x) cnt += (x == 0 || nb[x] != nb[x - 1]);
@@ -1632,17 +1576,14 @@ __global__ __launch_bounds__(kWG) void cot_laplacian_rows_k(const float *__restr
   }
 }
 
-inline size_t incidence_bytes(int64_t nV, int64_t nF) {
-  return align16((size_t)(nV + 1) * sizeof(int)) * 2 + align16((size_t)3 * nF * sizeof(int)) + scan_bytes(nV + 1);
-}
-
-// vptr / inc of the good faces (codes 3 f + c, ascending per vertex) after desc_face_k has counted into a zeroed vptr
-inline int incidence_build(const int *F, int64_t nV, int64_t nF, int *vptr, int *cursor, int *inc, int *sums, hipStream_t s) {
-  scan_in_place(vptr, nV + 1, sums, s);
-  const hipError_t e = sn_internal_copy2d(cursor, 0, vptr, 0, (int64_t)((size_t)(nV + 1) * sizeof(int)), 1, s);
-  if (e != hipSuccess) return (int)e;
-  if (nF > 0) hipLaunchKernelGGL(side_fill_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, nV, cursor, inc);
-  if (nV > 0) hipLaunchKernelGGL(vertex_sort_k, dim3(grid_for(nV)), dim3(kWG), 0, s, vptr, nV, inc);
+// ptr / bucket of the good faces (codes 3 f + c, ascending per vertex) after desc_face_k has counted into a zeroed ptr
+inline int incidence_build(const int *F, int64_t nV, int64_t nF, const BucketWs &b, hipStream_t s) {
+  const int st = bucket_offsets(b.ptr, b.cursor, b.sums, nV, s);
+  if (st != SN_OK) return st;
+  if (nF > 0)
+    hipLaunchKernelGGL((bucket_fill_k<kCornerVertex, kGoodFaces, 3>), dim3(grid_for(nF)), dim3(kWG), 0, s, F, (const int *)nullptr, nF, nV,
+                       b.cursor, b.bucket);
+  if (nV > 0) hipLaunchKernelGGL(vertex_sort_k, dim3(grid_for(nV)), dim3(kWG), 0, s, b.ptr, nV, b.bucket);
   return SN_OK;
 }
 
@@ -1651,11 +1592,7 @@ inline int incidence_build(const int *F, int64_t nV, int64_t nF, int *vptr, int 
 extern "C" {
 
 size_t sn_dirac_workspace_bytes(int64_t nV, int64_t nF) {
-  if (nV < 0) nV = 0;
-  if (nF < 0) nF = 0;
-  const size_t scan = (size_t)((nV + 1 + kScanTile - 1) / kScanTile + 1) * sizeof(int);
-  return align16((size_t)nF * sizeof(double)) + align16((size_t)nV * sizeof(double)) + align16((size_t)(nV + 1) * sizeof(int)) * 2 +
-         align16((size_t)3 * nF * sizeof(int)) + align16(scan);
+  return DiracWs(nullptr, at_least_0(nV), at_least_0(nF)).c.bytes;
 }
 
 int sn_dirac_bsr4_from_mesh(const float *V, const int32_t *F, int64_t nV, int64_t nF, int32_t *di_rowptr,
@@ -1669,24 +1606,17 @@ int sn_dirac_bsr4_from_mesh(const float *V, const int32_t *F, int64_t nV, int64_
   if (nF > 0 && (!V || !F || !di_colind || !di_vals || !diat_vals || !dia_colind || !dia_vals || !dit_vals)) return SN_E_NULL;
   if (workspace_bytes < sn_dirac_workspace_bytes(nV, nF) || !workspace) return SN_E_WORKSPACE;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  char *w = static_cast<char *>(workspace);
-  double *Af = reinterpret_cast<double *>(w); w += align16((size_t)nF * sizeof(double));
-  double *Av = reinterpret_cast<double *>(w); w += align16((size_t)nV * sizeof(double));
-  int *vptr = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
-  int *cursor = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
-  int *inc = reinterpret_cast<int *>(w); w += align16((size_t)3 * nF * sizeof(int));
-  int *sums = reinterpret_cast<int *>(w);
-  hipError_t e = sn_internal_fill(vptr, 0, (size_t)(nV + 1) * sizeof(int), s);
+  const DiracWs ws(workspace, nV, nF);
+  double *Af = ws.Af, *Av = ws.Av;
+  int *vptr = ws.b.ptr, *inc = ws.b.bucket;      // the faces are not validated on this path: codes 4 f + c of every face
+  const hipError_t e = sn_internal_fill(vptr, 0, (size_t)(nV + 1) * sizeof(int), s);
   if (e != hipSuccess) return (int)e;
   if (nF > 0) hipLaunchKernelGGL(face_area_k, dim3(grid_for(nF)), dim3(kWG), 0, s, V, F, nF, Af, vptr);
-  const int64_t n = nV + 1;
-  const int nblk = (int)((n + kScanTile - 1) / kScanTile);
-  hipLaunchKernelGGL(scan_sums_k, dim3(nblk), dim3(kWG), 0, s, vptr, n, sums);
-  hipLaunchKernelGGL(scan_top_k, dim3(1), dim3(kWG), 0, s, sums, nblk);
-  hipLaunchKernelGGL(scan_apply_k, dim3(nblk), dim3(kWG), 0, s, vptr, n, sums, vptr);
-  e = sn_internal_copy2d(cursor, 0, vptr, 0, (int64_t)((size_t)(nV + 1) * sizeof(int)), 1, s);
-  if (e != hipSuccess) return (int)e;
-  if (nF > 0) hipLaunchKernelGGL(incidence_scatter_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, cursor, inc);
+  const int st = bucket_offsets(vptr, ws.b.cursor, ws.b.sums, nV, s);
+  if (st != SN_OK) return st;
+  if (nF > 0)
+    hipLaunchKernelGGL((bucket_fill_k<kCornerVertex, kEveryFace, 4>), dim3(grid_for(nF)), dim3(kWG), 0, s, F, (const int *)nullptr, nF, nV,
+                       ws.b.cursor, inc);
   if (nV > 0) hipLaunchKernelGGL(vertex_lists_k, dim3(grid_for(nV)), dim3(kWG), 0, s, vptr, nV, inc, Af, Av, dia_colind);
   hipLaunchKernelGGL(di_fill_k, dim3(grid_for(nF + 1)), dim3(kWG), 0, s, V, F, nF, Af, Av, di_rowptr, di_colind, di_vals, diat_vals);
   hipLaunchKernelGGL(dia_fill_k, dim3(grid_for(nV + 1)), dim3(kWG), 0, s, V, F, nV, vptr, inc, Af, Av, dia_rowptr, dia_vals, dit_vals);
@@ -1706,15 +1636,9 @@ int sn_laplacian_csr_from_mesh(const float *V, const int32_t *F, int64_t nV, int
   if (phase == 1 && nV > 0 && (!colind || !vals)) return SN_E_NULL;
   if (workspace_bytes < sn_laplacian_workspace_bytes(nV, nF) || !workspace) return SN_E_WORKSPACE;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  char *w = static_cast<char *>(workspace);
-  double *Af = reinterpret_cast<double *>(w); w += align16((size_t)nF * sizeof(double));
-  w += align16((size_t)nV * sizeof(double));                                       // (Av slot of the Dirac layout, unused)
-  int *vptr = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
-  int *cursor = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
-  int *inc = reinterpret_cast<int *>(w); w += align16((size_t)3 * nF * sizeof(int));
-  int *sums = reinterpret_cast<int *>(w);
-  const int64_t n = nV + 1;
-  const int nblk = (int)((n + kScanTile - 1) / kScanTile);
+  const DiracWs ws(workspace, nV, nF);
+  double *Af = ws.Af;
+  int *vptr = ws.b.ptr, *inc = ws.b.bucket;
   if (phase == 0) {
     hipError_t e = sn_internal_fill(vptr, 0, (size_t)(nV + 1) * sizeof(int), s);
     if (e != hipSuccess) return (int)e;
@@ -1723,21 +1647,18 @@ int sn_laplacian_csr_from_mesh(const float *V, const int32_t *F, int64_t nV, int
       if (e != hipSuccess) return (int)e;
     }
     if (nF > 0) hipLaunchKernelGGL(face_area_k, dim3(grid_for(nF)), dim3(kWG), 0, s, V, F, nF, Af, vptr);
-    hipLaunchKernelGGL(scan_sums_k, dim3(nblk), dim3(kWG), 0, s, vptr, n, sums);
-    hipLaunchKernelGGL(scan_top_k, dim3(1), dim3(kWG), 0, s, sums, nblk);
-    hipLaunchKernelGGL(scan_apply_k, dim3(nblk), dim3(kWG), 0, s, vptr, n, sums, vptr);
-    e = sn_internal_copy2d(cursor, 0, vptr, 0, (int64_t)((size_t)(nV + 1) * sizeof(int)), 1, s);
-    if (e != hipSuccess) return (int)e;
-    if (nF > 0) hipLaunchKernelGGL(incidence_scatter_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, cursor, inc);
+    const int st = bucket_offsets(vptr, ws.b.cursor, ws.b.sums, nV, s);
+    if (st != SN_OK) return st;
+    if (nF > 0)
+      hipLaunchKernelGGL((bucket_fill_k<kCornerVertex, kEveryFace, 4>), dim3(grid_for(nF)), dim3(kWG), 0, s, F, (const int *)nullptr, nF,
+                         nV, ws.b.cursor, inc);
     if (nV > 0) hipLaunchKernelGGL(vertex_sort_k, dim3(grid_for(nV)), dim3(kWG), 0, s, vptr, nV, inc);
     e = sn_internal_fill(rowptr + nV, 0, sizeof(int), s);
     if (e != hipSuccess) return (int)e;
     if (nV > 0)
       hipLaunchKernelGGL((laplacian_rows_k<false>), dim3(grid_for(nV)), dim3(kWG), 0, s, V, F, nV, vptr, inc, Af, rowptr,
                          (int *)nullptr, (float *)nullptr, status_flag);
-    hipLaunchKernelGGL(scan_sums_k, dim3(nblk), dim3(kWG), 0, s, rowptr, n, sums);
-    hipLaunchKernelGGL(scan_top_k, dim3(1), dim3(kWG), 0, s, sums, nblk);
-    hipLaunchKernelGGL(scan_apply_k, dim3(nblk), dim3(kWG), 0, s, rowptr, n, sums, rowptr);
+    scan_in_place(rowptr, nV + 1, ws.b.sums, s);
   } else if (nV > 0) {
     hipLaunchKernelGGL((laplacian_rows_k<true>), dim3(grid_for(nV)), dim3(kWG), 0, s, V, F, nV, vptr, inc, Af, rowptr, colind,
                        vals, (int *)nullptr);
@@ -1798,9 +1719,7 @@ int sn_symmetrize_min_f32(float *G, int64_t n, int64_t ld, void *stream) {
 }
 
 size_t sn_mesh_corners_workspace_bytes(int64_t nV) {
-  if (nV < 0) nV = 0;
-  const size_t scan = (size_t)((nV + 1 + kScanTile - 1) / kScanTile + 1) * sizeof(int);
-  return align16((size_t)(nV + 1) * sizeof(int)) + align16(scan);
+  return CornersWs(nullptr, at_least_0(nV)).c.bytes;
 }
 
 int sn_mesh_corners_f32(const float *V, const int32_t *F, int64_t nV, int64_t nF, int32_t *cptr, void *corners,
@@ -1812,25 +1731,20 @@ int sn_mesh_corners_f32(const float *V, const int32_t *F, int64_t nV, int64_t nF
   if (nF > 0 && (!V || !F || !corners)) return SN_E_NULL;
   if (workspace_bytes < sn_mesh_corners_workspace_bytes(nV) || !workspace) return SN_E_WORKSPACE;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  char *w = static_cast<char *>(workspace);
-  int *cursor = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
-  int *sums = reinterpret_cast<int *>(w);
+  const CornersWs ws(workspace, nV);
   hipError_t e = sn_internal_fill(cptr, 0, (size_t)(nV + 1) * sizeof(int), s);
   if (e != hipSuccess) return (int)e;
   if (status_flag) {
     e = sn_internal_fill(status_flag, 0, sizeof(int), s);
     if (e != hipSuccess) return (int)e;
   }
-  if (nF > 0) hipLaunchKernelGGL(corner_count_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, nV, cptr, status_flag);
-  const int64_t n = nV + 1;
-  const int nblk = (int)((n + kScanTile - 1) / kScanTile);
-  hipLaunchKernelGGL(scan_sums_k, dim3(nblk), dim3(kWG), 0, s, cptr, n, sums);
-  hipLaunchKernelGGL(scan_top_k, dim3(1), dim3(kWG), 0, s, sums, nblk);
-  hipLaunchKernelGGL(scan_apply_k, dim3(nblk), dim3(kWG), 0, s, cptr, n, sums, cptr);
-  e = sn_internal_copy2d(cursor, 0, cptr, 0, (int64_t)((size_t)(nV + 1) * sizeof(int)), 1, s);
-  if (e != hipSuccess) return (int)e;
+  if (nF > 0)      // (the flag of this entry point is 1)
+    hipLaunchKernelGGL((bucket_count_k<kCornerVertex, kGoodFaces, 1>), dim3(grid_for(nF)), dim3(kWG), 0, s, F, (const int *)nullptr, nF, nV,
+                       cptr, status_flag);
+  const int st = bucket_offsets(cptr, ws.cursor, ws.sums, nV, s);
+  if (st != SN_OK) return st;
   if (nF > 0)
-    hipLaunchKernelGGL(corner_fill_k, dim3(grid_for(nF)), dim3(kWG), 0, s, V, F, nF, nV, cursor, static_cast<MeshCorner *>(corners));
+    hipLaunchKernelGGL(corner_fill_k, dim3(grid_for(nF)), dim3(kWG), 0, s, V, F, nF, nV, ws.cursor, static_cast<MeshCorner *>(corners));
   return launch_status();
 }
 
@@ -1859,10 +1773,7 @@ int sn_mesh_geodesics_f32(const int32_t *cptr, const void *corners, int64_t n, i
 }
 
 size_t sn_mesh_glue_workspace_bytes(int64_t nV, int64_t nF) {
-  if (nV < 0) nV = 0;
-  if (nF < 0) nF = 0;
-  const size_t scan = (size_t)((nV + 1 + kScanTile - 1) / kScanTile + 1) * sizeof(int);
-  return 2 * align16((size_t)(nV + 1) * sizeof(int)) + align16((size_t)3 * nF * sizeof(int)) + align16(scan);
+  return MeshBucketWs(nullptr, at_least_0(nV), at_least_0(nF)).c.bytes;
 }
 
 int sn_mesh_glue_i32(const float *V, const int32_t *F, int64_t nV, int64_t nF, int32_t *G, double *l, int32_t *status,
@@ -1875,30 +1786,23 @@ int sn_mesh_glue_i32(const float *V, const int32_t *F, int64_t nV, int64_t nF, i
   if (!V != !l && nF > 0) return SN_E_NULL;                      // the lengths need the coordinates, and nothing else does
   if (workspace_bytes < sn_mesh_glue_workspace_bytes(nV, nF) || !workspace) return SN_E_WORKSPACE;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  char *w = static_cast<char *>(workspace);
-  int *ptr = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
-  int *cursor = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
-  int *bucket = reinterpret_cast<int *>(w); w += align16((size_t)3 * nF * sizeof(int));
-  int *sums = reinterpret_cast<int *>(w);
-  hipError_t e = sn_internal_fill(ptr, 0, (size_t)(nV + 1) * sizeof(int), s);
+  const BucketWs b = MeshBucketWs(workspace, nV, nF).b;
+  hipError_t e = sn_internal_fill(b.ptr, 0, (size_t)(nV + 1) * sizeof(int), s);
   if (e != hipSuccess) return (int)e;
   e = sn_internal_fill(status, 0, sizeof(int), s);
   if (e != hipSuccess) return (int)e;
   if (nF == 0) return SN_OK;
-  hipLaunchKernelGGL(corner_count_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, nV, ptr, status);      // sets SN_IDT_BAD_FACE = 1
-  const int64_t n = nV + 1;
-  const int nblk = (int)((n + kScanTile - 1) / kScanTile);
-  hipLaunchKernelGGL(scan_sums_k, dim3(nblk), dim3(kWG), 0, s, ptr, n, sums);
-  hipLaunchKernelGGL(scan_top_k, dim3(1), dim3(kWG), 0, s, sums, nblk);
-  hipLaunchKernelGGL(scan_apply_k, dim3(nblk), dim3(kWG), 0, s, ptr, n, sums, ptr);
-  e = sn_internal_copy2d(cursor, 0, ptr, 0, (int64_t)((size_t)(nV + 1) * sizeof(int)), 1, s);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(side_fill_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, nV, cursor, bucket);
-  hipLaunchKernelGGL(glue_twin_k, dim3(grid_for(3 * nF)), dim3(kWG), 0, s, V, F, nF, nV, ptr, bucket, G, l, status);
+  hipLaunchKernelGGL((bucket_count_k<kCornerVertex, kGoodFaces, SN_IDT_BAD_FACE>), dim3(grid_for(nF)), dim3(kWG), 0, s, F,
+                     (const int *)nullptr, nF, nV, b.ptr, status);
+  const int st = bucket_offsets(b.ptr, b.cursor, b.sums, nV, s);
+  if (st != SN_OK) return st;
+  hipLaunchKernelGGL((bucket_fill_k<kCornerVertex, kGoodFaces, 3>), dim3(grid_for(nF)), dim3(kWG), 0, s, F, (const int *)nullptr, nF, nV,
+                     b.cursor, b.bucket);
+  hipLaunchKernelGGL(glue_twin_k, dim3(grid_for(3 * nF)), dim3(kWG), 0, s, V, F, nF, nV, b.ptr, b.bucket, G, l, status);
   return launch_status();
 }
 
-size_t sn_mesh_idt_workspace_bytes(int64_t nF) { return align16((size_t)(nF > 0 ? nF : 0) * sizeof(idt_claim_t)); }
+size_t sn_mesh_idt_workspace_bytes(int64_t nF) { return one_slice_bytes<idt_claim_t>(at_least_0(nF)); }
 
 int sn_mesh_idt_rounds_f64(int32_t *Fp, double *lp, int32_t *G, int64_t nF, int32_t round_begin, int32_t round_count,
                            int32_t max_rounds, int32_t *counters, int32_t *status, void *workspace, size_t workspace_bytes,
@@ -1933,7 +1837,7 @@ int sn_mesh_idt_rounds_f64(int32_t *Fp, double *lp, int32_t *G, int64_t nF, int3
 int64_t sn_mesh_idt_laplacian_items(int64_t nV, int64_t nF) { return nV < 0 || nF < 0 ? 0 : 12 * nF + nV; }
 
 size_t sn_mesh_idt_laplacian_workspace_bytes(int64_t nV, int64_t nF) {
-  return idt_lap_ws(nV > 0 ? nV : 0, nF > 0 ? nF : 0, nullptr, nullptr);
+  return IdtLapWs(nullptr, at_least_0(nV), at_least_0(nF)).c.bytes;
 }
 
 int sn_mesh_idt_laplacian_f32(const int32_t *Fp, const double *lp, int64_t nV, int64_t nF, int32_t phase, int64_t *keys,
@@ -1949,17 +1853,12 @@ int sn_mesh_idt_laplacian_f32(const int32_t *Fp, const double *lp, int64_t nV, i
   if (nF > 0 && (!Fp || !lp)) return SN_E_NULL;
   if (phase > 0 && ((N > 0 && !order) || !rowptr)) return SN_E_NULL;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  IdtLapWs ws;
-  idt_lap_ws(nV, nF, static_cast<char *>(workspace), &ws);
+  const IdtLapWs ws(workspace, nV, nF);
   if (phase == 0) {
     if (N > 0) hipLaunchKernelGGL(idt_contrib_k, dim3(grid_for(nF + nV)), dim3(kWG), 0, s, Fp, lp, nV, nF, keys, ws.cval, ws.cmass, status);
   } else if (phase == 1) {
-    const int64_t n = N + 1;
-    const int nblk = (int)((n + kScanTile - 1) / kScanTile);
-    hipLaunchKernelGGL(idt_heads_k, dim3(grid_for(n)), dim3(kWG), 0, s, keys, N, span, ws.hs);
-    hipLaunchKernelGGL(scan_sums_k, dim3(nblk), dim3(kWG), 0, s, ws.hs, n, ws.sums);
-    hipLaunchKernelGGL(scan_top_k, dim3(1), dim3(kWG), 0, s, ws.sums, nblk);
-    hipLaunchKernelGGL(scan_apply_k, dim3(nblk), dim3(kWG), 0, s, ws.hs, n, ws.sums, ws.hs);
+    hipLaunchKernelGGL(idt_heads_k, dim3(grid_for(N + 1)), dim3(kWG), 0, s, keys, N, span, ws.hs);
+    scan_in_place(ws.hs, N + 1, ws.sums, s);
     hipLaunchKernelGGL(idt_rowptr_k, dim3(grid_for(nV + 1)), dim3(kWG), 0, s, keys, N, nV, span, ws.hs, rowptr);
   } else if (N > 0) {
     if (!colind || !vals) return SN_E_NULL;
@@ -1972,11 +1871,7 @@ int sn_mesh_idt_laplacian_f32(const int32_t *Fp, const double *lp, int64_t nV, i
 }
 
 size_t sn_mesh_components_workspace_bytes(int64_t nV, int64_t nF, int32_t mode) {
-  if (nV < 0) nV = 0;
-  if (nF < 0) nF = 0;
-  size_t b = 16;                                                           // the winner word and the label counter
-  if (mode == SN_CC_EDGE) b += 2 * align16((size_t)(nV + 1) * sizeof(int)) + align16((size_t)3 * nF * sizeof(int)) + scan_bytes(nV + 1);
-  return b;
+  return ComponentsWs(nullptr, at_least_0(nV), at_least_0(nF), mode == SN_CC_EDGE).c.bytes;
 }
 
 int sn_mesh_components_i32(const int32_t *F, int64_t nV, int64_t nF, int32_t mode, int32_t *vlabel, int32_t *flabel,
@@ -1993,9 +1888,9 @@ int sn_mesh_components_i32(const int32_t *F, int64_t nV, int64_t nF, int32_t mod
   if (vertex && nV > 0 && !vlabel) return SN_E_NULL;
   if (workspace_bytes < sn_mesh_components_workspace_bytes(nV, nF, mode) || !workspace) return SN_E_WORKSPACE;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  char *w = static_cast<char *>(workspace);
-  cc_word_t *acc = reinterpret_cast<cc_word_t *>(w); w += 16;
-  hipError_t e = sn_internal_fill(acc, 0, 16, s);
+  const ComponentsWs ws(workspace, nV, nF, !vertex);
+  cc_word_t *acc = ws.acc;
+  hipError_t e = sn_internal_fill(acc, 0, 2 * sizeof(cc_word_t), s);
   if (e != hipSuccess) return (int)e;
   e = sn_internal_fill(status, 0, sizeof(int), s);
   if (e != hipSuccess) return (int)e;
@@ -2006,18 +1901,16 @@ int sn_mesh_components_i32(const int32_t *F, int64_t nV, int64_t nF, int32_t mod
     if (nV > 0) hipLaunchKernelGGL(cc_flatten_k, dim3(grid_for(nV)), dim3(kWG), 0, s, parent, nV, status);
     if (nF > 0) hipLaunchKernelGGL((cc_face_labels_k<true>), dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, nV, vlabel, flabel, count, status);
   } else if (nF > 0) {
-    int *ptr = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
-    int *cursor = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
-    int *bucket = reinterpret_cast<int *>(w); w += align16((size_t)3 * nF * sizeof(int));
-    int *sums = reinterpret_cast<int *>(w);
-    e = sn_internal_fill(ptr, 0, (size_t)(nV + 1) * sizeof(int), s);
+    const BucketWs &b = ws.b;
+    e = sn_internal_fill(b.ptr, 0, (size_t)(nV + 1) * sizeof(int), s);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(cc_side_count_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, (const int *)nullptr, nF, nV, ptr, status);
-    scan_in_place(ptr, nV + 1, sums, s);
-    e = sn_internal_copy2d(cursor, 0, ptr, 0, (int64_t)((size_t)(nV + 1) * sizeof(int)), 1, s);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(cc_side_fill_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, (const int *)nullptr, nF, nV, cursor, bucket);
-    hipLaunchKernelGGL(cc_edge_union_k, dim3(grid_for(3 * nF)), dim3(kWG), 0, s, F, nF, nV, ptr, bucket, parent, status);
+    hipLaunchKernelGGL((bucket_count_k<kLowerEnd, kGoodFaces, SN_CC_BAD_FACE>), dim3(grid_for(nF)), dim3(kWG), 0, s, F,
+                       (const int *)nullptr, nF, nV, b.ptr, status);
+    const int st = bucket_offsets(b.ptr, b.cursor, b.sums, nV, s);
+    if (st != SN_OK) return st;
+    hipLaunchKernelGGL((bucket_fill_k<kLowerEnd, kGoodFaces, 3>), dim3(grid_for(nF)), dim3(kWG), 0, s, F, (const int *)nullptr, nF, nV,
+                       b.cursor, b.bucket);
+    hipLaunchKernelGGL(cc_edge_union_k, dim3(grid_for(3 * nF)), dim3(kWG), 0, s, F, nF, nV, b.ptr, b.bucket, parent, status);
     hipLaunchKernelGGL((cc_face_labels_k<false>), dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, nV, (const int *)nullptr, flabel, count, status);
     hipLaunchKernelGGL(cc_bad_labels_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, nV, flabel);
   }
@@ -2037,9 +1930,7 @@ int sn_mesh_label_mask_i32(const int32_t *flabel, int64_t nF, const int32_t *lab
 }
 
 size_t sn_mesh_compact_workspace_bytes(int64_t nV, int64_t nF) {
-  if (nV < 0) nV = 0;
-  if (nF < 0) nF = 0;
-  return align16((size_t)(nV + 1) * sizeof(int)) + align16((size_t)(nF + 1) * sizeof(int)) + scan_bytes((nV > nF ? nV : nF) + 1);
+  return CompactWs(nullptr, at_least_0(nV), at_least_0(nF)).c.bytes;
 }
 
 int sn_mesh_compact_i32(const float *V, const int32_t *F, const int32_t *keep, int64_t nV, int64_t nF, int32_t *I, int32_t *J,
@@ -2054,10 +1945,8 @@ int sn_mesh_compact_i32(const float *V, const int32_t *F, const int32_t *keep, i
   if (nV > 0 && !V != !Vnew) return SN_E_NULL;                     // the coordinates are copied when both are given
   if (workspace_bytes < sn_mesh_compact_workspace_bytes(nV, nF) || !workspace) return SN_E_WORKSPACE;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  char *w = static_cast<char *>(workspace);
-  int *vpos = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
-  int *fpos = reinterpret_cast<int *>(w); w += align16((size_t)(nF + 1) * sizeof(int));
-  int *sums = reinterpret_cast<int *>(w);
+  const CompactWs ws(workspace, nV, nF);
+  int *vpos = ws.vpos, *fpos = ws.fpos, *sums = ws.sums;
   hipError_t e = sn_internal_fill(vpos, 0, (size_t)(nV + 1) * sizeof(int), s);
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(compact_mark_k, dim3(grid_for(nF + 1)), dim3(kWG), 0, s, F, keep, nF, nV, fpos, vpos);
@@ -2069,7 +1958,7 @@ int sn_mesh_compact_i32(const float *V, const int32_t *F, const int32_t *keep, i
 }
 
 size_t sn_mesh_descriptors_workspace_bytes(int64_t nV, int64_t nF) {
-  return incidence_bytes(nV < 0 ? 0 : nV, nF < 0 ? 0 : nF);
+  return MeshBucketWs(nullptr, at_least_0(nV), at_least_0(nF)).c.bytes;
 }
 
 int sn_mesh_descriptors_f32(const float *V, const int32_t *F, int64_t nV, int64_t nF, float *face_area, float *face_normal,
@@ -2083,18 +1972,15 @@ int sn_mesh_descriptors_f32(const float *V, const int32_t *F, int64_t nV, int64_
   if ((nF > 0 && (!V || !F)) || (nV > 0 && per_vertex && !V)) return SN_E_NULL;
   if (workspace_bytes < sn_mesh_descriptors_workspace_bytes(nV, nF) || !workspace) return SN_E_WORKSPACE;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  char *w = static_cast<char *>(workspace);
-  int *vptr = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
-  int *cursor = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
-  int *inc = reinterpret_cast<int *>(w); w += align16((size_t)3 * nF * sizeof(int));
-  int *sums = reinterpret_cast<int *>(w);
+  const BucketWs b = MeshBucketWs(workspace, nV, nF).b;
+  int *vptr = b.ptr, *inc = b.bucket;
   hipError_t e = sn_internal_fill(vptr, 0, (size_t)(nV + 1) * sizeof(int), s);
   if (e != hipSuccess) return (int)e;
   e = sn_internal_fill(status, 0, sizeof(int), s);
   if (e != hipSuccess) return (int)e;
   if (nF > 0) hipLaunchKernelGGL(desc_face_k, dim3(grid_for(nF)), dim3(kWG), 0, s, V, F, nF, nV, vptr, face_area, face_normal, status);
   if (per_vertex && nV > 0) {
-    const int st = incidence_build(F, nV, nF, vptr, cursor, inc, sums, s);
+    const int st = incidence_build(F, nV, nF, b, s);
     if (st != SN_OK) return st;
     hipLaunchKernelGGL(desc_vertex_k, dim3(grid_for(nV)), dim3(kWG), 0, s, V, F, nV, vptr, inc, n_area, n_uniform, n_angle, mass_bary,
                        mass_voronoi, gauss, mean, status);
@@ -2116,11 +2002,8 @@ int sn_mesh_cot_laplacian_f32(const float *V, const int32_t *F, int64_t nV, int6
   if (phase == 1 && nV > 0 && (!colind || !vals)) return SN_E_NULL;
   if (workspace_bytes < sn_mesh_cot_laplacian_workspace_bytes(nV, nF) || !workspace) return SN_E_WORKSPACE;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  char *w = static_cast<char *>(workspace);
-  int *vptr = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
-  int *cursor = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
-  int *inc = reinterpret_cast<int *>(w); w += align16((size_t)3 * nF * sizeof(int));
-  int *sums = reinterpret_cast<int *>(w);
+  const BucketWs b = MeshBucketWs(workspace, nV, nF).b;
+  int *vptr = b.ptr, *inc = b.bucket;
   const int voronoi = mass == SN_DESC_MASS_VORONOI;
   if (phase == 0) {
     hipError_t e = sn_internal_fill(vptr, 0, (size_t)(nV + 1) * sizeof(int), s);
@@ -2129,14 +2012,14 @@ int sn_mesh_cot_laplacian_f32(const float *V, const int32_t *F, int64_t nV, int6
     if (e != hipSuccess) return (int)e;
     if (nF > 0)
       hipLaunchKernelGGL(desc_face_k, dim3(grid_for(nF)), dim3(kWG), 0, s, V, F, nF, nV, vptr, (float *)nullptr, (float *)nullptr, status);
-    const int st = incidence_build(F, nV, nF, vptr, cursor, inc, sums, s);
+    const int st = incidence_build(F, nV, nF, b, s);
     if (st != SN_OK) return st;
     e = sn_internal_fill(rowptr + nV, 0, sizeof(int), s);
     if (e != hipSuccess) return (int)e;
     if (nV > 0)
       hipLaunchKernelGGL((cot_laplacian_rows_k<false>), dim3(grid_for(nV)), dim3(kWG), 0, s, V, F, nV, vptr, inc, voronoi, 0, 0.f, rowptr,
                          (int *)nullptr, (float *)nullptr, status);
-    scan_in_place(rowptr, nV + 1, sums, s);
+    scan_in_place(rowptr, nV + 1, b.sums, s);
   } else if (nV > 0) {
     hipLaunchKernelGGL((cot_laplacian_rows_k<true>), dim3(grid_for(nV)), dim3(kWG), 0, s, V, F, nV, vptr, inc, voronoi, clamp != 0,
                        (float)hack, rowptr, colind, vals, status);
@@ -2146,7 +2029,7 @@ int sn_mesh_cot_laplacian_f32(const float *V, const int32_t *F, int64_t nV, int6
 
 size_t sn_mesh_weld_workspace_bytes(int64_t nV) {
   if (nV < 0 || nV > kRepairMaxNodes) nV = 0;
-  return align16((size_t)repair_table_slots(nV) * sizeof(int));
+  return one_slice_bytes<int>(repair_table_slots(nV));
 }
 
 int sn_mesh_weld_f32(const float *V, const int32_t *F, int64_t nV, int64_t nF, double tol, int32_t weld, int32_t *rep, int32_t *Fw,
@@ -2180,7 +2063,7 @@ int sn_mesh_weld_f32(const float *V, const int32_t *F, int64_t nV, int64_t nF, d
 
 size_t sn_mesh_unique_faces_workspace_bytes(int64_t nF) {
   if (nF < 0 || nF > kRepairMaxNodes) nF = 0;
-  return align16((size_t)repair_table_slots(nF) * sizeof(int));
+  return one_slice_bytes<int>(repair_table_slots(nF));
 }
 
 int sn_mesh_unique_faces_i32(const float *V, const int32_t *F, int64_t nV, int64_t nF, int32_t unique, int32_t *keep,
@@ -2211,10 +2094,7 @@ int sn_mesh_unique_faces_i32(const float *V, const int32_t *F, int64_t nV, int64
 }
 
 size_t sn_mesh_orient_workspace_bytes(int64_t nV, int64_t nF) {
-  if (nV < 0) nV = 0;
-  if (nF < 0) nF = 0;
-  return 2 * align16((size_t)(nV + 1) * sizeof(int)) + align16((size_t)3 * nF * sizeof(int)) + align16((size_t)nF * sizeof(int)) +
-         scan_bytes(nV + 1);
+  return OrientWs(nullptr, at_least_0(nV), at_least_0(nF)).c.bytes;
 }
 
 int sn_mesh_orient_i32(const int32_t *F, const int32_t *keep, int64_t nV, int64_t nF, int32_t *flip, int32_t *label, int32_t *Fout,
@@ -2226,26 +2106,24 @@ int sn_mesh_orient_i32(const int32_t *F, const int32_t *keep, int64_t nV, int64_
   if (nF > 0 && (!F || !keep || !flip || !label)) return SN_E_NULL;
   if (workspace_bytes < sn_mesh_orient_workspace_bytes(nV, nF) || !workspace) return SN_E_WORKSPACE;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  char *w = static_cast<char *>(workspace);
-  int *ptr = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
-  int *cursor = reinterpret_cast<int *>(w); w += align16((size_t)(nV + 1) * sizeof(int));
-  int *bucket = reinterpret_cast<int *>(w); w += align16((size_t)3 * nF * sizeof(int));
-  int *conflict = reinterpret_cast<int *>(w); w += align16((size_t)nF * sizeof(int));
-  int *sums = reinterpret_cast<int *>(w);
+  const OrientWs ws(workspace, nV, nF);
+  const BucketWs &b = ws.b;
+  int *conflict = ws.conflict;
   hipError_t e = sn_internal_fill(counts, 0, 3 * sizeof(int), s);
   if (e != hipSuccess) return (int)e;
   e = sn_internal_fill(status, 0, sizeof(int), s);
   if (e != hipSuccess) return (int)e;
   if (nF == 0) return launch_status();
-  e = sn_internal_fill(ptr, 0, (size_t)(nV + 1) * sizeof(int), s);
+  e = sn_internal_fill(b.ptr, 0, (size_t)(nV + 1) * sizeof(int), s);
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(or_init_k, dim3(grid_for(nF)), dim3(kWG), 0, s, label, conflict, nF);
-  hipLaunchKernelGGL(cc_side_count_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, keep, nF, nV, ptr, status);
-  scan_in_place(ptr, nV + 1, sums, s);
-  e = sn_internal_copy2d(cursor, 0, ptr, 0, (int64_t)((size_t)(nV + 1) * sizeof(int)), 1, s);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(cc_side_fill_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, keep, nF, nV, cursor, bucket);
-  hipLaunchKernelGGL(or_link_k, dim3(grid_for(3 * nF)), dim3(kWG), 0, s, F, keep, nF, nV, ptr, bucket, label, conflict, counts, status);
+  hipLaunchKernelGGL((bucket_count_k<kLowerEnd, kGoodKeptFaces, SN_REPAIR_BAD_FACE>), dim3(grid_for(nF)), dim3(kWG), 0, s, F, keep, nF, nV,
+                     b.ptr, status);
+  const int st = bucket_offsets(b.ptr, b.cursor, b.sums, nV, s);
+  if (st != SN_OK) return st;
+  hipLaunchKernelGGL((bucket_fill_k<kLowerEnd, kGoodKeptFaces, 3>), dim3(grid_for(nF)), dim3(kWG), 0, s, F, keep, nF, nV, b.cursor,
+                     b.bucket);
+  hipLaunchKernelGGL(or_link_k, dim3(grid_for(3 * nF)), dim3(kWG), 0, s, F, keep, nF, nV, b.ptr, b.bucket, label, conflict, counts, status);
   hipLaunchKernelGGL(or_resolve_k, dim3(grid_for(nF)), dim3(kWG), 0, s, label, conflict, nF, status);
   hipLaunchKernelGGL(or_finish_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, keep, nF, nV, label, conflict, flip, Fout, counts, status);
   return launch_status();

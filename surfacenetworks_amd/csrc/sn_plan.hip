@@ -18,11 +18,8 @@
 #include <utility>
 #include <vector>
 
+#include "sn_internal.h"
 #include "sn_spmm.h"
-
-// fills and copies as kernels of this library (sn_kernels.hip says why they are not hipMemsetAsync / hipMemcpy2DAsync)
-hipError_t sn_internal_fill2d(void *dst, int64_t pitch, int value, int64_t width, int64_t rows, hipStream_t s);
-hipError_t sn_internal_copy2d(void *dst, int64_t dpitch, const void *src, int64_t spitch, int64_t width, int64_t rows, hipStream_t s);
 
 namespace {
 
@@ -96,8 +93,6 @@ struct sn_plan {
 struct sn_plan_exec {
   hipGraphExec_t exec = nullptr;
 };
-
-bool sn_internal_timing_on();
 
 static int walk(const sn_plan *p, const uint64_t *slot_base, void *stream, int32_t *failed_node) {
   hipStream_t s = (hipStream_t)stream;

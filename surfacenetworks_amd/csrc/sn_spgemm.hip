@@ -9,17 +9,13 @@
 #include <limits.h>
 #include <stdint.h>
 
+#include "sn_internal.h"
 #include "sn_spmm.h"
-
-// fills as kernels of this library (sn_kernels.hip says why not hipMemsetAsync)
-hipError_t sn_internal_fill(void *dst, int value, size_t bytes, hipStream_t s);
 
 namespace {
 
 constexpr int kWG = 256;
 constexpr int kWaves = kWG / 64;
-constexpr int kScanItems = 8;
-constexpr int kScanTile = kWG * kScanItems;
 constexpr int kMaxWindow = SN_SPGEMM_MAX_WINDOW;      // columns one result row may span: one bit each in LDS
 constexpr int kMaxWords = kMaxWindow / 32;            // 4096 words = 16 KiB per workgroup, 8 workgroups per CU fit 160 KiB
 constexpr int kRefusal = SN_SPGEMM_TOO_WIDE | SN_SPGEMM_TOO_LARGE;
@@ -34,24 +30,20 @@ inline unsigned grid_for(int64_t n, int per_block) {
   if (b > 65535 * 16) b = 65535 * 16;
   return (unsigned)b;
 }
-inline size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
-
-// ---- exclusive scan of int32 counts (the 3-launch scheme of sn_kernels.hip); the top level sums in int64 and refuses a total
-//      that does not fit the int32 row pointers ------------------------------------------------------------------------------
-template <class T>
-__device__ __forceinline__ T block_excl_scan(T v, T *total) {
-  __shared__ T wsum[kWaves];
+// exclusive scan of one value per thread across the workgroup (numbers a row's candidate columns); *total: the workgroup's sum
+__device__ __forceinline__ int block_excl_scan(int v, int *total) {
+  __shared__ int wsum[kWaves];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  T incl = v;
+  int incl = v;
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {
-    const T t = __shfl_up(incl, d, 64);
+    const int t = __shfl_up(incl, d, 64);
     if (lane >= d) incl += t;
   }
   __syncthreads();
   if (lane == 63) wsum[wave] = incl;
   __syncthreads();
-  T off = 0, tot = 0;
+  int off = 0, tot = 0;
 #pragma unroll
   for (int i = 0; i < kWaves; ++i) {
     if (i < wave) off += wsum[i];
@@ -60,57 +52,24 @@ __device__ __forceinline__ T block_excl_scan(T v, T *total) {
   *total = tot;
   return off + incl - v;
 }
-__global__ __launch_bounds__(kWG) void scan_sums_k(const int *__restrict__ in, int64_t n, int *__restrict__ sums) {
-  const int64_t base = (int64_t)blockIdx.x * kScanTile + threadIdx.x * kScanItems;
-  int s = 0;
-#pragma unroll
-  for (int i = 0; i < kScanItems; ++i)
-    if (base + i < n) s += in[base + i];       // (a count is at most kMaxWindow: a tile's sum stays below 2^28)
-  int tot;
-  block_excl_scan<int>(s, &tot);
-  if (threadIdx.x == 0) sums[blockIdx.x] = tot;
-}
-__global__ __launch_bounds__(kWG) void scan_top_k(int *__restrict__ sums, int nblk, int *__restrict__ status) {
-  long long carry = 0;
-  for (int b0 = 0; b0 < nblk; b0 += kWG) {
-    const int i = b0 + threadIdx.x;
-    const long long v = (i < nblk) ? sums[i] : 0;
-    long long tot;
-    const long long ex = block_excl_scan<long long>(v, &tot);
-    if (i < nblk) sums[i] = (int)(carry + ex);
-    carry += tot;
-    __syncthreads();
+
+// counts[0..M] (a zero at M) and the scratch of their scan: sn_csr_spgemm_workspace_bytes and both entry points
+struct CountsWs {
+  int *counts, *sums;
+  size_t bytes;
+  CountsWs(void *workspace, int64_t M) {
+    SnCarver c(workspace);
+    counts = c.take<int>(M + 1);
+    sums = c.take_scan(M + 1);
+    bytes = c.bytes;
   }
-  if (threadIdx.x == 0 && carry > INT_MAX && status) atomicOr(status, SN_SPGEMM_TOO_LARGE);
-}
-// out = exclusive scan; nothing is written once *status holds a refusal
-__global__ __launch_bounds__(kWG) void scan_apply_k(const int *__restrict__ in, int64_t n, const int *__restrict__ sums,
-                                                    int *__restrict__ out, const int *__restrict__ status) {
-  if (status && (*status & kRefusal)) return;
-  const int64_t base = (int64_t)blockIdx.x * kScanTile + threadIdx.x * kScanItems;
-  int v[kScanItems], s = 0;
-#pragma unroll
-  for (int i = 0; i < kScanItems; ++i) {
-    v[i] = (base + i < n) ? in[base + i] : 0;
-    s += v[i];
-  }
-  int tot;
-  int run = block_excl_scan<int>(s, &tot) + sums[blockIdx.x];
-#pragma unroll
-  for (int i = 0; i < kScanItems; ++i) {
-    if (base + i < n) out[base + i] = run;
-    run += v[i];
-  }
-}
-// counts[0..n-1] (+ a zero at n) -> out[0..n]
-int scan_counts(const int *counts, int64_t n1, int *sums, int *out, int *status, hipStream_t s) {
-  const int nblk = (int)((n1 + kScanTile - 1) / kScanTile);
-  hipLaunchKernelGGL(scan_sums_k, dim3(nblk), dim3(kWG), 0, s, counts, n1, sums);
-  hipLaunchKernelGGL(scan_top_k, dim3(1), dim3(kWG), 0, s, sums, nblk, status);
-  hipLaunchKernelGGL(scan_apply_k, dim3(nblk), dim3(kWG), 0, s, counts, n1, (const int *)sums, out, (const int *)status);
+};
+// counts[0..n1) -> out[0..n1), the scan of sn_kernels.hip.  With a status word a total that does not fit the int32 row pointers
+// is refused, and out is left as it is once the call is refused (a count is at most kMaxWindow: a tile's sum stays below 2^28)
+int scan_counts(const CountsWs &w, int64_t n1, int *out, int *status, hipStream_t s) {
+  sn_internal_scan_i32(w.counts, n1, out, w.sums, status, SN_SPGEMM_TOO_LARGE, kRefusal, s);
   return launch_status();
 }
-size_t scan_bytes(int64_t n1) { return align16((size_t)((n1 + kScanTile - 1) / kScanTile + 1) * sizeof(int)); }
 
 // ---- one result row per workgroup ---------------------------------------------------------------------------------------------
 // The row's candidate columns are the union of the rows j of B over the entries (i, j) of A.  They are marked as bits of an LDS
@@ -185,7 +144,7 @@ __global__ __launch_bounds__(kWG) void spgemm_row_k(const int *__restrict__ a_rp
       const int w0 = min(tid * wpt, nwords), w1 = min(w0 + wpt, nwords);
       int mine = 0;
       for (int w = w0; w < w1; ++w) mine += __popc(bits[w]);
-      int off = block_excl_scan<int>(mine, &total);
+      int off = block_excl_scan(mine, &total);
       if (FILL) {
         const int base = s_rowptr[row], end = s_colind && s_vals ? s_rowptr[row + 1] : base;      // (no arrays: nothing to fill)
         for (int w = w0; w < w1; ++w) {
@@ -310,8 +269,7 @@ extern "C" {
 int64_t sn_csr_spgemm_max_window(void) { return kMaxWindow; }
 
 size_t sn_csr_spgemm_workspace_bytes(int64_t M) {
-  if (M < 0) M = 0;
-  return align16((size_t)(M + 1) * sizeof(int)) + scan_bytes(M + 1);
+  return CountsWs(nullptr, M < 0 ? 0 : M).bytes;
 }
 
 int sn_csr_spgemm_f32(const int32_t *a_rowptr, const int32_t *a_colind, const float *a_vals, const int32_t *b_rowptr,
@@ -325,8 +283,8 @@ int sn_csr_spgemm_f32(const int32_t *a_rowptr, const int32_t *a_colind, const fl
   if (phase >= 1 && !rowptr) return SN_E_NULL;
   if (workspace_bytes < sn_csr_spgemm_workspace_bytes(M) || !workspace) return SN_E_WORKSPACE;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  int *counts = static_cast<int *>(workspace);
-  int *sums = reinterpret_cast<int *>(static_cast<char *>(workspace) + align16((size_t)(M + 1) * sizeof(int)));
+  const CountsWs ws(workspace, M);
+  int *counts = ws.counts;
   const unsigned grid = (unsigned)(M < 1 ? 1 : (M > 65535 * 16 ? 65535 * 16 : M));
   if (phase == 0) {
     hipError_t e = sn_internal_fill(status, 0, sizeof(int), s);
@@ -337,7 +295,7 @@ int sn_csr_spgemm_f32(const int32_t *a_rowptr, const int32_t *a_colind, const fl
       hipLaunchKernelGGL((spgemm_row_k<false>), dim3(grid), dim3(kWG), 0, s, a_rowptr, a_colind, a_vals, b_rowptr, b_colind, b_vals,
                          (int)M, (int)K, (int)N, counts, (const int *)nullptr, (int *)nullptr, (float *)nullptr, (int *)nullptr,
                          status);
-    return scan_counts(counts, M + 1, sums, s_rowptr, status, s);
+    return scan_counts(ws, M + 1, s_rowptr, status, s);
   }
   if (phase == 1) {
     // a product without structural entries has nothing to fill: s_colind / s_vals may then be NULL, the kernel writes neither
@@ -346,7 +304,7 @@ int sn_csr_spgemm_f32(const int32_t *a_rowptr, const int32_t *a_colind, const fl
     if (M > 0)
       hipLaunchKernelGGL((spgemm_row_k<true>), dim3(grid), dim3(kWG), 0, s, a_rowptr, a_colind, a_vals, b_rowptr, b_colind, b_vals,
                          (int)M, (int)K, (int)N, (int *)nullptr, (const int *)s_rowptr, s_colind, s_vals, counts, status);
-    return scan_counts(counts, M + 1, sums, rowptr, status, s);
+    return scan_counts(ws, M + 1, rowptr, status, s);
   }
   return compact(s_rowptr, s_colind, s_vals, M, rowptr, colind, vals, s);
 }
@@ -374,8 +332,8 @@ int sn_csr_scale_sym_f32(const int32_t *a_rowptr, const int32_t *a_colind, const
   if (!a_rowptr || !rowptr || !status) return SN_E_NULL;
   if (workspace_bytes < sn_csr_spgemm_workspace_bytes(M) || !workspace) return SN_E_WORKSPACE;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  int *counts = static_cast<int *>(workspace);
-  int *sums = reinterpret_cast<int *>(static_cast<char *>(workspace) + align16((size_t)(M + 1) * sizeof(int)));
+  const CountsWs ws(workspace, M);
+  int *counts = ws.counts;
   if (phase == 0) {
     hipError_t e = sn_internal_fill(status, 0, sizeof(int), s);
     if (e != hipSuccess) return (int)e;
@@ -386,7 +344,7 @@ int sn_csr_scale_sym_f32(const int32_t *a_rowptr, const int32_t *a_colind, const
       hipLaunchKernelGGL(scale_sym_k, dim3(grid_for(M, kWaves)), dim3(kWG), 0, s, a_rowptr, a_colind, a_vals, d, M, s_vals, counts,
                          status);
     }
-    return scan_counts(counts, M + 1, sums, rowptr, (int *)nullptr, s);
+    return scan_counts(ws, M + 1, rowptr, (int *)nullptr, s);
   }
   return compact(a_rowptr, a_colind, s_vals, M, rowptr, colind, vals, s);
 }
