@@ -1263,6 +1263,101 @@ int sn_mesh_cot_laplacian_f32(const float *V, const int32_t *F, int64_t nV, int6
                               size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * ARAP deformation: as-rigid-as-possible sequences from a rest mesh and moving handles, on the device.
+ *
+ * Replaces: nothing in the reference's tree — its data_plus/ sequences were made off-line with libigl and downloaded, and neither the
+ *           generator nor its parameters are there.  This is the textbook spokes-only algorithm (Sorkine & Alexa 2007), alternating
+ *           local and global steps, with this project's weights: NOT a reproduction of those files.
+ * Host statement: mesh_ops.arap_weights, arap_rotations, arap_rhs, arap_cg, arap_deform (numpy); the device equals it bit for bit.
+ * Everything is fp64 without contraction; only + - * / sqrt and comparisons are used, so numpy reproduces every rounding.
+ *
+ * Input.  Rest mesh V0 fp32 (nV, 3), widened to fp64 (P0); F int32 (nF, 3); handles int32 (nH): distinct, in range, at least one per
+ *   mesh; H fp32 (T, nH, 3), the handle positions of every frame; iters >= 1, tol, max_cg <= SN_ARAP_MAX_CG.  A batch is a disjoint
+ *   union: V0, F, handles index the union, voff[B + 1] and hoff[B + 1] (int32, ascending) cut vertices and handles into meshes, and
+ *   every entry of a row stays inside its mesh.  One mesh has at most sn_arap_max_vertices() vertices (its search direction lives in
+ *   the LDS of one compute unit).
+ * Weights.  w_ij = W[i, j] of the cotangent weights of the Laplacian section above on the rest mesh (Heron area with the 1e-6 floor,
+ *   denominator 8a + 1e-6): lengths l = sqrt((dx*dx + dy*dy) + dz*dz) in the face's own order (|v0 v1|, |v1 v2|, |v2 v0|),
+ *   h = ((l0 + l1) + l2) / 2, a = sqrt(((h (h-l0)) (h-l1)) (h-l2)) or 1e-6 when the radicand is <= 0; for the ordered corner triple
+ *   (p, q, r) the contribution to W[F[p], F[q]] is ((-l_pq^2 + l_qr^2) + l_rp^2) / (8a + 1e-6).  The pattern is the vertex adjacency
+ *   (no diagonal); a value is kept whatever it is, negative and zero included; columns ascend.  An entry is the serial sum, from its
+ *   first contribution on, over its contributions sorted by (face, permutation) — the rule of sn_mesh_idt_laplacian_f32.  W[i, j] and
+ *   W[j, i] differ in their last bits (the three squares are added in another order); row i uses W[i, .].  d_i = the serial sum of
+ *   w_ij from +0.0 in ascending column order.  A face with an index outside 0..nV-1 or a repeated index contributes nothing
+ *   (SN_ARAP_BAD_FACE); a vertex with more than SN_LAP_MAX_DEGREE incident good faces gets an empty row (SN_ARAP_DEGREE).
+ * Frame t = 0 .. T-1.  The rows of handles are set to H[t]; the free rows start from frame t-1's result, from P0 for t = 0.  Then
+ *   iters times a local and a global step.
+ * Local step.  S_i = sum over ascending j of w_ij e_ij e'_ij^T, e_ij = P0_i - P0_j, e'_ij = x_i - x_j, accumulated from +0.0 as
+ *   S[a][b] = S[a][b] + (w e[a]) e'[b].  R_i = the proper rotation maximising tr(R S_i):
+ *     G = S^T S, G[a][b] = (S[0][a] S[0][b] + S[1][a] S[1][b]) + S[2][a] S[2][b];  V = I;  SN_ARAP_JACOBI_SWEEPS sweeps over the pairs
+ *     (p, q) = (0,1), (0,2), (1,2), r the third index; a pair with G_pq == 0 is skipped, else theta = (G_qq - G_pp) / (2 G_pq),
+ *     t = 1 / (|theta| + sqrt(theta theta + 1)) negated when theta < 0, c = 1 / sqrt(t t + 1), s = t c;  G_pp -= t G_pq,
+ *     G_qq += t G_pq, (G_rp, G_rq) = (c G_rp - s G_rq, s G_rp + c G_rq), G_pq = 0, and every row k of V:
+ *     (V_kp, V_kq) = (c V_kp - s V_kq, s V_kp + c V_kq), all from the old values.  The diagonal and the columns of V are sorted by
+ *     the exchanges (0,1), (1,2), (0,1), each done when lambda_a < lambda_b.  v1, v2 = the first two columns, v3 = v1 x v2;
+ *     a1 = S v1, a2 = S v2 with (S v)[r] = (S[r][0] v[0] + S[r][1] v[1]) + S[r][2] v[2];  n1 = a1.a1, u1 = a1 / sqrt(n1);
+ *     a2' = a2 - (u1.a2) u1, n2 = a2'.a2', u2 = a2' / sqrt(n2), u3 = u1 x u2;  R[a][b] = (v1[a] u1[b] + v2[a] u2[b]) + v3[a] u3[b].
+ *     Dot products are (x x + y y) + z z, cross products (u_y w_z - u_z w_y, u_z w_x - u_x w_z, u_x w_y - u_y w_x).  The third
+ *     singular value is never divided by: a flat cloth (rank 2) is exact, a reflection turns the weakest direction.  Unless n1 > 0
+ *     and n2 > SN_ARAP_RANK_EPS n1 (rank below 2): R_i = I and SN_ARAP_DEGENERATE.
+ * Global step.  b_i = sum over ascending j of ((w_ij 0.5) ((R_i + R_j) e_ij)) from +0.0, the matrix-vector product as above.
+ *   Solve  d_i x_i - sum_j w_ij x_j = b_i  on the free rows, the handle rows held:  rhs_i = b_i plus, over the handle columns in
+ *   ascending order, w_ij x_j;  (A y)_i = d_i y_i - (sum over the FREE columns, ascending, from +0.0, of w_ij y_j).
+ *   Jacobi-preconditioned CG, the three coordinate columns sharing the matrix product, each with its own alpha and beta:
+ *     r = rhs - A x, z = r / d, p = z;  rz = <r z>, rr = <r r>, bb = <rhs rhs>;  a column is CONVERGED when sqrt(rr) <= tol sqrt(bb),
+ *     tested here and after every update, and stays so: it is FROZEN (x, r, p of that column are not touched again — an all-zero
+ *     column, a flat cloth moving in its plane, never divides 0 by 0).
+ *     Iteration, at most max_cg of them, none when every column is converged:  pAp = <p A p>;  a column that is not converged and
+ *     has not pAp > 0 ends the solve with SN_ARAP_BREAKDOWN;  alpha = rz / pAp;  x = x + alpha p, r = r - alpha (A p);  z = r / d;
+ *     rz' = <r z>, rr = <r r>;  convergence test;  beta = rz' / rz;  p = z + beta p and rz = rz' on the columns still running.
+ *     max_cg iterations done and a column left: SN_ARAP_NOT_CONVERGED.
+ *   <u v>, per column, over the free rows i (local index in the mesh): lane i mod SN_ARAP_THREADS adds its rows serially in ascending
+ *     order from +0.0;  then a halving tree inside every group of 64 consecutive lanes (lane l += lane l + s, s = 32 .. 1);  then a
+ *     halving tree over the 16 group sums (s = 8 .. 1).
+ *   A free row without d_i > 0 sets SN_ARAP_BREAKDOWN for the mesh: no step runs in any frame and every R is I.  After a breakdown
+ *     inside a solve the free rows go back to the values they had when the frame began and the frame's remaining steps are skipped
+ *     (their counts are 0).  This is what a component without a handle or a broken mesh ends in, if it does not simply fail to converge.
+ * Output per frame: the positions rounded once to fp32;  the CG iteration count of every global step;  the energy
+ *   sum_i sum_j w_ij |e'_ij - R_i e_ij|^2 after the last step, with the R of the last local step: per row serially over ascending j
+ *   from +0.0, each term w ((dx dx + dy dy) + dz dz), rows by the reduction above over ALL rows of the mesh.
+ *
+ * sn_arap_weights_f64 : rowptr[nV + 1], colind, w (sized for 6 nF entries by the caller, rowptr[nV] used), d[nV], *status (cleared
+ *                       first).  The by-vertex buckets are those of the other mesh builders (bucket_count_k / bucket_fill_k /
+ *                       sn_internal_scan_i32).  workspace: sn_arap_weights_workspace_bytes(nV, nF).  Does not synchronise.
+ * sn_arap_frames_f64  : frames frame_begin .. frame_begin + frame_count - 1 of T, one workgroup of SN_ARAP_THREADS threads per mesh,
+ *                       the local step, the right-hand side and the whole CG of a frame inside it; no workgroup waits for another,
+ *                       every loop is bounded by an argument, and every exit from the CG loop is decided from values all threads
+ *                       read after a barrier.  p (3 fp64 per vertex) is in LDS; x, r, A p, R and the frame's start values are in
+ *                       the workspace, each row read and written by its owner thread alone except x and R, which neighbours read
+ *                       after a barrier.  max_mesh_vertices: an upper bound of the meshes' sizes, > sn_arap_max_vertices() is
+ *                       SN_E_UNSUPPORTED; a mesh larger than the bound is skipped (frames = V0, SN_ARAP_TOO_LARGE).  The state
+ *                       between calls is the workspace (sn_arap_frames_workspace_bytes(nV)): a caller enqueues frames in chunks
+ *                       with the same workspace, frame_begin == 0 initialises it and clears status.  frames (T, nV, 3) fp32,
+ *                       cg_iters (B, T, iters) int32, energy (B, T) fp64, status (B) int32.  R_first (nV, 9) and rhs_first (nV, 3)
+ *                       fp64 (both or neither): R and b of the first local step of frame 0, written by the call that holds it.
+ * ------------------------------------------------------------------------------------------ */
+#define SN_ARAP_NOT_CONVERGED  1
+#define SN_ARAP_BREAKDOWN      2
+#define SN_ARAP_DEGENERATE     4
+#define SN_ARAP_BAD_FACE       8
+#define SN_ARAP_DEGREE         16
+#define SN_ARAP_TOO_LARGE      32
+#define SN_ARAP_THREADS        1024
+#define SN_ARAP_JACOBI_SWEEPS  6
+#define SN_ARAP_RANK_EPS       1e-20
+#define SN_ARAP_MAX_CG         65536
+int64_t sn_arap_max_vertices(void);
+size_t sn_arap_weights_workspace_bytes(int64_t nV, int64_t nF);
+int sn_arap_weights_f64(const float *V0, const int32_t *F, int64_t nV, int64_t nF, int32_t *rowptr, int32_t *colind, double *w,
+                        double *d, int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+size_t sn_arap_frames_workspace_bytes(int64_t nV);
+int sn_arap_frames_f64(const float *V0, const int32_t *rowptr, const int32_t *colind, const double *w, const double *d,
+                       const int32_t *voff, const int32_t *hoff, const int32_t *handles, const float *H, int64_t B, int64_t nV,
+                       int64_t nH, int64_t T, int64_t max_mesh_vertices, int32_t frame_begin, int32_t frame_count, int32_t iters,
+                       double tol, int32_t max_cg, float *frames, int32_t *cg_iters, double *energy, int32_t *status,
+                       double *R_first, double *rhs_first, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Sparse x sparse CSR products and the symmetric diagonal scaling: the operators of the 'amp' tower.
  *
  * Replaces: L = Dsq.dot(L).dot(Dsq); twice L = Dsq.dot(L).dot(Dsq), L = L.dot(L)     src/dense_correspondence/main.py:72-83

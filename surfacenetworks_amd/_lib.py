@@ -178,6 +178,12 @@ SIGNATURES = {
     "sn_mesh_descriptors_f32": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sn_mesh_cot_laplacian_workspace_bytes": (_sz, [_i64, _i64]),
     "sn_mesh_cot_laplacian_f32": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, C.c_double, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sn_arap_max_vertices": (_i64, []),
+    "sn_arap_weights_workspace_bytes": (_sz, [_i64, _i64]),
+    "sn_arap_weights_f64": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sn_arap_frames_workspace_bytes": (_sz, [_i64]),
+    "sn_arap_frames_f64": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32,
+                                     C.c_double, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sn_csr_spgemm_max_window": (_i64, []),
     "sn_csr_spgemm_workspace_bytes": (_sz, [_i64]),
     "sn_csr_spgemm_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

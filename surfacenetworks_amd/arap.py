@@ -20,7 +20,7 @@ import torch.nn.functional as F
 
 from . import kernels, mesh_ops
 from . import utils_pt as utils
-from .operators import OperatorPool, PackedSegments, h2d_async
+from .operators import OperatorPool, PackedSegments, arap_deform, h2d_async
 
 INPUT_FRAMES = 2       # main.py:105
 OUTPUT_FRAMES = 40     # main.py:106
@@ -236,7 +236,7 @@ class ClothSequences:
     operators in OperatorPools (entry s*op_frames + t is sequence s at frame t)."""
 
     def __init__(self, grids, frames=50, op_frames=2, seed=3, device="cuda", model="dir", permute=False,
-                 operators="pool", reorder="auto"):
+                 operators="pool", reorder="auto", dynamics="wave"):
         """permute: False (row-major grid numbering), True / "vertices" (seeded random vertex numbering) or
         "both" (faces shuffled too: what a scanned mesh looks like).
         reorder: "auto" (default) / True / False — the dataset is STORED in a locality numbering of its vertices and faces
@@ -247,7 +247,13 @@ class ClothSequences:
         operators="pool": per-frame operators precomputed (host, fp64 coordinates) and pooled in HBM, as the
         reference's dataset does.  operators="device": nothing is precomputed — the Dirac operators of the sampled
         frames are built on the GPU every step from the stored fp32 coordinates (sn_dirac_bsr4_from_mesh); needs
-        meshes of one size (no padding) and model="dir"."""
+        meshes of one size (no padding) and model="dir".
+        dynamics: "wave" (default) — the travelling wave above; "arap" — as-rigid-as-possible sequences made on the device: one
+        boundary edge of every cloth held, the opposite one in a seeded constant-velocity rigid motion
+        (mesh_ops.arap_handle_motion), the rest by operators.arap_deform."""
+        if dynamics not in ("wave", "arap"):
+            raise ValueError(dynamics)
+        self.dynamics = dynamics
         rng = np.random.default_rng(seed)
         self.device = torch.device(device)
         self.frames, self.op_frames, self.kind = frames, op_frames, model
@@ -258,7 +264,17 @@ class ClothSequences:
             raise ValueError("on-device operator construction supports the Dirac model on equally sized meshes")
         assert frames >= INPUT_FRAMES + OUTPUT_FRAMES + 1 and 1 <= op_frames
         Vs, Fs, mats = [], [], {"L": [], "Di": [], "DiA": []}
-        coords, faces_all, orders = [], [], []
+        coords, faces_all, orders, pending = [], [], [], []
+
+        def add_operators(Vt, F_):      # of the first op_frames frames, from fp64 coordinates
+            for tf in range(op_frames if operators == "pool" else 0):
+                if model == "dir":
+                    Di, DiA = mesh_ops.dirac(Vt[tf].astype(np.float64), F_)
+                    mats["Di"].append(Di.astype(np.float32))
+                    mats["DiA"].append(DiA.astype(np.float32))
+                else:
+                    mats["L"].append(mesh_ops.laplacian(Vt[tf].astype(np.float64), F_).astype(np.float32))
+
         for (n, m) in grids:
             V0, F_ = mesh_ops.grid_cloth(n, m, rng, permute=permute)
             order = mesh_ops.MeshOrder.of_mesh(F_, V0.shape[0], reorder)
@@ -267,22 +283,31 @@ class ClothSequences:
             amp = 0.03 * (0.5 + rng.random())
             k = 2 * np.pi * (1 + rng.integers(0, 3))
             ph = rng.random() * 2 * np.pi
+            Vs.append(V0.shape[0])
+            Fs.append(F_.shape[0])
+            faces_all.append(F_.astype(np.int32))
+            if dynamics == "arap":      # deformed below, the meshes of one shape as one batch
+                pending.append((V0.astype(np.float32), F_.astype(np.int32)) + mesh_ops.arap_handle_motion(V0, frames, rng) + (F_,))
+                coords.append(None)
+                continue
             t = np.arange(frames)[:, None]
             disp = amp * np.sin(k * V0[None, :, 0] + 0.25 * t + ph)            # (T, V)
             Vt = np.repeat(V0[None], frames, 0)
             Vt[:, :, 2] += disp
             Vt[:, :, 1] += 0.5 * amp * np.cos(k * V0[None, :, 1] + 0.2 * t)
             coords.append(Vt.astype(np.float32))
-            Vs.append(V0.shape[0])
-            Fs.append(F_.shape[0])
-            faces_all.append(F_.astype(np.int32))
-            for tf in range(op_frames if operators == "pool" else 0):
-                if model == "dir":
-                    Di, DiA = mesh_ops.dirac(Vt[tf].astype(np.float64), F_)
-                    mats["Di"].append(Di.astype(np.float32))
-                    mats["DiA"].append(DiA.astype(np.float32))
-                else:
-                    mats["L"].append(mesh_ops.laplacian(Vt[tf].astype(np.float64), F_).astype(np.float32))
+            add_operators(Vt, F_)
+        if pending:
+            groups = {}
+            for s, (V0, F_, handles, Hh, _) in enumerate(pending):
+                groups.setdefault((V0.shape[0], F_.shape[0], handles.size), []).append(s)
+            with torch.cuda.device(self.device):
+                for ids in groups.values():      # one workgroup per mesh
+                    got = arap_deform(*(np.stack([pending[s][k] for s in ids]) for k in range(4))).frames.cpu().numpy()
+                    for s, fr in zip(ids, got):
+                        coords[s] = fr
+            for s, c in enumerate(coords):
+                add_operators(c, pending[s][4])
         self.num_vertices = np.array(Vs)
         self.num_faces = np.array(Fs)
         self.n = len(grids)

@@ -25,6 +25,34 @@ bool sn_internal_timing_slot(int kind, int64_t rows, int64_t width, int64_t byte
 // launch status.
 void sn_internal_scan_i32(const int *in, int64_t n, int *out, int *sums, int *status, int too_large, int skip_mask, hipStream_t s);
 
+// By-vertex incidence of the good faces of F (sn_meshops.hip: bucket_count_k, bucket_offsets, bucket_fill_k, vertex_sort_k):
+// ptr[nV + 1] and inc[ptr[v] .. ptr[v + 1]) = the codes 3 f + c of the corners at vertex v, ascending.  A face with an index outside
+// 0..nV-1 or a repeated index is left out and raises SN_ARAP_BAD_FACE in *status (the bit of the one caller so far).  The arrays
+// live in the workspace (sn_internal_incidence_bytes); sums is scan scratch for nV + 1 items that the caller may use afterwards.
+size_t sn_internal_incidence_bytes(int64_t nV, int64_t nF);
+int sn_internal_incidence(const int *F, int64_t nV, int64_t nF, void *workspace, int *status, const int **ptr, const int **inc,
+                          int **sums, hipStream_t s);
+
+// stable insertion sort of key[b..e), ascending, that carries up to two payload arrays along
+template <class A = char, class B = char>
+__device__ __forceinline__ void sort_run(int *key, int b, int e, A *pa = nullptr, B *pb = nullptr) {
+  for (int i = b + 1; i < e; ++i) {
+    const int k = key[i];
+    const A va = pa ? pa[i] : A();
+    const B vb = pb ? pb[i] : B();
+    int j = i - 1;
+    while (j >= b && key[j] > k) {
+      key[j + 1] = key[j];
+      if (pa) pa[j + 1] = pa[j];
+      if (pb) pb[j + 1] = pb[j];
+      --j;
+    }
+    key[j + 1] = k;
+    if (pa) pa[j + 1] = va;
+    if (pb) pb[j + 1] = vb;
+  }
+}
+
 // Workspace layouts are written once, over a Carver: without a base it only measures, with one it hands out the slices, each
 // padded to 16 bytes.  The *_workspace_bytes query and the entry point run the same description.
 struct SnCarver {

@@ -108,26 +108,6 @@ inline int bucket_offsets(int *ptr, int *cursor, int *sums, int64_t nV, hipStrea
   return e == hipSuccess ? SN_OK : (int)e;
 }
 
-// stable insertion sort of key[b..e), ascending, that carries up to two payload arrays along
-template <class A = char, class B = char>
-__device__ __forceinline__ void sort_run(int *key, int b, int e, A *pa = nullptr, B *pb = nullptr) {
-  for (int i = b + 1; i < e; ++i) {
-    const int k = key[i];
-    const A va = pa ? pa[i] : A();
-    const B vb = pb ? pb[i] : B();
-    int j = i - 1;
-    while (j >= b && key[j] > k) {
-      key[j + 1] = key[j];
-      if (pa) pa[j + 1] = pa[j];
-      if (pb) pb[j + 1] = pb[j];
-      --j;
-    }
-    key[j + 1] = k;
-    if (pa) pa[j + 1] = va;
-    if (pb) pb[j + 1] = vb;
-  }
-}
-
 // sort each vertex's list, write DiA's block columns, and Av_j = sum_{incident faces, ascending} Af/3 (mesh.py:43-45)
 __global__ __launch_bounds__(kWG) void vertex_lists_k(const int *__restrict__ vptr, int64_t nV, int *__restrict__ inc,
                                                       const double *__restrict__ Af, double *__restrict__ Av,
@@ -1588,6 +1568,24 @@ inline int incidence_build(const int *F, int64_t nV, int64_t nF, const BucketWs 
 }
 
 }  // namespace
+
+// the by-vertex incidence of the good faces for the builders of other translation units (sn_internal.h)
+size_t sn_internal_incidence_bytes(int64_t nV, int64_t nF) { return MeshBucketWs(nullptr, at_least_0(nV), at_least_0(nF)).c.bytes; }
+
+int sn_internal_incidence(const int *F, int64_t nV, int64_t nF, void *workspace, int *status, const int **ptr, const int **inc,
+                          int **sums, hipStream_t s) {
+  const BucketWs b = MeshBucketWs(workspace, nV, nF).b;
+  const hipError_t e = sn_internal_fill(b.ptr, 0, (size_t)(nV + 1) * sizeof(int), s);
+  if (e != hipSuccess) return (int)e;
+  if (nF > 0)
+    hipLaunchKernelGGL((bucket_count_k<kCornerVertex, kGoodFaces, SN_ARAP_BAD_FACE>), dim3(grid_for(nF)), dim3(kWG), 0, s, F,
+                       (const int *)nullptr, nF, nV, b.ptr, status);
+  const int st = incidence_build(F, nV, nF, b, s);
+  *ptr = b.ptr;
+  *inc = b.bucket;
+  *sums = b.sums;
+  return st;
+}
 
 extern "C" {
 

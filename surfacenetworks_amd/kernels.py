@@ -2240,3 +2240,77 @@ def mesh_digits(images, seed: int = 0, R: int = 98304, min_points: int = 101, mi
               int(min_det), int(max_attempts), int(max_rounds), cells, _p(out.P), _p(out.count), _p(out.V), _p(out.F), _p(out.nF),
               _p(out.status), _p(out.attempts), _p(out.counts), _stream())
     return out
+
+
+# ---- ARAP deformation (include/sn_spmm.h, "ARAP deformation"; host statement mesh_ops.arap_*) ------------------------------------
+ARAP_NOT_CONVERGED, ARAP_BREAKDOWN, ARAP_DEGENERATE, ARAP_BAD_FACE, ARAP_DEGREE, ARAP_TOO_LARGE = 1, 2, 4, 8, 16, 32
+ARAP_MAX_CG = 65536                      # SN_ARAP_MAX_CG
+ARAP_FRAMES_PER_LAUNCH = 5               # LABNOTES.md#arapdeform: one launch stays a bounded piece of work
+
+ArapWeights = collections.namedtuple("ArapWeights", "rowptr colind w d status")
+ArapFrames = collections.namedtuple("ArapFrames", "frames cg_iters energy status R_first rhs_first")
+
+
+def arap_max_vertices() -> int:
+    """The largest mesh sn_arap_frames_f64 takes (its search direction lives in the LDS of one compute unit)."""
+    return int(_lib.load().sn_arap_max_vertices())
+
+
+def arap_weights(V0, F) -> ArapWeights:
+    """The ARAP weights of a rest mesh, or of a disjoint union of rest meshes, on the device (sn_arap_weights_f64): rowptr
+    (nV + 1,) int32, colind and w sized for 6 nF entries of which rowptr[nV] are used, d (nV,) fp64, status (1,) int32
+    (ARAP_BAD_FACE / ARAP_DEGREE).  V0 (nV, 3) fp32, F (nF, 3) int32.  Does not synchronise."""
+    _dev(V0, F)
+    _check_mesh("arap_weights", V0, F)
+    V0, F = V0.contiguous(), F.contiguous()
+    nV, nF = V0.shape[0], F.shape[0]
+    dev = V0.device
+    rowptr = torch.empty(nV + 1, dtype=torch.int32, device=dev)
+    colind = torch.empty(6 * nF, dtype=torch.int32, device=dev)
+    w = torch.empty(6 * nF, dtype=torch.float64, device=dev)
+    d = torch.empty(nV, dtype=torch.float64, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ws_bytes = int(_lib.load().sn_arap_weights_workspace_bytes(nV, nF))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    _lib.call("sn_arap_weights_f64", _p(V0), _p(F), nV, nF, rowptr.data_ptr(), _p(colind), _p(w), _p(d), status.data_ptr(), _p(ws),
+              ws_bytes, _stream())
+    return ArapWeights(rowptr, colind, w, d, status)
+
+
+def arap_frames(V0, weights: ArapWeights, voff, hoff, handles, H, max_mesh_vertices: int, iters: int = 2, tol: float = 1e-10,
+                max_cg: int = 4096, frames_per_launch: int = None, first_step: bool = False) -> ArapFrames:
+    """The frames of a batch of ARAP sequences (sn_arap_frames_f64), one workgroup per mesh, enqueued in chunks of
+    frames_per_launch frames (default: ARAP_FRAMES_PER_LAUNCH) that carry their state in one workspace.  V0 (nV, 3) fp32 and handles (nH,) int32 index the disjoint
+    union; voff, hoff (B + 1,) int32 device tensors cut it into meshes; H (T, nH, 3) fp32; max_mesh_vertices: the largest mesh
+    (a host number: nothing is read back).  Returns ArapFrames of device tensors: frames (T, nV, 3) fp32, cg_iters (B, T, iters)
+    int32, energy (B, T) fp64, status (B,) int32, and with first_step the rotations (nV, 3, 3) and right-hand side (nV, 3) of the
+    first local step of frame 0 (else None).  Does not synchronise."""
+    _dev(V0, voff, hoff, handles, H, *weights)
+    if V0.dtype != torch.float32 or V0.dim() != 2 or V0.shape[1] != 3:
+        raise TypeError("arap_frames wants V0 (nV, 3) float32")
+    if H.dtype != torch.float32 or H.dim() != 3 or H.shape[2] != 3 or handles.dtype != torch.int32 or H.shape[1] != handles.numel():
+        raise TypeError("arap_frames wants handles (nH,) int32 and H (T, nH, 3) float32")
+    if voff.dtype != torch.int32 or hoff.dtype != torch.int32 or voff.numel() != hoff.numel() or voff.numel() < 1:
+        raise TypeError("arap_frames wants voff and hoff (B + 1,) int32")
+    iters, max_cg, chunk = int(iters), int(max_cg), int(ARAP_FRAMES_PER_LAUNCH if frames_per_launch is None else frames_per_launch)
+    if iters < 1 or not 0 <= max_cg <= ARAP_MAX_CG or chunk < 1 or not float(tol) >= 0:
+        raise ValueError(f"arap_frames: iters >= 1, 0 <= max_cg <= {ARAP_MAX_CG}, frames_per_launch >= 1 and tol >= 0 are required")
+    if int(max_mesh_vertices) > arap_max_vertices():
+        raise ValueError(f"arap_frames: a mesh of {int(max_mesh_vertices)} vertices, at most {arap_max_vertices()} are supported")
+    V0, H, handles, voff, hoff = V0.contiguous(), H.contiguous(), handles.contiguous(), voff.contiguous(), hoff.contiguous()
+    nV, nH, T, B = V0.shape[0], handles.numel(), H.shape[0], voff.numel() - 1
+    dev = V0.device
+    frames = torch.empty(T, nV, 3, dtype=torch.float32, device=dev)
+    cg_iters = torch.empty(B, T, iters, dtype=torch.int32, device=dev)
+    energy = torch.empty(B, T, dtype=torch.float64, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    R_first = torch.empty(nV, 3, 3, dtype=torch.float64, device=dev) if first_step else None
+    rhs_first = torch.empty(nV, 3, dtype=torch.float64, device=dev) if first_step else None
+    ws_bytes = int(_lib.load().sn_arap_frames_workspace_bytes(nV))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    for begin in range(0, T, chunk):
+        _lib.call("sn_arap_frames_f64", _p(V0), weights.rowptr.data_ptr(), _p(weights.colind), _p(weights.w), _p(weights.d),
+                  voff.data_ptr(), hoff.data_ptr(), _p(handles), _p(H), B, nV, nH, T, int(max_mesh_vertices), begin,
+                  min(chunk, T - begin), iters, float(tol), max_cg, _p(frames), _p(cg_iters), _p(energy), _p(status), _p(R_first),
+                  _p(rhs_first), _p(ws), ws_bytes, _stream())
+    return ArapFrames(frames, cg_iters, energy, status, R_first, rhs_first)

@@ -39,6 +39,9 @@ __all__ = [
     "lattice_draw", "canonical_faces", "snap_to_lattice", "Delaunay2D", "PoissonDisc", "MeshDigitsResult",
     "DT_DEGENERATE", "DT_DUPLICATE", "DT_RANGE", "DT_TOO_LARGE", "DT_NOT_CONVERGED", "DT_REJECTED", "DT_INTERNAL",
     "DELAUNAY_MAX_POINTS", "DELAUNAY_COORD_LIMIT", "MESHDIGITS_MAX_ATTEMPTS", "MESHDIGITS_Q", "MESHDIGITS_MIN_DET",
+    "arap_weights", "arap_covariances", "arap_rotation_from_covariance", "arap_rotations", "arap_rhs", "arap_energy", "arap_cg",
+    "arap_deform", "arap_handle_motion", "ArapWeights", "ArapSolve", "ArapResult", "ARAP_NOT_CONVERGED", "ARAP_BREAKDOWN",
+    "ARAP_DEGENERATE", "ARAP_BAD_FACE", "ARAP_DEGREE", "ARAP_TOO_LARGE", "ARAP_REDUCE_WIDTH", "ARAP_JACOBI_SWEEPS", "ARAP_RANK_EPS", "ARAP_MAX_CG",
 ]
 
 _PERMS = np.array([[0, 1, 2], [0, 2, 1], [1, 0, 2], [1, 2, 0], [2, 0, 1], [2, 1, 0]])  # itertools.permutations order
@@ -1221,3 +1224,346 @@ def mesh_digits(images, seed: int = 0, r: float = 1.5, min_points: int = 101, mi
             V[b, :n, 2] = lattice_intensity(images[b], s.P)
             break
     return MeshDigitsResult(P, count, V, F, nF, status, attempts)
+
+
+# --------------------------------------------------------------------------------------------------
+# ARAP deformation (include/sn_spmm.h, "ARAP deformation"): the numpy statement the device equals bit for bit.
+# Every sum below is written out in the header's order: slot by slot over the ascending columns of a row, rows strided over
+# ARAP_REDUCE_WIDTH partial sums, then the two halving trees.
+# --------------------------------------------------------------------------------------------------
+ARAP_NOT_CONVERGED, ARAP_BREAKDOWN, ARAP_DEGENERATE, ARAP_BAD_FACE, ARAP_DEGREE, ARAP_TOO_LARGE = 1, 2, 4, 8, 16, 32
+ARAP_REDUCE_WIDTH = 1024      # SN_ARAP_THREADS
+ARAP_WAVE = 64
+ARAP_JACOBI_SWEEPS = 6        # SN_ARAP_JACOBI_SWEEPS
+ARAP_RANK_EPS = 1e-20         # SN_ARAP_RANK_EPS
+ARAP_MAX_CG = 65536           # SN_ARAP_MAX_CG
+
+ArapWeights = collections.namedtuple("ArapWeights", "rowptr colind w d status")
+ArapSolve = collections.namedtuple("ArapSolve", "x iters status")
+ArapResult = collections.namedtuple("ArapResult", "frames frames64 cg_iters energy status R_first rhs_first")
+
+
+def arap_weights(V0, F) -> ArapWeights:
+    """w_ij = W[i, j] of cotangent_weights on the rest mesh over the vertex adjacency, kept whatever its value, columns
+    ascending; every entry summed serially over its contributions in (face, permutation) order; d_i = sum_j w_ij in ascending
+    column order.  V0 fp32 (nV, 3), widened; F (nF, 3).  A bad face (good_faces) contributes nothing and sets ARAP_BAD_FACE; a
+    vertex with more than LAP_MAX_DEGREE incident good faces gets an empty row and sets ARAP_DEGREE."""
+    V = np.asarray(V0, dtype=np.float32).astype(np.float64)
+    F = np.asarray(F, dtype=np.int64).reshape(-1, 3)
+    nV = V.shape[0]
+    good = good_faces(F, nV)
+    status = 0 if good.all() else ARAP_BAD_FACE
+    fid = np.nonzero(good)[0]
+    Fg = F[fid]
+    l = edge_lengths(V, Fg)
+    den = 8 * heron_areas(l) + 1e-6
+    l2 = l * l
+    e2 = np.empty((Fg.shape[0], 3, 3))
+    e2[:, 0, 1] = e2[:, 1, 0] = l2[:, 0]
+    e2[:, 1, 2] = e2[:, 2, 1] = l2[:, 1]
+    e2[:, 2, 0] = e2[:, 0, 2] = l2[:, 2]
+    rows = np.stack([Fg[:, p] for p, q, r in _PERMS], axis=1).ravel()
+    cols = np.stack([Fg[:, q] for p, q, r in _PERMS], axis=1).ravel()
+    vals = np.stack([((-e2[:, p, q] + e2[:, q, r]) + e2[:, r, p]) / den for p, q, r in _PERMS], axis=1).ravel()
+    incident = np.bincount(Fg.ravel(), minlength=nV)
+    if (incident > LAP_MAX_DEGREE).any():
+        status |= ARAP_DEGREE
+        keep = incident[rows] <= LAP_MAX_DEGREE
+        rows, cols, vals = rows[keep], cols[keep], vals[keep]
+    order = np.lexsort((np.arange(rows.size), cols, rows))          # (row, col, face, permutation): the input is face-major
+    rows, cols, vals = rows[order], cols[order], vals[order]
+    head = np.ones(rows.size, bool)
+    head[1:] = (rows[1:] != rows[:-1]) | (cols[1:] != cols[:-1])
+    group = np.cumsum(head) - 1
+    starts = np.nonzero(head)[0]
+    w = np.zeros(starts.size)
+    rank = np.arange(rows.size) - starts[group] if rows.size else np.zeros(0, np.int64)
+    for k in range(int(rank.max()) + 1 if rank.size else 0):       # serial: the k-th contribution of every entry
+        sel = rank == k
+        w[group[sel]] = vals[sel] if k == 0 else w[group[sel]] + vals[sel]
+    colind = cols[starts].astype(np.int32)
+    rowptr = np.zeros(nV + 1, np.int32)
+    rowptr[1:] = np.cumsum(np.bincount(rows[starts], minlength=nV))
+    Wt = ArapWeights(rowptr, colind, w, None, status)
+    col, wp, valid = _arap_padded(Wt)
+    d = np.zeros(nV)
+    for k in range(col.shape[1]):
+        d = np.where(valid[:, k], d + wp[:, k], d)
+    return Wt._replace(d=d)
+
+
+def _arap_padded(Wt):
+    """(col, w, valid), each (nV, D): slot k of row i is its k-th entry; D = the largest row."""
+    rowptr = np.asarray(Wt.rowptr, dtype=np.int64)
+    deg = np.diff(rowptr)
+    D = int(deg.max()) if deg.size else 0
+    slot = np.arange(D)[None, :]
+    valid = slot < deg[:, None]
+    idx = np.where(valid, rowptr[:-1, None] + slot, 0)
+    if Wt.colind.size == 0:
+        return np.zeros((deg.size, 0), np.int64), np.zeros((deg.size, 0)), np.zeros((deg.size, 0), bool)
+    return np.where(valid, np.asarray(Wt.colind, dtype=np.int64)[idx], 0), np.where(valid, Wt.w[idx], 0.0), valid
+
+
+def _arap_reduce(c: np.ndarray) -> np.ndarray:
+    """The header's reduction of c (n,) or (n, k) over its rows: partial sums strided over ARAP_REDUCE_WIDTH lanes, each serial
+    in ascending row order from +0.0; a halving tree inside every group of ARAP_WAVE lanes; a halving tree over the groups."""
+    c = np.asarray(c, dtype=np.float64)
+    c2 = c.reshape(c.shape[0], -1)
+    n, k = c2.shape
+    rows = -(-n // ARAP_REDUCE_WIDTH)
+    pad = np.zeros((rows * ARAP_REDUCE_WIDTH, k))
+    pad[:n] = c2
+    pad = pad.reshape(rows, ARAP_REDUCE_WIDTH, k)
+    part = np.zeros((ARAP_REDUCE_WIDTH, k))
+    for r in range(rows):
+        part = part + pad[r]
+    a = part.reshape(ARAP_REDUCE_WIDTH // ARAP_WAVE, ARAP_WAVE, k).copy()
+    s = ARAP_WAVE // 2
+    while s:
+        a[:, :s] = a[:, :s] + a[:, s:2 * s]
+        s //= 2
+    g = a[:, 0].copy()
+    s = g.shape[0] // 2
+    while s:
+        g[:s] = g[:s] + g[s:2 * s]
+        s //= 2
+    return g[0].reshape(c.shape[1:])
+
+
+def _dot3s(u, w):
+    return (u[..., 0] * w[..., 0] + u[..., 1] * w[..., 1]) + u[..., 2] * w[..., 2]
+
+
+def _matvec3(M, v):
+    return np.stack([(M[..., a, 0] * v[..., 0] + M[..., a, 1] * v[..., 1]) + M[..., a, 2] * v[..., 2] for a in range(3)], axis=-1)
+
+
+def _cross3s(u, w):
+    return np.stack([u[..., 1] * w[..., 2] - u[..., 2] * w[..., 1], u[..., 2] * w[..., 0] - u[..., 0] * w[..., 2],
+                     u[..., 0] * w[..., 1] - u[..., 1] * w[..., 0]], axis=-1)
+
+
+def arap_covariances(Wt: ArapWeights, P0, P) -> np.ndarray:
+    """S_i = sum_j w_ij e_ij e'_ij^T over ascending j, S[a][b] += (w e[a]) e'[b]."""
+    col, wp, valid = _arap_padded(Wt)
+    S = np.zeros((P0.shape[0], 3, 3))
+    for k in range(col.shape[1]):
+        j = col[:, k]
+        we = wp[:, k, None] * (P0 - P0[j])
+        S = np.where(valid[:, k, None, None], S + we[:, :, None] * (P - P[j])[:, None, :], S)
+    return S
+
+
+def arap_rotation_from_covariance(S):
+    """(R, degenerate) for S (m, 3, 3): the proper rotation maximising tr(R S), by the header's procedure — cyclic Jacobi
+    (ARAP_JACOBI_SWEEPS sweeps over (0,1), (0,2), (1,2)) on G = S^T S, eigenvalues sorted descending by the network (0,1), (1,2),
+    (0,1), image vectors S v1, S v2 orthonormalised by one Gram-Schmidt step, third vectors by cross products, R = sum_k v_k u_k^T.
+    Only + - * / sqrt.  Rank below 2: R = I and degenerate."""
+    S = np.asarray(S, dtype=np.float64).reshape(-1, 3, 3)
+    m = S.shape[0]
+    A = [[None] * 3 for _ in range(3)]
+    for a in range(3):
+        for b in range(a, 3):
+            A[a][b] = (S[:, 0, a] * S[:, 0, b] + S[:, 1, a] * S[:, 1, b]) + S[:, 2, a] * S[:, 2, b]
+    Vc = [[np.full(m, 1.0 if r == c else 0.0) for c in range(3)] for r in range(3)]      # Vc[r][c]: row r of column c
+
+    def sym(a, b):
+        return (a, b) if a < b else (b, a)
+
+    with np.errstate(all="ignore"):
+        for _ in range(ARAP_JACOBI_SWEEPS):
+            for p, q in ((0, 1), (0, 2), (1, 2)):
+                r = 3 - p - q
+                apq, app, aqq = A[p][q], A[p][p], A[q][q]
+                arp, arq = A[sym(r, p)[0]][sym(r, p)[1]], A[sym(r, q)[0]][sym(r, q)[1]]
+                nz = apq != 0
+                theta = (aqq - app) / np.where(nz, 2 * apq, 1.0)
+                t = 1 / (np.abs(theta) + np.sqrt(theta * theta + 1))
+                t = np.where(theta < 0, -t, t)
+                c = 1 / np.sqrt(t * t + 1)
+                s = t * c
+                A[p][p] = np.where(nz, app - t * apq, app)
+                A[q][q] = np.where(nz, aqq + t * apq, aqq)
+                A[p][q] = np.where(nz, 0.0, apq)
+                A[sym(r, p)[0]][sym(r, p)[1]] = np.where(nz, c * arp - s * arq, arp)
+                A[sym(r, q)[0]][sym(r, q)[1]] = np.where(nz, s * arp + c * arq, arq)
+                for k in range(3):
+                    vp, vq = Vc[k][p], Vc[k][q]
+                    Vc[k][p] = np.where(nz, c * vp - s * vq, vp)
+                    Vc[k][q] = np.where(nz, s * vp + c * vq, vq)
+        lam = [A[0][0], A[1][1], A[2][2]]
+        for a, b in ((0, 1), (1, 2), (0, 1)):
+            sw = lam[a] < lam[b]
+            lam[a], lam[b] = np.where(sw, lam[b], lam[a]), np.where(sw, lam[a], lam[b])
+            for k in range(3):
+                Vc[k][a], Vc[k][b] = np.where(sw, Vc[k][b], Vc[k][a]), np.where(sw, Vc[k][a], Vc[k][b])
+        v1 = np.stack([Vc[k][0] for k in range(3)], axis=-1)
+        v2 = np.stack([Vc[k][1] for k in range(3)], axis=-1)
+        v3 = _cross3s(v1, v2)
+        a1, a2 = _matvec3(S, v1), _matvec3(S, v2)
+        n1 = _dot3s(a1, a1)
+        u1 = a1 / np.sqrt(n1)[:, None]
+        a2p = a2 - _dot3s(u1, a2)[:, None] * u1
+        n2 = _dot3s(a2p, a2p)
+        u2 = a2p / np.sqrt(n2)[:, None]
+        u3 = _cross3s(u1, u2)
+        R = (v1[:, :, None] * u1[:, None, :] + v2[:, :, None] * u2[:, None, :]) + v3[:, :, None] * u3[:, None, :]
+        ok = (n1 > 0) & (n2 > ARAP_RANK_EPS * n1)
+    return np.where(ok[:, None, None], R, np.eye(3)[None]), ~ok
+
+
+def arap_rotations(Wt: ArapWeights, P0, P):
+    """The local step: (R (nV, 3, 3), degenerate (nV,) bool)."""
+    return arap_rotation_from_covariance(arap_covariances(Wt, np.asarray(P0, np.float64), np.asarray(P, np.float64)))
+
+
+def arap_rhs(Wt: ArapWeights, P0, R) -> np.ndarray:
+    """b_i = sum_j (w_ij / 2) (R_i + R_j) e_ij over ascending j."""
+    P0 = np.asarray(P0, np.float64)
+    col, wp, valid = _arap_padded(Wt)
+    b = np.zeros((P0.shape[0], 3))
+    for k in range(col.shape[1]):
+        j = col[:, k]
+        v = _matvec3(R + R[j], P0 - P0[j])
+        b = np.where(valid[:, k, None], b + (wp[:, k] * 0.5)[:, None] * v, b)
+    return b
+
+
+def arap_energy(Wt: ArapWeights, P0, P, R) -> float:
+    """sum_i sum_j w_ij |e'_ij - R_i e_ij|^2, rows by the header's reduction."""
+    P0, P = np.asarray(P0, np.float64), np.asarray(P, np.float64)
+    col, wp, valid = _arap_padded(Wt)
+    e = np.zeros(P0.shape[0])
+    for k in range(col.shape[1]):
+        j = col[:, k]
+        df = (P - P[j]) - _matvec3(R, P0 - P0[j])
+        e = np.where(valid[:, k], e + wp[:, k] * _dot3s(df, df), e)
+    return float(_arap_reduce(e))
+
+
+def _arap_offdiag(col, wp, valid, free, x):
+    """s_i = sum over the FREE columns j of row i, ascending, of w_ij x_j, from +0.0."""
+    s = np.zeros_like(x)
+    for k in range(col.shape[1]):
+        j = col[:, k]
+        s = np.where((valid[:, k] & free[j])[:, None], s + wp[:, k, None] * x[j], s)
+    return s
+
+
+def arap_cg(Wt: ArapWeights, fixed, b, x0, tol: float = 1e-10, max_cg: int = 4096) -> ArapSolve:
+    """The global step: Jacobi-preconditioned CG on the free rows of sum_j w_ij (x_i - x_j) = b_i, the rows of `fixed` held at
+    their values in x0 and moved to the right-hand side; three columns, one matrix product, own alpha and beta, a converged
+    column frozen.  Returns (x, iterations, status bits)."""
+    fixed = np.asarray(fixed, dtype=bool)
+    free = ~fixed
+    x = np.array(x0, dtype=np.float64)
+    col, wp, valid = _arap_padded(Wt)
+    d = Wt.d
+    fm = free[:, None]
+    rhs = np.array(b, dtype=np.float64)
+    for k in range(col.shape[1]):
+        j = col[:, k]
+        rhs = np.where((valid[:, k] & fixed[j])[:, None], rhs + wp[:, k, None] * x[j], rhs)
+    with np.errstate(all="ignore"):
+        r = rhs - (d[:, None] * x - _arap_offdiag(col, wp, valid, free, x))
+        z = r / d[:, None]
+        p = np.where(fm, z, 0.0)
+        red = _arap_reduce(np.where(fm, np.concatenate([r * z, r * r, rhs * rhs], axis=1), 0.0))
+        rz, rr, bb = red[0:3], red[3:6], red[6:9]
+        thr = tol * np.sqrt(bb)
+        conv = np.sqrt(rr) <= thr
+        status, it = 0, 0
+        while it < max_cg and not conv.all():
+            Ap = d[:, None] * p - _arap_offdiag(col, wp, valid, free, p)
+            pAp = _arap_reduce(np.where(fm, p * Ap, 0.0))
+            if (~conv & ~(pAp > 0)).any():
+                status |= ARAP_BREAKDOWN
+                break
+            alpha = rz / pAp
+            upd = fm & ~conv[None, :]
+            x = np.where(upd, x + alpha[None, :] * p, x)
+            r = np.where(upd, r - alpha[None, :] * Ap, r)
+            z = r / d[:, None]
+            red = _arap_reduce(np.where(fm, np.concatenate([r * z, r * r], axis=1), 0.0))
+            it += 1
+            conv_new = conv | (np.sqrt(red[3:6]) <= thr)
+            beta = red[0:3] / rz
+            p = np.where(fm & ~conv_new[None, :], z + beta[None, :] * p, p)
+            rz = np.where(conv_new, rz, red[0:3])
+            conv = conv_new
+        if not conv.all() and not status:
+            status |= ARAP_NOT_CONVERGED
+    return ArapSolve(x, it, status)
+
+
+def arap_deform(V0, F, handles, H, iters: int = 2, tol: float = 1e-10, max_cg: int = 4096, weights: ArapWeights = None) -> ArapResult:
+    """The whole definition for one mesh.  V0 (nV, 3) fp32, handles (nH,), H (T, nH, 3) fp32.  Returns ArapResult: frames
+    (T, nV, 3) fp32, frames64 the same before the rounding, cg_iters (T, iters) int32, energy (T,) fp64 after the last step of
+    every frame, status, and the rotations and right-hand side of the first local step of frame 0."""
+    V0 = np.asarray(V0, dtype=np.float32)
+    P0 = V0.astype(np.float64)
+    H = np.asarray(H, dtype=np.float32).astype(np.float64)
+    handles = np.asarray(handles, dtype=np.int64)
+    Wt = weights if weights is not None else arap_weights(V0, F)
+    nV, T = P0.shape[0], H.shape[0]
+    fixed = np.zeros(nV, bool)
+    fixed[handles] = True
+    status = int(Wt.status)
+    dbad = bool((~fixed & ~(Wt.d > 0)).any())
+    if dbad:
+        status |= ARAP_BREAKDOWN
+    x = P0.copy()
+    R = np.broadcast_to(np.eye(3), (nV, 3, 3)).copy()
+    frames64 = np.zeros((T, nV, 3))
+    cg_iters = np.zeros((T, iters), np.int32)
+    energy = np.zeros(T)
+    R_first = rhs_first = None
+    for t in range(T):
+        x[handles] = H[t]
+        start = x.copy()
+        for it in range(0 if dbad else iters):
+            R, deg = arap_rotations(Wt, P0, x)
+            if deg.any():
+                status |= ARAP_DEGENERATE
+            b = arap_rhs(Wt, P0, R)
+            if t == 0 and it == 0:
+                R_first, rhs_first = R.copy(), b.copy()
+            sol = arap_cg(Wt, fixed, b, x, tol, max_cg)
+            cg_iters[t, it] = sol.iters
+            status |= sol.status
+            x = sol.x
+            if sol.status & ARAP_BREAKDOWN:
+                x = start.copy()
+                break
+        energy[t] = arap_energy(Wt, P0, x, R)
+        frames64[t] = x
+    return ArapResult(frames64.astype(np.float32), frames64, cg_iters, energy, status, R_first, rhs_first)
+
+
+def arap_handle_motion(V0, frames: int, rng: np.random.Generator):
+    """Handles and their positions for a cloth: the vertices of the boundary edge of smallest x are held, those of the edge of
+    largest x move rigidly with constant velocity — a rotation about a seeded axis through their centroid plus a translation, so
+    that two frames determine the continuation.  Returns (handles (nH,) int32 ascending, H (frames, nH, 3) fp32)."""
+    V = np.asarray(V0, dtype=np.float32).astype(np.float64)
+    x = V[:, 0]
+    ext = V.max(axis=0) - V.min(axis=0)
+    h = np.sqrt(max(ext[0] * ext[1], 1e-30) / max(V.shape[0], 1))          # about one grid spacing
+    held = np.nonzero(x < x.min() + 0.5 * h)[0]
+    moved = np.nonzero(x > x.max() - 0.5 * h)[0]
+    moved = np.setdiff1d(moved, held)
+    axis = rng.standard_normal(3)
+    axis /= np.linalg.norm(axis)
+    omega = 0.01 + 0.01 * rng.random()                                       # radians per frame
+    vel = 0.004 * rng.standard_normal(3)
+    c = V[moved].mean(axis=0) if moved.size else np.zeros(3)
+    K = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+    handles = np.concatenate([held, moved])
+    order = np.argsort(handles, kind="stable")
+    H = np.zeros((frames, handles.size, 3))
+    for t in range(frames):
+        a = omega * t
+        Rm = np.eye(3) + np.sin(a) * K + (1 - np.cos(a)) * (K @ K)
+        H[t, : held.size] = V[held]
+        H[t, held.size:] = c + (V[moved] - c) @ Rm.T + vel * t
+    return handles[order].astype(np.int32), H[:, order].astype(np.float32)

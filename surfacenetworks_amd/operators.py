@@ -18,6 +18,7 @@ from __future__ import annotations
 import collections
 import dataclasses
 import os
+import warnings
 import weakref
 from typing import Optional, Sequence
 
@@ -29,7 +30,7 @@ from . import kernels
 __all__ = ["SparseOperator", "OperatorPool", "PackedSegments", "as_operator", "dirac_operators_from_mesh",
            "laplacian_operator_from_mesh", "geodesic_matrix_from_mesh", "spgemm", "amplify_sequence_operators",
            "clean_mesh", "CleanMesh", "repair_mesh", "RepairedMesh", "vertex_descriptors", "MeshDescriptors", "vertex_normals", "face_areas", "vertex_mass",
-           "gaussian_curvature", "delaunay_2d", "Delaunay2D"]
+           "gaussian_curvature", "delaunay_2d", "Delaunay2D", "arap_deform", "ArapDeformation"]
 
 # A BSR4 copy is kept when zero-fill costs at most this much extra storage over CSR entries.
 _BSR4_MAX_FILL = 1.6
@@ -1153,3 +1154,81 @@ class OperatorPool:
         op._bsr4 = opt._bsr4 = False
         self._attach_band(op, sel, size0 == size1)
         return op
+
+
+ArapDeformation = collections.namedtuple("ArapDeformation", "frames cg_iters energy status")
+
+_ARAP_REASONS = ((kernels.ARAP_NOT_CONVERGED, "a conjugate-gradient solve stopped at max_cg iterations before reaching tol"),
+                 (kernels.ARAP_BREAKDOWN, "a solve broke down (p.Ap <= 0 or a free row without a positive diagonal): the frame keeps "
+                                          "its start values"),
+                 (kernels.ARAP_DEGENERATE, "a vertex has spokes of rank below 2: its rotation is the identity"),
+                 (kernels.ARAP_BAD_FACE, "a face has an index outside the mesh or a repeated index and was left out"),
+                 (kernels.ARAP_DEGREE, "a vertex has more incident faces than SN_LAP_MAX_DEGREE and got no weights"),
+                 (kernels.ARAP_TOO_LARGE, "a mesh was too large for the launch and was left at rest"))
+
+
+def arap_deform(V0, F, handles, H, iters: int = 2, tol: float = 1e-10, max_cg: int = 4096) -> ArapDeformation:
+    """As-rigid-as-possible deformation sequences on the device: spokes-only ARAP (Sorkine & Alexa 2007), local and global steps
+    alternating `iters` times per frame, the global step by Jacobi-preconditioned CG, fp64 inside, frames rounded once to fp32.
+    include/sn_spmm.h ("ARAP deformation") has the definition, mesh_ops.arap_deform the host statement, which this equals bit
+    for bit; kernels.arap_weights / arap_frames do the work.  The textbook algorithm with this project's weights — not a
+    reproduction of the reference's downloaded sequences, whose generator is not in its tree.
+    V0 (nV, 3) rest mesh, F (nF, 3), handles (nH,) distinct vertex ids, H (T, nH, 3) their positions in every frame; or a batch
+    of equally sized meshes (B, nV, 3), (B, nF, 3), (B, nH), (B, T, nH, 3).  Device tensors or numpy (then moved to the current
+    device).  Frame t starts from frame t - 1, frame 0 from V0.
+    Returns ArapDeformation of device tensors: frames (T, nV, 3) fp32, cg_iters (T, iters) int32, energy (T,) fp64 after the last
+    step of every frame, status () int32 — each with a leading B for a batch.  ValueError for a handle out of range or repeated,
+    and for a mesh in which a connected component (a vertex no face uses is one) has no handle; a warning with the reason when a
+    status bit comes back.  Synchronises (the checks and the status are read).  A CPU tensor is refused as
+    everywhere in this package; a numpy array is checked on the host and then uploaded."""
+    def tensor(a, dtype):      # numpy stays on the host until the checks that need no device have passed
+        return a.to(dtype) if torch.is_tensor(a) else torch.from_numpy(np.array(a)).to(dtype)
+
+    given = (V0, F, handles, H)
+    V0, F, handles, H = tensor(V0, torch.float32), tensor(F, torch.int32), tensor(handles, torch.int32), tensor(H, torch.float32)
+    single = V0.dim() == 2
+    if single:
+        V0, F, handles, H = V0[None], F[None], handles[None], H[None]
+    if (V0.dim() != 3 or V0.shape[2] != 3 or F.dim() != 3 or F.shape[2] != 3 or handles.dim() != 2 or H.dim() != 4 or H.shape[3] != 3
+            or not V0.shape[0] == F.shape[0] == handles.shape[0] == H.shape[0] or H.shape[2] != handles.shape[1]):
+        raise ValueError(f"arap_deform wants V0 (nV, 3), F (nF, 3), handles (nH,), H (T, nH, 3), or all four with a leading batch "
+                         f"dimension; got {tuple(V0.shape)}, {tuple(F.shape)}, {tuple(handles.shape)}, {tuple(H.shape)}")
+    B, nV, nH, T = V0.shape[0], V0.shape[1], handles.shape[1], H.shape[1]
+    if nH < 1:
+        raise ValueError("arap_deform: at least one handle is required")
+    if nV > kernels.arap_max_vertices():
+        raise ValueError(f"arap_deform: {nV} vertices, at most {kernels.arap_max_vertices()} are supported")
+    hs = handles.sort(dim=1).values
+    ok_range, ok_distinct = torch.stack([((handles >= 0) & (handles < nV)).all(), (hs[:, 1:] != hs[:, :-1]).all()]).tolist()
+    if not ok_range:
+        raise ValueError(f"arap_deform: a handle lies outside 0..{nV - 1}")
+    if not ok_distinct:
+        raise ValueError("arap_deform: a handle is repeated")
+    V0, F, handles, H = (t if torch.is_tensor(g) else t.to("cuda") for t, g in zip((V0, F, handles, H), given))
+    kernels._dev(V0, F, handles, H)
+    dev = V0.device
+    base = torch.arange(B, device=dev, dtype=torch.int32)[:, None] * nV
+    Vu = V0.reshape(B * nV, 3).contiguous()
+    Fu = (F + base[:, :, None]).reshape(-1, 3).contiguous()
+    hu = (handles + base).reshape(-1).contiguous()
+    cc = kernels.mesh_components(Fu, B * nV, "vertex")
+    has = torch.zeros(B * nV, dtype=torch.bool, device=dev)
+    has[cc.vlabel[hu.long()].long()] = True
+    if not bool(has[cc.vlabel.long()].all()):
+        raise ValueError("arap_deform: a connected component of the mesh has no handle (its positions are not determined)")
+    weights = kernels.arap_weights(Vu, Fu)
+    voff = torch.arange(B + 1, device=dev, dtype=torch.int32) * nV
+    hoff = torch.arange(B + 1, device=dev, dtype=torch.int32) * nH
+    Hu = H.permute(1, 0, 2, 3).reshape(T, B * nH, 3).contiguous()
+    out = kernels.arap_frames(Vu, weights, voff, hoff, hu, Hu, nV, iters, tol, max_cg)
+    status = out.status | weights.status          # the builder's word covers the union
+    bits = 0
+    for word in status.tolist():
+        bits |= word
+    for bit, reason in _ARAP_REASONS:
+        if bits & bit:
+            warnings.warn(f"arap_deform: {reason}", RuntimeWarning, stacklevel=2)
+    frames = out.frames.reshape(T, B, nV, 3).permute(1, 0, 2, 3).contiguous()
+    if single:
+        return ArapDeformation(frames[0], out.cg_iters[0], out.energy[0], status[0])
+    return ArapDeformation(frames, out.cg_iters, out.energy, status)
