@@ -1245,6 +1245,14 @@ int sn_mesh_digits_u8(const uint8_t *images, int64_t B, int32_t rows, int32_t co
  *     Two phases as sn_laplacian_csr_from_mesh (phase 0: rowptr and *status, cleared first; the caller reads rowptr[nV] and the
  *     status, allocates, calls phase 1 with the same workspace, which ORs SN_DESC_CLAMPED into *status).  A vertex with more
  *     than SN_LAP_MAX_DEGREE incident good faces sets SN_DESC_DEGREE in phase 0: the caller launches nothing further.
+ *
+ * sn_mesh_cot_pencil_f64 : the same sums left in fp64 and undivided, the pencil (S, M) of the "Spectral" section below.
+ *     rowptr / colind: the pattern of sn_mesh_cot_laplacian_f32 (every neighbour plus the diagonal, columns ascending, exact
+ *     zeros kept).  S[nnz] fp64: S_vj = 0 - C_vj off the diagonal, S_vv = sum_j C_vj over ascending j from +0.0.  mass[nV]: fp64
+ *     M_voronoi, unrounded.  C_vj and C_jv sum the same corners (the two that lie opposite the edge v-j) in the same ascending
+ *     face order, so S equals its transpose BIT FOR BIT.  The same two phases, the same workspace (its size is
+ *     sn_mesh_cot_laplacian_workspace_bytes(nV, nF), else SN_E_WORKSPACE) and the same status bits (phase 1 writes colind, S and
+ *     mass and adds no bit).  Host statement: mesh_ops.cot_pencil.
  * ------------------------------------------------------------------------------------------ */
 #define SN_DESC_BAD_FACE   1
 #define SN_DESC_FLAT_FACE  2
@@ -1261,6 +1269,63 @@ size_t sn_mesh_cot_laplacian_workspace_bytes(int64_t nV, int64_t nF);
 int sn_mesh_cot_laplacian_f32(const float *V, const int32_t *F, int64_t nV, int64_t nF, int32_t phase, int32_t mass, int32_t clamp,
                               double hack, int32_t *rowptr, int32_t *colind, float *vals, int32_t *status, void *workspace,
                               size_t workspace_bytes, void *stream);
+int sn_mesh_cot_pencil_f64(const float *V, const int32_t *F, int64_t nV, int64_t nF, int32_t phase, int32_t *rowptr, int32_t *colind,
+                           double *S, double *mass, int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Spectral: the lowest eigenpairs of the cotangent pencil and the wave kernel signature, on the device.
+ *
+ * Replaces: compute_wks src/utils/geom_utils.py:407-440 (scipy.sparse.linalg.eigsh(-L, M=Am, sigma=-1e-5, k=300), a shift-invert
+ *           Lanczos with a sparse LU on the host, then the WKS sums), the 'wks': 100 input of src/normal_predict/train_4_normal.py:126.
+ * Host statement: mesh_ops.cot_pencil, spectral_start, cheb_filter_step, laplacian_eigenpairs, wks_weights, wks_contract,
+ *           wave_kernel_signature.  The three kernels below equal their numpy statements bit for bit (fp64, no contraction, only
+ *           + - * / and conversions); the solver as a whole (operators.laplacian_eigenpairs) takes the statement's steps with
+ *           the statement's parameters and differs from it in the rounding order of the library QR, eigh and dense products.
+ *
+ * Problem.  S phi = lambda diag(Am) phi for the k lowest lambda of every mesh of a block-diagonal batch; voff[B + 1] (int32,
+ *   ascending, voff[0] = 0, voff[B] = n) holds the first row of every mesh.
+ *   1. Mass: Am = max(M_voronoi, 1e-8), then Am /= sum(Am) per mesh (compute_wks:415-416).  A clipped vertex: SN_EIG_CLIPPED_MASS.
+ *   2. Standard form: A = D S D, D = Am^-1/2, A_ij = (D_i S_ij) D_j: S's pattern, symmetric.
+ *   3. Upper bound: b = max_i sum_j |A_ij| per mesh (Gershgorin); S is positive semidefinite, so the spectrum lies in [0, b].
+ *   4. Start block: m = min(n_b, k + guard) columns (the smallest mesh decides for the batch), sn_spectral_start_f64, orthonormalised (QR).
+ *   5. Outer iteration, at most max_outer times: Rayleigh-Ritz (H = X^T A X, symmetrised, eigh, X and A X rotated), residuals
+ *      r_i = |A x_i - theta_i x_i|_2, converged when r_i <= tol b for all i < k; else a Chebyshev filter of degree deg on [a, b],
+ *      a = theta_{m-1}, scaled at a0 = theta_0 (Zhou & Saad): e = (b - a) / 2, c = (b + a) / 2, sigma_1 = e / (a0 - c),
+ *      Y_1 = (sigma_1 / e) (A X - c X), sigma_{j+1} = 1 / (2 / sigma_1 - sigma_j),
+ *      Y_{j+1} = (2 sigma_{j+1} / e) (A Y_j - c Y_j) - sigma_j sigma_{j+1} Y_{j-1}: deg calls of sn_cheb_filter_step_f64 with
+ *      per-mesh scalars, then QR again.  A mesh that has converged is left alone (alpha = 0, beta = -1 hands X through).
+ *   6. Result: values theta_i and vectors phi = D x (phi^T diag(Am) phi = I).  Not converged: SN_EIG_NOT_CONVERGED.
+ *   The SN_EIG_* bits share the status word with the pencil's SN_DESC_* bits.
+ *
+ * sn_spectral_start_f64 : X[i, c] = (double)(h >> 11) * 2^-53 - 0.5, h = mix64(mix64(seed + G + r) + G + c) modulo 2^64, r the
+ *     row's number inside its mesh, G = 0x9E3779B97F4A7C15, mix64 the splitmix64 finaliser of the Mesh-MNIST maker: a fixed
+ *     function of (seed, row in mesh, column), so a mesh starts from the same block alone and in a batch.  X: (n, m) row-major.
+ *
+ * sn_cheb_filter_step_f64 : Z[i, c] = (alpha_b * ((sum_j A_ij Y[j, c]) - shift_b * Y[i, c])) - beta_b * X[i, c] for every row i
+ *     and column c < m, b the mesh of row i.  A: fp64 CSR (rowptr[n + 1], colind, vals; int32); X, Y, Z: (n, m) row-major fp64,
+ *     m >= 1 of any value (no alignment or width is assumed); alpha, beta, shift: [B] fp64 in DEVICE memory, so the steps of a
+ *     filter need no host synchronisation.  The row sum is serial over the stored entries in ascending position from +0.0, every
+ *     product and sum rounded on its own.  A X = the step with alpha = 1, beta = 0, shift = 0.  Z may BE X (every element of X
+ *     is read only by the thread that writes it); Z must not overlap Y, nor X in part: SN_E_SHAPE.  Lanes run over columns (a
+ *     gather of Y[j, :] is contiguous); one wave takes up to 256 columns of one row, or 64 / W rows when m <= W < 64.
+ *     A stored column outside 0..n-1 is passed over.  Does not synchronise; two runs are bit-identical.
+ *
+ * sn_wks_f64 : out[v, i] = (sum_k phi[v, k]^2 W[b, k, i]) / C[b, i], b the mesh of vertex v: phi (nV, k), W (B, k, N), C (B, N)
+ *     fp64 row-major; the square is formed on load, the sum is serial over ascending k from +0.0, the division is in the store.
+ *     out: (nV, N) fp64, or fp32 (out_f32 != 0: the quotient rounded once).  W and C are compute_wks:423-438 on the values:
+ *     E = sorted |values|, logE = log(max(E, 1e-6)), ee = linspace(logE[1], max(logE) / 1.02, N), sigma = 6 (ee[1] - ee[0]),
+ *     W_ki = exp(-(ee_i - logE_k)^2 / (2 sigma^2)), C_i = sum_k W_ki — a few kilobytes, made by the caller.
+ *
+ * All three: B < 1, m < 1, k < 1, N < 1 or a negative size: SN_E_SHAPE.  n or B past int32: SN_E_RANGE.
+ * ------------------------------------------------------------------------------------------ */
+#define SN_EIG_NOT_CONVERGED 256
+#define SN_EIG_CLIPPED_MASS  512
+int sn_spectral_start_f64(uint64_t seed, const int32_t *voff, int64_t B, int64_t n, int64_t m, double *X, void *stream);
+int sn_cheb_filter_step_f64(const int32_t *rowptr, const int32_t *colind, const double *vals, const int32_t *voff, int64_t B, int64_t n,
+                            int64_t m, const double *alpha, const double *beta, const double *shift, const double *X, const double *Y,
+                            double *Z, void *stream);
+int sn_wks_f64(const double *phi, const int32_t *voff, int64_t B, int64_t nV, int64_t k, int64_t N, const double *W, const double *Cn,
+               int32_t out_f32, void *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * ARAP deformation: as-rigid-as-possible sequences from a rest mesh and moving handles, on the device.

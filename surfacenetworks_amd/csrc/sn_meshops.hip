@@ -1500,13 +1500,15 @@ __device__ __forceinline__ float cot_entry(double x, int clamp, float hack, int 
   return v;
 }
 
-// L = M^-1 C by rows, the frame of laplacian_rows_k: neighbour lists in registers, hence its degree limit
-template <bool FILL>
+// L = M^-1 C by rows, the frame of laplacian_rows_k: neighbour lists in registers, hence its degree limit.  PENCIL: the same
+// sums left in fp64 and undivided, S = -C into vals64 and the mass into mass64 (sn_mesh_cot_pencil_f64)
+template <bool FILL, bool PENCIL = false>
 __global__ __launch_bounds__(kWG) void cot_laplacian_rows_k(const float *__restrict__ V, const int *__restrict__ F, int64_t nV,
                                                             const int *__restrict__ vptr, const int *__restrict__ inc, int voronoi,
                                                             int clamp, float hack, int *__restrict__ rowptr,
                                                             int *__restrict__ colind, float *__restrict__ vals,
-                                                            int *__restrict__ status) {
+                                                            int *__restrict__ status, double *__restrict__ vals64 = nullptr,
+                                                            double *__restrict__ mass64 = nullptr) {
   for (int64_t i = (int64_t)blockIdx.x * kWG + threadIdx.x; i < nV; i += (int64_t)gridDim.x * kWG) {
     const int b = vptr[i], e = vptr[i + 1];
     if (e - b > kMaxDeg) {
@@ -1545,12 +1547,17 @@ __global__ __launch_bounds__(kWG) void cot_laplacian_rows_k(const float *__restr
         S += C;
         if (dpos < 0 && kn > i) dpos = out++;            // the diagonal slot, filled below
         colind[out] = kn;
-        vals[out] = cot_entry(C / M, clamp, hack, &flags);
+        if constexpr (PENCIL) vals64[out] = 0 - C; else vals[out] = cot_entry(C / M, clamp, hack, &flags);
         ++out;
       }
       if (dpos < 0) dpos = out;
       colind[dpos] = (int)i;
-      vals[dpos] = cot_entry((0 - S) / M, clamp, hack, &flags);
+      if constexpr (PENCIL) {
+        vals64[dpos] = S;
+        mass64[i] = M;
+      } else {
+        vals[dpos] = cot_entry((0 - S) / M, clamp, hack, &flags);
+      }
       if (flags) atomicOr(status, flags);
     }
   }
@@ -1988,21 +1995,17 @@ int sn_mesh_descriptors_f32(const float *V, const int32_t *F, int64_t nV, int64_
 
 size_t sn_mesh_cot_laplacian_workspace_bytes(int64_t nV, int64_t nF) { return sn_mesh_descriptors_workspace_bytes(nV, nF); }
 
-int sn_mesh_cot_laplacian_f32(const float *V, const int32_t *F, int64_t nV, int64_t nF, int32_t phase, int32_t mass, int32_t clamp,
-                              double hack, int32_t *rowptr, int32_t *colind, float *vals, int32_t *status, void *workspace,
-                              size_t workspace_bytes, void *stream) {
-  (void)hipGetLastError();
-  if (nV < 0 || nF < 0 || (phase != 0 && phase != 1)) return SN_E_SHAPE;
-  if (mass != SN_DESC_MASS_BARYCENTRIC && mass != SN_DESC_MASS_VORONOI) return SN_E_SHAPE;
-  if (nV + 1 > INT_MAX || 3 * nF > INT_MAX) return SN_E_RANGE;
-  if (!rowptr || !status) return SN_E_NULL;
-  if ((nF > 0 || nV > 0) && (!V || (nF > 0 && !F))) return SN_E_NULL;
-  if (phase == 1 && nV > 0 && (!colind || !vals)) return SN_E_NULL;
-  if (workspace_bytes < sn_mesh_cot_laplacian_workspace_bytes(nV, nF) || !workspace) return SN_E_WORKSPACE;
+}  // extern "C"
+
+namespace {
+
+// both phases of sn_mesh_cot_laplacian_f32 (vals) and of sn_mesh_cot_pencil_f64 (vals64 and mass64) after their argument checks
+int cot_rows_phases(const float *V, const int32_t *F, int64_t nV, int64_t nF, int32_t phase, int voronoi, int32_t clamp, double hack,
+                    int32_t *rowptr, int32_t *colind, float *vals, double *vals64, double *mass64, int32_t *status, void *workspace,
+                    void *stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   const BucketWs b = MeshBucketWs(workspace, nV, nF).b;
   int *vptr = b.ptr, *inc = b.bucket;
-  const int voronoi = mass == SN_DESC_MASS_VORONOI;
   if (phase == 0) {
     hipError_t e = sn_internal_fill(vptr, 0, (size_t)(nV + 1) * sizeof(int), s);
     if (e != hipSuccess) return (int)e;
@@ -2018,11 +2021,45 @@ int sn_mesh_cot_laplacian_f32(const float *V, const int32_t *F, int64_t nV, int6
       hipLaunchKernelGGL((cot_laplacian_rows_k<false>), dim3(grid_for(nV)), dim3(kWG), 0, s, V, F, nV, vptr, inc, voronoi, 0, 0.f, rowptr,
                          (int *)nullptr, (float *)nullptr, status);
     scan_in_place(rowptr, nV + 1, b.sums, s);
+  } else if (nV > 0 && vals64) {
+    hipLaunchKernelGGL((cot_laplacian_rows_k<true, true>), dim3(grid_for(nV)), dim3(kWG), 0, s, V, F, nV, vptr, inc, voronoi, 0, 0.f,
+                       rowptr, colind, (float *)nullptr, status, vals64, mass64);
   } else if (nV > 0) {
     hipLaunchKernelGGL((cot_laplacian_rows_k<true>), dim3(grid_for(nV)), dim3(kWG), 0, s, V, F, nV, vptr, inc, voronoi, clamp != 0,
                        (float)hack, rowptr, colind, vals, status);
   }
   return launch_status();
+}
+
+}  // namespace
+
+extern "C" {
+
+int sn_mesh_cot_laplacian_f32(const float *V, const int32_t *F, int64_t nV, int64_t nF, int32_t phase, int32_t mass, int32_t clamp,
+                              double hack, int32_t *rowptr, int32_t *colind, float *vals, int32_t *status, void *workspace,
+                              size_t workspace_bytes, void *stream) {
+  (void)hipGetLastError();
+  if (nV < 0 || nF < 0 || (phase != 0 && phase != 1)) return SN_E_SHAPE;
+  if (mass != SN_DESC_MASS_BARYCENTRIC && mass != SN_DESC_MASS_VORONOI) return SN_E_SHAPE;
+  if (nV + 1 > INT_MAX || 3 * nF > INT_MAX) return SN_E_RANGE;
+  if (!rowptr || !status) return SN_E_NULL;
+  if ((nF > 0 || nV > 0) && (!V || (nF > 0 && !F))) return SN_E_NULL;
+  if (phase == 1 && nV > 0 && (!colind || !vals)) return SN_E_NULL;
+  if (workspace_bytes < sn_mesh_cot_laplacian_workspace_bytes(nV, nF) || !workspace) return SN_E_WORKSPACE;
+  return cot_rows_phases(V, F, nV, nF, phase, mass == SN_DESC_MASS_VORONOI, clamp, hack, rowptr, colind, vals, nullptr, nullptr, status,
+                         workspace, stream);
+}
+
+int sn_mesh_cot_pencil_f64(const float *V, const int32_t *F, int64_t nV, int64_t nF, int32_t phase, int32_t *rowptr, int32_t *colind,
+                           double *S, double *mass, int32_t *status, void *workspace, size_t workspace_bytes, void *stream) {
+  (void)hipGetLastError();
+  if (nV < 0 || nF < 0 || (phase != 0 && phase != 1)) return SN_E_SHAPE;
+  if (nV + 1 > INT_MAX || 3 * nF > INT_MAX) return SN_E_RANGE;
+  if (!rowptr || !status) return SN_E_NULL;
+  if ((nF > 0 || nV > 0) && (!V || (nF > 0 && !F))) return SN_E_NULL;
+  if (phase == 1 && nV > 0 && (!colind || !S || !mass)) return SN_E_NULL;
+  if (workspace_bytes < sn_mesh_cot_laplacian_workspace_bytes(nV, nF) || !workspace) return SN_E_WORKSPACE;
+  return cot_rows_phases(V, F, nV, nF, phase, 1, 0, 0.0, rowptr, colind, nullptr, S, mass, status, workspace, stream);
 }
 
 size_t sn_mesh_weld_workspace_bytes(int64_t nV) {

@@ -353,7 +353,8 @@ def faust_frame_from_mesh(V, F, label=None, device="cuda", symmetric=True, geode
     return frame
 
 
-def normal_frame_from_mesh(V, F, model="lap", uniform_mesh=True, hack=1, target="area", name=None, device="cuda", repair=False):
+def normal_frame_from_mesh(V, F, model="lap", uniform_mesh=True, hack=1, target="area", name=None, device="cuda", repair=False,
+                           inputs=("V",), wks_k=300):
     """The frame dict of the reference's normal-prediction sampler (src/normal_predict/sampler.py:21-91, read_npz) from a raw
     triangle mesh, built on the device: {'V' (nV, 3) fp32, 'F' (nF, 3) int64, 'input' (= V), 'target_dist' (nV, 3), 'name'} and
     'L' (model="lap") or 'Di', 'DiA' (model="dir") as SparseOperators.
@@ -366,14 +367,21 @@ def normal_frame_from_mesh(V, F, model="lap", uniform_mesh=True, hack=1, target=
     after a warnings.warn naming the reason.
     repair: True first runs operators.repair_mesh on the mesh as given (welding, duplicate faces, one winding per component:
     what keeps the target normals from cancelling) and builds the frame from its result; the frame gains 'repair', the
-    RepairedMesh with the maps back to the input.  Still missing of the reference's pipeline: principal curvatures, WKS inputs
-    and the edge flips that fix_degenerate.py applies to zero-area faces (repair only counts those)."""
+    RepairedMesh with the maps back to the input.
+    inputs: what 'input' holds, concatenated column-wise in the order given (train_4_normal.py:126's input table): "V" (3
+    columns, the default: 'input' is then V itself) and "wks" (100 columns: operators.wave_kernel_signature of the rescaled
+    mesh on the wks_k lowest eigenpairs, geom_utils.compute_wks; the reference uses 300).  With "wks" the frame gains
+    'eigenpairs', the operators.Eigenpairs behind it.  Still missing of the reference's pipeline: principal curvatures and the
+    edge flips that fix_degenerate.py applies to zero-area faces (repair only counts those)."""
     import warnings
 
     from .operators import dirac_operators_from_mesh, laplacian_operator_from_mesh, repair_mesh, vertex_normals
 
     if model not in ("lap", "dir"):
         raise ValueError(f'normal_frame_from_mesh: model must be "lap" or "dir", got {model!r}')
+    inputs = tuple(inputs)
+    if not inputs or any(i not in ("V", "wks") for i in inputs) or len(set(inputs)) != len(inputs):
+        raise ValueError(f'normal_frame_from_mesh: inputs is a sequence of distinct names out of "V" and "wks", got {inputs!r}')
     repaired = None
     if repair:
         Vt = V if torch.is_tensor(V) else torch.from_numpy(np.array(V, dtype=np.float32))
@@ -412,6 +420,14 @@ def normal_frame_from_mesh(V, F, model="lap", uniform_mesh=True, hack=1, target=
         if not bool(torch.isfinite(L.vals).all()):
             return refuse("non-finite Laplacian values")
         frame["L"] = L
+    if inputs != ("V",):
+        from .operators import laplacian_eigenpairs, wave_kernel_signature
+
+        cols = {"V": Vd}
+        if "wks" in inputs:
+            frame["eigenpairs"] = laplacian_eigenpairs(Vd, Fd, k=wks_k)
+            cols["wks"] = wave_kernel_signature(Vd, Fd, N=100, eigenpairs=frame["eigenpairs"])
+        frame["input"] = torch.cat([cols[i] for i in inputs], dim=1)
     return frame
 
 

@@ -1224,6 +1224,101 @@ def cot_laplacian_from_mesh(V, F, mass: str = "barycentric", hack=None):
     return rowptr, colind, vals, int(status.item())
 
 
+EIG_NOT_CONVERGED, EIG_CLIPPED_MASS = 256, 512        # SN_EIG_* status bits, next to the pencil's DESC_* bits in one word
+
+
+def cot_pencil_from_mesh(V, F):
+    """The cotangent pencil of one mesh (or a batch laid out as one disjoint mesh) in fp64, built on the device:
+    (rowptr, colind, S, mass, status) — S = -C in CSR with ascending columns, the diagonal and explicit zeros kept, symmetric bit
+    for bit; mass (nV,) the unrounded Voronoi mass; status a Python int (DESC_BAD_FACE / DESC_FLAT_FACE).
+    sn_mesh_cot_pencil_f64; host statement mesh_ops.cot_pencil.  Synchronises once (nnz and the status of phase 0).  When a
+    vertex has more than SN_LAP_MAX_DEGREE incident faces the status carries DESC_DEGREE, nothing further is launched and
+    colind, S and mass are None: there is no other path, the caller refuses."""
+    _dev(V, F)
+    _check_mesh("cot_pencil_from_mesh", V, F)
+    V, F = V.contiguous(), F.contiguous()
+    nV, nF = V.shape[0], F.shape[0]
+    dev = V.device
+    rowptr = torch.empty(nV + 1, dtype=torch.int32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ws_bytes = int(_lib.load().sn_mesh_cot_laplacian_workspace_bytes(nV, nF))      # the pencil shares the query
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    head = (_p(V), _p(F), nV, nF)
+    _lib.call("sn_mesh_cot_pencil_f64", *head, 0, _p(rowptr), None, None, None, status.data_ptr(), _p(ws), ws_bytes, _stream())
+    nnz, st = torch.cat([rowptr[-1:], status]).tolist()
+    if st & DESC_DEGREE:
+        return rowptr, None, None, None, st
+    colind = torch.empty(nnz, dtype=torch.int32, device=dev)
+    S = torch.empty(nnz, dtype=torch.float64, device=dev)
+    mass = torch.empty(nV, dtype=torch.float64, device=dev)
+    _lib.call("sn_mesh_cot_pencil_f64", *head, 1, _p(rowptr), _p(colind), _p(S), _p(mass), status.data_ptr(), _p(ws), ws_bytes,
+              _stream())
+    return rowptr, colind, S, mass, st
+
+
+def _check_voff(who: str, voff) -> int:
+    if voff.dtype != torch.int32 or voff.dim() != 1 or voff.numel() < 2 or not voff.is_contiguous():
+        raise TypeError(f"{who} wants voff (B + 1,) int32, contiguous")
+    return voff.numel() - 1
+
+
+def spectral_start(seed: int, voff, n: int, m: int):
+    """The (n, m) fp64 start block of the eigen-solver, a fixed function of (seed, row in its mesh, column)
+    (sn_spectral_start_f64; host statement mesh_ops.spectral_start).  voff (B + 1,) int32 on the device, voff[B] = n."""
+    _dev(voff)
+    B = _check_voff("spectral_start", voff)
+    if n < 0 or m < 1:
+        raise ValueError(f"spectral_start: n >= 0 and m >= 1 are required, got {n} and {m}")
+    X = torch.empty(n, m, dtype=torch.float64, device=voff.device)
+    _lib.call("sn_spectral_start_f64", int(seed) & ((1 << 64) - 1), _p(voff), B, n, m, _p(X), _stream())
+    return X
+
+
+def cheb_filter_step(rowptr, colind, vals, voff, alpha, beta, shift, X, Y, out=None):
+    """Z = alpha_b (A Y - shift_b Y) - beta_b X, one launch over a block-diagonal batch (sn_cheb_filter_step_f64; host statement
+    mesh_ops.cheb_filter_step): A fp64 CSR with int32 rowptr / colind, X and Y (n, m) fp64, alpha / beta / shift (B,) fp64 on
+    the device, b the mesh of a row through voff (B + 1,) int32.  out: where Z goes (a new tensor when None); it may be X, it
+    must not be Y (SnError, SN_E_SHAPE).  Does not synchronise; two runs are bit-identical."""
+    _dev(rowptr, colind, vals, voff, alpha, beta, shift, X, Y, out)
+    n = rowptr.numel() - 1
+    B = _check_voff("cheb_filter_step", voff)
+    _check_graph("cheb_filter_step", rowptr, colind, n)
+    Z = torch.empty_like(Y) if out is None else out
+    for name, t in (("X", X), ("Y", Y), ("out", Z)):
+        if t.dtype != torch.float64 or t.dim() != 2 or t.shape != Y.shape or not t.is_contiguous():
+            raise TypeError(f"cheb_filter_step wants {name} (n, m) float64, contiguous, all of one shape; got {tuple(t.shape)} {t.dtype}")
+    if Y.shape[0] != n or Y.shape[1] < 1:
+        raise ValueError(f"cheb_filter_step: the matrix has {n} rows, the blocks are {tuple(Y.shape)}")
+    if vals.dtype != torch.float64 or vals.shape != colind.shape or not vals.is_contiguous():
+        raise TypeError("cheb_filter_step wants vals (nnz,) float64, contiguous")
+    for name, t in (("alpha", alpha), ("beta", beta), ("shift", shift)):
+        if t.dtype != torch.float64 or t.shape != (B,) or not t.is_contiguous():
+            raise TypeError(f"cheb_filter_step wants {name} (B,) = ({B},) float64, contiguous")
+    _lib.call("sn_cheb_filter_step_f64", _p(rowptr), _p(colind), _p(vals), _p(voff), B, n, Y.shape[1], _p(alpha), _p(beta), _p(shift),
+              _p(X), _p(Y), _p(Z), _stream())
+    return Z
+
+
+def wks_contract(phi, voff, W, C, dtype=torch.float32):
+    """WKS[v, i] = (sum_k phi[v, k]^2 W[b, k, i]) / C[b, i] (sn_wks_f64; host statement mesh_ops.wks_contract): phi (nV, k),
+    W (B, k, N), C (B, N) fp64 on the device, b the mesh of vertex v through voff (B + 1,) int32.  Returns (nV, N) in dtype
+    (torch.float32: the quotient rounded once, or torch.float64).  Does not synchronise; two runs are bit-identical."""
+    _dev(phi, voff, W, C)
+    nV = phi.shape[0]
+    B = _check_voff("wks_contract", voff)
+    if dtype not in (torch.float32, torch.float64):
+        raise TypeError("wks_contract returns torch.float32 or torch.float64")
+    if phi.dtype != torch.float64 or phi.dim() != 2 or W.dtype != torch.float64 or W.dim() != 3 or C.dtype != torch.float64:
+        raise TypeError("wks_contract wants phi (nV, k), W (B, k, N) and C (B, N) float64")
+    k, N = phi.shape[1], W.shape[2]
+    if W.shape != (B, k, N) or C.shape != (B, N) or k < 1 or N < 1:
+        raise ValueError(f"wks_contract: phi {tuple(phi.shape)}, W {tuple(W.shape)} and C {tuple(C.shape)} do not fit {B} meshes")
+    phi, W, C = phi.contiguous(), W.contiguous(), C.contiguous()
+    out = torch.empty(nV, N, dtype=dtype, device=phi.device)
+    _lib.call("sn_wks_f64", _p(phi), _p(voff), B, nV, k, N, _p(W), _p(C), int(dtype == torch.float32), _p(out), _stream())
+    return out
+
+
 def _check_graph(who: str, rowptr, colind, n: int) -> None:
     if rowptr.dtype != torch.int32 or colind.dtype != torch.int32:
         raise TypeError(f"{who} wants int32 rowptr and colind")

@@ -20,6 +20,7 @@ Also here: the synthetic mesh generators SURVEY.md §8(d) prescribes for the ben
 from __future__ import annotations
 
 import collections
+import warnings
 
 import numpy as np
 import scipy.sparse as sp
@@ -42,6 +43,9 @@ __all__ = [
     "arap_weights", "arap_covariances", "arap_rotation_from_covariance", "arap_rotations", "arap_rhs", "arap_energy", "arap_cg",
     "arap_deform", "arap_handle_motion", "ArapWeights", "ArapSolve", "ArapResult", "ARAP_NOT_CONVERGED", "ARAP_BREAKDOWN",
     "ARAP_DEGENERATE", "ARAP_BAD_FACE", "ARAP_DEGREE", "ARAP_TOO_LARGE", "ARAP_REDUCE_WIDTH", "ARAP_JACOBI_SWEEPS", "ARAP_RANK_EPS", "ARAP_MAX_CG",
+    "cot_pencil", "spectral_start", "cheb_filter_step", "cheb_filter_scalars", "eig_normalised_mass", "eig_guard",
+    "laplacian_eigenpairs", "wks_weights", "wks_contract", "wave_kernel_signature", "Eigenpairs", "EIG_NOT_CONVERGED",
+    "EIG_CLIPPED_MASS", "EIG_MASS_FLOOR",
 ]
 
 _PERMS = np.array([[0, 1, 2], [0, 2, 1], [1, 0, 2], [1, 2, 0], [2, 0, 1], [2, 1, 0]])  # itertools.permutations order
@@ -1567,3 +1571,197 @@ def arap_handle_motion(V0, frames: int, rng: np.random.Generator):
         H[t, : held.size] = V[held]
         H[t, held.size:] = c + (V[moved] - c) @ Rm.T + vel * t
     return handles[order].astype(np.int32), H[:, order].astype(np.float32)
+
+
+# --------------------------------------------------------------------------------------------------
+# spectral: the cotangent pencil in fp64, Chebyshev-filtered subspace iteration for its lowest eigenpairs, and the wave kernel
+# signature (definition: include/sn_spmm.h, "Spectral").  The host statement of geom_utils.compute_wks without its shift-invert
+# eigsh: the same steps and parameters as operators.laplacian_eigenpairs, the three kernels' arithmetic bit for bit (elementwise
+# ufuncs, products and sums rounded one by one), the dense steps through numpy's LAPACK where the device uses torch's.
+# --------------------------------------------------------------------------------------------------
+EIG_NOT_CONVERGED, EIG_CLIPPED_MASS = 256, 512        # SN_EIG_* status bits: they share a word with the pencil's DESC_* bits
+EIG_MASS_FLOOR = 1e-8                                  # compute_wks clips the Voronoi mass here before normalising it
+
+Eigenpairs = collections.namedtuple("Eigenpairs", "values vectors residuals bound outer_iterations mass status")
+
+
+def eig_guard(k: int) -> int:
+    """The default number of guard vectors next to the k wanted ones."""
+    return max(16, int(k) // 8)
+
+
+def cot_pencil(V: np.ndarray, F: np.ndarray):
+    """(S, mass, status): the symmetric cotangent stiffness matrix S = -C of libigl_laplacian's C as fp64 scipy CSR (every
+    neighbour plus the diagonal, columns ascending, exact zeros kept: S_vj = 0 - C_vj, S_vv = sum_j C_vj over ascending j from
+    +0.0), the unrounded fp64 M_voronoi (nV,), and the DESC_BAD_FACE / DESC_FLAT_FACE status word (sn_mesh_cot_pencil_f64).
+    C_vj and C_jv sum the same corners in the same order, so S equals its transpose bit for bit."""
+    s = descriptor_sums(V, F)
+    nV = s["M_voronoi"].shape[0]
+    v, a, b = s["corner_v"], s["corner_a"], s["corner_b"]
+    rows = np.stack([v, v], axis=1).ravel()
+    cols = np.stack([a, b], axis=1).ravel()
+    cw = np.stack([0.5 * s["corner_cot_b"], 0.5 * s["corner_cot_a"]], axis=1).ravel()
+    keys, inv = np.unique(rows * max(nV, 1) + cols, return_inverse=True)          # ascending (row, col)
+    krow, kcol = keys // max(nV, 1), keys % max(nV, 1)
+    Cv = np.zeros(keys.size)
+    D = np.zeros(nV)
+    with np.errstate(all="ignore"):
+        np.add.at(Cv, inv.ravel(), cw)                                             # face order inside every entry
+        np.add.at(D, krow, Cv)                                                     # j ascending inside every row
+        vals = np.concatenate([0 - Cv, D])
+    r = np.concatenate([krow, np.arange(nV)])
+    c = np.concatenate([kcol, np.arange(nV)])
+    o = np.lexsort((c, r))
+    status = (0 if s["good"].all() else DESC_BAD_FACE) | (DESC_FLAT_FACE if (s["good"] & ~s["valid"]).any() else 0)
+    rowptr = np.zeros(nV + 1, dtype=np.int32)
+    np.cumsum(np.bincount(r, minlength=nV), out=rowptr[1:])
+    return sp.csr_matrix((vals[o], c[o].astype(np.int32), rowptr), shape=(nV, nV)), s["M_voronoi"].copy(), status
+
+
+def _mix64_array(z: np.ndarray) -> np.ndarray:
+    """_mix64 on a uint64 array (the arithmetic wraps modulo 2^64)."""
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def spectral_start(seed: int, voff, m: int) -> np.ndarray:
+    """The start block (n, m) fp64 of the eigen-solver, a fixed function of (seed, row in its mesh, column)
+    (sn_spectral_start_f64): h = mix64(mix64(seed + G + row) + G + column) modulo 2^64, G = 0x9E3779B97F4A7C15, and
+    x = (h >> 11) 2^-53 - 0.5.  voff (B + 1,): the first row of every mesh."""
+    voff = np.asarray(voff, dtype=np.int64)
+    n = int(voff[-1])
+    row = np.arange(n, dtype=np.int64) - np.repeat(voff[:-1], np.diff(voff))
+    g = np.uint64(_GOLDEN)
+    with np.errstate(over="ignore"):
+        h = _mix64_array(np.uint64(int(seed) & _M64) + g + row.astype(np.uint64))
+        h = _mix64_array(h[:, None] + g + np.arange(m, dtype=np.uint64)[None, :])
+    return (h >> np.uint64(11)).astype(np.float64) * 2.0 ** -53 - 0.5
+
+
+def cheb_filter_step(rowptr, colind, vals, voff, alpha, beta, shift, X, Y) -> np.ndarray:
+    """Z[i, c] = (alpha_b ((sum_j A_ij Y[j, c]) - shift_b Y[i, c])) - beta_b X[i, c], b the mesh of row i (sn_cheb_filter_step_f64):
+    the row sum runs over the stored entries in ascending position from +0.0, every product and sum rounded on its own."""
+    rowptr = np.asarray(rowptr, dtype=np.int64)
+    colind = np.asarray(colind, dtype=np.int64)
+    vals = np.asarray(vals, dtype=np.float64)
+    voff = np.asarray(voff, dtype=np.int64)
+    X, Y = np.asarray(X, dtype=np.float64), np.asarray(Y, dtype=np.float64)
+    n = rowptr.size - 1
+    cnt = np.diff(rowptr)
+    acc = np.zeros((n, Y.shape[1]))
+    with np.errstate(all="ignore"):
+        for t in range(int(cnt.max()) if n else 0):
+            rows = np.nonzero(cnt > t)[0]
+            at = rowptr[rows] + t
+            acc[rows] = acc[rows] + vals[at][:, None] * Y[colind[at]]
+        per_row = lambda x: np.repeat(np.asarray(x, dtype=np.float64), np.diff(voff))[:, None]
+        return per_row(alpha) * (acc - per_row(shift) * Y) - per_row(beta) * X
+
+
+def eig_normalised_mass(mass, voff):
+    """(Am, clipped): compute_wks lines 415-416 per mesh — max(mass, 1e-8) divided by its sum (np.sum) over the mesh."""
+    mass = np.asarray(mass, dtype=np.float64)
+    Am = np.maximum(mass, EIG_MASS_FLOOR)
+    clipped = bool((~(mass >= EIG_MASS_FLOOR)).any())
+    for b in range(len(voff) - 1):
+        Am[voff[b]:voff[b + 1]] /= np.sum(Am[voff[b]:voff[b + 1]])
+    return Am, clipped
+
+
+def cheb_filter_scalars(theta0: float, theta_last: float, bound: float, deg: int):
+    """(alpha, beta, shift) of the deg steps of Zhou & Saad's scaled Chebyshev filter on [a, b] = [theta_last, bound], scaled at
+    a0 = theta0: e = (b - a) / 2, c = (b + a) / 2, sigma_1 = e / (a0 - c), step 1 has alpha = sigma_1 / e and beta = 0, step
+    j + 1 has sigma_{j+1} = 1 / (2 / sigma_1 - sigma_j), alpha = 2 sigma_{j+1} / e, beta = sigma_j sigma_{j+1}; shift = c."""
+    e = (bound - theta_last) / 2
+    c = (bound + theta_last) / 2
+    sigma1 = e / (theta0 - c)
+    alpha, beta = [sigma1 / e], [0.0]
+    sigma = sigma1
+    for _ in range(1, deg):
+        nxt = 1 / (2 / sigma1 - sigma)
+        alpha.append(2 * nxt / e)
+        beta.append(sigma * nxt)
+        sigma = nxt
+    return np.array(alpha), np.array(beta), np.full(deg, c)
+
+
+def laplacian_eigenpairs(V, F, k: int = 300, guard: int = None, deg: int = 24, tol: float = 1e-10, max_outer: int = 40,
+                         seed: int = 0) -> Eigenpairs:
+    """The k lowest eigenpairs S phi = lambda diag(Am) phi of one mesh's cotangent pencil by Chebyshev-filtered subspace
+    iteration: the numpy statement of operators.laplacian_eigenpairs (include/sn_spmm.h, "Spectral", has the steps).
+    Eigenpairs(values (k,) ascending, vectors (nV, k) with phi^T diag(Am) phi = I, residuals (k,) of the standard form
+    A = D S D, D = Am^-1/2, bound = its Gershgorin bound, outer_iterations, mass = Am, status = DESC_* | EIG_* bits); EIG_NOT_CONVERGED comes with a RuntimeWarning, as on the device."""
+    S, mass, status = cot_pencil(V, F)
+    n = S.shape[0]
+    k = int(k)
+    if k < 1 or k > n:
+        raise ValueError(f"laplacian_eigenpairs: k must lie in 1..{n} (the vertices of the mesh), got {k}")
+    voff = np.array([0, n])
+    Am, clipped = eig_normalised_mass(mass, voff)
+    if clipped:
+        status |= EIG_CLIPPED_MASS
+    d = 1 / np.sqrt(Am)
+    rowptr, colind = S.indptr, S.indices
+    rows = np.repeat(np.arange(n), np.diff(rowptr))
+    A = (d[rows] * S.data) * d[colind]
+    absrow = np.zeros(n)
+    np.add.at(absrow, rows, np.abs(A))
+    bound = float(absrow.max())
+    m = min(n, k + (eig_guard(k) if guard is None else int(guard)))
+    one, zero = np.ones(1), np.zeros(1)
+    matvec = lambda Y: cheb_filter_step(rowptr, colind, A, voff, one, zero, zero, Y, Y)
+    X = np.linalg.qr(spectral_start(seed, voff, m))[0]
+    outer = 0
+    while True:
+        outer += 1
+        AX = matvec(X)
+        H = X.T @ AX
+        theta, Q = np.linalg.eigh((H + H.T) / 2)
+        X, AX = X @ Q, AX @ Q
+        res = np.sqrt(((AX - X * theta) ** 2).sum(axis=0))
+        if (res[:k] <= tol * bound).all():
+            break
+        if outer == max_outer:
+            status |= EIG_NOT_CONVERGED
+            warnings.warn(f"laplacian_eigenpairs: the mesh did not reach tol = {tol:g} within max_outer = {max_outer} outer iterations",
+                          RuntimeWarning, stacklevel=2)
+            break
+        alpha, beta, shift = cheb_filter_scalars(theta[0], theta[m - 1], bound, deg)
+        T = X
+        for j in range(deg):            # two buffers: Z takes the place of the older block
+            X, T = cheb_filter_step(rowptr, colind, A, voff, alpha[j:j + 1], beta[j:j + 1], shift[j:j + 1], T, X), X
+        X = np.linalg.qr(X)[0]
+    return Eigenpairs(theta[:k].copy(), d[:, None] * X[:, :k], res[:k].copy(), bound, outer, Am, status)
+
+
+def wks_weights(values, N: int = 100):
+    """(W (k, N), C (N,)) of compute_wks lines 423-438 for one mesh: E = sorted |values|, logE = log(max(E, 1e-6)),
+    ee = linspace(logE[1], max(logE) / 1.02, N), sigma = 6 (ee[1] - ee[0]), W_ki = exp(-(ee_i - logE_k)^2 / (2 sigma^2)),
+    C_i = sum_k W_ki."""
+    E = np.sort(np.abs(np.asarray(values, dtype=np.float64)))
+    if N < 2 or E.size < 2:
+        raise ValueError(f"wave_kernel_signature: N >= 2 and k >= 2 are required, got N = {N} and k = {E.size}")
+    logE = np.log(np.clip(E, 1e-6, np.inf))
+    ee = np.linspace(logE[1], max(logE) / 1.02, N)
+    sigma = (ee[1] - ee[0]) * 6
+    W = np.exp((-(ee[None, :] - logE[:, None]) ** 2) / (2 * sigma ** 2))
+    return W, np.sum(W, axis=0)
+
+
+def wks_contract(phi, W, C) -> np.ndarray:
+    """WKS[v, i] = (sum_k phi_vk^2 W_ki) / C_i, the sum serial over ascending k from +0.0 (sn_wks_f64), fp64."""
+    phi, W = np.asarray(phi, dtype=np.float64), np.asarray(W, dtype=np.float64)
+    acc = np.zeros((phi.shape[0], W.shape[1]))
+    for j in range(W.shape[0]):
+        acc = acc + (phi[:, j] * phi[:, j])[:, None] * W[j][None, :]
+    return acc / np.asarray(C, dtype=np.float64)[None, :]
+
+
+def wave_kernel_signature(V, F, N: int = 100, k: int = 300, eigenpairs: Eigenpairs = None, dtype=np.float32) -> np.ndarray:
+    """(nV, N) wave kernel signature of one mesh, geom_utils.compute_wks line for line on the eigenpairs of
+    laplacian_eigenpairs(V, F, k) (or the ones given): the numpy statement of operators.wave_kernel_signature."""
+    ep = eigenpairs if eigenpairs is not None else laplacian_eigenpairs(V, F, k)
+    W, C = wks_weights(ep.values, N)
+    order = np.argsort(np.abs(ep.values), kind="stable")
+    return wks_contract(ep.vectors[:, order], W, C).astype(dtype)

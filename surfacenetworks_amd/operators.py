@@ -30,7 +30,8 @@ from . import kernels
 __all__ = ["SparseOperator", "OperatorPool", "PackedSegments", "as_operator", "dirac_operators_from_mesh",
            "laplacian_operator_from_mesh", "geodesic_matrix_from_mesh", "spgemm", "amplify_sequence_operators",
            "clean_mesh", "CleanMesh", "repair_mesh", "RepairedMesh", "vertex_descriptors", "MeshDescriptors", "vertex_normals", "face_areas", "vertex_mass",
-           "gaussian_curvature", "delaunay_2d", "Delaunay2D", "arap_deform", "ArapDeformation"]
+           "gaussian_curvature", "delaunay_2d", "Delaunay2D", "arap_deform", "ArapDeformation", "laplacian_eigenpairs", "Eigenpairs",
+           "wave_kernel_signature"]
 
 # A BSR4 copy is kept when zero-fill costs at most this much extra storage over CSR entries.
 _BSR4_MAX_FILL = 1.6
@@ -1232,3 +1233,168 @@ def arap_deform(V0, F, handles, H, iters: int = 2, tol: float = 1e-10, max_cg: i
     if single:
         return ArapDeformation(frames[0], out.cg_iters[0], out.energy[0], status[0])
     return ArapDeformation(frames, out.cg_iters, out.energy, status)
+
+
+@dataclasses.dataclass
+class Eigenpairs:
+    """What operators.laplacian_eigenpairs returns: fp64 device tensors over the B meshes of the call.  values (B, k) ascending;
+    vectors (n, k) with phi^T diag(mass) phi = I inside every mesh, n the rows of the whole batch; residuals (B, k) of the
+    standard form A = D S D; bound (B,) its Gershgorin bound b; outer_iterations (B,) int64; mass (n,) = Am, the clipped and
+    normalised Voronoi mass; voff (B + 1,) int32, the first row of every mesh; status a Python int of kernels.DESC_* and
+    kernels.EIG_* bits (of the whole batch)."""
+    values: torch.Tensor
+    vectors: torch.Tensor
+    residuals: torch.Tensor
+    bound: torch.Tensor
+    outer_iterations: torch.Tensor
+    mass: torch.Tensor
+    voff: torch.Tensor
+    status: int
+
+
+# The m x m eigh of the Rayleigh-Ritz step: torch.linalg.eigh in fp64 on the device (LABNOTES.md#spectral says what was measured);
+# True moves that one factorisation, at most about 1 MB per outer iteration, to the host.
+_EIGH_ON_HOST = False
+
+
+def _sym_eigh(H: torch.Tensor):
+    if _EIGH_ON_HOST:
+        w, Q = np.linalg.eigh(H.cpu().numpy())
+        return torch.from_numpy(w).to(H.device), torch.from_numpy(Q).to(H.device)
+    return torch.linalg.eigh(H)
+
+
+def _spectral_layout(who: str, V, F, sizes):
+    """(Vg, Fg, B, voff as a list): a single mesh, a batch through _offset_batch, or a ragged batch given as one disjoint mesh
+    with the vertex counts of its parts."""
+    if not torch.is_tensor(V) or not torch.is_tensor(F) or not V.is_cuda or not F.is_cuda:
+        raise ValueError(f"{who} wants V and F as device tensors (there is no host path in this package; mesh_ops has the statement)")
+    if sizes is None:
+        Vg, Fg, B, nV, _ = _offset_batch(who, V, F)
+        return Vg, Fg, B, [b * nV for b in range(B + 1)]
+    sizes = [int(x) for x in sizes]
+    if V.dim() != 2 or V.shape[1] != 3 or F.dim() != 2 or F.shape[1] != 3 or not sizes or min(sizes) < 0 or sum(sizes) != V.shape[0]:
+        raise ValueError(f"{who}: with sizes, V (n, 3) and F (nF, 3) hold the meshes as one disjoint mesh and the sizes add up to n; "
+                         f"got {tuple(V.shape)}, {tuple(F.shape)} and {sizes}")
+    return V.float(), F.to(torch.int32), len(sizes), [0] + [int(x) for x in np.cumsum(sizes)]
+
+
+def laplacian_eigenpairs(V, F, k: int = 300, guard: Optional[int] = None, deg: int = 24, tol: float = 1e-10, max_outer: int = 40,
+                         seed: int = 0, sizes: Optional[Sequence[int]] = None) -> Eigenpairs:
+    """The k lowest eigenpairs S phi = lambda diag(Am) phi of the cotangent pencil of every mesh, on the device: what
+    geom_utils.compute_wks takes from scipy's shift-invert eigsh(-L, M=Am, sigma=-1e-5, k=300), and the basis of any spectral
+    descriptor.  Chebyshev-filtered subspace iteration (Zhou & Saad's scaled filter) on the standard form A = D S D,
+    D = Am^-1/2: include/sn_spmm.h ("Spectral") has the steps, mesh_ops.laplacian_eigenpairs the numpy statement with the same
+    steps and parameters.  The pencil (kernels.cot_pencil_from_mesh), the start block and every product with A
+    (kernels.cheb_filter_step: deg launches per filter, per-mesh scalars read on the device) are this package's kernels; QR,
+    X^T A X, eigh and the rotations are torch's fp64 linear algebra, mesh by mesh.
+    V (nV, 3) and F (nF, 3); a batch V (B, nV, 3) with F shared or (B, nF, 3); or, with sizes, a ragged batch laid out as one
+    disjoint mesh whose parts have these vertex counts.  Am = max(M_voronoi, 1e-8) normalised to sum 1 per mesh.
+    m = min(smallest mesh, k + guard) columns, guard = max(16, k // 8) by default.  Converged when every residual
+    |A x_i - theta_i x_i| <= tol b, i < k, b the Gershgorin bound; a warning and EIG_NOT_CONVERGED after max_outer iterations.
+    ValueError for k < 1, k above the vertices of the smallest mesh, a non-tensor or host tensor, a vertex with more incident
+    faces than SN_LAP_MAX_DEGREE.  Synchronises once per outer iteration (the convergence test)."""
+    who = "laplacian_eigenpairs"
+    Vg, Fg, B, voff_h = _spectral_layout(who, V, F, sizes)
+    n = voff_h[-1]
+    smallest = min(voff_h[b + 1] - voff_h[b] for b in range(B))
+    k = int(k)
+    if k < 1 or k > smallest:
+        raise ValueError(f"{who}: k must lie in 1..{smallest} (the vertices of the smallest mesh), got {k}")
+    if deg < 1 or max_outer < 1:
+        raise ValueError(f"{who}: deg >= 1 and max_outer >= 1 are required, got {deg} and {max_outer}")
+    from . import mesh_ops
+
+    dev = Vg.device
+    rowptr, colind, S, mass, status = kernels.cot_pencil_from_mesh(Vg, Fg)
+    if status & kernels.DESC_DEGREE:
+        raise ValueError(f"{who}: a vertex has more incident faces than SN_LAP_MAX_DEGREE (status SN_DESC_DEGREE)")
+    parts = [slice(voff_h[b], voff_h[b + 1]) for b in range(B)]
+    voff = torch.tensor(voff_h, dtype=torch.int32, device=dev)
+    Am = mass.clamp_min(mesh_ops.EIG_MASS_FLOOR)
+    clipped = (~(mass >= mesh_ops.EIG_MASS_FLOOR)).any()
+    for p in parts:
+        Am[p] /= Am[p].sum()
+    d = 1 / torch.sqrt(Am)
+    rows = torch.repeat_interleave(torch.arange(n, device=dev), (rowptr[1:] - rowptr[:-1]).long())
+    A = (d[rows] * S) * d[colind.long()]
+    one = torch.ones(B, dtype=torch.float64, device=dev)
+    zero = torch.zeros(B, dtype=torch.float64, device=dev)
+    ones = torch.ones(n, 1, dtype=torch.float64, device=dev)
+    absrow = kernels.cheb_filter_step(rowptr, colind, A.abs(), voff, one, zero, zero, ones, ones)      # row sums in stored order
+    bound = torch.stack([absrow[p].max() for p in parts])
+    bound_h, clipped = bound.tolist(), bool(clipped)
+    if clipped:
+        status |= kernels.EIG_CLIPPED_MASS
+    m = min(smallest, k + (mesh_ops.eig_guard(k) if guard is None else int(guard)))
+    X = kernels.spectral_start(seed, voff, n, m)
+    for p in parts:
+        X[p] = torch.linalg.qr(X[p])[0]
+    AX, T = torch.empty_like(X), torch.empty_like(X)
+    theta = torch.zeros(B, m, dtype=torch.float64, device=dev)
+    res = torch.zeros(B, k, dtype=torch.float64, device=dev)
+    active, outer = [True] * B, [0] * B
+    for it in range(1, max_outer + 1):
+        kernels.cheb_filter_step(rowptr, colind, A, voff, one, zero, zero, X, X, out=AX)
+        for b, p in enumerate(parts):
+            if active[b]:
+                H = X[p].T @ AX[p]
+                theta[b], Q = _sym_eigh((H + H.T) / 2)
+                X[p], AX[p] = X[p] @ Q, AX[p] @ Q
+                res[b] = (AX[p] - X[p] * theta[b]).square().sum(dim=0).sqrt()[:k]
+        theta_h, res_h = theta.tolist(), res.tolist()
+        for b in range(B):
+            if active[b]:
+                outer[b] = it
+                active[b] = not all(r <= tol * bound_h[b] for r in res_h[b])
+        if not any(active):
+            break
+        if it == max_outer:
+            status |= kernels.EIG_NOT_CONVERGED
+            warnings.warn(f"{who}: a mesh did not reach tol = {tol:g} within max_outer = {max_outer} outer iterations", RuntimeWarning,
+                          stacklevel=2)
+            break
+        # a converged mesh is handed through: Z = 0 (...) + X
+        sc = [mesh_ops.cheb_filter_scalars(theta_h[b][0], theta_h[b][m - 1], bound_h[b], deg) if active[b]
+              else (np.zeros(deg), np.full(deg, -1.0), np.zeros(deg)) for b in range(B)]
+        alpha, beta, shift = (torch.from_numpy(np.stack([s[j] for s in sc], axis=1)).to(dev) for j in range(3))      # (deg, B) each
+        old, cur = X, X                       # two buffers: Z takes the place of the older block
+        for j in range(deg):
+            kernels.cheb_filter_step(rowptr, colind, A, voff, alpha[j], beta[j], shift[j], old, cur, out=T if j == 0 else old)
+            old, cur = (cur, T) if j == 0 else (cur, old)
+        if cur is not X:
+            X, T = T, X
+        for b, p in enumerate(parts):
+            if active[b]:
+                X[p] = torch.linalg.qr(X[p])[0]
+    return Eigenpairs(theta[:, :k].contiguous(), (d[:, None] * X[:, :k]).contiguous(), res, bound,
+                      torch.tensor(outer, device=dev), Am, voff, status)
+
+
+def wave_kernel_signature(V, F, N: int = 100, k: int = 300, eigenpairs: Optional[Eigenpairs] = None, dtype=torch.float32,
+                          sizes: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """(nV, N) wave kernel signature on the device, geom_utils.compute_wks line for line (the 'wks': 100 input channels of the
+    reference's normal prediction): E = sorted |values|, logE = log(max(E, 1e-6)), ee = linspace(logE[1], max(logE) / 1.02, N),
+    sigma = 6 (ee[1] - ee[0]), W_ki = exp(-(ee_i - logE_k)^2 / (2 sigma^2)), WKS[v, i] = (sum_k phi_vk^2 W_ki) / sum_k W_ki.
+    The eigenpairs are laplacian_eigenpairs(V, F, k, sizes=sizes) unless given; W and C (a few kilobytes) are torch
+    expressions, the nV x k x N contraction is kernels.wks_contract.  Host statement: mesh_ops.wave_kernel_signature.
+    dtype: torch.float32 (default) or torch.float64.  A batch (B, nV, 3) keeps its leading axis: (B, nV, N).  N >= 2, k >= 2."""
+    who = "wave_kernel_signature"
+    if N < 2 or (eigenpairs is None and k < 2) or (eigenpairs is not None and eigenpairs.values.shape[1] < 2):
+        raise ValueError(f"{who}: N >= 2 and k >= 2 are required")
+    ep = eigenpairs if eigenpairs is not None else laplacian_eigenpairs(V, F, k, sizes=sizes)
+    B, kk = ep.values.shape
+    E, order = ep.values.abs().sort(dim=1, stable=True)
+    logE = torch.log(E.clamp_min(1e-6))
+    start, stop = logE[:, 1], logE.max(dim=1).values / 1.02
+    step = (stop - start) / (N - 1)                                                                       # numpy's linspace
+    ee = torch.arange(N, dtype=torch.float64, device=E.device)[None, :] * step[:, None] + start[:, None]
+    ee[:, -1] = stop
+    sigma = (ee[:, 1] - ee[:, 0]) * 6
+    W = torch.exp((-(ee[:, None, :] - logE[:, :, None]) ** 2) / (2 * sigma ** 2)[:, None, None])
+    C = W.sum(dim=1)
+    counts = (ep.voff[1:] - ep.voff[:-1]).long()
+    seg = torch.repeat_interleave(torch.arange(B, device=E.device), counts)
+    phi = ep.vectors.gather(1, order[seg])
+    out = kernels.wks_contract(phi, ep.voff, W, C, dtype)
+    return out.view(V.shape[0], V.shape[1], N) if torch.is_tensor(V) and V.dim() == 3 else out
