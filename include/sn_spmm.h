@@ -1273,6 +1273,73 @@ int sn_mesh_cot_pencil_f64(const float *V, const int32_t *F, int64_t nV, int64_t
                            double *S, double *mass, int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Principal curvatures: k1 >= k2 and their directions from a quadric fitted over the k-ring patch of every vertex.
+ *
+ * Replaces: igl.principal_curvature in compute_curv4 src/utils/geom_utils.py:390-405 (an un-vendored pyigl fork, on the host, one
+ *           mesh at a time), the 'curv4': 4 input of src/normal_predict/train_4_normal.py:126.
+ * This is this project's own definition in libigl's conventions (igl::principal_curvature with its defaults: k-ring patch,
+ * projection-plane check, averaged normal, quadric z = a x^2 + b x y + c y^2 + d x + e y), not its bits: no igl was at hand to
+ * compare with, so nothing here claims agreement with it beyond the conventions.  Host statement: mesh_ops.principal_curvatures.
+ *
+ * Arithmetic.  As "Mesh descriptors": P = the fp32 coordinates widened to fp64, every product and sum rounded on its own, (x + y) + z,
+ *   u.w = (u_x w_x + u_y w_y) + u_z w_z, u x w as there, sums from +0.0; outputs rounded to fp32 at the end.  Only + - * / sqrt and
+ *   comparisons occur, so the device equals the host statement bit for bit.  A vertex takes the first failure it meets in the
+ *   order of this text, gets that one bit, and stops.
+ * Vertex normals.  n_x = N_area / sqrt(N_area.N_area) of "Mesh descriptors" in fp64, before its rounding; (0, 0, 0) where that
+ *   length is not > 0.  Computed once per vertex into the workspace.
+ * Ring.  Two vertices are neighbours when a face that is not BAD holds both (a FLAT face still connects).  S_0 = {v}, S_(i+1) = S_i
+ *   and the neighbours of its members, S = S_radius, radius >= 1.  More than SN_CURV_MAX_RING members: SN_CURV_OVERFLOW, and
+ *   ring_size = SN_CURV_MAX_RING + 1.
+ * Projection-plane check.  n_v = (0, 0, 0): SN_CURV_NO_NORMAL (an isolated vertex, or one with flat faces only).
+ *   S' = {x in S : n_x.n_v > 0}; if SN_CURV_MIN_POINTS <= |S'| < |S| then S = S'.  ring_size = |S|.  |S| < SN_CURV_MIN_POINTS:
+ *   SN_CURV_FEW_POINTS.
+ * Order.  S is a set.  Every sum below runs over its members in ascending vertex id; the order in which the search found them
+ *   reaches no arithmetic.
+ * Fit normal.  m = sum n_x, then divided componentwise by l = sqrt(m.m).  l not > 0: SN_CURV_DEGENERATE (all four causes share
+ *   the bit; they are tested in this order: l, the frame, h, the pivots).
+ * Frame.  For a neighbour a of v (a member of S_1 other than v, whether or not the check kept it): c = P_a - P_v,
+ *   t = c - (c.m) m componentwise (c_x - (c.m) m_x).  The a of smallest id with sqrt(t.t) > 0 is taken: e1 = t / sqrt(t.t),
+ *   e2 = m x e1.  None: SN_CURV_DEGENERATE.
+ * Local coordinates.  c = P_x - P_v for x in S (v included, a zero row).  h = sqrt(the largest c.c), found by `if (c.c > best)`
+ *   from 0.  h not > 0: SN_CURV_DEGENERATE.  xi = (c.e1) / h, eta = (c.e2) / h, zeta = (c.m) / h.
+ * Normal equations.  r = (xi xi, xi eta, eta eta, xi, eta).  G_ab = sum r_a r_b (a <= b, 15 sums, mirrored), g_a = sum zeta r_a.
+ *   Cholesky G = L L^T without pivoting, column j = 0..4: d = G_jj, then d = d - L_jk L_jk for k = 0..j-1; a pivot that is not
+ *   d > SN_CURV_PIVOT_FLOOR G_jj: SN_CURV_DEGENERATE; L_jj = sqrt(d); for i = j+1..4: x = G_ij, x = x - L_ik L_jk for k = 0..j-1,
+ *   L_ij = x / L_jj.  Forward: y_i = (g_i minus L_ik y_k, k = 0..i-1, one after the other) / L_ii, i = 0..4.  Backward:
+ *   q_i = (y_i minus L_ki q_k, k = i+1..4, one after the other) / L_ii, i = 4..0.  (a, b, c, d, e) = (q_0 / h, q_1 / h, q_2 / h,
+ *   q_3, q_4).  (On well-shaped patches the smallest L_jj is 0.4-1.2 with this scaling: the floor does not touch them.)
+ * Fundamental forms.  E = 1 + d d, F = d e, G = 1 + e e, w = sqrt((1 + d d) + e e), L = (2 a) / w, M = b / w, N = (2 c) / w,
+ *   den = E G - F F, s11 = (L G - M F) / den, s12 = (M E - L F) / den, s22 = (N E - M F) / den: the symmetric matrix libigl forms.
+ * Eigenvalues.  tr2 = (s11 + s22) / 2, df = s11 - s22, disc = df df + 4 (s12 s12), rt = sqrt(disc) / 2.  The curvatures are the
+ *   negated eigenvalues: k1 = rt - tr2, k2 = (0 - tr2) - rt, so k1 >= k2 and a plane has k1 = k2 = +0.0.  A sphere of radius r with
+ *   outward faces has k1 = k2 = +1/r, the sign of H in "Mesh descriptors".
+ * Directions.  For d1: lambda = tr2 - rt; for d2: lambda = tr2 + rt.  If |s11 - lambda| >= |s22 - lambda| then (u1, u2) =
+ *   (s12, lambda - s11), else (lambda - s22, s12) — orthogonal to the row of S - lambda I with the larger diagonal entry.  If u1 < 0,
+ *   or u1 = 0 and u2 < 0, both are negated.  D = u1 e1 + u2 e2 componentwise, divided by sqrt(D.D).  Where disc is not > 0 (an
+ *   umbilic) or that length is not > 0: d1 = e1, d2 = e2.  Both lie in the plane perpendicular to m, the averaged normal, which is
+ *   not n_v.
+ * Failures.  A vertex that fails gets NaN (0x7FC00000) in every output that was asked for, ring_size as stated, and its bit OR-ed
+ *   into *status; its neighbours are unaffected.  A BAD face sets SN_DESC_BAD_FACE; FLAT faces raise nothing here.
+ *
+ * sn_mesh_principal_curvature_f32 : k1, k2 [nV] fp32, d1, d2 [nV][3] fp32, ring_size [nV] int32; any of them may be NULL and is
+ *     then not written.  *status is cleared, then OR-ed.  One wavefront per vertex: the patch is a list of ids in LDS beside an
+ *     open-addressing table, grown level by level, filtered, sorted (bitonic), and only then summed, serially.  Batches are one
+ *     disjoint mesh with offset faces.  workspace: sn_mesh_curvature_workspace_bytes(nV, nF), else SN_E_WORKSPACE.  Negative nV
+ *     or nF, radius < 1: SN_E_SHAPE.  nV + 1 or 3 nF past int32: SN_E_RANGE.  Does not synchronise; two runs are bit-identical.
+ * ------------------------------------------------------------------------------------------ */
+#define SN_CURV_FEW_POINTS   32
+#define SN_CURV_NO_NORMAL    64
+#define SN_CURV_OVERFLOW     128
+#define SN_CURV_DEGENERATE   1024
+#define SN_CURV_MAX_RING     1024
+#define SN_CURV_MIN_POINTS   6
+#define SN_CURV_PIVOT_FLOOR  1e-12
+size_t sn_mesh_curvature_workspace_bytes(int64_t nV, int64_t nF);
+int sn_mesh_principal_curvature_f32(const float *V, const int32_t *F, int64_t nV, int64_t nF, int32_t radius, float *k1, float *k2,
+                                    float *d1, float *d2, int32_t *ring_size, int32_t *status, void *workspace,
+                                    size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Spectral: the lowest eigenpairs of the cotangent pencil and the wave kernel signature, on the device.
  *
  * Replaces: compute_wks src/utils/geom_utils.py:407-440 (scipy.sparse.linalg.eigsh(-L, M=Am, sigma=-1e-5, k=300), a shift-invert

@@ -179,6 +179,8 @@ SIGNATURES = {
     "sn_mesh_cot_laplacian_workspace_bytes": (_sz, [_i64, _i64]),
     "sn_mesh_cot_laplacian_f32": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, C.c_double, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sn_mesh_cot_pencil_f64": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sn_mesh_curvature_workspace_bytes": (_sz, [_i64, _i64]),
+    "sn_mesh_principal_curvature_f32": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sn_spectral_start_f64": (C.c_int, [C.c_uint64, _vp, _i64, _i64, _i64, _vp, _vp]),
     "sn_cheb_filter_step_f64": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sn_wks_f64": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _vp]),

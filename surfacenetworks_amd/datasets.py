@@ -354,7 +354,7 @@ def faust_frame_from_mesh(V, F, label=None, device="cuda", symmetric=True, geode
 
 
 def normal_frame_from_mesh(V, F, model="lap", uniform_mesh=True, hack=1, target="area", name=None, device="cuda", repair=False,
-                           inputs=("V",), wks_k=300):
+                           inputs=("V",), wks_k=300, curv_radius=5):
     """The frame dict of the reference's normal-prediction sampler (src/normal_predict/sampler.py:21-91, read_npz) from a raw
     triangle mesh, built on the device: {'V' (nV, 3) fp32, 'F' (nF, 3) int64, 'input' (= V), 'target_dist' (nV, 3), 'name'} and
     'L' (model="lap") or 'Di', 'DiA' (model="dir") as SparseOperators.
@@ -371,8 +371,11 @@ def normal_frame_from_mesh(V, F, model="lap", uniform_mesh=True, hack=1, target=
     inputs: what 'input' holds, concatenated column-wise in the order given (train_4_normal.py:126's input table): "V" (3
     columns, the default: 'input' is then V itself) and "wks" (100 columns: operators.wave_kernel_signature of the rescaled
     mesh on the wks_k lowest eigenpairs, geom_utils.compute_wks; the reference uses 300).  With "wks" the frame gains
-    'eigenpairs', the operators.Eigenpairs behind it.  Still missing of the reference's pipeline: principal curvatures and the
-    edge flips that fix_degenerate.py applies to zero-area faces (repair only counts those)."""
+    'eigenpairs', the operators.Eigenpairs behind it.  "curv4" (4 columns: operators.curv4 of the rescaled mesh over
+    curv_radius-ring patches, geom_utils.compute_curv4; the frame is None after its warning where curv4 is None, as read_npz
+    gives up), "N" (3 columns: the area-weighted unit normals, compute_normals) and "G" (1 column: the raw angle defect,
+    operators.gaussian_curvature(area_avg=False)).  Still missing of the reference's pipeline: the edge flips that
+    fix_degenerate.py applies to zero-area faces (repair only counts those)."""
     import warnings
 
     from .operators import dirac_operators_from_mesh, laplacian_operator_from_mesh, repair_mesh, vertex_normals
@@ -380,8 +383,9 @@ def normal_frame_from_mesh(V, F, model="lap", uniform_mesh=True, hack=1, target=
     if model not in ("lap", "dir"):
         raise ValueError(f'normal_frame_from_mesh: model must be "lap" or "dir", got {model!r}')
     inputs = tuple(inputs)
-    if not inputs or any(i not in ("V", "wks") for i in inputs) or len(set(inputs)) != len(inputs):
-        raise ValueError(f'normal_frame_from_mesh: inputs is a sequence of distinct names out of "V" and "wks", got {inputs!r}')
+    if not inputs or any(i not in ("V", "wks", "curv4", "N", "G") for i in inputs) or len(set(inputs)) != len(inputs):
+        raise ValueError('normal_frame_from_mesh: inputs is a sequence of distinct names out of "V", "wks", "curv4", "N" and "G", '
+                         f'got {inputs!r}')
     repaired = None
     if repair:
         Vt = V if torch.is_tensor(V) else torch.from_numpy(np.array(V, dtype=np.float32))
@@ -427,6 +431,18 @@ def normal_frame_from_mesh(V, F, model="lap", uniform_mesh=True, hack=1, target=
         if "wks" in inputs:
             frame["eigenpairs"] = laplacian_eigenpairs(Vd, Fd, k=wks_k)
             cols["wks"] = wave_kernel_signature(Vd, Fd, N=100, eigenpairs=frame["eigenpairs"])
+        if "curv4" in inputs:
+            from .operators import curv4
+
+            cols["curv4"] = curv4(Vd, Fd.to(torch.int32), radius=curv_radius)
+            if cols["curv4"] is None:
+                return refuse("no principal curvatures")
+        if "N" in inputs:
+            cols["N"] = vertex_normals(Vd, Fd, weighting="area")
+        if "G" in inputs:
+            from .operators import gaussian_curvature
+
+            cols["G"] = gaussian_curvature(Vd, Fd, area_avg=False).unsqueeze(1)
         frame["input"] = torch.cat([cols[i] for i in inputs], dim=1)
     return frame
 

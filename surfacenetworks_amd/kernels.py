@@ -1193,6 +1193,44 @@ def mesh_descriptors(V, F, want=None) -> dict:
     return out
 
 
+CURV_FEW_POINTS, CURV_NO_NORMAL, CURV_OVERFLOW, CURV_DEGENERATE = 32, 64, 128, 1024      # SN_CURV_* status bits
+CURV_MAX_RING = 1024                                                                      # SN_CURV_MAX_RING
+# output name -> (dtype, trailing width) in the argument order of sn_mesh_principal_curvature_f32
+CURVATURE_FIELDS = {"k1": (torch.float32, 1), "k2": (torch.float32, 1), "d1": (torch.float32, 3), "d2": (torch.float32, 3),
+                    "ring_size": (torch.int32, 1)}
+
+
+def mesh_principal_curvature(V, F, radius: int = 5, want=None) -> dict:
+    """Principal curvatures k1 >= k2 and their directions from a quadric fitted over the `radius`-ring patch of every vertex of
+    one triangle mesh (or a batch laid out as one disjoint mesh) on the device: sn_mesh_principal_curvature_f32, definition in
+    include/sn_spmm.h ("Principal curvatures"), host statement mesh_ops.principal_curvatures, equal to it bit for bit.
+    V: (nV, 3) fp32, F: (nF, 3) int32.  want: the names of CURVATURE_FIELDS to compute, None = all.  Returns a dict with every
+    name of CURVATURE_FIELDS — k1, k2 (nV,) fp32, d1, d2 (nV, 3) fp32, ring_size (nV,) int32, or None when it was not asked
+    for — plus "status": a 1-element int32 device tensor of DESC_BAD_FACE and CURV_* bits, not read here.  A vertex that failed
+    holds NaN.  Does not synchronise; two runs are bit-identical."""
+    _dev(V, F)
+    _check_mesh("mesh_principal_curvature", V, F)
+    radius = int(radius)
+    if radius < 1:
+        raise ValueError(f"mesh_principal_curvature: radius must be at least 1, got {radius}")
+    names = list(CURVATURE_FIELDS) if want is None else list(want)
+    unknown = [n for n in names if n not in CURVATURE_FIELDS]
+    if unknown:
+        raise ValueError(f"mesh_principal_curvature: unknown output {unknown[0]!r}; the outputs are {', '.join(CURVATURE_FIELDS)}")
+    V, F = V.contiguous(), F.contiguous()
+    nV, nF = V.shape[0], F.shape[0]
+    dev = V.device
+    out = {}
+    for name, (dtype, width) in CURVATURE_FIELDS.items():
+        out[name] = torch.empty((nV,) if width == 1 else (nV, width), dtype=dtype, device=dev) if name in names else None
+    out["status"] = torch.empty(1, dtype=torch.int32, device=dev)
+    ws_bytes = int(_lib.load().sn_mesh_curvature_workspace_bytes(nV, nF))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    _lib.call("sn_mesh_principal_curvature_f32", _p(V), _p(F), nV, nF, radius, *[_p(out[n]) for n in CURVATURE_FIELDS],
+              out["status"].data_ptr(), _p(ws), ws_bytes, _stream())
+    return out
+
+
 def cot_laplacian_from_mesh(V, F, mass: str = "barycentric", hack=None):
     """The libigl-convention Laplacian L = M^-1 C of one mesh (or a batch laid out as one disjoint mesh) built on the device:
     (rowptr, colind, vals, status) — CSR with ascending columns and explicit zeros kept, and the status word as a Python int

@@ -20,6 +20,7 @@ Also here: the synthetic mesh generators SURVEY.md §8(d) prescribes for the ben
 from __future__ import annotations
 
 import collections
+import dataclasses
 import warnings
 
 import numpy as np
@@ -36,6 +37,8 @@ __all__ = [
     "REPAIR_BAD_FACE", "REPAIR_NONFINITE", "REPAIR_NONORIENTABLE", "REPAIR_NONMANIFOLD", "REPAIR_INTERNAL",
     "descriptor_sums", "vertex_descriptors", "libigl_laplacian", "Descriptors", "LAP_MAX_DEGREE",
     "DESC_BAD_FACE", "DESC_FLAT_FACE", "DESC_NO_NORMAL", "DESC_CLAMPED", "DESC_DEGREE",
+    "principal_curvatures", "curv4", "curv4_columns", "curvature_status_names", "PrincipalCurvatures", "CURV_FEW_POINTS",
+    "CURV_NO_NORMAL", "CURV_OVERFLOW", "CURV_DEGENERATE", "CURV_MAX_RING", "CURV_MIN_POINTS", "CURV_PIVOT_FLOOR", "CURV_CLIP",
     "delaunay_2d", "poisson_disc", "poisson_grid", "mesh_digits", "lattice_orient", "lattice_incircle", "lattice_intensity",
     "lattice_draw", "canonical_faces", "snap_to_lattice", "Delaunay2D", "PoissonDisc", "MeshDigitsResult",
     "DT_DEGENERATE", "DT_DUPLICATE", "DT_RANGE", "DT_TOO_LARGE", "DT_NOT_CONVERGED", "DT_REJECTED", "DT_INTERNAL",
@@ -747,6 +750,233 @@ def libigl_laplacian(V: np.ndarray, F: np.ndarray, mass: str = "barycentric", ha
     rowptr = np.zeros(nV + 1, dtype=np.int32)
     np.cumsum(np.bincount(r, minlength=nV), out=rowptr[1:])
     return sp.csr_matrix((vals, c.astype(np.int32), rowptr), shape=(nV, nV)), status
+
+
+# --------------------------------------------------------------------------------------------------
+# principal curvatures: a quadric fitted over the k-ring patch of every vertex (definition: include/sn_spmm.h, "Principal
+# curvatures").  The host statement of geom_utils.compute_curv4 (igl.principal_curvature) in this project's own definition:
+# numpy float64, every ufunc rounding on its own, the patch sums serial over ascending vertex id.
+# --------------------------------------------------------------------------------------------------
+CURV_FEW_POINTS, CURV_NO_NORMAL, CURV_OVERFLOW, CURV_DEGENERATE = 32, 64, 128, 1024      # SN_CURV_* status bits
+CURV_MAX_RING = 1024         # SN_CURV_MAX_RING: the largest patch
+CURV_MIN_POINTS = 6          # SN_CURV_MIN_POINTS: the smallest patch a quadric is fitted to
+CURV_PIVOT_FLOOR = 1e-12     # SN_CURV_PIVOT_FLOOR: a Cholesky pivot must exceed this times its diagonal entry of G
+CURV_CLIP = 100.0            # compute_curv4 clips the four columns to +-100
+_CURV_CHUNK = 4096           # vertices taken together by the host statement (memory only, no effect on any value)
+_CURV_PAIRS = [(i, j) for i in range(5) for j in range(i, 5)]
+
+
+@dataclasses.dataclass
+class PrincipalCurvatures:
+    """k1 >= k2 (nV,) fp32, d1 / d2 (nV, 3) fp32 unit directions, ring_size (nV,) int32 (the final patch size, CURV_MAX_RING + 1
+    where the search overflowed), status: DESC_BAD_FACE and CURV_* bits (an int on the host, a 1-element int32 tensor on the
+    device).  A vertex that failed holds NaN."""
+    k1: object = None
+    k2: object = None
+    d1: object = None
+    d2: object = None
+    ring_size: object = None
+    status: object = None
+
+
+def _padded_rows(indptr, indices, rows, skip=None):
+    """(idx, mask): the CSR rows `rows` side by side, padded with 0 / False; skip: rows left empty."""
+    cnt = indptr[rows + 1] - indptr[rows]
+    if skip is not None:
+        cnt = np.where(skip, 0, cnt)
+    width = int(cnt.max()) if cnt.size else 0
+    j = np.arange(width)[None, :]
+    mask = j < cnt[:, None]
+    if not indices.size:
+        return np.zeros(mask.shape, dtype=np.int64), mask
+    pos = np.minimum(indptr[rows][:, None] + j, indices.size - 1)
+    return np.where(mask, indices[pos], 0).astype(np.int64), mask
+
+
+def principal_curvatures(V: np.ndarray, F: np.ndarray, radius: int = 5) -> PrincipalCurvatures:
+    """Principal curvatures and directions of every vertex from a quadric fitted over its `radius`-ring patch: the numpy
+    statement of sn_mesh_principal_curvature_f32, scalar for scalar (include/sn_spmm.h, "Principal curvatures", has the text).
+    Replaces igl.principal_curvature in geom_utils.compute_curv4 with this project's own definition in libigl's conventions."""
+    radius = int(radius)
+    if radius < 1:
+        raise ValueError(f"principal_curvatures: radius must be at least 1, got {radius}")
+    P = np.asarray(V, dtype=np.float32).astype(np.float64).reshape(-1, 3)
+    F = np.asarray(F, dtype=np.int64).reshape(-1, 3)
+    nV = P.shape[0]
+    s = descriptor_sums(V, F)
+    status = 0 if s["good"].all() else DESC_BAD_FACE
+    with np.errstate(all="ignore"):
+        Na = s["N_area"]
+        length = np.sqrt(_dot3(Na, Na))
+        has_normal = length > 0
+        n = np.where(has_normal[:, None], Na / length[:, None], 0.0)
+    # neighbours through the faces that are not bad; A: the 1-ring with the vertex itself, R: the patch
+    Fg = F[s["good"]]
+    r = np.concatenate([Fg[:, 0], Fg[:, 1], Fg[:, 2], Fg[:, 0], Fg[:, 1], Fg[:, 2], np.arange(nV)])
+    c = np.concatenate([Fg[:, 1], Fg[:, 2], Fg[:, 0], Fg[:, 2], Fg[:, 0], Fg[:, 1], np.arange(nV)])
+    A = sp.csr_matrix((np.ones(r.size, dtype=np.int32), (r, c)), shape=(nV, nV))
+    A.sum_duplicates()
+    A.data[:] = 1
+    R = A
+    for _ in range(radius - 1):
+        R = R @ A
+        R.data[:] = 1
+    A.sort_indices()
+    R.sort_indices()
+    k1 = np.full(nV, np.nan, dtype=np.float32)
+    k2 = np.full(nV, np.nan, dtype=np.float32)
+    d1 = np.full((nV, 3), np.nan, dtype=np.float32)
+    d2 = np.full((nV, 3), np.nan, dtype=np.float32)
+    ring_size = np.zeros(nV, dtype=np.int32)
+    for begin in range(0, nV, _CURV_CHUNK):
+        vs = np.arange(begin, min(begin + _CURV_CHUNK, nV))
+        out = _curvature_chunk(P, n, has_normal, A, R, vs)
+        k1[vs], k2[vs], d1[vs], d2[vs], ring_size[vs] = out[:5]
+        status |= out[5]
+    return PrincipalCurvatures(k1, k2, d1, d2, ring_size, int(status))
+
+
+def _curvature_chunk(P, n, has_normal, A, R, vs):
+    nb = vs.size
+    col = lambda x: x[:, None]
+    with np.errstate(all="ignore"):
+        count = (R.indptr[vs + 1] - R.indptr[vs]).astype(np.int64)
+        fail = np.where(count > CURV_MAX_RING, CURV_OVERFLOW, 0)
+        idx, mask = _padded_rows(R.indptr, R.indices, vs, skip=fail != 0)
+        W = idx.shape[1]
+        Pv, nv = P[vs], n[vs]
+        fail = np.where((fail == 0) & ~has_normal[vs], CURV_NO_NORMAL, fail)
+        # projection-plane check
+        keep = mask & (_dot3(n[idx].reshape(-1, 3), np.repeat(nv, W, axis=0)).reshape(nb, W) > 0)
+        kept = keep.sum(axis=1)
+        use = (kept >= CURV_MIN_POINTS) & (kept < count) & (fail == 0)
+        mask = np.where(col(use), keep, mask)
+        count = np.where(use, kept, count)
+        ring_size = np.where(fail == CURV_OVERFLOW, CURV_MAX_RING + 1, count).astype(np.int32)
+        fail = np.where((fail == 0) & (count < CURV_MIN_POINTS), CURV_FEW_POINTS, fail)
+        # fit normal and the patch's extent, serial over ascending ids
+        m = np.zeros((nb, 3))
+        h2 = np.zeros(nb)
+        for j in range(W):
+            mj = mask[:, j]
+            m = np.where(col(mj), m + n[idx[:, j]], m)
+            cj = P[idx[:, j]] - Pv
+            cc = _dot3(cj, cj)
+            h2 = np.where(mj & (cc > h2), cc, h2)
+        lm = np.sqrt(_dot3(m, m))
+        fail = np.where((fail == 0) & ~(lm > 0), CURV_DEGENERATE, fail)
+        m = m / col(lm)
+        # frame: the neighbour of smallest id with a projection of positive length
+        nidx, nmask = _padded_rows(A.indptr, A.indices, vs)
+        nmask &= nidx != col(vs)
+        t = np.zeros((nb, 3))
+        lt = np.zeros(nb)
+        for j in range(nidx.shape[1]):
+            cj = P[nidx[:, j]] - Pv
+            tj = cj - col(_dot3(cj, m)) * m
+            lj = np.sqrt(_dot3(tj, tj))
+            take = nmask[:, j] & ~(lt > 0) & (lj > 0)
+            t = np.where(col(take), tj, t)
+            lt = np.where(take, lj, lt)
+        fail = np.where((fail == 0) & ~(lt > 0), CURV_DEGENERATE, fail)
+        e1 = t / col(lt)
+        e2 = _cross3(m, e1)
+        h = np.sqrt(h2)
+        fail = np.where((fail == 0) & ~(h > 0), CURV_DEGENERATE, fail)
+        # normal equations of z = a x^2 + b x y + c y^2 + d x + e y in the scaled frame
+        G = np.zeros((nb, 5, 5))
+        g = np.zeros((nb, 5))
+        for j in range(W):
+            mj = mask[:, j]
+            cj = P[idx[:, j]] - Pv
+            xi, eta, zeta = _dot3(cj, e1) / h, _dot3(cj, e2) / h, _dot3(cj, m) / h
+            row = [xi * xi, xi * eta, eta * eta, xi, eta]
+            for a, b in _CURV_PAIRS:
+                G[:, a, b] = np.where(mj, G[:, a, b] + row[a] * row[b], G[:, a, b])
+            for a in range(5):
+                g[:, a] = np.where(mj, g[:, a] + zeta * row[a], g[:, a])
+        for a, b in _CURV_PAIRS:
+            G[:, b, a] = G[:, a, b]
+        # Cholesky G = L L^T without pivoting, column by column
+        L = np.zeros((nb, 5, 5))
+        for j in range(5):
+            d = G[:, j, j].copy()
+            for k in range(j):
+                d = d - L[:, j, k] * L[:, j, k]
+            fail = np.where((fail == 0) & ~(d > CURV_PIVOT_FLOOR * G[:, j, j]), CURV_DEGENERATE, fail)
+            L[:, j, j] = np.sqrt(d)
+            for i in range(j + 1, 5):
+                x = G[:, i, j].copy()
+                for k in range(j):
+                    x = x - L[:, i, k] * L[:, j, k]
+                L[:, i, j] = x / L[:, j, j]
+        y = np.zeros((nb, 5))
+        for i in range(5):
+            x = g[:, i].copy()
+            for k in range(i):
+                x = x - L[:, i, k] * y[:, k]
+            y[:, i] = x / L[:, i, i]
+        q = np.zeros((nb, 5))
+        for i in range(4, -1, -1):
+            x = y[:, i].copy()
+            for k in range(i + 1, 5):
+                x = x - L[:, k, i] * q[:, k]
+            q[:, i] = x / L[:, i, i]
+        qa, qb, qc, qd, qe = q[:, 0] / h, q[:, 1] / h, q[:, 2] / h, q[:, 3], q[:, 4]
+        # fundamental forms and the symmetric 2 x 2 matrix
+        E, Ff, Gg = 1 + qd * qd, qd * qe, 1 + qe * qe
+        w = np.sqrt((1 + qd * qd) + qe * qe)
+        Lf, Mf, Nf = (2 * qa) / w, qb / w, (2 * qc) / w
+        den = E * Gg - Ff * Ff
+        s11, s12, s22 = (Lf * Gg - Mf * Ff) / den, (Mf * E - Lf * Ff) / den, (Nf * E - Mf * Ff) / den
+        # eigenvalues (negated: k = -lambda) and directions
+        tr2 = (s11 + s22) / 2
+        df = s11 - s22
+        disc = df * df + 4 * (s12 * s12)
+        rt = np.sqrt(disc) / 2
+        k1 = rt - tr2
+        k2 = (0 - tr2) - rt
+        dirs = []
+        for lam, fallback in ((tr2 - rt, e1), (tr2 + rt, e2)):
+            p, q2 = s11 - lam, s22 - lam
+            first = np.abs(p) >= np.abs(q2)
+            u1 = np.where(first, s12, lam - s22)
+            u2 = np.where(first, lam - s11, s12)
+            flip = (u1 < 0) | ((u1 == 0) & (u2 < 0))
+            u1, u2 = np.where(flip, -u1, u1), np.where(flip, -u2, u2)
+            dv = col(u1) * e1 + col(u2) * e2
+            ld = np.sqrt(_dot3(dv, dv))
+            dirs.append(np.where(col((disc > 0) & (ld > 0)), dv / col(ld), fallback))
+        bad = fail != 0
+        f32 = lambda x: np.where(bad if x.ndim == 1 else col(bad), np.nan, x).astype(np.float32)
+        status = int(np.bitwise_or.reduce(fail)) if nb else 0
+        return f32(k1), f32(k2), f32(dirs[0]), f32(dirs[1]), ring_size, status
+
+
+def curv4_columns(k1, k2):
+    """[k1, k2, (k1 + k2) / 2, k1 k2] clipped to +-CURV_CLIP, in the dtype of k1 (every operation rounds on its own)."""
+    half = k1.dtype.type(2)
+    return np.clip(np.stack([k1, k2, (k1 + k2) / half, k1 * k2], axis=1), -k1.dtype.type(CURV_CLIP), k1.dtype.type(CURV_CLIP))
+
+
+def curv4(V: np.ndarray, F: np.ndarray, radius: int = 5):
+    """geom_utils.compute_curv4 on principal_curvatures: (nV, 4) fp32 [k1, k2, H, K] with H = (k1 + k2) / 2 and K = k1 k2, formed
+    in fp32 from the fp32 curvatures, clipped to +-100 and divided column by column by the largest magnitude (an fp32 division).
+    None after a warning where a vertex failed (the reference's `return None`)."""
+    pc = principal_curvatures(V, F, radius)
+    if np.isnan(pc.k1).any() or np.isnan(pc.k2).any():
+        warnings.warn(f"curv4: {int(np.isnan(pc.k1).sum())} vertices have no curvature ({curvature_status_names(pc.status)}); "
+                      "no columns")
+        return None
+    C = curv4_columns(pc.k1, pc.k2)
+    with np.errstate(all="ignore"):
+        return C / np.abs(C).max(axis=0, keepdims=True)
+
+
+def curvature_status_names(status: int) -> str:
+    names = [(DESC_BAD_FACE, "BAD_FACE"), (CURV_FEW_POINTS, "FEW_POINTS"), (CURV_NO_NORMAL, "NO_NORMAL"),
+             (CURV_OVERFLOW, "OVERFLOW"), (CURV_DEGENERATE, "DEGENERATE")]
+    return " | ".join(name for bit, name in names if status & bit) or "no status bit"
 
 
 # --------------------------------------------------------------------------------------------------

@@ -31,7 +31,7 @@ __all__ = ["SparseOperator", "OperatorPool", "PackedSegments", "as_operator", "d
            "laplacian_operator_from_mesh", "geodesic_matrix_from_mesh", "spgemm", "amplify_sequence_operators",
            "clean_mesh", "CleanMesh", "repair_mesh", "RepairedMesh", "vertex_descriptors", "MeshDescriptors", "vertex_normals", "face_areas", "vertex_mass",
            "gaussian_curvature", "delaunay_2d", "Delaunay2D", "arap_deform", "ArapDeformation", "laplacian_eigenpairs", "Eigenpairs",
-           "wave_kernel_signature"]
+           "wave_kernel_signature", "principal_curvatures", "PrincipalCurvatures", "curv4"]
 
 # A BSR4 copy is kept when zero-fill costs at most this much extra storage over CSR entries.
 _BSR4_MAX_FILL = 1.6
@@ -497,6 +497,71 @@ def gaussian_curvature(V: torch.Tensor, F: torch.Tensor, area_avg: bool = False)
     geom_utils.gaussian_curvature does."""
     d = vertex_descriptors(V, F, want=["gauss", "mass_voronoi"] if area_avg else ["gauss"])
     return d.gauss / d.mass_voronoi if area_avg else d.gauss
+
+
+@dataclasses.dataclass
+class PrincipalCurvatures:
+    """What operators.principal_curvatures returns: device tensors, None for an output that was not asked for.  k1 >= k2 are
+    (nV,) fp32, d1 / d2 (nV, 3) fp32 unit directions, ring_size (nV,) int32 (the final patch size; kernels.CURV_MAX_RING + 1 where
+    the search overflowed), with a leading batch axis for a batch; status is a 1-element int32 device tensor of
+    kernels.DESC_BAD_FACE and kernels.CURV_* bits (of the whole batch).  A vertex that failed holds NaN."""
+    k1: Optional[torch.Tensor] = None
+    k2: Optional[torch.Tensor] = None
+    d1: Optional[torch.Tensor] = None
+    d2: Optional[torch.Tensor] = None
+    ring_size: Optional[torch.Tensor] = None
+    status: Optional[torch.Tensor] = None
+
+
+def _mesh_tensors(V, F, device="cuda"):
+    """Tensors as given, numpy arrays as fp32 / int32 tensors on `device`."""
+    if not torch.is_tensor(V):
+        V = torch.from_numpy(np.array(V, dtype=np.float32)).to(device)
+    if not torch.is_tensor(F):
+        F = torch.from_numpy(np.array(F, dtype=np.int32)).to(V.device)
+    return V, F
+
+
+def principal_curvatures(V, F, radius: int = 5, want=None) -> PrincipalCurvatures:
+    """Principal curvatures and directions of a triangle mesh on the device, from a quadric fitted over the `radius`-ring patch of
+    every vertex (kernels.mesh_principal_curvature; include/sn_spmm.h, "Principal curvatures", has the definition and
+    mesh_ops.principal_curvatures the host statement, which the device equals bit for bit) — igl.principal_curvature of
+    geom_utils.compute_curv4 in this project's own definition.  V: (nV, 3), F: (nF, 3), tensors or numpy arrays, or a batch
+    V: (B, nV, 3) with F shared or (B, nF, 3): one launch sequence over the offset faces, bit-identical to the per-mesh calls.
+    want: names of the PrincipalCurvatures fields to compute (None: all of them).  A vertex whose patch cannot be fitted (fewer
+    than six members, more than kernels.CURV_MAX_RING, no normal, a degenerate patch) holds NaN and is reported in `status`.
+    Does not synchronise."""
+    V, F = _mesh_tensors(V, F)
+    kernels._dev(V, F)
+    Vg, Fg, B, nV, nF = _offset_batch("principal_curvatures", V, F)
+    out = kernels.mesh_principal_curvature(Vg, Fg, radius, want)
+    if V.dim() == 3:
+        for name, (_, width) in kernels.CURVATURE_FIELDS.items():
+            if out[name] is not None:
+                out[name] = out[name].view((B, nV) + ((width,) if width > 1 else ()))
+    return PrincipalCurvatures(**out)
+
+
+_CURV_REASONS = ((kernels.DESC_BAD_FACE, "a face has an index outside the mesh or a repeated index"),
+                 (kernels.CURV_FEW_POINTS, "a patch has fewer than six members"),
+                 (kernels.CURV_NO_NORMAL, "a vertex has no normal"),
+                 (kernels.CURV_OVERFLOW, f"a patch has more than {kernels.CURV_MAX_RING} members"),
+                 (kernels.CURV_DEGENERATE, "a patch is degenerate"))
+
+
+def curv4(V, F, radius: int = 5):
+    """geom_utils.compute_curv4 on the device: (nV, 4) fp32 columns [k1, k2, H, K] with H = (k1 + k2) / 2 and K = k1 k2 formed in
+    fp32 from principal_curvatures, clipped to +-100, each column divided (in fp32) by its largest magnitude — per mesh for a
+    batch, (B, nV, 4).  Where any entry is NaN it returns None after a warnings.warn naming the status bits, the reference's
+    `return None`.  Synchronises (it reads whether a NaN occurred)."""
+    pc = principal_curvatures(V, F, radius, want=["k1", "k2"])
+    C = torch.stack([pc.k1, pc.k2, (pc.k1 + pc.k2) / 2, pc.k1 * pc.k2], dim=-1).clamp(-100.0, 100.0)
+    if bool(torch.isnan(C).any()):
+        status = int(pc.status.item())
+        why = "; ".join(text for bit, text in _CURV_REASONS if status & bit and bit != kernels.DESC_BAD_FACE) or "non-finite input"
+        warnings.warn(f"curv4: {int(torch.isnan(pc.k1).sum())} vertices have no curvature (status {status}: {why}); no columns")
+        return None
+    return C / C.abs().amax(dim=-2, keepdim=True)
 
 
 def laplacian_operator_from_mesh(V: torch.Tensor, F: torch.Tensor, intrinsic: bool = False, max_rounds: int = 1024,
