@@ -21,16 +21,6 @@ constexpr int kLdsBytes = 160 * 1024 - 1024;      // dynamic LDS of a frame work
 constexpr int kMaxN = (kLdsBytes - kRedDoubles * 8) / 24;
 constexpr int kMaxDeg = SN_LAP_MAX_DEGREE;
 
-inline int launch_status() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? SN_OK : (int)e;
-}
-inline unsigned grid_for(int64_t n) {
-  int64_t b = (n + kWG - 1) / kWG;
-  if (b < 1) b = 1;
-  if (b > 65535 * 16) b = 65535 * 16;
-  return (unsigned)b;
-}
 
 __device__ __forceinline__ double edge_len(const float *__restrict__ V, int a, int b) {
   const double dx = (double)V[3 * a] - (double)V[3 * b];
@@ -499,17 +489,17 @@ int sn_arap_weights_f64(const float *V0, const int32_t *F, int64_t nV, int64_t n
   if (e != hipSuccess) return (int)e;
   const int *vptr, *inc;
   int *sums;
-  const int st = sn_internal_incidence(F, nV, nF, workspace, status, &vptr, &inc, &sums, s);
+  const int st = sn_internal_incidence(F, nV, nF, workspace, status, SN_ARAP_BAD_FACE, &vptr, &inc, &sums, s);
   if (st != SN_OK) return st;
   e = sn_internal_fill(rowptr + nV, 0, sizeof(int), s);
   if (e != hipSuccess) return (int)e;
   if (nV > 0) {
-    hipLaunchKernelGGL((arap_weight_rows_k<false>), dim3(grid_for(nV)), dim3(kWG), 0, s, V0, F, nV, vptr, inc, rowptr, (int *)nullptr,
+    hipLaunchKernelGGL((arap_weight_rows_k<false>), dim3(grid_for(nV, kWG)), dim3(kWG), 0, s, V0, F, nV, vptr, inc, rowptr, (int *)nullptr,
                        (double *)nullptr, (double *)nullptr, status);
   }
   sn_internal_scan_i32(rowptr, nV + 1, rowptr, sums, nullptr, 0, 0, s);
   if (nV > 0)
-    hipLaunchKernelGGL((arap_weight_rows_k<true>), dim3(grid_for(nV)), dim3(kWG), 0, s, V0, F, nV, vptr, inc, rowptr, colind, w, d,
+    hipLaunchKernelGGL((arap_weight_rows_k<true>), dim3(grid_for(nV, kWG)), dim3(kWG), 0, s, V0, F, nV, vptr, inc, rowptr, colind, w, d,
                        status);
   return launch_status();
 }

@@ -21,17 +21,6 @@ constexpr int kTableBits = 11;
 static_assert(kTable == 1 << kTableBits, "the hash keeps kTableBits bits");
 static_assert((kMaxRing & (kMaxRing - 1)) == 0, "the sort pads the list to a power of two inside the list");
 
-inline int launch_status() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? SN_OK : (int)e;
-}
-inline unsigned grid_for(int64_t n, int wg) {
-  int64_t b = (n + wg - 1) / wg;
-  if (b < 1) b = 1;
-  if (b > 65535 * 16) b = 65535 * 16;
-  return (unsigned)b;
-}
-
 __device__ __forceinline__ double dot3(double ax, double ay, double az, double bx, double by, double bz) {
   return (ax * bx + ay * by) + az * bz;
 }
@@ -40,19 +29,16 @@ struct CurvWs {      // the shared incidence first (it takes the front of the wo
   size_t inc_bytes;
   SnCarver c;
   double *normal;    // [nV][3] the unit area-weighted normals in fp64, zero where a vertex has none
-  int *inc_status;   // the incidence builder's own status word (its bad-face bit is another section's)
   CurvWs(void *w, int64_t nV, int64_t nF)
       : inc_bytes((sn_internal_incidence_bytes(nV, nF) + 15) & ~(size_t)15), c(w ? static_cast<char *>(w) + inc_bytes : nullptr),
-        normal(c.take<double>(3 * nV)), inc_status(c.take<int>(1)) {}
+        normal(c.take<double>(3 * nV)) {}
   size_t bytes() const { return inc_bytes + c.bytes; }
 };
 
 // n_x of the definition: one thread per vertex streams over its sorted incidence list, as desc_vertex_k does for N_area
 __global__ __launch_bounds__(kWG) void curv_normals_k(const float *__restrict__ V, const int *__restrict__ F, int64_t nV,
                                                       const int *__restrict__ vptr, const int *__restrict__ inc,
-                                                      const int *__restrict__ inc_status, double *__restrict__ normal,
-                                                      int *__restrict__ status) {
-  if (blockIdx.x == 0 && threadIdx.x == 0 && *inc_status) atomicOr(status, SN_DESC_BAD_FACE);
+                                                      double *__restrict__ normal) {
   for (int64_t v = (int64_t)blockIdx.x * kWG + threadIdx.x; v < nV; v += (int64_t)gridDim.x * kWG) {
     double sx = 0, sy = 0, sz = 0;
     for (int o = vptr[v]; o < vptr[v + 1]; ++o) {
@@ -403,13 +389,11 @@ int sn_mesh_principal_curvature_f32(const float *V, const int32_t *F, int64_t nV
   if (e != hipSuccess) return (int)e;
   if (nV == 0) return launch_status();
   const CurvWs ws(workspace, nV, nF);
-  e = sn_internal_fill(ws.inc_status, 0, sizeof(int), s);
-  if (e != hipSuccess) return (int)e;
   const int *vptr, *inc;
   int *sums;
-  const int st = sn_internal_incidence(F, nV, nF, workspace, ws.inc_status, &vptr, &inc, &sums, s);
+  const int st = sn_internal_incidence(F, nV, nF, workspace, status, SN_DESC_BAD_FACE, &vptr, &inc, &sums, s);
   if (st != SN_OK) return st;
-  hipLaunchKernelGGL(curv_normals_k, dim3(grid_for(nV, kWG)), dim3(kWG), 0, s, V, F, nV, vptr, inc, ws.inc_status, ws.normal, status);
+  hipLaunchKernelGGL(curv_normals_k, dim3(grid_for(nV, kWG)), dim3(kWG), 0, s, V, F, nV, vptr, inc, ws.normal);
   const CurvOut out = {k1, k2, d1, d2, ring_size, status};
   hipLaunchKernelGGL(curv_fit_k, dim3(grid_for(nV, 1)), dim3(kWave), 0, s, V, F, nV, vptr, inc, ws.normal, (int)radius, out);
   return launch_status();

@@ -22,10 +22,6 @@ __device__ __forceinline__ f16v mfma_f16(const u4 &a, const u4 &b, const f16v &c
   return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8v, a), __builtin_bit_cast(h8v, b), c, 0, 0, 0);
 }
 
-inline int launch_status() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? SN_OK : (int)e;
-}
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace

@@ -28,10 +28,6 @@ constexpr int kWG = 256;
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f16v __attribute__((ext_vector_type(16)));
 
-inline int launch_status() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? SN_OK : (int)e;
-}
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 // the split kernels keep a lane's byte offset inside a 32-row tile in 32 bits: leading dimensions below 2^24 elements
 inline bool ld32(int64_t a, int64_t b = 0, int64_t c = 0, int64_t d = 0, int64_t e = 0) {

@@ -7,6 +7,19 @@
 
 #include "sn_spmm.h"
 
+// what an entry point returns after its launches: SN_OK, or the runtime's error
+inline int launch_status() {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? SN_OK : (int)e;
+}
+// workgroups for n items at per_block items each: at least one, at most cap (grid-stride loops take the rest)
+inline unsigned grid_for(int64_t n, int per_block, int64_t cap = 65535 * 16) {
+  int64_t b = (n + per_block - 1) / per_block;
+  if (b < 1) b = 1;
+  if (b > cap) b = cap;
+  return (unsigned)b;
+}
+
 // compute units of the current device (256 when there is no device to ask)
 int sn_internal_cu_count();
 
@@ -27,11 +40,12 @@ void sn_internal_scan_i32(const int *in, int64_t n, int *out, int *sums, int *st
 
 // By-vertex incidence of the good faces of F (sn_meshops.hip: bucket_count_k, bucket_offsets, bucket_fill_k, vertex_sort_k):
 // ptr[nV + 1] and inc[ptr[v] .. ptr[v + 1]) = the codes 3 f + c of the corners at vertex v, ascending.  A face with an index outside
-// 0..nV-1 or a repeated index is left out and raises SN_ARAP_BAD_FACE in *status (the bit of the one caller so far).  The arrays
-// live in the workspace (sn_internal_incidence_bytes); sums is scan scratch for nV + 1 items that the caller may use afterwards.
+// 0..nV-1 or a repeated index is left out and raises bad_face_bit in *status: the caller's own bit in its own status word
+// (SN_ARAP_BAD_FACE for sn_arap_weights_f64, SN_DESC_BAD_FACE for sn_mesh_principal_curvature_f32).  The arrays live in the
+// workspace (sn_internal_incidence_bytes); sums is scan scratch for nV + 1 items that the caller may use afterwards.
 size_t sn_internal_incidence_bytes(int64_t nV, int64_t nF);
-int sn_internal_incidence(const int *F, int64_t nV, int64_t nF, void *workspace, int *status, const int **ptr, const int **inc,
-                          int **sums, hipStream_t s);
+int sn_internal_incidence(const int *F, int64_t nV, int64_t nF, void *workspace, int *status, int bad_face_bit, const int **ptr,
+                          const int **inc, int **sums, hipStream_t s);
 
 // stable insertion sort of key[b..e), ascending, that carries up to two payload arrays along
 template <class A = char, class B = char>

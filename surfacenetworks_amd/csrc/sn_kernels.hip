@@ -1835,18 +1835,9 @@ __global__ __launch_bounds__(kWG) void elu_bwd_k(const float *__restrict__ gdst,
 // ------------------------------------------------------------------------------------------------
 // host-side helpers
 // ------------------------------------------------------------------------------------------------
-inline int launch_status() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? SN_OK : (int)e;
-}
-
-// Elementwise passes: one 16-byte item per thread and as many workgroups as that takes (measured faster than a capped
-// grid-stride loop: 6.5 vs 4.9 TB/s on a 1 GiB copy, tools/scratch/copybench.hip), non-temporal loads/stores (kStreamNT).
-inline unsigned grid_for(int64_t work_items, int per_block) {
-  int64_t b = (work_items + per_block - 1) / per_block;
-  if (b < 1) b = 1;
-  return (unsigned)(b < (int64_t)INT_MAX ? b : (int64_t)INT_MAX);
-}
+// Elementwise passes: one 16-byte item per thread and as many workgroups as that takes — grid_for(.., .., INT_MAX), no cap —
+// (measured faster than a capped grid-stride loop: 6.5 vs 4.9 TB/s on a 1 GiB copy, tools/scratch/copybench.hip), non-temporal
+// loads/stores (kStreamNT).
 
 // XCDs of the current device: hipDeviceAttributeNumberOfXccs, read once per device (a value that is not 1, 2, 4 or 8 — or a
 // failed query — keeps 8); the device-side copy c_xcd is rewritten the first time a device reports something else.
@@ -2132,7 +2123,7 @@ static int spmm_csr_launch(const int32_t *rowptr, const int32_t *colind, const f
     else
       SN_DISPATCH_N(spmm_csr_rows, N, x_group, y_group, grid, s, rowptr, colind, vals, (int)M, X, ldx, Y, ldy, (int)nchunks, iters);
   } else {
-    SN_KLAUNCH(spmm_csr_any, grid_for(M * (int64_t)N, kWG), s, rowptr, colind, vals, M, (int)N, X, ldx, (int)x_group, Y,
+    SN_KLAUNCH(spmm_csr_any, grid_for(M * (int64_t)N, kWG, INT_MAX), s, rowptr, colind, vals, M, (int)N, X, ldx, (int)x_group, Y,
                ldy, (int)y_group);
   }
   return launch_status();
@@ -2197,7 +2188,7 @@ int sn_rb4_count(const int32_t *rowptr, const int32_t *colind, int64_t M, int64_
   hipError_t e = sn_internal_fill(b_ptr + Mb, 0, sizeof(int), s);
   if (e != hipSuccess) return (int)e;
   if (Mb > 0)
-    hipLaunchKernelGGL((rb4_merge<false>), dim3(grid_for(Mb, kWG)), dim3(kWG), 0, s, rowptr, colind, (const float *)nullptr, M, Mb,
+    hipLaunchKernelGGL((rb4_merge<false>), dim3(grid_for(Mb, kWG, INT_MAX)), dim3(kWG), 0, s, rowptr, colind, (const float *)nullptr, M, Mb,
                        b_ptr, (int *)nullptr, (float *)nullptr);
   return exclusive_scan_i32(b_ptr, Mb + 1, b_ptr, workspace, workspace_bytes, s);
 }
@@ -2211,7 +2202,7 @@ int sn_rb4_fill(const int32_t *rowptr, const int32_t *colind, const float *vals,
   if (Mb == 0) return SN_OK;
   if (!colind || !vals || !b_col || !b_val) return SN_E_NULL;
   if (!aligned16(b_val)) return SN_E_ALIGN;
-  hipLaunchKernelGGL((rb4_merge<true>), dim3(grid_for(Mb, kWG)), dim3(kWG), 0, static_cast<hipStream_t>(stream), rowptr, colind,
+  hipLaunchKernelGGL((rb4_merge<true>), dim3(grid_for(Mb, kWG, INT_MAX)), dim3(kWG), 0, static_cast<hipStream_t>(stream), rowptr, colind,
                      vals, M, Mb, const_cast<int *>(b_ptr), b_col, b_val);
   return launch_status();
 }
@@ -2637,7 +2628,7 @@ int sn_elu_tail_finish_f32(float *g, int64_t ldg, const float *E, int64_t lde, c
   if (!g || !E || !center || !B || !Cc) return SN_E_NULL;
   if (!aligned16(g) || !aligned16(E) || !aligned16(center) || !aligned16(B) || !aligned16(Cc) || (ldg & 3) || (lde & 3))
     return SN_E_ALIGN;
-  hipLaunchKernelGGL(tail_finish_k, dim3(grid_for(rows * (C / 4), kWG)), dim3(kWG), 0, static_cast<hipStream_t>(stream), g, ldg, E,
+  hipLaunchKernelGGL(tail_finish_k, dim3(grid_for(rows * (C / 4), kWG, INT_MAX)), dim3(kWG), 0, static_cast<hipStream_t>(stream), g, ldg, E,
                      lde, center, B, Cc, rows, (int)(C / 4));
   return launch_status();
 }
@@ -2653,7 +2644,7 @@ int sn_bsr4_to_q3_f32(const int32_t *b_colind, const float *b_vals, int64_t nblo
   if (nblocks == 0) return SN_OK;
   if (!b_colind || !b_vals || !q_blk) return SN_E_NULL;
   if (!aligned16(b_vals) || !aligned16(q_blk)) return SN_E_ALIGN;
-  hipLaunchKernelGGL(bsr4_to_q3_k, dim3(grid_for(nblocks, kWG)), dim3(kWG), 0, s, b_colind, b_vals, nblocks,
+  hipLaunchKernelGGL(bsr4_to_q3_k, dim3(grid_for(nblocks, kWG, INT_MAX)), dim3(kWG), 0, s, b_colind, b_vals, nblocks,
                      reinterpret_cast<f4 *>(q_blk), not_quaternion);
   return launch_status();
 }
@@ -2667,7 +2658,7 @@ int sn_coo_to_csr_i32(const int64_t *idx_batch, const int64_t *idx_row, const in
   if (!fits_i32(M + 1) || !fits_i32(B * Kb) || !fits_i32(nnz)) return SN_E_RANGE;
   if (!rowptr || (nnz > 0 && (!idx_row || !idx_col || !colind))) return SN_E_NULL;
   const int64_t n = (M + 1 > nnz) ? M + 1 : nnz;
-  hipLaunchKernelGGL(coo_to_csr_k, dim3(grid_for(n, kWG)), dim3(kWG), 0, static_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(coo_to_csr_k, dim3(grid_for(n, kWG, INT_MAX)), dim3(kWG), 0, static_cast<hipStream_t>(stream),
                      idx_batch, idx_row, idx_col, nnz, M, R, Kb, rowptr, colind);
   return launch_status();
 }
@@ -2703,14 +2694,14 @@ int sn_csr_transpose_f32(const int32_t *rowptr, const int32_t *colind, const flo
   int *cursor = static_cast<int *>(workspace);
   const size_t cursor_bytes = ((size_t)K * sizeof(int) + 15) & ~(size_t)15;
   void *scan_ws = static_cast<char *>(workspace) + cursor_bytes;
-  hipLaunchKernelGGL(histogram_cols, dim3(grid_for(nnz, kWG)), dim3(kWG), 0, s, colind, nnz, t_rowptr);
+  hipLaunchKernelGGL(histogram_cols, dim3(grid_for(nnz, kWG, INT_MAX)), dim3(kWG), 0, s, colind, nnz, t_rowptr);
   int st = exclusive_scan_i32(t_rowptr, K + 1, t_rowptr, scan_ws, workspace_bytes - cursor_bytes, s);
   if (st) return st;
   e = sn_internal_copy2d(cursor, 0, t_rowptr, 0, (int64_t)((size_t)K * sizeof(int)), 1, s);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(transpose_scatter, dim3(grid_for(M, kWG)), dim3(kWG), 0, s, rowptr, colind, vals, M,
+  hipLaunchKernelGGL(transpose_scatter, dim3(grid_for(M, kWG, INT_MAX)), dim3(kWG), 0, s, rowptr, colind, vals, M,
                      cursor, t_colind, t_vals);
-  hipLaunchKernelGGL(sort_rows_by_col, dim3(grid_for(K, kWG)), dim3(kWG), 0, s, t_rowptr, K, t_colind,
+  hipLaunchKernelGGL(sort_rows_by_col, dim3(grid_for(K, kWG, INT_MAX)), dim3(kWG), 0, s, t_rowptr, K, t_colind,
                      t_vals);
   return launch_status();
 }
@@ -2728,7 +2719,7 @@ int sn_bsr4_count(const int32_t *rowptr, const int32_t *colind, int64_t M, int64
   hipError_t e = sn_internal_fill(b_rowptr + Mb, 0, sizeof(int), s);
   if (e != hipSuccess) return (int)e;
   if (Mb > 0)
-    hipLaunchKernelGGL((bsr4_merge<false>), dim3(grid_for(Mb, kWG)), dim3(kWG), 0, s, rowptr, colind,
+    hipLaunchKernelGGL((bsr4_merge<false>), dim3(grid_for(Mb, kWG, INT_MAX)), dim3(kWG), 0, s, rowptr, colind,
                        (const float *)nullptr, Mb, b_rowptr, (int *)nullptr, (float *)nullptr);
   return exclusive_scan_i32(b_rowptr, Mb + 1, b_rowptr, workspace, workspace_bytes, s);
 }
@@ -2743,7 +2734,7 @@ int sn_bsr4_fill(const int32_t *rowptr, const int32_t *colind, const float *vals
   if (Mb == 0) return SN_OK;
   if (!colind || !vals || !b_colind || !b_vals) return SN_E_NULL;
   if (!aligned16(b_vals)) return SN_E_ALIGN;
-  hipLaunchKernelGGL((bsr4_merge<true>), dim3(grid_for(Mb, kWG)), dim3(kWG), 0,
+  hipLaunchKernelGGL((bsr4_merge<true>), dim3(grid_for(Mb, kWG, INT_MAX)), dim3(kWG), 0,
                      static_cast<hipStream_t>(stream), rowptr, colind, vals, Mb,
                      const_cast<int *>(b_rowptr), b_colind, b_vals);
   return launch_status();
@@ -2762,17 +2753,17 @@ int sn_blockdiag_concat_i32(const int32_t *pool_rowptr, const int32_t *pool_coli
   if (total > 0 && (!pool_vals || !out_vals || (vals_per_entry != 4 && (!pool_colind || !out_colind)))) return SN_E_NULL;
   if (vals_per_entry != 1 && total > 0 && (!aligned16(pool_vals) || !aligned16(out_vals))) return SN_E_ALIGN;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(blockdiag_rowptr, dim3(grid_for(B * size0 + 1, kWG)), dim3(kWG), 0, s, pool_rowptr,
+  hipLaunchKernelGGL(blockdiag_rowptr, dim3(grid_for(B * size0 + 1, kWG, INT_MAX)), dim3(kWG), 0, s, pool_rowptr,
                      desc, B, size0, total, out_rowptr);
   if (total > 0) {
     if (vals_per_entry == 1)
-      hipLaunchKernelGGL((blockdiag_entries<1>), dim3(grid_for(total, kWG)), dim3(kWG), 0, s, pool_colind,
+      hipLaunchKernelGGL((blockdiag_entries<1>), dim3(grid_for(total, kWG, INT_MAX)), dim3(kWG), 0, s, pool_colind,
                          pool_vals, desc, B, size1, total, out_colind, out_vals);
     else if (vals_per_entry == 4)
-      hipLaunchKernelGGL((blockdiag_entries<4>), dim3(grid_for(total, kWG)), dim3(kWG), 0, s, pool_colind,
+      hipLaunchKernelGGL((blockdiag_entries<4>), dim3(grid_for(total, kWG, INT_MAX)), dim3(kWG), 0, s, pool_colind,
                          pool_vals, desc, B, size1, total, out_colind, out_vals);
     else
-      hipLaunchKernelGGL((blockdiag_entries<16>), dim3(grid_for(total, kWG)), dim3(kWG), 0, s, pool_colind,
+      hipLaunchKernelGGL((blockdiag_entries<16>), dim3(grid_for(total, kWG, INT_MAX)), dim3(kWG), 0, s, pool_colind,
                          pool_vals, desc, B, size1, total, out_colind, out_vals);
   }
   return launch_status();
@@ -2796,10 +2787,10 @@ int sn_blockdiag_concat_ragged_i32(const int32_t *pool_rowptr, const int32_t *po
     hipError_t e = sn_internal_fill(out_rowptr, 0, sizeof(int32_t), s);
     return e == hipSuccess ? SN_OK : (int)e;
   }
-  hipLaunchKernelGGL(blockdiag_rowptr_ragged, dim3(grid_for(total_rows + 1, kWG)), dim3(kWG), 0, s, pool_rowptr, desc, B,
+  hipLaunchKernelGGL(blockdiag_rowptr_ragged, dim3(grid_for(total_rows + 1, kWG, INT_MAX)), dim3(kWG), 0, s, pool_rowptr, desc, B,
                      total_rows, total, out_rowptr);
   if (total > 0) {
-    const unsigned grid = grid_for(total, kWG);
+    const unsigned grid = grid_for(total, kWG, INT_MAX);
     if (vals_per_entry == 1)
       hipLaunchKernelGGL((blockdiag_entries_ragged<1>), dim3(grid), dim3(kWG), 0, s, pool_colind, pool_vals, desc, B, total, out_colind, out_vals);
     else if (vals_per_entry == 4)
@@ -2821,7 +2812,7 @@ int sn_validate_csr_i32(const int32_t *rowptr, const int32_t *colind, const floa
   if (e != hipSuccess) return (int)e;
   if (M == 0) return SN_OK;
   if (!rowptr || (nnz > 0 && !colind)) return SN_E_NULL;
-  hipLaunchKernelGGL(validate_csr_k, dim3(grid_for(M, kWG)), dim3(kWG), 0, s, rowptr, colind, vals, M, K, nnz, flags);
+  hipLaunchKernelGGL(validate_csr_k, dim3(grid_for(M, kWG, INT_MAX)), dim3(kWG), 0, s, rowptr, colind, vals, M, K, nnz, flags);
   return launch_status();
 }
 
@@ -2843,7 +2834,7 @@ int sn_segment_colsum_ragged_f32(const float *x, int64_t ld, const int64_t *tile
   double *partial = static_cast<double *>(workspace);
   if (ntiles > 0)
     hipLaunchKernelGGL(seg_colsum_ragged_tiles_k, dim3((unsigned)ntiles), dim3(kWG), 0, s, x, ld, tiles, (int)C, partial);
-  hipLaunchKernelGGL(seg_colsum_ragged_final_k, dim3(grid_for(nseg * (int64_t)C, kWG)), dim3(kWG), 0, s, partial, seg_tile_ptr, nseg,
+  hipLaunchKernelGGL(seg_colsum_ragged_final_k, dim3(grid_for(nseg * (int64_t)C, kWG, INT_MAX)), dim3(kWG), 0, s, partial, seg_tile_ptr, nseg,
                      (int)C, scale, out);
   return launch_status();
 }
@@ -2870,10 +2861,10 @@ int sn_elu_into_f32(const float *src, int64_t lds, float *dst, int64_t ldd, int6
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool vec = (C % 4 == 0) && (lds % 4 == 0) && (ldd % 4 == 0) && aligned16(src) && aligned16(dst);
   if (vec)
-    hipLaunchKernelGGL((elu_into_k<true>), dim3(grid_for(rows * (C / 4), kWG)), dim3(kWG), 0, s, src, lds,
+    hipLaunchKernelGGL((elu_into_k<true>), dim3(grid_for(rows * (C / 4), kWG, INT_MAX)), dim3(kWG), 0, s, src, lds,
                        dst, ldd, rows, (int)C, kStreamNT);
   else
-    hipLaunchKernelGGL((elu_into_k<false>), dim3(grid_for(rows * (int64_t)C, kWG)), dim3(kWG), 0, s, src,
+    hipLaunchKernelGGL((elu_into_k<false>), dim3(grid_for(rows * (int64_t)C, kWG, INT_MAX)), dim3(kWG), 0, s, src,
                        lds, dst, ldd, rows, (int)C, kStreamNT);
   return launch_status();
 }
@@ -2889,7 +2880,7 @@ int sn_elu_bwd_acc_f32(const float *gdst, int64_t ldg, const float *gdst2, int64
   const bool vec = (C % 4 == 0) && (ldg % 4 == 0) && (ldo % 4 == 0) && (ldgs % 4 == 0) &&
                    aligned16(gdst) && aligned16(out) && aligned16(gsrc) && (!gdst2 || (aligned16(gdst2) && ldg2 % 4 == 0)) &&
                    (!gadd || (aligned16(gadd) && ldga % 4 == 0));
-  const unsigned grid = grid_for(vec ? rows * (C / 4) : rows * (int64_t)C, kWG);
+  const unsigned grid = grid_for(vec ? rows * (C / 4) : rows * (int64_t)C, kWG, INT_MAX);
   if (vec) {
     if (accumulate) hipLaunchKernelGGL((elu_bwd_k<true, true>), dim3(grid), dim3(kWG), 0, s, gdst, ldg, gdst2, ldg2, gadd, ldga, out, ldo, gsrc, ldgs, rows, (int)C, kStreamNT);
     else hipLaunchKernelGGL((elu_bwd_k<true, false>), dim3(grid), dim3(kWG), 0, s, gdst, ldg, gdst2, ldg2, gadd, ldga, out, ldo, gsrc, ldgs, rows, (int)C, kStreamNT);

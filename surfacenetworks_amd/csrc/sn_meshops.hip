@@ -14,16 +14,6 @@ namespace {
 
 constexpr int kWG = 256;
 
-inline int launch_status() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? SN_OK : (int)e;
-}
-inline unsigned grid_for(int64_t n) {
-  int64_t b = (n + kWG - 1) / kWG;
-  if (b < 1) b = 1;
-  if (b > 65535 * 16) b = 65535 * 16;
-  return (unsigned)b;
-}
 
 // mesh.dist entry: sqrt(((V[a]-V[b])**2).sum())  — (dx² + dy²) + dz², as numpy sums three terms
 __device__ __forceinline__ double edge_len(const float *__restrict__ V, int a, int b) {
@@ -74,15 +64,15 @@ __device__ __forceinline__ bool bucket_takes(const int (&v)[3], const int *__res
   return !*bad;
 }
 
-// STATUS_BIT is raised in *status (when there is one) for a face that fails face_ok
-template <BucketKey KEY, BucketFilter FILTER, int STATUS_BIT>
+// status_bit is raised in *status (when there is one) for a face that fails face_ok
+template <BucketKey KEY, BucketFilter FILTER>
 __global__ __launch_bounds__(kWG) void bucket_count_k(const int *__restrict__ F, const int *__restrict__ keep, int64_t nF, int64_t nV,
-                                                      int *__restrict__ count, int *__restrict__ status) {
+                                                      int *__restrict__ count, int *__restrict__ status, int status_bit) {
   for (int64_t f = (int64_t)blockIdx.x * kWG + threadIdx.x; f < nF; f += (int64_t)gridDim.x * kWG) {
     const int v[3] = {F[3 * f], F[3 * f + 1], F[3 * f + 2]};
     bool bad;
     if (!bucket_takes<FILTER>(v, keep, f, nV, &bad)) {
-      if (bad && status) atomicOr(status, STATUS_BIT);
+      if (bad && status) atomicOr(status, status_bit);
       continue;
     }
 #pragma unroll
@@ -1568,9 +1558,9 @@ inline int incidence_build(const int *F, int64_t nV, int64_t nF, const BucketWs 
   const int st = bucket_offsets(b.ptr, b.cursor, b.sums, nV, s);
   if (st != SN_OK) return st;
   if (nF > 0)
-    hipLaunchKernelGGL((bucket_fill_k<kCornerVertex, kGoodFaces, 3>), dim3(grid_for(nF)), dim3(kWG), 0, s, F, (const int *)nullptr, nF, nV,
+    hipLaunchKernelGGL((bucket_fill_k<kCornerVertex, kGoodFaces, 3>), dim3(grid_for(nF, kWG)), dim3(kWG), 0, s, F, (const int *)nullptr, nF, nV,
                        b.cursor, b.bucket);
-  if (nV > 0) hipLaunchKernelGGL(vertex_sort_k, dim3(grid_for(nV)), dim3(kWG), 0, s, b.ptr, nV, b.bucket);
+  if (nV > 0) hipLaunchKernelGGL(vertex_sort_k, dim3(grid_for(nV, kWG)), dim3(kWG), 0, s, b.ptr, nV, b.bucket);
   return SN_OK;
 }
 
@@ -1579,14 +1569,14 @@ inline int incidence_build(const int *F, int64_t nV, int64_t nF, const BucketWs 
 // the by-vertex incidence of the good faces for the builders of other translation units (sn_internal.h)
 size_t sn_internal_incidence_bytes(int64_t nV, int64_t nF) { return MeshBucketWs(nullptr, at_least_0(nV), at_least_0(nF)).c.bytes; }
 
-int sn_internal_incidence(const int *F, int64_t nV, int64_t nF, void *workspace, int *status, const int **ptr, const int **inc,
-                          int **sums, hipStream_t s) {
+int sn_internal_incidence(const int *F, int64_t nV, int64_t nF, void *workspace, int *status, int bad_face_bit, const int **ptr,
+                          const int **inc, int **sums, hipStream_t s) {
   const BucketWs b = MeshBucketWs(workspace, nV, nF).b;
   const hipError_t e = sn_internal_fill(b.ptr, 0, (size_t)(nV + 1) * sizeof(int), s);
   if (e != hipSuccess) return (int)e;
   if (nF > 0)
-    hipLaunchKernelGGL((bucket_count_k<kCornerVertex, kGoodFaces, SN_ARAP_BAD_FACE>), dim3(grid_for(nF)), dim3(kWG), 0, s, F,
-                       (const int *)nullptr, nF, nV, b.ptr, status);
+    hipLaunchKernelGGL((bucket_count_k<kCornerVertex, kGoodFaces>), dim3(grid_for(nF, kWG)), dim3(kWG), 0, s, F,
+                       (const int *)nullptr, nF, nV, b.ptr, status, bad_face_bit);
   const int st = incidence_build(F, nV, nF, b, s);
   *ptr = b.ptr;
   *inc = b.bucket;
@@ -1616,15 +1606,15 @@ int sn_dirac_bsr4_from_mesh(const float *V, const int32_t *F, int64_t nV, int64_
   int *vptr = ws.b.ptr, *inc = ws.b.bucket;      // the faces are not validated on this path: codes 4 f + c of every face
   const hipError_t e = sn_internal_fill(vptr, 0, (size_t)(nV + 1) * sizeof(int), s);
   if (e != hipSuccess) return (int)e;
-  if (nF > 0) hipLaunchKernelGGL(face_area_k, dim3(grid_for(nF)), dim3(kWG), 0, s, V, F, nF, Af, vptr);
+  if (nF > 0) hipLaunchKernelGGL(face_area_k, dim3(grid_for(nF, kWG)), dim3(kWG), 0, s, V, F, nF, Af, vptr);
   const int st = bucket_offsets(vptr, ws.b.cursor, ws.b.sums, nV, s);
   if (st != SN_OK) return st;
   if (nF > 0)
-    hipLaunchKernelGGL((bucket_fill_k<kCornerVertex, kEveryFace, 4>), dim3(grid_for(nF)), dim3(kWG), 0, s, F, (const int *)nullptr, nF, nV,
+    hipLaunchKernelGGL((bucket_fill_k<kCornerVertex, kEveryFace, 4>), dim3(grid_for(nF, kWG)), dim3(kWG), 0, s, F, (const int *)nullptr, nF, nV,
                        ws.b.cursor, inc);
-  if (nV > 0) hipLaunchKernelGGL(vertex_lists_k, dim3(grid_for(nV)), dim3(kWG), 0, s, vptr, nV, inc, Af, Av, dia_colind);
-  hipLaunchKernelGGL(di_fill_k, dim3(grid_for(nF + 1)), dim3(kWG), 0, s, V, F, nF, Af, Av, di_rowptr, di_colind, di_vals, diat_vals);
-  hipLaunchKernelGGL(dia_fill_k, dim3(grid_for(nV + 1)), dim3(kWG), 0, s, V, F, nV, vptr, inc, Af, Av, dia_rowptr, dia_vals, dit_vals);
+  if (nV > 0) hipLaunchKernelGGL(vertex_lists_k, dim3(grid_for(nV, kWG)), dim3(kWG), 0, s, vptr, nV, inc, Af, Av, dia_colind);
+  hipLaunchKernelGGL(di_fill_k, dim3(grid_for(nF + 1, kWG)), dim3(kWG), 0, s, V, F, nF, Af, Av, di_rowptr, di_colind, di_vals, diat_vals);
+  hipLaunchKernelGGL(dia_fill_k, dim3(grid_for(nV + 1, kWG)), dim3(kWG), 0, s, V, F, nV, vptr, inc, Af, Av, dia_rowptr, dia_vals, dit_vals);
   return launch_status();
 }
 
@@ -1651,21 +1641,21 @@ int sn_laplacian_csr_from_mesh(const float *V, const int32_t *F, int64_t nV, int
       e = sn_internal_fill(status_flag, 0, sizeof(int), s);
       if (e != hipSuccess) return (int)e;
     }
-    if (nF > 0) hipLaunchKernelGGL(face_area_k, dim3(grid_for(nF)), dim3(kWG), 0, s, V, F, nF, Af, vptr);
+    if (nF > 0) hipLaunchKernelGGL(face_area_k, dim3(grid_for(nF, kWG)), dim3(kWG), 0, s, V, F, nF, Af, vptr);
     const int st = bucket_offsets(vptr, ws.b.cursor, ws.b.sums, nV, s);
     if (st != SN_OK) return st;
     if (nF > 0)
-      hipLaunchKernelGGL((bucket_fill_k<kCornerVertex, kEveryFace, 4>), dim3(grid_for(nF)), dim3(kWG), 0, s, F, (const int *)nullptr, nF,
+      hipLaunchKernelGGL((bucket_fill_k<kCornerVertex, kEveryFace, 4>), dim3(grid_for(nF, kWG)), dim3(kWG), 0, s, F, (const int *)nullptr, nF,
                          nV, ws.b.cursor, inc);
-    if (nV > 0) hipLaunchKernelGGL(vertex_sort_k, dim3(grid_for(nV)), dim3(kWG), 0, s, vptr, nV, inc);
+    if (nV > 0) hipLaunchKernelGGL(vertex_sort_k, dim3(grid_for(nV, kWG)), dim3(kWG), 0, s, vptr, nV, inc);
     e = sn_internal_fill(rowptr + nV, 0, sizeof(int), s);
     if (e != hipSuccess) return (int)e;
     if (nV > 0)
-      hipLaunchKernelGGL((laplacian_rows_k<false>), dim3(grid_for(nV)), dim3(kWG), 0, s, V, F, nV, vptr, inc, Af, rowptr,
+      hipLaunchKernelGGL((laplacian_rows_k<false>), dim3(grid_for(nV, kWG)), dim3(kWG), 0, s, V, F, nV, vptr, inc, Af, rowptr,
                          (int *)nullptr, (float *)nullptr, status_flag);
     scan_in_place(rowptr, nV + 1, ws.b.sums, s);
   } else if (nV > 0) {
-    hipLaunchKernelGGL((laplacian_rows_k<true>), dim3(grid_for(nV)), dim3(kWG), 0, s, V, F, nV, vptr, inc, Af, rowptr, colind,
+    hipLaunchKernelGGL((laplacian_rows_k<true>), dim3(grid_for(nV, kWG)), dim3(kWG), 0, s, V, F, nV, vptr, inc, Af, rowptr, colind,
                        vals, (int *)nullptr);
   }
   return launch_status();
@@ -1679,7 +1669,7 @@ int sn_edge_lengths_csr_f32(const float *V, const int32_t *rowptr, const int32_t
   if (!V || !rowptr) return SN_E_NULL;
   if (!colind != !w) return SN_E_NULL;
   if (!colind) return SN_OK;                                     // a pattern without entries
-  hipLaunchKernelGGL(edge_lengths_csr_k, dim3(grid_for(n)), dim3(kWG), 0, static_cast<hipStream_t>(stream), V, rowptr, colind, n, w);
+  hipLaunchKernelGGL(edge_lengths_csr_k, dim3(grid_for(n, kWG)), dim3(kWG), 0, static_cast<hipStream_t>(stream), V, rowptr, colind, n, w);
   return launch_status();
 }
 
@@ -1744,12 +1734,12 @@ int sn_mesh_corners_f32(const float *V, const int32_t *F, int64_t nV, int64_t nF
     if (e != hipSuccess) return (int)e;
   }
   if (nF > 0)      // (the flag of this entry point is 1)
-    hipLaunchKernelGGL((bucket_count_k<kCornerVertex, kGoodFaces, 1>), dim3(grid_for(nF)), dim3(kWG), 0, s, F, (const int *)nullptr, nF, nV,
-                       cptr, status_flag);
+    hipLaunchKernelGGL((bucket_count_k<kCornerVertex, kGoodFaces>), dim3(grid_for(nF, kWG)), dim3(kWG), 0, s, F, (const int *)nullptr, nF, nV,
+                       cptr, status_flag, 1);
   const int st = bucket_offsets(cptr, ws.cursor, ws.sums, nV, s);
   if (st != SN_OK) return st;
   if (nF > 0)
-    hipLaunchKernelGGL(corner_fill_k, dim3(grid_for(nF)), dim3(kWG), 0, s, V, F, nF, nV, ws.cursor, static_cast<MeshCorner *>(corners));
+    hipLaunchKernelGGL(corner_fill_k, dim3(grid_for(nF, kWG)), dim3(kWG), 0, s, V, F, nF, nV, ws.cursor, static_cast<MeshCorner *>(corners));
   return launch_status();
 }
 
@@ -1797,13 +1787,13 @@ int sn_mesh_glue_i32(const float *V, const int32_t *F, int64_t nV, int64_t nF, i
   e = sn_internal_fill(status, 0, sizeof(int), s);
   if (e != hipSuccess) return (int)e;
   if (nF == 0) return SN_OK;
-  hipLaunchKernelGGL((bucket_count_k<kCornerVertex, kGoodFaces, SN_IDT_BAD_FACE>), dim3(grid_for(nF)), dim3(kWG), 0, s, F,
-                     (const int *)nullptr, nF, nV, b.ptr, status);
+  hipLaunchKernelGGL((bucket_count_k<kCornerVertex, kGoodFaces>), dim3(grid_for(nF, kWG)), dim3(kWG), 0, s, F,
+                     (const int *)nullptr, nF, nV, b.ptr, status, SN_IDT_BAD_FACE);
   const int st = bucket_offsets(b.ptr, b.cursor, b.sums, nV, s);
   if (st != SN_OK) return st;
-  hipLaunchKernelGGL((bucket_fill_k<kCornerVertex, kGoodFaces, 3>), dim3(grid_for(nF)), dim3(kWG), 0, s, F, (const int *)nullptr, nF, nV,
+  hipLaunchKernelGGL((bucket_fill_k<kCornerVertex, kGoodFaces, 3>), dim3(grid_for(nF, kWG)), dim3(kWG), 0, s, F, (const int *)nullptr, nF, nV,
                      b.cursor, b.bucket);
-  hipLaunchKernelGGL(glue_twin_k, dim3(grid_for(3 * nF)), dim3(kWG), 0, s, V, F, nF, nV, b.ptr, b.bucket, G, l, status);
+  hipLaunchKernelGGL(glue_twin_k, dim3(grid_for(3 * nF, kWG)), dim3(kWG), 0, s, V, F, nF, nV, b.ptr, b.bucket, G, l, status);
   return launch_status();
 }
 
@@ -1831,9 +1821,9 @@ int sn_mesh_idt_rounds_f64(int32_t *Fp, double *lp, int32_t *G, int64_t nF, int3
   }
   const int64_t nS = 3 * nF;
   for (int r = round_begin; r < round_begin + round_count; ++r) {
-    hipLaunchKernelGGL(idt_claim_k, dim3(grid_for(nS)), dim3(kWG), 0, s, lp, G, nS, claim, (unsigned)r, r == max_rounds - 1 ? 1 : 0,
+    hipLaunchKernelGGL(idt_claim_k, dim3(grid_for(nS, kWG)), dim3(kWG), 0, s, lp, G, nS, claim, (unsigned)r, r == max_rounds - 1 ? 1 : 0,
                        counters + 2 * (int64_t)r, status);
-    hipLaunchKernelGGL(idt_flip_k, dim3(grid_for(nS)), dim3(kWG), 0, s, Fp, lp, G, nS, claim, (unsigned)r, counters + 2 * (int64_t)r,
+    hipLaunchKernelGGL(idt_flip_k, dim3(grid_for(nS, kWG)), dim3(kWG), 0, s, Fp, lp, G, nS, claim, (unsigned)r, counters + 2 * (int64_t)r,
                        status);
   }
   return launch_status();
@@ -1860,16 +1850,16 @@ int sn_mesh_idt_laplacian_f32(const int32_t *Fp, const double *lp, int64_t nV, i
   hipStream_t s = static_cast<hipStream_t>(stream);
   const IdtLapWs ws(workspace, nV, nF);
   if (phase == 0) {
-    if (N > 0) hipLaunchKernelGGL(idt_contrib_k, dim3(grid_for(nF + nV)), dim3(kWG), 0, s, Fp, lp, nV, nF, keys, ws.cval, ws.cmass, status);
+    if (N > 0) hipLaunchKernelGGL(idt_contrib_k, dim3(grid_for(nF + nV, kWG)), dim3(kWG), 0, s, Fp, lp, nV, nF, keys, ws.cval, ws.cmass, status);
   } else if (phase == 1) {
-    hipLaunchKernelGGL(idt_heads_k, dim3(grid_for(N + 1)), dim3(kWG), 0, s, keys, N, span, ws.hs);
+    hipLaunchKernelGGL(idt_heads_k, dim3(grid_for(N + 1, kWG)), dim3(kWG), 0, s, keys, N, span, ws.hs);
     scan_in_place(ws.hs, N + 1, ws.sums, s);
-    hipLaunchKernelGGL(idt_rowptr_k, dim3(grid_for(nV + 1)), dim3(kWG), 0, s, keys, N, nV, span, ws.hs, rowptr);
+    hipLaunchKernelGGL(idt_rowptr_k, dim3(grid_for(nV + 1, kWG)), dim3(kWG), 0, s, keys, N, nV, span, ws.hs, rowptr);
   } else if (N > 0) {
     if (!colind || !vals) return SN_E_NULL;
-    hipLaunchKernelGGL((idt_entries_k<true>), dim3(grid_for(N)), dim3(kWG), 0, s, keys, order, N, nV, span, ws.hs, ws.cmass, ws.A,
+    hipLaunchKernelGGL((idt_entries_k<true>), dim3(grid_for(N, kWG)), dim3(kWG), 0, s, keys, order, N, nV, span, ws.hs, ws.cmass, ws.A,
                        (int *)nullptr, (float *)nullptr);
-    hipLaunchKernelGGL((idt_entries_k<false>), dim3(grid_for(N)), dim3(kWG), 0, s, keys, order, N, nV, span, ws.hs, ws.cval, ws.A,
+    hipLaunchKernelGGL((idt_entries_k<false>), dim3(grid_for(N, kWG)), dim3(kWG), 0, s, keys, order, N, nV, span, ws.hs, ws.cval, ws.A,
                        colind, vals);
   }
   return launch_status();
@@ -1900,26 +1890,26 @@ int sn_mesh_components_i32(const int32_t *F, int64_t nV, int64_t nF, int32_t mod
   e = sn_internal_fill(status, 0, sizeof(int), s);
   if (e != hipSuccess) return (int)e;
   int *parent = vertex ? vlabel : flabel;
-  if (n > 0) hipLaunchKernelGGL(cc_init_k, dim3(grid_for(n)), dim3(kWG), 0, s, parent, count, n);
+  if (n > 0) hipLaunchKernelGGL(cc_init_k, dim3(grid_for(n, kWG)), dim3(kWG), 0, s, parent, count, n);
   if (vertex) {
-    if (nF > 0) hipLaunchKernelGGL(cc_vertex_union_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, nV, parent, status);
-    if (nV > 0) hipLaunchKernelGGL(cc_flatten_k, dim3(grid_for(nV)), dim3(kWG), 0, s, parent, nV, status);
-    if (nF > 0) hipLaunchKernelGGL((cc_face_labels_k<true>), dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, nV, vlabel, flabel, count, status);
+    if (nF > 0) hipLaunchKernelGGL(cc_vertex_union_k, dim3(grid_for(nF, kWG)), dim3(kWG), 0, s, F, nF, nV, parent, status);
+    if (nV > 0) hipLaunchKernelGGL(cc_flatten_k, dim3(grid_for(nV, kWG)), dim3(kWG), 0, s, parent, nV, status);
+    if (nF > 0) hipLaunchKernelGGL((cc_face_labels_k<true>), dim3(grid_for(nF, kWG)), dim3(kWG), 0, s, F, nF, nV, vlabel, flabel, count, status);
   } else if (nF > 0) {
     const BucketWs &b = ws.b;
     e = sn_internal_fill(b.ptr, 0, (size_t)(nV + 1) * sizeof(int), s);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((bucket_count_k<kLowerEnd, kGoodFaces, SN_CC_BAD_FACE>), dim3(grid_for(nF)), dim3(kWG), 0, s, F,
-                       (const int *)nullptr, nF, nV, b.ptr, status);
+    hipLaunchKernelGGL((bucket_count_k<kLowerEnd, kGoodFaces>), dim3(grid_for(nF, kWG)), dim3(kWG), 0, s, F,
+                       (const int *)nullptr, nF, nV, b.ptr, status, SN_CC_BAD_FACE);
     const int st = bucket_offsets(b.ptr, b.cursor, b.sums, nV, s);
     if (st != SN_OK) return st;
-    hipLaunchKernelGGL((bucket_fill_k<kLowerEnd, kGoodFaces, 3>), dim3(grid_for(nF)), dim3(kWG), 0, s, F, (const int *)nullptr, nF, nV,
+    hipLaunchKernelGGL((bucket_fill_k<kLowerEnd, kGoodFaces, 3>), dim3(grid_for(nF, kWG)), dim3(kWG), 0, s, F, (const int *)nullptr, nF, nV,
                        b.cursor, b.bucket);
-    hipLaunchKernelGGL(cc_edge_union_k, dim3(grid_for(3 * nF)), dim3(kWG), 0, s, F, nF, nV, b.ptr, b.bucket, parent, status);
-    hipLaunchKernelGGL((cc_face_labels_k<false>), dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, nV, (const int *)nullptr, flabel, count, status);
-    hipLaunchKernelGGL(cc_bad_labels_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, nV, flabel);
+    hipLaunchKernelGGL(cc_edge_union_k, dim3(grid_for(3 * nF, kWG)), dim3(kWG), 0, s, F, nF, nV, b.ptr, b.bucket, parent, status);
+    hipLaunchKernelGGL((cc_face_labels_k<false>), dim3(grid_for(nF, kWG)), dim3(kWG), 0, s, F, nF, nV, (const int *)nullptr, flabel, count, status);
+    hipLaunchKernelGGL(cc_bad_labels_k, dim3(grid_for(nF, kWG)), dim3(kWG), 0, s, F, nF, nV, flabel);
   }
-  if (n > 0) hipLaunchKernelGGL(cc_winner_k, dim3(grid_for(n)), dim3(kWG), 0, s, count, n, acc);
+  if (n > 0) hipLaunchKernelGGL(cc_winner_k, dim3(grid_for(n, kWG)), dim3(kWG), 0, s, count, n, acc);
   hipLaunchKernelGGL(cc_summary_k, dim3(1), dim3(64), 0, s, acc, summary);
   return launch_status();
 }
@@ -1930,7 +1920,7 @@ int sn_mesh_label_mask_i32(const int32_t *flabel, int64_t nF, const int32_t *lab
   if (3 * nF > INT_MAX) return SN_E_RANGE;
   if (nF == 0) return SN_OK;
   if (!flabel || !label || !keep) return SN_E_NULL;
-  hipLaunchKernelGGL(label_mask_k, dim3(grid_for(nF)), dim3(kWG), 0, static_cast<hipStream_t>(stream), flabel, nF, label, keep);
+  hipLaunchKernelGGL(label_mask_k, dim3(grid_for(nF, kWG)), dim3(kWG), 0, static_cast<hipStream_t>(stream), flabel, nF, label, keep);
   return launch_status();
 }
 
@@ -1954,11 +1944,11 @@ int sn_mesh_compact_i32(const float *V, const int32_t *F, const int32_t *keep, i
   int *vpos = ws.vpos, *fpos = ws.fpos, *sums = ws.sums;
   hipError_t e = sn_internal_fill(vpos, 0, (size_t)(nV + 1) * sizeof(int), s);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(compact_mark_k, dim3(grid_for(nF + 1)), dim3(kWG), 0, s, F, keep, nF, nV, fpos, vpos);
+  hipLaunchKernelGGL(compact_mark_k, dim3(grid_for(nF + 1, kWG)), dim3(kWG), 0, s, F, keep, nF, nV, fpos, vpos);
   scan_in_place(fpos, nF + 1, sums, s);
   scan_in_place(vpos, nV + 1, sums, s);
-  hipLaunchKernelGGL(compact_vertices_k, dim3(grid_for(nV + 1)), dim3(kWG), 0, s, V, nV, vpos, I, J, Vnew, fpos, nF, sizes);
-  if (nF > 0) hipLaunchKernelGGL(compact_faces_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, nF, fpos, vpos, Fsrc, Fnew);
+  hipLaunchKernelGGL(compact_vertices_k, dim3(grid_for(nV + 1, kWG)), dim3(kWG), 0, s, V, nV, vpos, I, J, Vnew, fpos, nF, sizes);
+  if (nF > 0) hipLaunchKernelGGL(compact_faces_k, dim3(grid_for(nF, kWG)), dim3(kWG), 0, s, F, nF, fpos, vpos, Fsrc, Fnew);
   return launch_status();
 }
 
@@ -1983,11 +1973,11 @@ int sn_mesh_descriptors_f32(const float *V, const int32_t *F, int64_t nV, int64_
   if (e != hipSuccess) return (int)e;
   e = sn_internal_fill(status, 0, sizeof(int), s);
   if (e != hipSuccess) return (int)e;
-  if (nF > 0) hipLaunchKernelGGL(desc_face_k, dim3(grid_for(nF)), dim3(kWG), 0, s, V, F, nF, nV, vptr, face_area, face_normal, status);
+  if (nF > 0) hipLaunchKernelGGL(desc_face_k, dim3(grid_for(nF, kWG)), dim3(kWG), 0, s, V, F, nF, nV, vptr, face_area, face_normal, status);
   if (per_vertex && nV > 0) {
     const int st = incidence_build(F, nV, nF, b, s);
     if (st != SN_OK) return st;
-    hipLaunchKernelGGL(desc_vertex_k, dim3(grid_for(nV)), dim3(kWG), 0, s, V, F, nV, vptr, inc, n_area, n_uniform, n_angle, mass_bary,
+    hipLaunchKernelGGL(desc_vertex_k, dim3(grid_for(nV, kWG)), dim3(kWG), 0, s, V, F, nV, vptr, inc, n_area, n_uniform, n_angle, mass_bary,
                        mass_voronoi, gauss, mean, status);
   }
   return launch_status();
@@ -2012,20 +2002,20 @@ int cot_rows_phases(const float *V, const int32_t *F, int64_t nV, int64_t nF, in
     e = sn_internal_fill(status, 0, sizeof(int), s);
     if (e != hipSuccess) return (int)e;
     if (nF > 0)
-      hipLaunchKernelGGL(desc_face_k, dim3(grid_for(nF)), dim3(kWG), 0, s, V, F, nF, nV, vptr, (float *)nullptr, (float *)nullptr, status);
+      hipLaunchKernelGGL(desc_face_k, dim3(grid_for(nF, kWG)), dim3(kWG), 0, s, V, F, nF, nV, vptr, (float *)nullptr, (float *)nullptr, status);
     const int st = incidence_build(F, nV, nF, b, s);
     if (st != SN_OK) return st;
     e = sn_internal_fill(rowptr + nV, 0, sizeof(int), s);
     if (e != hipSuccess) return (int)e;
     if (nV > 0)
-      hipLaunchKernelGGL((cot_laplacian_rows_k<false>), dim3(grid_for(nV)), dim3(kWG), 0, s, V, F, nV, vptr, inc, voronoi, 0, 0.f, rowptr,
+      hipLaunchKernelGGL((cot_laplacian_rows_k<false>), dim3(grid_for(nV, kWG)), dim3(kWG), 0, s, V, F, nV, vptr, inc, voronoi, 0, 0.f, rowptr,
                          (int *)nullptr, (float *)nullptr, status);
     scan_in_place(rowptr, nV + 1, b.sums, s);
   } else if (nV > 0 && vals64) {
-    hipLaunchKernelGGL((cot_laplacian_rows_k<true, true>), dim3(grid_for(nV)), dim3(kWG), 0, s, V, F, nV, vptr, inc, voronoi, 0, 0.f,
+    hipLaunchKernelGGL((cot_laplacian_rows_k<true, true>), dim3(grid_for(nV, kWG)), dim3(kWG), 0, s, V, F, nV, vptr, inc, voronoi, 0, 0.f,
                        rowptr, colind, (float *)nullptr, status, vals64, mass64);
   } else if (nV > 0) {
-    hipLaunchKernelGGL((cot_laplacian_rows_k<true>), dim3(grid_for(nV)), dim3(kWG), 0, s, V, F, nV, vptr, inc, voronoi, clamp != 0,
+    hipLaunchKernelGGL((cot_laplacian_rows_k<true>), dim3(grid_for(nV, kWG)), dim3(kWG), 0, s, V, F, nV, vptr, inc, voronoi, clamp != 0,
                        (float)hack, rowptr, colind, vals, status);
   }
   return launch_status();
@@ -2087,12 +2077,12 @@ int sn_mesh_weld_f32(const float *V, const int32_t *F, int64_t nV, int64_t nF, d
     if (weld) {
       e = sn_internal_fill(table, 0xff, (size_t)slots * sizeof(int), s);                    // kRepairEmpty in every slot
       if (e != hipSuccess) return (int)e;
-      hipLaunchKernelGGL((repair_insert_k<false>), dim3(grid_for(nV)), dim3(kWG), 0, s, V, (const int *)nullptr, nV, nV, tol, table,
+      hipLaunchKernelGGL((repair_insert_k<false>), dim3(grid_for(nV, kWG)), dim3(kWG), 0, s, V, (const int *)nullptr, nV, nV, tol, table,
                          slots - 1, status);
     }
-    hipLaunchKernelGGL(weld_rep_k, dim3(grid_for(nV)), dim3(kWG), 0, s, V, nV, tol, (int)weld, table, slots - 1, rep, counts, status);
+    hipLaunchKernelGGL(weld_rep_k, dim3(grid_for(nV, kWG)), dim3(kWG), 0, s, V, nV, tol, (int)weld, table, slots - 1, rep, counts, status);
   }
-  if (nF > 0) hipLaunchKernelGGL(weld_faces_k, dim3(grid_for(3 * nF)), dim3(kWG), 0, s, V, F, nF, nV, tol, (int)weld, rep, Fw, status);
+  if (nF > 0) hipLaunchKernelGGL(weld_faces_k, dim3(grid_for(3 * nF, kWG)), dim3(kWG), 0, s, V, F, nF, nV, tol, (int)weld, rep, Fw, status);
   return launch_status();
 }
 
@@ -2120,10 +2110,10 @@ int sn_mesh_unique_faces_i32(const float *V, const int32_t *F, int64_t nV, int64
   if (unique) {
     e = sn_internal_fill(table, 0xff, (size_t)slots * sizeof(int), s);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((repair_insert_k<true>), dim3(grid_for(nF)), dim3(kWG), 0, s, (const float *)nullptr, F, nF, nV, 0.0, table,
+    hipLaunchKernelGGL((repair_insert_k<true>), dim3(grid_for(nF, kWG)), dim3(kWG), 0, s, (const float *)nullptr, F, nF, nV, 0.0, table,
                        slots - 1, status);
   }
-  hipLaunchKernelGGL(unique_keep_k, dim3(grid_for(nF)), dim3(kWG), 0, s, V, F, nF, nV, (int)unique, table, slots - 1, keep, counts,
+  hipLaunchKernelGGL(unique_keep_k, dim3(grid_for(nF, kWG)), dim3(kWG), 0, s, V, F, nF, nV, (int)unique, table, slots - 1, keep, counts,
                      status);
   return launch_status();
 }
@@ -2151,16 +2141,16 @@ int sn_mesh_orient_i32(const int32_t *F, const int32_t *keep, int64_t nV, int64_
   if (nF == 0) return launch_status();
   e = sn_internal_fill(b.ptr, 0, (size_t)(nV + 1) * sizeof(int), s);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(or_init_k, dim3(grid_for(nF)), dim3(kWG), 0, s, label, conflict, nF);
-  hipLaunchKernelGGL((bucket_count_k<kLowerEnd, kGoodKeptFaces, SN_REPAIR_BAD_FACE>), dim3(grid_for(nF)), dim3(kWG), 0, s, F, keep, nF, nV,
-                     b.ptr, status);
+  hipLaunchKernelGGL(or_init_k, dim3(grid_for(nF, kWG)), dim3(kWG), 0, s, label, conflict, nF);
+  hipLaunchKernelGGL((bucket_count_k<kLowerEnd, kGoodKeptFaces>), dim3(grid_for(nF, kWG)), dim3(kWG), 0, s, F, keep, nF, nV,
+                     b.ptr, status, SN_REPAIR_BAD_FACE);
   const int st = bucket_offsets(b.ptr, b.cursor, b.sums, nV, s);
   if (st != SN_OK) return st;
-  hipLaunchKernelGGL((bucket_fill_k<kLowerEnd, kGoodKeptFaces, 3>), dim3(grid_for(nF)), dim3(kWG), 0, s, F, keep, nF, nV, b.cursor,
+  hipLaunchKernelGGL((bucket_fill_k<kLowerEnd, kGoodKeptFaces, 3>), dim3(grid_for(nF, kWG)), dim3(kWG), 0, s, F, keep, nF, nV, b.cursor,
                      b.bucket);
-  hipLaunchKernelGGL(or_link_k, dim3(grid_for(3 * nF)), dim3(kWG), 0, s, F, keep, nF, nV, b.ptr, b.bucket, label, conflict, counts, status);
-  hipLaunchKernelGGL(or_resolve_k, dim3(grid_for(nF)), dim3(kWG), 0, s, label, conflict, nF, status);
-  hipLaunchKernelGGL(or_finish_k, dim3(grid_for(nF)), dim3(kWG), 0, s, F, keep, nF, nV, label, conflict, flip, Fout, counts, status);
+  hipLaunchKernelGGL(or_link_k, dim3(grid_for(3 * nF, kWG)), dim3(kWG), 0, s, F, keep, nF, nV, b.ptr, b.bucket, label, conflict, counts, status);
+  hipLaunchKernelGGL(or_resolve_k, dim3(grid_for(nF, kWG)), dim3(kWG), 0, s, label, conflict, nF, status);
+  hipLaunchKernelGGL(or_finish_k, dim3(grid_for(nF, kWG)), dim3(kWG), 0, s, F, keep, nF, nV, label, conflict, flip, Fout, counts, status);
   return launch_status();
 }
 

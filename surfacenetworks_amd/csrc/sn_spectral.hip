@@ -16,16 +16,6 @@ namespace {
 constexpr int kWG = 256;
 constexpr int kMaxT = 4;      // columns a lane of the filter step keeps at once
 
-inline int launch_status() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? SN_OK : (int)e;
-}
-inline unsigned grid_for(int64_t n) {
-  int64_t b = (n + kWG - 1) / kWG;
-  if (b < 1) b = 1;
-  if (b > 65535 * 16) b = 65535 * 16;
-  return (unsigned)b;
-}
 
 // the mesh of row i: the last b with voff[b] <= i (meshes without rows are passed over)
 __device__ __forceinline__ int mesh_of(const int *__restrict__ voff, int B, int i) {
@@ -105,7 +95,7 @@ template <int W, int T>
 void cheb_launch(const int *rowptr, const int *colind, const double *vals, const int *voff, int B, int64_t n, int64_t m, int64_t chunks,
                  const double *alpha, const double *beta, const double *shift, const double *X, const double *Y, double *Z,
                  hipStream_t s) {
-  hipLaunchKernelGGL((cheb_step_k<W, T>), dim3(grid_for(n * chunks * W)), dim3(kWG), 0, s, rowptr, colind, vals, voff, B, n, m, chunks,
+  hipLaunchKernelGGL((cheb_step_k<W, T>), dim3(grid_for(n * chunks * W, kWG)), dim3(kWG), 0, s, rowptr, colind, vals, voff, B, n, m, chunks,
                      alpha, beta, shift, X, Y, Z);
 }
 
@@ -138,7 +128,7 @@ int sn_spectral_start_f64(uint64_t seed, const int32_t *voff, int64_t B, int64_t
   if (n > INT_MAX - 1 || B > INT_MAX - 1) return SN_E_RANGE;
   if (!voff || (n > 0 && !X)) return SN_E_NULL;
   if (n > 0)
-    hipLaunchKernelGGL(spectral_start_k, dim3(grid_for(n * m)), dim3(kWG), 0, static_cast<hipStream_t>(stream), seed, voff, (int)B, n, m,
+    hipLaunchKernelGGL(spectral_start_k, dim3(grid_for(n * m, kWG)), dim3(kWG), 0, static_cast<hipStream_t>(stream), seed, voff, (int)B, n, m,
                        X);
   return launch_status();
 }
@@ -187,9 +177,9 @@ int sn_wks_f64(const double *phi, const int32_t *voff, int64_t B, int64_t nV, in
   if (!phi || !W || !Cn || !out) return SN_E_NULL;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (out_f32)
-    hipLaunchKernelGGL((wks_k<float>), dim3(grid_for(nV * N)), dim3(kWG), 0, s, phi, voff, (int)B, nV, k, N, W, Cn, (float *)out);
+    hipLaunchKernelGGL((wks_k<float>), dim3(grid_for(nV * N, kWG)), dim3(kWG), 0, s, phi, voff, (int)B, nV, k, N, W, Cn, (float *)out);
   else
-    hipLaunchKernelGGL((wks_k<double>), dim3(grid_for(nV * N)), dim3(kWG), 0, s, phi, voff, (int)B, nV, k, N, W, Cn, (double *)out);
+    hipLaunchKernelGGL((wks_k<double>), dim3(grid_for(nV * N, kWG)), dim3(kWG), 0, s, phi, voff, (int)B, nV, k, N, W, Cn, (double *)out);
   return launch_status();
 }
 

@@ -20,16 +20,6 @@ constexpr int kMaxWindow = SN_SPGEMM_MAX_WINDOW;      // columns one result row 
 constexpr int kMaxWords = kMaxWindow / 32;            // 4096 words = 16 KiB per workgroup, 8 workgroups per CU fit 160 KiB
 constexpr int kRefusal = SN_SPGEMM_TOO_WIDE | SN_SPGEMM_TOO_LARGE;
 
-inline int launch_status() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? SN_OK : (int)e;
-}
-inline unsigned grid_for(int64_t n, int per_block) {
-  int64_t b = (n + per_block - 1) / per_block;
-  if (b < 1) b = 1;
-  if (b > 65535 * 16) b = 65535 * 16;
-  return (unsigned)b;
-}
 // exclusive scan of one value per thread across the workgroup (numbers a row's candidate columns); *total: the workgroup's sum
 __device__ __forceinline__ int block_excl_scan(int v, int *total) {
   __shared__ int wsum[kWaves];

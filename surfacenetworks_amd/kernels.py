@@ -11,7 +11,9 @@ import collections
 
 import torch
 
-from . import _lib
+from . import _lib, constants
+# the status bits and limits of include/sn_spmm.h, kept once in constants.py and exposed here under the same names
+from .constants import *  # noqa: F401,F403
 
 __all__ = [
     "note_absmax", "take_absmax", "absmax_wanted", "clear_absmax", "tile_sums_supported", "new_tile_sums", "avg_stats_from_tiles", "spmm_csr", "spmm_bsr4", "spmm_csr_elubwd", "spmm_bsr4_elubwd", "spmm_q3", "spmm_q3_stats", "spmm_q3_stats_supported", "spmm_csr_stats", "spmm_csr_stats_supported", "csr_to_rb4", "spmm_rb4", "spmm_rb4_stats", "spmm_rb4_supported", "spmm_ring", "spmm_ring_stats", "spmm_ring_supported", "ring_half_window", "csr_band", "bsr4_to_q3", "coo_to_csr", "csr_transpose", "csr_to_bsr4", "blockdiag_concat", "blockdiag_concat_ragged", "validate_csr",
@@ -35,6 +37,13 @@ def _dev(*tensors) -> None:
 
 def _p(t):
     return None if t is None or t.numel() == 0 else t.data_ptr()
+
+
+def _workspace(query: str, device, *dims, least: int = 16):
+    """(uint8 tensor of max(bytes, least) bytes on `device`, bytes): the scratch buffer of an entry point, sized by its
+    sn_*_workspace_bytes query.  Allocated where it is called, so a wrapper's allocations keep their order."""
+    nbytes = int(getattr(_lib.load(), query)(*dims))
+    return torch.empty(max(nbytes, least), dtype=torch.uint8, device=device), nbytes
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -93,8 +102,7 @@ def spmm_csr_stats(rowptr, colind, vals, M: int, K: int, x, y):
     ldy = _check_dense(y, M, 1, N, "y")
     lib = _lib.load()
     part = torch.empty((int(lib.sn_spmm_q3_stats_blocks()), 2, 128), dtype=torch.float64, device=y.device)
-    ws_bytes = int(lib.sn_spmm_csr_stats_workspace_bytes(M))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=y.device)
+    ws, ws_bytes = _workspace("sn_spmm_csr_stats_workspace_bytes", y.device, M)
     _lib.call("sn_spmm_csr_stats_f32", _p(rowptr), _p(colind), _p(vals), M, K, int(colind.numel()), _p(x), ldx, 1, N, _p(y), ldy, 1,
               _p(part), _p(ws), ws_bytes, _stream())
     return part
@@ -108,8 +116,7 @@ def csr_to_rb4(rowptr, colind, vals, M: int, K: int):
     Mb = (M + 3) // 4
     nnz = int(colind.numel())
     b_ptr = torch.empty(Mb + 1, dtype=torch.int32, device=dev)
-    ws_bytes = int(_lib.load().sn_scan_workspace_bytes(Mb + 1))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace("sn_scan_workspace_bytes", dev, Mb + 1)
     _lib.call("sn_rb4_count", _p(rowptr), _p(colind), M, K, _p(b_ptr), _p(ws), ws_bytes, _stream())
     b_col = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)[:nnz]
     b_val = torch.empty((max(nnz, 1), 4), dtype=torch.float32, device=dev)[:nnz]
@@ -155,8 +162,7 @@ def spmm_rb4_stats(b_ptr, b_col, b_val, M: int, K: int, x, y):
     ldy = _check_dense(y, M, 1, N, "y")
     lib = _lib.load()
     part = torch.empty((int(lib.sn_spmm_q3_stats_blocks()), 2, 128), dtype=torch.float64, device=y.device)
-    ws_bytes = int(lib.sn_spmm_rb4_stats_workspace_bytes(M))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=y.device)
+    ws, ws_bytes = _workspace("sn_spmm_rb4_stats_workspace_bytes", y.device, M)
     _lib.call("sn_spmm_rb4_stats_f32", _p(b_ptr), _p(b_col), _p(b_val), M, K, int(b_col.numel()), _p(x), ldx, N, _p(y), ldy,
               _p(part), _p(ws), ws_bytes, _stream())
     return part
@@ -224,8 +230,7 @@ def spmm_ring_stats(rowptr, colind, vals, M: int, K: int, x, y):
     ldy = _check_dense(y, M, 1, N, "y")
     lib = _lib.load()
     part = torch.empty((int(lib.sn_spmm_q3_stats_blocks()), 2, 128), dtype=torch.float64, device=y.device)
-    ws_bytes = int(lib.sn_spmm_csr_ring_stats_workspace_bytes(M))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=y.device)
+    ws, ws_bytes = _workspace("sn_spmm_csr_ring_stats_workspace_bytes", y.device, M)
     _lib.call("sn_spmm_csr_ring_stats_f32", _p(rowptr), _p(colind), _p(vals), M, K, int(colind.numel()), _p(x), ldx, N, _p(y), ldy,
               _p(part), _p(ws), ws_bytes, _stream())
     return part
@@ -330,8 +335,7 @@ def spmm_q3_stats(b_rowptr, q_blk, Mb: int, Kb: int, x, y, group: int = 4):
     ldy = _check_dense(y, 4 * Mb, group, N, "y")
     lib = _lib.load()
     part = torch.empty((int(lib.sn_spmm_q3_stats_blocks()), 2, 4 * N), dtype=torch.float64, device=y.device)
-    ws_bytes = int(lib.sn_spmm_q3_stats_workspace_bytes(Mb))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=y.device)
+    ws, ws_bytes = _workspace("sn_spmm_q3_stats_workspace_bytes", y.device, Mb)
     _lib.call("sn_spmm_q3_stats_f32", _p(b_rowptr), _p(q_blk), Mb, Kb, int(q_blk.shape[0]), _p(x), ldx, group, N, _p(y), ldy,
               group, _p(part), _p(ws), ws_bytes, _stream())
     return part
@@ -368,8 +372,7 @@ def csr_transpose(rowptr, colind, vals, M: int, K: int):
     t_rowptr = torch.empty(K + 1, dtype=torch.int32, device=dev)
     t_colind = torch.empty(nnz, dtype=torch.int32, device=dev)
     t_vals = torch.empty(nnz, dtype=torch.float32, device=dev)
-    ws_bytes = int(_lib.load().sn_csr_transpose_workspace_bytes(M, K, nnz))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace("sn_csr_transpose_workspace_bytes", dev, M, K, nnz)
     _lib.call("sn_csr_transpose_f32", _p(rowptr), _p(colind), _p(vals), M, K, nnz, _p(t_rowptr), _p(t_colind),
               _p(t_vals), _p(ws), ws_bytes, _stream())
     return t_rowptr, t_colind, t_vals
@@ -383,8 +386,7 @@ def csr_to_bsr4(rowptr, colind, vals, M: int, K: int):
     dev = rowptr.device
     Mb = M // 4
     b_rowptr = torch.empty(Mb + 1, dtype=torch.int32, device=dev)
-    ws_bytes = int(_lib.load().sn_scan_workspace_bytes(Mb + 1))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace("sn_scan_workspace_bytes", dev, Mb + 1)
     _lib.call("sn_bsr4_count", _p(rowptr), _p(colind), M, K, _p(b_rowptr), _p(ws), ws_bytes, _stream())
     nblocks = int(b_rowptr[-1].item())
     b_colind = torch.empty(nblocks, dtype=torch.int32, device=dev)
@@ -453,8 +455,7 @@ def colstats(x):
     _dev(x)
     rows, C = x.shape
     out = torch.empty((2, C), dtype=torch.float64, device=x.device)
-    ws_bytes = int(_lib.load().sn_colstats_workspace_bytes(rows, C))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x.device)
+    ws, ws_bytes = _workspace("sn_colstats_workspace_bytes", x.device, rows, C)
     _lib.call("sn_colstats_f32", _p(x), _ld(x), rows, C, _p(out), _p(ws), ws_bytes, _stream())
     return out
 
@@ -590,8 +591,7 @@ def wgrad(dy, x, center=None, want_colsum: bool = False, bounds=None):
         raise ValueError("wgrad: row mismatch")
     G = torch.empty((J, C), dtype=torch.float32, device=x.device)
     dysum = torch.empty(J, dtype=torch.float64, device=x.device) if want_colsum else None
-    ws_bytes = int(_lib.load().sn_wgrad_workspace_bytes(rows, J, C))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x.device)
+    ws, ws_bytes = _workspace("sn_wgrad_workspace_bytes", x.device, rows, J, C)
     if bounds is not None:
         _lib.call("sn_wgrad_bounded_f32", _p(dy), _ld(dy), _p(x), _ld(x), _p(center), rows, J, C, _p(G), _p(dysum), _p(ws), ws_bytes,
                   *_bounds_args(bounds, C), _stream())
@@ -673,8 +673,7 @@ def segment_colsum(x, mask, rows_per_seg: int, nseg: int):
     if x.shape[0] != rows_per_seg * nseg:
         raise ValueError("segment_colsum: row count mismatch")
     out = torch.empty((nseg, C), dtype=torch.float32, device=x.device)
-    ws_bytes = int(_lib.load().sn_segment_colsum_workspace_bytes(rows_per_seg, nseg, C))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x.device)
+    ws, ws_bytes = _workspace("sn_segment_colsum_workspace_bytes", x.device, rows_per_seg, nseg, C)
     _lib.call("sn_segment_colsum_f32", _p(x), _ld(x), _p(mask), rows_per_seg, nseg, C, _p(out), _p(ws), ws_bytes, _stream())
     return out
 
@@ -686,8 +685,7 @@ def segment_colsum_ragged(x, tiles, seg_tile_ptr, nseg: int, scale=None):
     C = x.shape[1]
     nt = int(tiles.shape[0])
     out = torch.empty((nseg, C), dtype=torch.float32, device=x.device)
-    ws_bytes = int(_lib.load().sn_segment_colsum_ragged_workspace_bytes(nt, C))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x.device)
+    ws, ws_bytes = _workspace("sn_segment_colsum_ragged_workspace_bytes", x.device, nt, C)
     _lib.call("sn_segment_colsum_ragged_f32", _p(x), _ld(x), _p(tiles), nt, _p(seg_tile_ptr), nseg, C, _p(scale), _p(out), _p(ws),
               ws_bytes, _stream())
     return out
@@ -732,8 +730,7 @@ def dirac_from_mesh(V, F):
     f32 = lambda n: torch.empty(n, dtype=torch.float32, device=dev)
     di_rp, di_ci, di_v, diat_v = i32(nF + 1), i32(3 * nF), f32(48 * nF), f32(48 * nF)
     dia_rp, dia_ci, dia_v, dit_v = i32(nV + 1), i32(3 * nF), f32(48 * nF), f32(48 * nF)
-    ws_bytes = int(_lib.load().sn_dirac_workspace_bytes(nV, nF))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace("sn_dirac_workspace_bytes", dev, nV, nF)
     _lib.call("sn_dirac_bsr4_from_mesh", _p(V), _p(F), nV, nF, _p(di_rp), _p(di_ci), _p(di_v), _p(diat_v), _p(dia_rp),
               _p(dia_ci), _p(dia_v), _p(dit_v), _p(ws), ws_bytes, _stream())
     return (di_rp, di_ci, di_v), (di_rp, di_ci, diat_v), (dia_rp, dia_ci, dia_v), (dia_rp, dia_ci, dit_v)
@@ -750,8 +747,7 @@ def laplacian_from_mesh(V, F):
     dev = V.device
     rowptr = torch.empty(nV + 1, dtype=torch.int32, device=dev)
     flag = torch.zeros(1, dtype=torch.int32, device=dev)
-    ws_bytes = int(_lib.load().sn_laplacian_workspace_bytes(nV, nF))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace("sn_laplacian_workspace_bytes", dev, nV, nF)
     _lib.call("sn_laplacian_csr_from_mesh", _p(V), _p(F), nV, nF, 0, _p(rowptr), None, None, _p(flag), _p(ws), ws_bytes, _stream())
     nnz, bad = int(rowptr[-1].item()), int(flag.item())
     if bad:
@@ -760,9 +756,6 @@ def laplacian_from_mesh(V, F):
     vals = torch.empty(nnz, dtype=torch.float32, device=dev)
     _lib.call("sn_laplacian_csr_from_mesh", _p(V), _p(F), nV, nF, 1, _p(rowptr), _p(colind), _p(vals), None, _p(ws), ws_bytes, _stream())
     return rowptr, colind, vals
-
-
-SPGEMM_BAD_COLUMN, SPGEMM_TOO_WIDE, SPGEMM_TOO_LARGE, CSR_NO_OFFDIAGONAL = 1, 2, 4, 8      # SN_SPGEMM_* / SN_CSR_* status bits
 
 
 def spgemm_max_window() -> int:
@@ -780,16 +773,17 @@ def _check_csr(who: str, arrays, rows: int):
     return rowptr.contiguous(), colind.contiguous(), vals.contiguous()
 
 
+def raise_for_status(who: str, family: str, st: int, errors) -> None:
+    """Raise for the first bit of `errors` — ((bit, exception type), ...), in the order they are tested — that is set in the
+    status word st, with the sentence constants.STATUS_FAMILIES has for it."""
+    for bit, exc in errors:
+        if st & bit:
+            raise exc(f"{who}: {constants.status_sentences(family, bit)[0]}")
+
+
 def _raise_for_spgemm_status(who: str, st: int) -> None:
-    if st & SPGEMM_BAD_COLUMN:
-        raise ValueError(f"{who}: a column index is outside the operand's column range")
-    if st & CSR_NO_OFFDIAGONAL:
-        raise ValueError(f"{who}: a row holds fewer than two entries (no off-diagonal entry: D^-1/2 divides by zero)")
-    if st & SPGEMM_TOO_WIDE:
-        raise RuntimeError(f"{who}: a result row spans more than spgemm_max_window() = {spgemm_max_window()} columns; "
-                           "there is no other path")
-    if st & SPGEMM_TOO_LARGE:
-        raise RuntimeError(f"{who}: the result's structural entries do not fit int32 row pointers")
+    raise_for_status(who, "spgemm", st, ((SPGEMM_BAD_COLUMN, ValueError), (CSR_NO_OFFDIAGONAL, ValueError),
+                                         (SPGEMM_TOO_WIDE, RuntimeError), (SPGEMM_TOO_LARGE, RuntimeError)))
 
 
 def csr_spgemm(A_arrays, B_arrays, shape, keep_zeros: bool = False):
@@ -802,8 +796,7 @@ def csr_spgemm(A_arrays, B_arrays, shape, keep_zeros: bool = False):
     a_rp, a_ci, a_v = _check_csr("csr_spgemm (A)", A_arrays, M)
     b_rp, b_ci, b_v = _check_csr("csr_spgemm (B)", B_arrays, K)
     dev = a_rp.device
-    ws_bytes = int(_lib.load().sn_csr_spgemm_workspace_bytes(M))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace("sn_csr_spgemm_workspace_bytes", dev, M)
     heads = torch.zeros(2, M + 1, dtype=torch.int32, device=dev)             # structural and final row pointers
     s_rp, rp = heads[0], heads[1]
     status = torch.empty(1, dtype=torch.int32, device=dev)
@@ -855,8 +848,7 @@ def csr_scale_sym(A_arrays, d, M: int):
         raise TypeError(f"csr_scale_sym wants d float32 of {M} entries")
     d = d.contiguous()
     dev = a_rp.device
-    ws_bytes = int(_lib.load().sn_csr_spgemm_workspace_bytes(M))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace("sn_csr_spgemm_workspace_bytes", dev, M)
     rp = torch.empty(M + 1, dtype=torch.int32, device=dev)
     s_v = torch.empty_like(a_v)
     status = torch.empty(1, dtype=torch.int32, device=dev)
@@ -873,7 +865,6 @@ def csr_scale_sym(A_arrays, d, M: int):
     return rp, ci, v
 
 
-IDT_BAD_FACE, IDT_NOT_CONVERGED, IDT_DEGENERATE, IDT_NON_MANIFOLD, IDT_ORIENTATION = 1, 2, 4, 8, 16      # SN_IDT_* status bits
 IDT_CHUNK = 8                 # flip rounds enqueued between two reads of the counters
 
 
@@ -902,8 +893,7 @@ def mesh_glue(F, num_vertices: int, V=None):
             raise ValueError(f"mesh_glue: V has {V.shape[0]} rows for {nV} vertices")
         V = V.contiguous()
         l = torch.empty(nF, 3, dtype=torch.float64, device=dev)
-    ws_bytes = int(_lib.load().sn_mesh_glue_workspace_bytes(nV, nF))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace("sn_mesh_glue_workspace_bytes", dev, nV, nF)
     _lib.call("sn_mesh_glue_i32", _p(V) if V is not None else None, _p(F), nV, nF, _p(G), _p(l) if l is not None else None,
               status.data_ptr(), _p(ws), ws_bytes, _stream())
     return (G, status) if V is None else (G, status, l)
@@ -926,8 +916,7 @@ def intrinsic_delaunay(V, F, max_rounds: int = 1024):
     G, status, l = mesh_glue(F, nV, V)
     Fp = F.contiguous().clone()
     counters = torch.empty(max_rounds, 2, dtype=torch.int32, device=dev)
-    ws_bytes = int(_lib.load().sn_mesh_idt_workspace_bytes(nF))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace("sn_mesh_idt_workspace_bytes", dev, nF)
     rounds = flips = 0
     while rounds < max_rounds:
         n = min(IDT_CHUNK, max_rounds - rounds)
@@ -943,16 +932,10 @@ def intrinsic_delaunay(V, F, max_rounds: int = 1024):
     return Fp, l, G, int(status.item()), rounds, flips
 
 
-def _raise_for_idt_status(who: str, st: int, max_rounds: int) -> None:
-    if st & IDT_BAD_FACE:
-        raise ValueError(f"{who}: a face has an index outside 0..nV-1 or a repeated index")
-    if st & IDT_NON_MANIFOLD:
-        raise ValueError(f"{who}: an edge has more than two faces (the mesh is not manifold)")
-    if st & IDT_ORIENTATION:
-        raise ValueError(f"{who}: an edge is traversed in the same direction by its two faces (the mesh is not consistently "
-                         "oriented)")
-    if st & IDT_NOT_CONVERGED:
-        raise RuntimeError(f"{who}: round {max_rounds} of max_rounds = {max_rounds} still found a non-Delaunay side")
+def _raise_for_idt_status(who: str, st: int) -> None:
+    raise_for_status(who, "idt", st,
+                     ((IDT_BAD_FACE, ValueError), (IDT_NON_MANIFOLD, ValueError), (IDT_ORIENTATION, ValueError),
+                      (IDT_NOT_CONVERGED, RuntimeError)))
 
 
 def intrinsic_laplacian_from_mesh(V, F, max_rounds: int = 1024, state=None):
@@ -967,13 +950,12 @@ def intrinsic_laplacian_from_mesh(V, F, max_rounds: int = 1024, state=None):
     if state is None:
         state = intrinsic_delaunay(V, F, max_rounds)
     Fp, l, _, st = state[:4]
-    _raise_for_idt_status("intrinsic_laplacian_from_mesh", st, max_rounds)
+    _raise_for_idt_status("intrinsic_laplacian_from_mesh", st)
     nV, nF = V.shape[0], Fp.shape[0]
     dev = V.device
     lib = _lib.load()
     N = int(lib.sn_mesh_idt_laplacian_items(nV, nF))
-    ws_bytes = int(lib.sn_mesh_idt_laplacian_workspace_bytes(nV, nF))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace("sn_mesh_idt_laplacian_workspace_bytes", dev, nV, nF)
     keys = torch.empty(N, dtype=torch.int64, device=dev)
     rowptr = torch.empty(nV + 1, dtype=torch.int32, device=dev)
     args = (_p(Fp), _p(l), nV, nF)
@@ -988,8 +970,6 @@ def intrinsic_laplacian_from_mesh(V, F, max_rounds: int = 1024, state=None):
     return rowptr, colind, vals
 
 
-CC_EDGE, CC_VERTEX = 0, 1                # SN_CC_EDGE / SN_CC_VERTEX
-CC_BAD_FACE, CC_INTERNAL = 1, 2          # status bits of mesh_components
 _CC_MODES = {"edge": CC_EDGE, "vertex": CC_VERTEX}
 
 MeshComponents = collections.namedtuple("MeshComponents", "vlabel flabel count summary status")
@@ -1018,8 +998,7 @@ def mesh_components(F, num_vertices: int, mode: str = "edge") -> MeshComponents:
     count = torch.empty(nV if vertex else nF, dtype=torch.int32, device=dev)
     summary = torch.empty(3, dtype=torch.int32, device=dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
-    ws_bytes = int(_lib.load().sn_mesh_components_workspace_bytes(nV, nF, _CC_MODES[mode]))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace("sn_mesh_components_workspace_bytes", dev, nV, nF, _CC_MODES[mode])
     _lib.call("sn_mesh_components_i32", _p(F), nV, nF, _CC_MODES[mode], _p(vlabel), _p(flabel), _p(count), summary.data_ptr(),
               status.data_ptr(), _p(ws), ws_bytes, _stream())
     return MeshComponents(vlabel, flabel, count, summary, status)
@@ -1064,15 +1043,11 @@ def mesh_compact(F, keep, num_vertices: int, V=None) -> MeshCompacted:
         V = V.contiguous()
         Vnew = torch.empty(nV, 3, dtype=torch.float32, device=dev)
     sizes = torch.empty(2, dtype=torch.int32, device=dev)
-    ws_bytes = int(_lib.load().sn_mesh_compact_workspace_bytes(nV, nF))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace("sn_mesh_compact_workspace_bytes", dev, nV, nF)
     _lib.call("sn_mesh_compact_i32", _p(V), _p(F), _p(keep), nV, nF, _p(I), _p(J), _p(Fsrc), _p(Fnew), _p(Vnew), sizes.data_ptr(),
               _p(ws), ws_bytes, _stream())
     return MeshCompacted(I, J, Fsrc, Fnew, Vnew, sizes)
 
-
-# SN_REPAIR_* status bits
-REPAIR_BAD_FACE, REPAIR_NONFINITE, REPAIR_NONORIENTABLE, REPAIR_NONMANIFOLD, REPAIR_INTERNAL = 1, 2, 4, 8, 16
 
 MeshWeld = collections.namedtuple("MeshWeld", "rep F counts status")
 MeshUniqueFaces = collections.namedtuple("MeshUniqueFaces", "keep counts status")
@@ -1098,8 +1073,7 @@ def mesh_weld(V, F, tol: float = 0.0, weld: bool = True) -> MeshWeld:
     Fw = torch.empty(nF, 3, dtype=torch.int32, device=dev)
     counts = torch.empty(1, dtype=torch.int32, device=dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
-    ws_bytes = int(_lib.load().sn_mesh_weld_workspace_bytes(nV))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace("sn_mesh_weld_workspace_bytes", dev, nV)
     _lib.call("sn_mesh_weld_f32", _p(V), _p(F), nV, nF, tol, 1 if weld else 0, _p(rep), _p(Fw), counts.data_ptr(), status.data_ptr(),
               _p(ws), ws_bytes, _stream())
     return MeshWeld(rep, Fw, counts, status)
@@ -1121,8 +1095,7 @@ def mesh_unique_faces(F, num_vertices: int, V=None, unique: bool = True) -> Mesh
     keep = torch.empty(nF, dtype=torch.int32, device=dev)
     counts = torch.empty(3, dtype=torch.int32, device=dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
-    ws_bytes = int(_lib.load().sn_mesh_unique_faces_workspace_bytes(nF))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace("sn_mesh_unique_faces_workspace_bytes", dev, nF)
     _lib.call("sn_mesh_unique_faces_i32", _p(V), _p(F), nV, nF, 1 if unique else 0, _p(keep), counts.data_ptr(), status.data_ptr(),
               _p(ws), ws_bytes, _stream())
     return MeshUniqueFaces(keep, counts, status)
@@ -1150,19 +1123,32 @@ def mesh_orient(F, keep, num_vertices: int) -> MeshOrient:
     Fout = torch.empty(nF, 3, dtype=torch.int32, device=dev)
     counts = torch.empty(3, dtype=torch.int32, device=dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
-    ws_bytes = int(_lib.load().sn_mesh_orient_workspace_bytes(nV, nF))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace("sn_mesh_orient_workspace_bytes", dev, nV, nF)
     _lib.call("sn_mesh_orient_i32", _p(F), _p(keep), nV, nF, _p(flip), _p(label), _p(Fout), counts.data_ptr(), status.data_ptr(),
               _p(ws), ws_bytes, _stream())
     return MeshOrient(flip, label, Fout, counts, status)
 
 
-DESC_BAD_FACE, DESC_FLAT_FACE, DESC_NO_NORMAL, DESC_CLAMPED, DESC_DEGREE = 1, 2, 4, 8, 16      # SN_DESC_* status bits
 # output name -> (per face?, trailing width) in the argument order of sn_mesh_descriptors_f32
 DESCRIPTOR_FIELDS = {"face_area": (True, 1), "face_normal": (True, 3), "n_area": (False, 3), "n_uniform": (False, 3),
                      "n_angle": (False, 3), "mass_bary": (False, 1), "mass_voronoi": (False, 1), "gauss": (False, 1),
                      "mean": (False, 1)}
-_DESC_MASS = {"barycentric": 0, "voronoi": 1}                 # SN_DESC_MASS_*
+_DESC_MASS = {"barycentric": DESC_MASS_BARYCENTRIC, "voronoi": DESC_MASS_VORONOI}
+
+
+def _new_outputs(who: str, fields: dict, want, layout, dev) -> dict:
+    """The optional outputs of an entry point over its FIELDS table: a new device tensor for every name of `want` (None: all of
+    `fields`), None for the others, and "status", a 1-element int32 tensor.  layout(entry) = (rows, trailing width, dtype)."""
+    names = list(fields) if want is None else list(want)
+    unknown = [n for n in names if n not in fields]
+    if unknown:
+        raise ValueError(f"{who}: unknown output {unknown[0]!r}; the outputs are {', '.join(fields)}")
+    out = {}
+    for name, entry in fields.items():
+        rows, width, dtype = layout(entry)
+        out[name] = torch.empty((rows,) if width == 1 else (rows, width), dtype=dtype, device=dev) if name in names else None
+    out["status"] = torch.empty(1, dtype=torch.int32, device=dev)
+    return out
 
 
 def mesh_descriptors(V, F, want=None) -> dict:
@@ -1174,27 +1160,16 @@ def mesh_descriptors(V, F, want=None) -> dict:
     synchronise; two runs are bit-identical."""
     _dev(V, F)
     _check_mesh("mesh_descriptors", V, F)
-    names = list(DESCRIPTOR_FIELDS) if want is None else list(want)
-    unknown = [n for n in names if n not in DESCRIPTOR_FIELDS]
-    if unknown:
-        raise ValueError(f"mesh_descriptors: unknown output {unknown[0]!r}; the outputs are {', '.join(DESCRIPTOR_FIELDS)}")
     V, F = V.contiguous(), F.contiguous()
     nV, nF = V.shape[0], F.shape[0]
     dev = V.device
-    out = {}
-    for name, (per_face, width) in DESCRIPTOR_FIELDS.items():
-        rows = nF if per_face else nV
-        out[name] = torch.empty((rows,) if width == 1 else (rows, width), dtype=torch.float32, device=dev) if name in names else None
-    out["status"] = torch.empty(1, dtype=torch.int32, device=dev)
-    ws_bytes = int(_lib.load().sn_mesh_descriptors_workspace_bytes(nV, nF))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    out = _new_outputs("mesh_descriptors", DESCRIPTOR_FIELDS, want, lambda f: (nF if f[0] else nV, f[1], torch.float32), dev)
+    ws, ws_bytes = _workspace("sn_mesh_descriptors_workspace_bytes", dev, nV, nF)
     _lib.call("sn_mesh_descriptors_f32", _p(V), _p(F), nV, nF, *[_p(out[n]) for n in DESCRIPTOR_FIELDS], out["status"].data_ptr(),
               _p(ws), ws_bytes, _stream())
     return out
 
 
-CURV_FEW_POINTS, CURV_NO_NORMAL, CURV_OVERFLOW, CURV_DEGENERATE = 32, 64, 128, 1024      # SN_CURV_* status bits
-CURV_MAX_RING = 1024                                                                      # SN_CURV_MAX_RING
 # output name -> (dtype, trailing width) in the argument order of sn_mesh_principal_curvature_f32
 CURVATURE_FIELDS = {"k1": (torch.float32, 1), "k2": (torch.float32, 1), "d1": (torch.float32, 3), "d2": (torch.float32, 3),
                     "ring_size": (torch.int32, 1)}
@@ -1213,19 +1188,11 @@ def mesh_principal_curvature(V, F, radius: int = 5, want=None) -> dict:
     radius = int(radius)
     if radius < 1:
         raise ValueError(f"mesh_principal_curvature: radius must be at least 1, got {radius}")
-    names = list(CURVATURE_FIELDS) if want is None else list(want)
-    unknown = [n for n in names if n not in CURVATURE_FIELDS]
-    if unknown:
-        raise ValueError(f"mesh_principal_curvature: unknown output {unknown[0]!r}; the outputs are {', '.join(CURVATURE_FIELDS)}")
     V, F = V.contiguous(), F.contiguous()
     nV, nF = V.shape[0], F.shape[0]
     dev = V.device
-    out = {}
-    for name, (dtype, width) in CURVATURE_FIELDS.items():
-        out[name] = torch.empty((nV,) if width == 1 else (nV, width), dtype=dtype, device=dev) if name in names else None
-    out["status"] = torch.empty(1, dtype=torch.int32, device=dev)
-    ws_bytes = int(_lib.load().sn_mesh_curvature_workspace_bytes(nV, nF))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    out = _new_outputs("mesh_principal_curvature", CURVATURE_FIELDS, want, lambda f: (nV, f[1], f[0]), dev)
+    ws, ws_bytes = _workspace("sn_mesh_curvature_workspace_bytes", dev, nV, nF)
     _lib.call("sn_mesh_principal_curvature_f32", _p(V), _p(F), nV, nF, radius, *[_p(out[n]) for n in CURVATURE_FIELDS],
               out["status"].data_ptr(), _p(ws), ws_bytes, _stream())
     return out
@@ -1247,22 +1214,17 @@ def cot_laplacian_from_mesh(V, F, mass: str = "barycentric", hack=None):
     dev = V.device
     rowptr = torch.empty(nV + 1, dtype=torch.int32, device=dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
-    ws_bytes = int(_lib.load().sn_mesh_cot_laplacian_workspace_bytes(nV, nF))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace("sn_mesh_cot_laplacian_workspace_bytes", dev, nV, nF)
     head = (_p(V), _p(F), nV, nF)
     tail = (_DESC_MASS[mass], int(hack is not None), float(0 if hack is None else hack))
     _lib.call("sn_mesh_cot_laplacian_f32", *head, 0, *tail, _p(rowptr), None, None, status.data_ptr(), _p(ws), ws_bytes, _stream())
     nnz, st = torch.cat([rowptr[-1:], status]).tolist()
-    if st & DESC_DEGREE:
-        raise _lib.SnError("cot_laplacian_from_mesh: a vertex has more incident faces than SN_LAP_MAX_DEGREE (status SN_DESC_DEGREE)")
+    raise_for_status("cot_laplacian_from_mesh", "descriptors", st, ((DESC_DEGREE, _lib.SnError),))
     colind = torch.empty(nnz, dtype=torch.int32, device=dev)
     vals = torch.empty(nnz, dtype=torch.float32, device=dev)
     _lib.call("sn_mesh_cot_laplacian_f32", *head, 1, *tail, _p(rowptr), _p(colind), _p(vals), status.data_ptr(), _p(ws), ws_bytes,
               _stream())
     return rowptr, colind, vals, int(status.item())
-
-
-EIG_NOT_CONVERGED, EIG_CLIPPED_MASS = 256, 512        # SN_EIG_* status bits, next to the pencil's DESC_* bits in one word
 
 
 def cot_pencil_from_mesh(V, F):
@@ -1279,8 +1241,7 @@ def cot_pencil_from_mesh(V, F):
     dev = V.device
     rowptr = torch.empty(nV + 1, dtype=torch.int32, device=dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
-    ws_bytes = int(_lib.load().sn_mesh_cot_laplacian_workspace_bytes(nV, nF))      # the pencil shares the query
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace("sn_mesh_cot_laplacian_workspace_bytes", dev, nV, nF)      # the pencil shares the query
     head = (_p(V), _p(F), nV, nF)
     _lib.call("sn_mesh_cot_pencil_f64", *head, 0, _p(rowptr), None, None, None, status.data_ptr(), _p(ws), ws_bytes, _stream())
     nnz, st = torch.cat([rowptr[-1:], status]).tolist()
@@ -1439,9 +1400,6 @@ def symmetrize_min_(G, n: int = None):
     return G
 
 
-MESH_CORNER_BYTES = 40        # SN_MESH_CORNER_BYTES: int32 a, b; float l_a, l_b; double c, s_b, h
-
-
 class MeshCorners:
     """Corner table of a triangle mesh (include/sn_spmm.h, "Geodesic distance matrices that cross triangles"): a CSR by
     vertex.  cptr: (n + 1,) int32; records: (3 * nF, 40) uint8, the first cptr[n] rows are written, one record per corner
@@ -1466,8 +1424,7 @@ def _mesh_corner_table(V, F):
     cptr = torch.empty(nV + 1, dtype=torch.int32, device=dev)
     records = torch.empty(3 * nF, MESH_CORNER_BYTES, dtype=torch.uint8, device=dev)
     flag = torch.zeros(1, dtype=torch.int32, device=dev)
-    ws_bytes = int(_lib.load().sn_mesh_corners_workspace_bytes(nV))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace("sn_mesh_corners_workspace_bytes", dev, nV)
     _lib.call("sn_mesh_corners_f32", _p(V), _p(F), nV, nF, _p(cptr), _p(records), _p(flag), _p(ws), ws_bytes, _stream())
     return MeshCorners(cptr, records), flag
 
@@ -1477,7 +1434,7 @@ def mesh_corners(V, F) -> MeshCorners:
     F: (nF, 3) int32.  Synchronises once (reads the flag); a face with an index outside the mesh or a repeated index raises."""
     corners, flag = _mesh_corner_table(V, F)
     if int(flag.item()):
-        raise _lib.SnError("mesh_corners: a face has an index outside 0..nV-1 or a repeated index")
+        raise _lib.SnError(f"mesh_corners: {constants.BAD_FACE_SENTENCE}")
     return corners
 
 
@@ -1678,8 +1635,7 @@ def colstats_into(x, out, offset: int):
     rows, C = x.shape
     if out.dim() != 2 or out.shape[0] != 2 or out.dtype != torch.float64 or not out.is_contiguous() or offset + C > out.shape[1]:
         raise ValueError("colstats_into: out must be a contiguous (2, width) float64 tensor with width >= offset + C")
-    ws_bytes = int(_lib.load().sn_colstats_workspace_bytes(rows, C))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x.device)
+    ws, ws_bytes = _workspace("sn_colstats_workspace_bytes", x.device, rows, C)
     _lib.call("sn_colstats_into_f32", _p(x), _ld(x), rows, C, _p(out), out.shape[1], offset, _p(ws), ws_bytes, _stream())
     return out
 
@@ -1712,8 +1668,7 @@ def colstats_halves(x, part, part_hi=None):
             raise ValueError("colstats_halves: 64-channel GEMM partials need the SpMM's partials too")
         else:
             xs = x[:, half * C:(half + 1) * C]
-            ws_bytes = int(lib.sn_colstats_workspace_bytes(rows, C))
-            ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x.device)
+            ws, ws_bytes = _workspace("sn_colstats_workspace_bytes", x.device, rows, C)
             _lib.call("sn_colstats_into_f32", _p(xs), _ld(xs), rows, C, _p(out), C2, half * C, _p(ws), ws_bytes, _stream())
     return out
 
@@ -1798,8 +1753,7 @@ def avg_stats(e, mask, inv_count, rows_per_seg: int, nseg: int):
     C = e.shape[1]
     m = torch.empty((nseg, C), dtype=torch.float32, device=e.device)
     stats = torch.empty((2, 2 * C), dtype=torch.float64, device=e.device)
-    ws_bytes = int(_lib.load().sn_avg_stats_workspace_bytes(rows_per_seg, nseg, C))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=e.device)
+    ws, ws_bytes = _workspace("sn_avg_stats_workspace_bytes", e.device, rows_per_seg, nseg, C)
     _lib.call("sn_avg_stats_f32", _p(e), _ld(e), _p(mask), _p(inv_count.contiguous()), rows_per_seg, nseg, C, _p(m), _p(stats),
               _p(ws), ws_bytes, _stream())
     return m, stats
@@ -1917,8 +1871,7 @@ def wgrad_seg(dy, x, center, rows_per_seg: int, bounds=None):
     G = torch.empty((J, C), dtype=torch.float32, device=dev)
     dysum = torch.empty(J, dtype=torch.float64, device=dev)
     seg = torch.empty((nseg, J), dtype=torch.float32, device=dev)
-    ws_bytes = int(_lib.load().sn_wgrad_seg_workspace_bytes(rows, rows_per_seg, J, C))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace("sn_wgrad_seg_workspace_bytes", dev, rows, rows_per_seg, J, C)
     if bounds is not None:
         _lib.call("sn_wgrad_seg_bounded_f32", _p(dy), _ld(dy), _p(x), _ld(x), _p(center), rows, rows_per_seg, J, C, _p(G), _p(dysum),
                   _p(seg), _p(ws), ws_bytes, *_bounds_args(bounds, C), _stream())
@@ -2013,8 +1966,7 @@ def wgrad_thin(dy, x, want_bias: bool = True):
     dev = dy.device
     G = torch.empty((J, C), dtype=torch.float32, device=dev)
     db = torch.empty(J, dtype=torch.float32, device=dev) if want_bias else None
-    ws_bytes = int(_lib.load().sn_wgrad_thin_workspace_bytes(rows, J, C))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace("sn_wgrad_thin_workspace_bytes", dev, rows, J, C)
     _lib.call("sn_wgrad_thin_f32", _p(dy), _ld(dy), _p(x), _ld(x), rows, J, C, _p(G), _p(db), _p(ws), ws_bytes, _stream())
     return G, db
 
@@ -2095,8 +2047,7 @@ def pair_fused_fwd(FA, FB, target, NA: int, NB: int):
         raise TypeError("pair_fused_fwd: int64 targets and features of one width expected")
     if not (0 < NA <= FA.shape[0] and 0 < NB <= FB.shape[0]) or target.numel() != NA:
         raise ValueError("pair_fused_fwd: NA / NB do not fit the feature matrices / target vector")
-    nbytes = _lib.load().sn_pair_fused_workspace_bytes(FA.shape[0], FB.shape[0])
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=FA.device)
+    ws, nbytes = _workspace("sn_pair_fused_workspace_bytes", FA.device, FA.shape[0], FB.shape[0], least=0)
     lse = torch.empty(NA, dtype=torch.float32, device=FA.device)
     rowloss = torch.empty(NA, dtype=torch.float32, device=FA.device)
     _lib.call("sn_pair_fused_fwd_f32", _p(FA), FA.stride(0), _p(FB), FB.stride(0), _p(target.contiguous()), NA, NB, FA.shape[0], FB.shape[0],
@@ -2133,8 +2084,7 @@ def pair_soft_fwd(FA, FB, mapA, mapB, geo, ldgA: int, ldgB: int, NA: int, NB: in
     FB (rowsB x K) and the two label-order geodesic matrices whose device addresses `geo` (int64[2] on the device) holds
     (sn_pair_soft_fwd_f32).  stats = lse | softmin offset, 2 NA floats; the loss is rowloss.sum()."""
     _pair_loss_args("pair_soft_fwd", FA, FB, mapA, mapB, geo, NA, NB)
-    nbytes = _lib.load().sn_pair_loss_workspace_bytes(FA.shape[0], FB.shape[0])
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=FA.device)
+    ws, nbytes = _workspace("sn_pair_loss_workspace_bytes", FA.device, FA.shape[0], FB.shape[0], least=0)
     stats = torch.empty(2 * NA, dtype=torch.float32, device=FA.device)
     rowloss = torch.empty(NA, dtype=torch.float32, device=FA.device)
     _lib.call("sn_pair_soft_fwd_f32", _p(FA), FA.stride(0), _p(FB), FB.stride(0), _p(mapA), _p(mapB), _p(geo), ldgA, ldgB, NA, NB,
@@ -2156,8 +2106,7 @@ def pair_sl1_fwd(FA, FB, mapA, mapB, geo, ldgA: int, ldgB: int, NA: int, NB: int
     """(rowloss (fp64, rowsA), workspace) of the smooth-L1 loss against the zero-padded geodesic sum (main.py:197-214):
     sn_pair_sl1_fwd_f32; the loss is rowloss.sum() / (rowsA rowsB)."""
     _pair_loss_args("pair_sl1_fwd", FA, FB, mapA, mapB, geo, NA, NB)
-    nbytes = _lib.load().sn_pair_loss_workspace_bytes(FA.shape[0], FB.shape[0])
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=FA.device)
+    ws, nbytes = _workspace("sn_pair_loss_workspace_bytes", FA.device, FA.shape[0], FB.shape[0], least=0)
     rowloss = torch.empty(FA.shape[0], dtype=torch.float64, device=FA.device)
     _lib.call("sn_pair_sl1_fwd_f32", _p(FA), FA.stride(0), _p(FB), FB.stride(0), _p(mapA), _p(mapB), _p(geo), ldgA, ldgB, NA, NB,
               FA.shape[0], FB.shape[0], FA.shape[1], _p(rowloss), _p(ws), nbytes, _stream())
@@ -2197,8 +2146,7 @@ def pair_match(FA, FB, NA: int, NB: int, both: bool = True, geoB=None, truthA=No
             raise ValueError("pair_match: geoB holds fewer than NB x NB entries, or truthA not NA")
         truthA = truthA.contiguous()
     dev = FA.device
-    nbytes = _lib.load().sn_pair_match_workspace_bytes(FA.shape[0], FB.shape[0])
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws, nbytes = _workspace("sn_pair_match_workspace_bytes", dev, FA.shape[0], FB.shape[0], least=0)
     colA = torch.empty(NA, dtype=torch.int64, device=dev)
     bestA = torch.empty(NA, dtype=torch.float32, device=dev)
     rowB = torch.empty(NB, dtype=torch.int64, device=dev) if both else None
@@ -2215,8 +2163,7 @@ def masked_smooth_l1_fwd(out2d, target2d, rowmask, scale: float):
     _dev(out2d, target2d, rowmask)
     rows, C = out2d.shape
     loss = torch.empty((), dtype=torch.float32, device=out2d.device)
-    ws_bytes = int(_lib.load().sn_masked_smooth_l1_workspace_bytes(rows, C))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=out2d.device)
+    ws, ws_bytes = _workspace("sn_masked_smooth_l1_workspace_bytes", out2d.device, rows, C, least=0)
     _lib.call("sn_masked_smooth_l1_fwd_f32", _p(out2d), _ld(out2d), _p(target2d), _ld(target2d), _p(rowmask), rows, C,
               float(scale), _p(loss), _p(ws), ws_bytes, _stream())
     return loss
@@ -2239,8 +2186,7 @@ def masked_smooth_l1_fwdg(out2d, target2d, rowmask, scale: float):
     rows, C = out2d.shape
     loss = torch.empty((), dtype=torch.float32, device=out2d.device)
     g = torch.empty((rows, C), dtype=torch.float32, device=out2d.device)
-    ws_bytes = int(_lib.load().sn_masked_smooth_l1_workspace_bytes(rows, C))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=out2d.device)
+    ws, ws_bytes = _workspace("sn_masked_smooth_l1_workspace_bytes", out2d.device, rows, C, least=0)
     _lib.call("sn_masked_smooth_l1_fwdg_f32", _p(out2d), _ld(out2d), _p(target2d), _ld(target2d), _p(rowmask), rows, C,
               float(scale), _p(loss), _p(g), C, _p(ws), ws_bytes, _stream())
     return loss, g
@@ -2288,9 +2234,6 @@ def linear_dgrad_eluseg(dy, W, x, center, B, Cc, segvec, rows_per_seg: int, rowm
 
 
 # ---- lattice Delaunay, Poisson-disc sampling, the Mesh-MNIST maker (csrc/sn_delaunay.hip) -------------------------------------
-DT_DEGENERATE, DT_DUPLICATE, DT_RANGE, DT_TOO_LARGE, DT_NOT_CONVERGED, DT_REJECTED, DT_INTERNAL = 1, 2, 4, 8, 16, 32, 64   # SN_DT_*
-MESHDIGITS_MAX_ATTEMPTS = 8                      # SN_MESHDIGITS_MAX_ATTEMPTS
-MESHDIGITS_MIN_DET = 85899345                    # SN_MESHDIGITS_MIN_DET
 DT_MAX_ROUNDS = 4096                             # default flip-round budget (210 random points take about 50 rounds)
 
 Delaunay2D = collections.namedtuple("Delaunay2D", "F nF status counts")
@@ -2376,8 +2319,6 @@ def mesh_digits(images, seed: int = 0, R: int = 98304, min_points: int = 101, mi
 
 
 # ---- ARAP deformation (include/sn_spmm.h, "ARAP deformation"; host statement mesh_ops.arap_*) ------------------------------------
-ARAP_NOT_CONVERGED, ARAP_BREAKDOWN, ARAP_DEGENERATE, ARAP_BAD_FACE, ARAP_DEGREE, ARAP_TOO_LARGE = 1, 2, 4, 8, 16, 32
-ARAP_MAX_CG = 65536                      # SN_ARAP_MAX_CG
 ARAP_FRAMES_PER_LAUNCH = 5               # LABNOTES.md#arapdeform: one launch stays a bounded piece of work
 
 ArapWeights = collections.namedtuple("ArapWeights", "rowptr colind w d status")
@@ -2403,8 +2344,7 @@ def arap_weights(V0, F) -> ArapWeights:
     w = torch.empty(6 * nF, dtype=torch.float64, device=dev)
     d = torch.empty(nV, dtype=torch.float64, device=dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
-    ws_bytes = int(_lib.load().sn_arap_weights_workspace_bytes(nV, nF))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace("sn_arap_weights_workspace_bytes", dev, nV, nF)
     _lib.call("sn_arap_weights_f64", _p(V0), _p(F), nV, nF, rowptr.data_ptr(), _p(colind), _p(w), _p(d), status.data_ptr(), _p(ws),
               ws_bytes, _stream())
     return ArapWeights(rowptr, colind, w, d, status)
@@ -2439,8 +2379,7 @@ def arap_frames(V0, weights: ArapWeights, voff, hoff, handles, H, max_mesh_verti
     status = torch.empty(B, dtype=torch.int32, device=dev)
     R_first = torch.empty(nV, 3, 3, dtype=torch.float64, device=dev) if first_step else None
     rhs_first = torch.empty(nV, 3, dtype=torch.float64, device=dev) if first_step else None
-    ws_bytes = int(_lib.load().sn_arap_frames_workspace_bytes(nV))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace("sn_arap_frames_workspace_bytes", dev, nV)
     for begin in range(0, T, chunk):
         _lib.call("sn_arap_frames_f64", _p(V0), weights.rowptr.data_ptr(), _p(weights.colind), _p(weights.w), _p(weights.d),
                   voff.data_ptr(), hoff.data_ptr(), _p(handles), _p(H), B, nV, nH, T, int(max_mesh_vertices), begin,

@@ -26,6 +26,10 @@ import warnings
 import numpy as np
 import scipy.sparse as sp
 
+from . import constants
+# the status bits and limits of include/sn_spmm.h, kept once in constants.py and exposed here under the same names
+from .constants import *  # noqa: F401,F403
+
 __all__ = [
     "edge_lengths", "heron_areas", "cotangent_weights", "laplacian", "dirac", "mesh_operators",
     "grid_cloth", "torus_grid", "delaunay_disc", "read_ply_ascii",
@@ -170,7 +174,6 @@ def mesh_operators(V: np.ndarray, F: np.ndarray, dtype=np.float32):
 # Delta-complex keyed by FACE SIDES (code 3 f + s): after flips two faces may share two edges, a face may have a self-edge and
 # one vertex pair may carry several edges, so nothing here is keyed by vertex pairs.
 # --------------------------------------------------------------------------------------------------
-IDT_THRESHOLD = -1e-12       # a glued side is non-Delaunay iff cot_f + cot_g < IDT_THRESHOLD (part of the definition)
 
 
 def mesh_glue(F: np.ndarray, num_vertices: int) -> np.ndarray:
@@ -356,9 +359,6 @@ def intrinsic_laplacian(V: np.ndarray, F: np.ndarray, order: str = "fifo", seed:
 # of igl.facet_components + scipy.stats.mode + igl.slice + igl.remove_unreferenced as the reference's
 # src/dense_correspondence/largest_component.py:28-47 chains them; what the device kernels are compared to, bit for bit.
 # --------------------------------------------------------------------------------------------------
-CC_BAD_FACE = 1              # SN_CC_BAD_FACE: a face has an index outside 0..nV-1 or a repeated index
-CC_INTERNAL = 2              # SN_CC_INTERNAL: a device loop bound was hit (never set here)
-
 Components = collections.namedtuple("Components", "vlabel flabel count summary status")
 Compacted = collections.namedtuple("Compacted", "I J Fsrc Fnew Vnew sizes")
 
@@ -463,8 +463,6 @@ def largest_component(V, F: np.ndarray, connectivity: str = "edge"):
 # igl.remove_duplicate_vertices + igl.bfs_orient and the face filter of src/normal_predict/fix_degenerate.py, by sorting and
 # frontier sweeps; what the device's hash tables and parity union-find are compared to, bit for bit.
 # --------------------------------------------------------------------------------------------------
-REPAIR_BAD_FACE, REPAIR_NONFINITE, REPAIR_NONORIENTABLE, REPAIR_NONMANIFOLD, REPAIR_INTERNAL = 1, 2, 4, 8, 16   # SN_REPAIR_*
-
 Welded = collections.namedtuple("Welded", "rep F counts status")
 UniqueFaces = collections.namedtuple("UniqueFaces", "keep counts status")
 Oriented = collections.namedtuple("Oriented", "flip label F counts status")
@@ -621,9 +619,6 @@ def repair_mesh(V, F, tol: float = 0.0, weld: bool = True, unique: bool = True, 
 # descriptors").  The host statement of what src/utils/geom_utils.py takes from pyigl, in numpy float64 with the operation
 # order of the header: elementwise ufuncs only (each rounds on its own), np.add.at for the ordered sums, no np.sum, no np.cross.
 # --------------------------------------------------------------------------------------------------
-DESC_BAD_FACE, DESC_FLAT_FACE, DESC_NO_NORMAL, DESC_CLAMPED, DESC_DEGREE = 1, 2, 4, 8, 16      # SN_DESC_* status bits
-LAP_MAX_DEGREE = 24          # SN_LAP_MAX_DEGREE: the device row kernels keep a vertex's neighbours in registers
-
 Descriptors = collections.namedtuple("Descriptors", "face_area face_normal n_area n_uniform n_angle mass_bary mass_voronoi gauss "
                                                     "mean status")
 
@@ -757,10 +752,6 @@ def libigl_laplacian(V: np.ndarray, F: np.ndarray, mass: str = "barycentric", ha
 # curvatures").  The host statement of geom_utils.compute_curv4 (igl.principal_curvature) in this project's own definition:
 # numpy float64, every ufunc rounding on its own, the patch sums serial over ascending vertex id.
 # --------------------------------------------------------------------------------------------------
-CURV_FEW_POINTS, CURV_NO_NORMAL, CURV_OVERFLOW, CURV_DEGENERATE = 32, 64, 128, 1024      # SN_CURV_* status bits
-CURV_MAX_RING = 1024         # SN_CURV_MAX_RING: the largest patch
-CURV_MIN_POINTS = 6          # SN_CURV_MIN_POINTS: the smallest patch a quadric is fitted to
-CURV_PIVOT_FLOOR = 1e-12     # SN_CURV_PIVOT_FLOOR: a Cholesky pivot must exceed this times its diagonal entry of G
 CURV_CLIP = 100.0            # compute_curv4 clips the four columns to +-100
 _CURV_CHUNK = 4096           # vertices taken together by the host statement (memory only, no effect on any value)
 _CURV_PAIRS = [(i, j) for i in range(5) for j in range(i, 5)]
@@ -974,9 +965,7 @@ def curv4(V: np.ndarray, F: np.ndarray, radius: int = 5):
 
 
 def curvature_status_names(status: int) -> str:
-    names = [(DESC_BAD_FACE, "BAD_FACE"), (CURV_FEW_POINTS, "FEW_POINTS"), (CURV_NO_NORMAL, "NO_NORMAL"),
-             (CURV_OVERFLOW, "OVERFLOW"), (CURV_DEGENERATE, "DEGENERATE")]
-    return " | ".join(name for bit, name in names if status & bit) or "no status bit"
+    return " | ".join(constants.status_names("curvature", status)) or "no status bit"
 
 
 # --------------------------------------------------------------------------------------------------
@@ -1163,12 +1152,8 @@ def read_ply_ascii(path: str):
 # Definition: include/sn_spmm.h ("Lattice Delaunay and the Mesh-MNIST maker").  Everything below is Python-int arithmetic — no
 # floating-point predicate, no transcendental function — and is NOT the device algorithm: a scan over the whole hull instead of a
 # walk, one flip at a time from a stack instead of claim-then-flip rounds.  The device is compared to it bit for bit.
-DT_DEGENERATE, DT_DUPLICATE, DT_RANGE, DT_TOO_LARGE, DT_NOT_CONVERGED, DT_REJECTED, DT_INTERNAL = 1, 2, 4, 8, 16, 32, 64   # SN_DT_*
-DELAUNAY_MAX_POINTS = 1024           # SN_DELAUNAY_MAX_POINTS
 DELAUNAY_COORD_LIMIT = 1 << 24       # |x|, |y| < 2^24
-MESHDIGITS_MAX_ATTEMPTS = 8          # SN_MESHDIGITS_MAX_ATTEMPTS
 MESHDIGITS_Q = 1 << 16               # lattice units per pixel
-MESHDIGITS_MIN_DET = 85899345        # SN_MESHDIGITS_MIN_DET = floor(0.02 * 2^32): area <= 1e-2 pixel^2  <=>  det <= this
 POISSON_CANDIDATES, POISSON_RETRIES = 30, 32
 
 Delaunay2D = collections.namedtuple("Delaunay2D", "F nF status flips cocircular boundary")
@@ -1465,12 +1450,7 @@ def mesh_digits(images, seed: int = 0, r: float = 1.5, min_points: int = 101, mi
 # Every sum below is written out in the header's order: slot by slot over the ascending columns of a row, rows strided over
 # ARAP_REDUCE_WIDTH partial sums, then the two halving trees.
 # --------------------------------------------------------------------------------------------------
-ARAP_NOT_CONVERGED, ARAP_BREAKDOWN, ARAP_DEGENERATE, ARAP_BAD_FACE, ARAP_DEGREE, ARAP_TOO_LARGE = 1, 2, 4, 8, 16, 32
-ARAP_REDUCE_WIDTH = 1024      # SN_ARAP_THREADS
 ARAP_WAVE = 64
-ARAP_JACOBI_SWEEPS = 6        # SN_ARAP_JACOBI_SWEEPS
-ARAP_RANK_EPS = 1e-20         # SN_ARAP_RANK_EPS
-ARAP_MAX_CG = 65536           # SN_ARAP_MAX_CG
 
 ArapWeights = collections.namedtuple("ArapWeights", "rowptr colind w d status")
 ArapSolve = collections.namedtuple("ArapSolve", "x iters status")
@@ -1809,8 +1789,7 @@ def arap_handle_motion(V0, frames: int, rng: np.random.Generator):
 # eigsh: the same steps and parameters as operators.laplacian_eigenpairs, the three kernels' arithmetic bit for bit (elementwise
 # ufuncs, products and sums rounded one by one), the dense steps through numpy's LAPACK where the device uses torch's.
 # --------------------------------------------------------------------------------------------------
-EIG_NOT_CONVERGED, EIG_CLIPPED_MASS = 256, 512        # SN_EIG_* status bits: they share a word with the pencil's DESC_* bits
-EIG_MASS_FLOOR = 1e-8                                  # compute_wks clips the Voronoi mass here before normalising it
+EIG_MASS_FLOOR = 1e-8                                # compute_wks clips the Voronoi mass here before normalising it
 
 Eigenpairs = collections.namedtuple("Eigenpairs", "values vectors residuals bound outer_iterations mass status")
 

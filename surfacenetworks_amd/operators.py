@@ -25,7 +25,7 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from . import kernels
+from . import constants, kernels
 
 __all__ = ["SparseOperator", "OperatorPool", "PackedSegments", "as_operator", "dirac_operators_from_mesh",
            "laplacian_operator_from_mesh", "geodesic_matrix_from_mesh", "spgemm", "amplify_sequence_operators",
@@ -401,17 +401,8 @@ def dirac_operators_from_mesh(V: torch.Tensor, F: torch.Tensor):
 
     V: (nV,3) and F: (nF,3) for one mesh, or V: (B,nV,3) and F: (nF,3) shared / (B,nF,3) per-mesh faces for a batch
     of equally sized meshes, which yields the block-diagonal batched operators directly."""
-    if V.dim() == 3:
-        B, nV = V.shape[0], V.shape[1]
-        Fb = F if F.dim() == 3 else F.unsqueeze(0).expand(B, -1, -1)
-        nF = Fb.shape[1]
-        off = (torch.arange(B, device=V.device, dtype=torch.int32) * nV).view(B, 1, 1)
-        Fg = (Fb.to(torch.int32) + off).reshape(B * nF, 3)
-        Vg = V.reshape(B * nV, 3)
-    else:
-        B, nV, nF = 1, V.shape[0], F.shape[0]
-        Vg, Fg = V, F.to(torch.int32)
-    di, diat, dia, dit = kernels.dirac_from_mesh(Vg.float(), Fg)
+    Vg, Fg, B, nV, nF = _offset_batch("dirac_operators_from_mesh", V, F, guard=False)
+    di, diat, dia, dit = kernels.dirac_from_mesh(Vg, Fg)
     Di = SparseOperator.from_bsr4(di, dit, (4 * B * nF, 4 * B * nV), batch=B)
     DiA = SparseOperator.from_bsr4(dia, diat, (4 * B * nV, 4 * B * nF), batch=B)
     for o in (Di, Di._t, DiA, DiA._t):           # quaternion blocks by construction: pack without reading the check flag
@@ -419,18 +410,27 @@ def dirac_operators_from_mesh(V: torch.Tensor, F: torch.Tensor):
     return Di, DiA
 
 
-def _offset_batch(who: str, V: torch.Tensor, F: torch.Tensor):
-    """(Vg, Fg, B, nV, nF): a batch (B, nV, 3) with shared (nF, 3) or per-mesh (B, nF, 3) faces laid out as one disjoint mesh."""
+def _mesh_offsets(B: int, nV: int, device) -> torch.Tensor:
+    """(B,) int32: the first vertex of every mesh of a batch laid out as one disjoint mesh."""
+    return torch.arange(B, device=device, dtype=torch.int32) * nV
+
+
+def _offset_batch(who: str, V: torch.Tensor, F: torch.Tensor, guard: bool = True):
+    """(Vg, Fg, B, nV, nF): a batch (B, nV, 3) with shared (nF, 3) or per-mesh (B, nF, 3) faces laid out as one disjoint mesh.
+    guard: an index outside its own mesh becomes -1, so that it stays outside the batch and cannot land in a neighbour's block.
+    That is for entry points that validate their faces and leave a bad one out.  sn_dirac_bsr4_from_mesh and
+    sn_laplacian_csr_from_mesh do not: they would read V at -1, so their callers pass guard=False and get the plain F + b nV
+    (arap_deform too: the layout it has always handed to its kernels)."""
     if V.dim() == 3:
         if V.shape[2] != 3 or F.dim() not in (2, 3) or F.shape[-1] != 3 or (F.dim() == 3 and F.shape[0] != V.shape[0]):
             raise ValueError(f"{who} wants V (B, nV, 3) with F (nF, 3) or (B, nF, 3), got {tuple(V.shape)} and {tuple(F.shape)}")
         B, nV = V.shape[0], V.shape[1]
         Fb = F if F.dim() == 3 else F.unsqueeze(0).expand(B, -1, -1)
-        off = (torch.arange(B, device=V.device, dtype=torch.int32) * nV).view(B, 1, 1)
         Fi = Fb.to(torch.int32)
-        # an index outside its own mesh stays outside the batch (it must not land in a neighbour's block)
-        Fg = torch.where((Fi >= 0) & (Fi < nV), Fi + off, torch.full_like(Fi, -1)).reshape(-1, 3)
-        return V.reshape(B * nV, 3).float(), Fg, B, nV, Fb.shape[1]
+        Fg = Fi + _mesh_offsets(B, nV, V.device).view(B, 1, 1)
+        if guard:
+            Fg = torch.where((Fi >= 0) & (Fi < nV), Fg, torch.full_like(Fi, -1))
+        return V.reshape(B * nV, 3).float(), Fg.reshape(-1, 3), B, nV, Fb.shape[1]
     if V.dim() != 2 or V.shape[1] != 3 or F.dim() != 2 or F.shape[1] != 3:
         raise ValueError(f"{who} wants V (nV, 3) and F (nF, 3), got {tuple(V.shape)} and {tuple(F.shape)}")
     return V.float(), F.to(torch.int32), 1, V.shape[0], F.shape[0]
@@ -513,12 +513,25 @@ class PrincipalCurvatures:
     status: Optional[torch.Tensor] = None
 
 
-def _mesh_tensors(V, F, device="cuda"):
-    """Tensors as given, numpy arrays as fp32 / int32 tensors on `device`."""
-    if not torch.is_tensor(V):
-        V = torch.from_numpy(np.array(V, dtype=np.float32)).to(device)
-    if not torch.is_tensor(F):
-        F = torch.from_numpy(np.array(F, dtype=np.int32)).to(V.device)
+def _mesh_tensors(who: str, V, F, device="cuda", checked: bool = False):
+    """V as an fp32 and F as an int32 tensor: a tensor is cast where it is, anything else goes through numpy, is cast on the host
+    and moved to `device` (F to where V is); device=None leaves it on the host, for checks that need no device.
+    checked: V (nV, 3) floating point and F (nF, 3) int32 or int64 are required, ValueError for a shape and TypeError for a
+    type; without it the layout checks of the caller follow."""
+    v_given, f_given = torch.is_tensor(V), torch.is_tensor(F)
+    if not v_given:
+        V = torch.from_numpy(np.array(V, dtype=np.float32))
+    if not f_given:
+        F = torch.from_numpy(np.array(F))
+    if checked:
+        if V.dim() != 2 or V.shape[1] != 3 or F.dim() != 2 or F.shape[1] != 3:
+            raise ValueError(f"{who} wants V (nV, 3) and F (nF, 3), got {tuple(V.shape)} and {tuple(F.shape)}")
+        if F.dtype not in (torch.int32, torch.int64) or not V.is_floating_point():
+            raise TypeError(f"{who} wants floating-point V and int32 or int64 F")
+    V, F = V.float(), F.to(torch.int32)
+    if device is not None:
+        V = V if v_given else V.to(device)
+        F = F if f_given else F.to(V.device)
     return V, F
 
 
@@ -531,7 +544,7 @@ def principal_curvatures(V, F, radius: int = 5, want=None) -> PrincipalCurvature
     want: names of the PrincipalCurvatures fields to compute (None: all of them).  A vertex whose patch cannot be fitted (fewer
     than six members, more than kernels.CURV_MAX_RING, no normal, a degenerate patch) holds NaN and is reported in `status`.
     Does not synchronise."""
-    V, F = _mesh_tensors(V, F)
+    V, F = _mesh_tensors("principal_curvatures", V, F)
     kernels._dev(V, F)
     Vg, Fg, B, nV, nF = _offset_batch("principal_curvatures", V, F)
     out = kernels.mesh_principal_curvature(Vg, Fg, radius, want)
@@ -540,13 +553,6 @@ def principal_curvatures(V, F, radius: int = 5, want=None) -> PrincipalCurvature
             if out[name] is not None:
                 out[name] = out[name].view((B, nV) + ((width,) if width > 1 else ()))
     return PrincipalCurvatures(**out)
-
-
-_CURV_REASONS = ((kernels.DESC_BAD_FACE, "a face has an index outside the mesh or a repeated index"),
-                 (kernels.CURV_FEW_POINTS, "a patch has fewer than six members"),
-                 (kernels.CURV_NO_NORMAL, "a vertex has no normal"),
-                 (kernels.CURV_OVERFLOW, f"a patch has more than {kernels.CURV_MAX_RING} members"),
-                 (kernels.CURV_DEGENERATE, "a patch is degenerate"))
 
 
 def curv4(V, F, radius: int = 5):
@@ -558,7 +564,7 @@ def curv4(V, F, radius: int = 5):
     C = torch.stack([pc.k1, pc.k2, (pc.k1 + pc.k2) / 2, pc.k1 * pc.k2], dim=-1).clamp(-100.0, 100.0)
     if bool(torch.isnan(C).any()):
         status = int(pc.status.item())
-        why = "; ".join(text for bit, text in _CURV_REASONS if status & bit and bit != kernels.DESC_BAD_FACE) or "non-finite input"
+        why = "; ".join(constants.status_sentences("curvature", status & ~kernels.DESC_BAD_FACE)) or "non-finite input"
         warnings.warn(f"curv4: {int(torch.isnan(pc.k1).sum())} vertices have no curvature (status {status}: {why}); no columns")
         return None
     return C / C.abs().amax(dim=-2, keepdim=True)
@@ -592,19 +598,11 @@ def laplacian_operator_from_mesh(V: torch.Tensor, F: torch.Tensor, intrinsic: bo
         return L
     if mass != "barycentric" or hack is not None:
         raise ValueError('laplacian_operator_from_mesh: mass and hack belong to convention="libigl"')
-    if V.dim() == 3:
-        B, nV = V.shape[0], V.shape[1]
-        Fb = F if F.dim() == 3 else F.unsqueeze(0).expand(B, -1, -1)
-        off = (torch.arange(B, device=V.device, dtype=torch.int32) * nV).view(B, 1, 1)
-        Fg = (Fb.to(torch.int32) + off).reshape(-1, 3)
-        Vg = V.reshape(B * nV, 3)
-    else:
-        B, nV = 1, V.shape[0]
-        Vg, Fg = V, F.to(torch.int32)
+    Vg, Fg, B, nV, _ = _offset_batch("laplacian_operator_from_mesh", V, F, guard=False)
     if intrinsic:
-        rowptr, colind, vals = kernels.intrinsic_laplacian_from_mesh(Vg.float(), Fg, max_rounds)
+        rowptr, colind, vals = kernels.intrinsic_laplacian_from_mesh(Vg, Fg, max_rounds)
     else:
-        rowptr, colind, vals = kernels.laplacian_from_mesh(Vg.float(), Fg)
+        rowptr, colind, vals = kernels.laplacian_from_mesh(Vg, Fg)
     return SparseOperator(rowptr, colind, vals, (B * nV, B * nV), batch=B)
 
 
@@ -711,16 +709,9 @@ def clean_mesh(V, F, component="largest", connectivity: str = "edge") -> CleanMe
             raise ValueError(f'clean_mesh: component must be "largest", "all" or an integer label, got {component!r}')
     elif isinstance(component, bool) or not isinstance(component, (int, np.integer)):
         raise TypeError(f'clean_mesh: component must be "largest", "all" or an integer label, got {component!r}')
-    if not torch.is_tensor(V):
-        V = torch.from_numpy(np.array(V, dtype=np.float32)).to("cuda")
-    if not torch.is_tensor(F):
-        F = torch.from_numpy(np.array(F)).to(V.device)
-    if V.dim() != 2 or V.shape[1] != 3 or F.dim() != 2 or F.shape[1] != 3:
-        raise ValueError(f"clean_mesh wants V (nV, 3) and F (nF, 3), got {tuple(V.shape)} and {tuple(F.shape)}")
-    if F.dtype not in (torch.int32, torch.int64) or not V.is_floating_point():
-        raise TypeError("clean_mesh wants floating-point V and int32 or int64 F")
+    V, F = _mesh_tensors("clean_mesh", V, F, checked=True)
     kernels._dev(V, F)
-    Vf, Fi = V.float().contiguous(), F.to(torch.int32).contiguous()
+    Vf, Fi = V.contiguous(), F.contiguous()
     nV, nF = Vf.shape[0], Fi.shape[0]
     cc = kernels.mesh_components(Fi, nV, connectivity)
     if isinstance(component, str) and component == "all":
@@ -738,8 +729,7 @@ def clean_mesh(V, F, component="largest", connectivity: str = "edge") -> CleanMe
     out = kernels.mesh_compact(Fi, keep, nV, Vf)
     bad = (cc.flabel < 0).sum(dtype=torch.int32).view(1)
     nVk, nFk, ncomp, _, _, st, nbad, npicked = torch.cat([out.sizes, cc.summary, cc.status, bad, picked]).tolist()   # the one read
-    if st & kernels.CC_INTERNAL:
-        raise RuntimeError("clean_mesh: the component kernels hit a loop bound (status SN_CC_INTERNAL)")
+    kernels.raise_for_status("clean_mesh", "components", st, ((kernels.CC_INTERNAL, RuntimeError),))
     if ncomp == 0:
         raise ValueError("clean_mesh: the mesh has no face with three distinct vertices of the mesh")
     if npicked == 0:
@@ -774,16 +764,9 @@ def repair_mesh(V, F, tol: float = 0.0, weld: bool = True, unique: bool = True, 
     tol = float(tol)
     if not 0.0 <= tol < float("inf"):
         raise ValueError(f"repair_mesh: tol must be finite and >= 0, got {tol!r}")
-    if not torch.is_tensor(V):
-        V = torch.from_numpy(np.array(V, dtype=np.float32)).to("cuda")
-    if not torch.is_tensor(F):
-        F = torch.from_numpy(np.array(F)).to(V.device)
-    if V.dim() != 2 or V.shape[1] != 3 or F.dim() != 2 or F.shape[1] != 3:
-        raise ValueError(f"repair_mesh wants V (nV, 3) and F (nF, 3), got {tuple(V.shape)} and {tuple(F.shape)}")
-    if F.dtype not in (torch.int32, torch.int64) or not V.is_floating_point():
-        raise TypeError("repair_mesh wants floating-point V and int32 or int64 F")
+    V, F = _mesh_tensors("repair_mesh", V, F, checked=True)
     kernels._dev(V, F)
-    Vf, Fi = V.float().contiguous(), F.to(torch.int32).contiguous()
+    Vf, Fi = V.contiguous(), F.contiguous()
     nV = Vf.shape[0]
     w = kernels.mesh_weld(Vf, Fi, tol, weld)
     u = kernels.mesh_unique_faces(w.F, nV, Vf, unique)
@@ -798,8 +781,7 @@ def repair_mesh(V, F, tol: float = 0.0, weld: bool = True, unique: bool = True, 
     got = torch.cat([out.sizes] + words).tolist()                                         # the one read
     nVk, nFk, welded, bad, dup, flat, st_w, st_u = got[:8]
     nonman, twisted, classes, st_o = got[8:] if orient else (-1, -1, -1, 0)
-    if (st_w | st_u | st_o) & kernels.REPAIR_INTERNAL:
-        raise RuntimeError("repair_mesh: the repair kernels hit a loop bound (status SN_REPAIR_INTERNAL)")
+    kernels.raise_for_status("repair_mesh", "repair", st_w | st_u | st_o, ((kernels.REPAIR_INTERNAL, RuntimeError),))
     face_map = out.Fsrc[:nFk]
     return RepairedMesh(out.Vnew[:nVk], out.Fnew[:nFk], out.J[:nVk], out.I[w.rep.long()], face_map, flip[face_map.long()], welded, bad,
                         dup, flat, nonman, twisted, classes)
@@ -1224,14 +1206,6 @@ class OperatorPool:
 
 ArapDeformation = collections.namedtuple("ArapDeformation", "frames cg_iters energy status")
 
-_ARAP_REASONS = ((kernels.ARAP_NOT_CONVERGED, "a conjugate-gradient solve stopped at max_cg iterations before reaching tol"),
-                 (kernels.ARAP_BREAKDOWN, "a solve broke down (p.Ap <= 0 or a free row without a positive diagonal): the frame keeps "
-                                          "its start values"),
-                 (kernels.ARAP_DEGENERATE, "a vertex has spokes of rank below 2: its rotation is the identity"),
-                 (kernels.ARAP_BAD_FACE, "a face has an index outside the mesh or a repeated index and was left out"),
-                 (kernels.ARAP_DEGREE, "a vertex has more incident faces than SN_LAP_MAX_DEGREE and got no weights"),
-                 (kernels.ARAP_TOO_LARGE, "a mesh was too large for the launch and was left at rest"))
-
 
 def arap_deform(V0, F, handles, H, iters: int = 2, tol: float = 1e-10, max_cg: int = 4096) -> ArapDeformation:
     """As-rigid-as-possible deformation sequences on the device: spokes-only ARAP (Sorkine & Alexa 2007), local and global steps
@@ -1251,7 +1225,7 @@ def arap_deform(V0, F, handles, H, iters: int = 2, tol: float = 1e-10, max_cg: i
         return a.to(dtype) if torch.is_tensor(a) else torch.from_numpy(np.array(a)).to(dtype)
 
     given = (V0, F, handles, H)
-    V0, F, handles, H = tensor(V0, torch.float32), tensor(F, torch.int32), tensor(handles, torch.int32), tensor(H, torch.float32)
+    (V0, F), handles, H = _mesh_tensors("arap_deform", V0, F, device=None), tensor(handles, torch.int32), tensor(H, torch.float32)
     single = V0.dim() == 2
     if single:
         V0, F, handles, H = V0[None], F[None], handles[None], H[None]
@@ -1273,27 +1247,23 @@ def arap_deform(V0, F, handles, H, iters: int = 2, tol: float = 1e-10, max_cg: i
     V0, F, handles, H = (t if torch.is_tensor(g) else t.to("cuda") for t, g in zip((V0, F, handles, H), given))
     kernels._dev(V0, F, handles, H)
     dev = V0.device
-    base = torch.arange(B, device=dev, dtype=torch.int32)[:, None] * nV
-    Vu = V0.reshape(B * nV, 3).contiguous()
-    Fu = (F + base[:, :, None]).reshape(-1, 3).contiguous()
-    hu = (handles + base).reshape(-1).contiguous()
+    Vu, Fu = _offset_batch("arap_deform", V0, F, guard=False)[:2]
+    voff, hoff = _mesh_offsets(B + 1, nV, dev), _mesh_offsets(B + 1, nH, dev)
+    hu = (handles + voff[:B, None]).reshape(-1).contiguous()
     cc = kernels.mesh_components(Fu, B * nV, "vertex")
     has = torch.zeros(B * nV, dtype=torch.bool, device=dev)
     has[cc.vlabel[hu.long()].long()] = True
     if not bool(has[cc.vlabel.long()].all()):
         raise ValueError("arap_deform: a connected component of the mesh has no handle (its positions are not determined)")
     weights = kernels.arap_weights(Vu, Fu)
-    voff = torch.arange(B + 1, device=dev, dtype=torch.int32) * nV
-    hoff = torch.arange(B + 1, device=dev, dtype=torch.int32) * nH
     Hu = H.permute(1, 0, 2, 3).reshape(T, B * nH, 3).contiguous()
     out = kernels.arap_frames(Vu, weights, voff, hoff, hu, Hu, nV, iters, tol, max_cg)
     status = out.status | weights.status          # the builder's word covers the union
     bits = 0
     for word in status.tolist():
         bits |= word
-    for bit, reason in _ARAP_REASONS:
-        if bits & bit:
-            warnings.warn(f"arap_deform: {reason}", RuntimeWarning, stacklevel=2)
+    for reason in constants.status_sentences("arap", bits):
+        warnings.warn(f"arap_deform: {reason}", RuntimeWarning, stacklevel=2)
     frames = out.frames.reshape(T, B, nV, 3).permute(1, 0, 2, 3).contiguous()
     if single:
         return ArapDeformation(frames[0], out.cg_iters[0], out.energy[0], status[0])
