@@ -435,7 +435,7 @@ int sn_wgrad_seg_f32(const float *dy, int64_t lddy, const float *x, int64_t ldx,
  * batch maximum, src/as_rigid_as_possible/main.py:172-185): the caller supplies the row slabs, slab b = rows
  * [slab_off[b], slab_off[b+1]) (device int64[nslab + 1], consecutive, none crossing a mesh boundary) and the slabs of every
  * mesh, [seg_slab_ptr[m], seg_slab_ptr[m+1]) (device int64[nseg + 1]); seg_dysum is (nseg x J).  Workspace:
- * nslab * 128 * (C + 1) floats.  Uniform-wave kernel only (SN_E_UNSUPPORTED with SN_GEMM_VARIANT=0 / SN_WGRAD_VARIANT=1). */
+ * nslab * 128 * (C + 1) floats.  16-bit matrix-pipe kernel only (SN_E_UNSUPPORTED with SN_GEMM_VARIANT=0). */
 int sn_wgrad_slabs_f32(const float *dy, int64_t lddy, const float *x, int64_t ldx, const float *center, int64_t rows,
                        const int64_t *slab_off, int32_t nslab, const int64_t *seg_slab_ptr, int32_t nseg, int32_t J, int32_t C,
                        float *G, double *dysum, float *seg_dysum, void *workspace, size_t workspace_bytes, void *stream);
@@ -451,8 +451,7 @@ int sn_wgrad_slabs_f32(const float *dy, int64_t lddy, const float *x, int64_t ld
  *             every row of x:  |x[r][c] - center[c]| <= sqrt(stat_rows) / xinvstd[c]  holds for every row, rigorously.
  * Both operands are scaled so that their bound lands in [2^14, 2^15) (nothing can overflow); an element keeps 22 significant
  * bits down to 2^-17 of its operand's bound and 2^-25 of the scaled unit (2^-39 of the bound) in absolute terms below that
- * (SN_WGRAD_H=1: a second accumulator for low pieces scaled by a further 2^11 — 2^-28 / 2^-50 — at the cost of the second row
- * block in flight); results leave multiplied by the exact inverse scales.  Eval-mode BatchNorm (running statistics) offers no such bound: use the unbounded forms.
+ * (one accumulator, the low pieces unscaled); results leave multiplied by the exact inverse scales.  Eval-mode BatchNorm (running statistics) offers no such bound: use the unbounded forms.
  * Same arguments, workspace and status codes as the forms above; SN_E_SHAPE when stat_rows < rows, SN_E_NULL without bounds. */
 int sn_wgrad_bounded_f32(const float *dy, int64_t lddy, const float *x, int64_t ldx, const float *center, int64_t rows,
                          int32_t J, int32_t C, float *G, double *dysum, void *workspace, size_t workspace_bytes,

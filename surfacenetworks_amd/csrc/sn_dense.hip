@@ -3,7 +3,8 @@
 //   colstats_k / colstats_final_k   per-channel sum and sum of squares, fp64 accumulation (HBM-bound, one pass)
 //   wgrad_mfma_k / wgrad_reduce_k   G = dyᵀ·x for tall-skinny operands: split-K over row slabs on the fp32 MFMA
 //                                   (v_mfma_f32_32x32x2_f32: exact fp32, 64 FLOP/clk/SIMD)
-//   wgrad_u_k / wgrad_h_k           the same product on three bf16 / two scaled fp16 pieces
+//   wgrad16_k<CT, Pieces>           the same product on the 16-bit matrix pipe: one kernel skeleton, two piece forms —
+//                                   WgradBf3 (three bf16 pieces) and WgradHalf2 (two scaled fp16 pieces)
 //   affine_cols_acc_k               dx += x*B[c] + C[c]  (tail of the BatchNorm backward)
 //   ... and, each under its own banner below: BatchNorm fold and backward coefficients, the thin Linear layers, segment sums,
 //   global average, masked smooth-L1, segment gathers, and the losses on a MATERIALISED score matrix (pair_argmin*, pair_ce_*).
@@ -11,8 +12,6 @@
 //
 // Interfaces and the reference code they replace: include/sn_spmm.h.
 
-#include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
 #include <limits.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -22,8 +21,6 @@
 #include "sn_dense_common.h"
 
 namespace {
-
-#define kCUs sn_internal_cu_count()      // compute units of the current device (256 on an MI355X in SPX mode)
 
 __device__ __forceinline__ f4 ld4_s(const float *p, int nt) {
   return nt ? __builtin_nontemporal_load(reinterpret_cast<const f4 *>(p)) : *reinterpret_cast<const f4 *>(p);
@@ -294,62 +291,220 @@ __global__ __launch_bounds__(kWG, 2) void wgrad_mfma_k(const float *__restrict__
 // 8 rows x 1 column becomes one 16-byte slot per piece.  Slot of (column c, row group g): g·PL + (c%4)·QP + c/4 with QP =
 // (#columns/4) + 4: consecutive writer lanes hit consecutive slots, the 16-lane groups of a fragment ds_read_b128 fall on 16
 // different slot residues mod 16 — both directions conflict-free.  Columns 0..127 are dy (zero past J), the rest x - center.
-// Two kernels: wgrad_h_k (two scaled fp16 pieces, needs bounds on its operands; the default of the training step) and
-// wgrad_u_k (three bf16 pieces, no bounds needed: eval-mode BatchNorm, dy from a kernel that leaves no maxima).  Rounds 1-3's
-// wave-specialised and LDS-DMA forms are described in LABNOTES (k23, wgrad_d).
-// ------------------------------------------------------------------------------------------------
-typedef __bf16 bf8v __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ f16v mfma_bf16(const u4 &a, const u4 &b, const f16v &c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf8v, a), __builtin_bit_cast(bf8v, b), c, 0, 0, 0);
-}
-constexpr int kWgradThreads = 512;          // 8 waves, two per SIMD
-
-
-// ------------------------------------------------------------------------------------------------
-// wgrad_u_k — the three-piece bf16 weight gradient (six exact partial products per term), uniform waves.
+// ONE kernel, wgrad16_k<CT, Pieces>, in two piece forms: WgradHalf2 (two scaled fp16 pieces, needs bounds on its operands; the
+// default of the training step) and WgradBf3 (three bf16 pieces, no bounds needed: eval-mode BatchNorm, dy from a kernel
+// that leaves no maxima).  Rounds 1-3's wave-specialised and LDS-DMA forms are described in LABNOTES (k23, wgrad_d).
 //
-// All 8 waves do both jobs: per 32-row block a wave converts its share of the operands — units of 8 rows x 1 column, one
-// 16-byte LDS slot per piece: 3 units per lane at C = 256, 2 at C = 128, every lane of every wave busy — and multiplies
-// 2 x CT output tiles (2 dy tiles x CT x tiles).
+// The skeleton — uniform waves.  All 8 waves do both jobs: per 32-row block a wave converts its share of the operands — units
+// of 8 rows x 1 column, one 16-byte LDS slot per piece: 3 units per lane at C = 256, 2 at C = 128, every lane of every wave
+// busy — and multiplies 2 x CT output tiles (2 dy tiles x CT x tiles).
 //   * conversion slot 0 of wave w = the dy half-block (row group w/2, 64 columns (w%2)·64 ..), slots 1.. = x half-blocks
 //     w + 8(k-1) of the 4 row groups x 2·CT half-blocks: roles are compile-time, a slot has one row group; global loads are
 //     dword-per-lane over 64 consecutive columns (256 contiguous bytes per row and instruction) through a raw buffer
-//     resource whose extent ends with the slab (rows past it read 0: no masks, no clamps); block b+2 is requested into the
-//     registers block b+1 was converted from, while block b is multiplied;
-//   * one workgroup barrier per 32-row block, two LDS images of 4 row groups (154 KB at C = 256); slot layout as above;
+//     resource whose extent ends with the slab (rows past it read 0: no masks, no clamps); block b+1+SETS is requested into
+//     the registers block b+1 was converted from, while block b is multiplied;
+//   * one workgroup barrier per 32-row block, two LDS images of 4 row groups; slot layout as above;
 //   * the two co-resident waves of a SIMD run the same stream, and a wave is in-order: what overlaps the matrix pipe, the
 //     vector ALU and the memory pipe is the MIX inside the stream — a pair of rows converted every few MFMAs, one load at a
 //     time behind it (program order pinned by sched_barrier).
-// Measurements, the structures tried on the way and the ablation builds: LABNOTES k22.
+// A piece form (Pieces) holds what differs: the number of pieces and how a pair of rows splits into them, which piece pair
+// feeds MFMA t of a tile and step (small terms first) and on which instruction, the scale of the result, the register sets
+// of rows in flight, and the schedule — behind which MFMA of a block a pair is converted, a row reloaded and a slot written
+// (pairs are converted behind MFMA q·NM/NPAIR in both; the rest differs and is kept as measured, down to the order inside a
+// chunk: at 230-238 VGPRs the register allocation follows it).  Measurements, the structures tried on the way and the
+// ablation builds: LABNOTES k22, r4wgrad, wgradskel.
 // ------------------------------------------------------------------------------------------------
-template <int I>
-struct WIC {
-  static constexpr int value = I;
-};
-template <int I, int N, class F>
-__device__ __forceinline__ void wstatic_for(F &&f) {
-  if constexpr (I < N) {
-    f(WIC<I>{});
-    wstatic_for<I + 1, N>(f);
-  }
-}
+typedef __bf16 bf8v __attribute__((ext_vector_type(8)));
+constexpr int kWgradThreads = 512;          // 8 waves, two per SIMD
 
-template <int CT /* C / 128: 1 or 2 */>
-__global__ __launch_bounds__(kWgradThreads, 1) void wgrad_u_k(const float *__restrict__ dy, int64_t lddy,
+// Three bf16 pieces, six exact partial products per term: x = h + m + l by packed fp32 subtractions, each piece the upper 16
+// bits of an exact remainder (≈10 vector instructions a pair).  154 KB of LDS images at C = 256.
+struct WgradBf3 {
+  static constexpr int kPieces = 3, kProducts = 6, kSets = 1;      // (a second register set, two blocks ahead, measured no faster)
+  struct Args {};
+  // pieces of (dy, x) in product t: (l,h) (h,l) (m,m) (m,h) (h,m) (h,h)
+  static constexpr int piece_a(int t) { return (0x001102 >> (4 * t)) & 15; }
+  static constexpr int piece_b(int t) { return (0x010120 >> (4 * t)) & 15; }
+  // The schedule, behind MFMA M of a block (NM = 24·CT of them): one pair of rows converted every PSTEP MFMAs (the slot's
+  // window opened with its first pair); requests of the next block into the registers just converted: ONE load at a time —
+  // eight in a row fill the memory pipe's queue and stall the wave, hence the MFMAs behind them, for hundreds of cycles (the
+  // kernel is HBM-bound: a CU's share of the bandwidth is one 256-byte load per ≈26 cycles); the three LDS slots of a unit
+  // after its fourth pair.
+  static constexpr int load_at(int CT, int m) {      // row 8k + j requested behind MFMA m, or -1
+    return CT == 2 ? (m % 2 == 1 ? (m - 1) / 2 : -1) : (m % 3 != 0 ? (m / 3) * 2 + (m % 3 - 1) : -1);
+  }
+  static constexpr int write_at(int CT, int m) {     // slot written behind MFMA m, or -1
+    return CT == 2 ? (m % 16 == 14 ? m / 16 : -1) : (m % 12 == 11 ? m / 12 : -1);
+  }
+  template <int CT, int M, class Open, class Pair, class Load, class Write>
+  static __device__ __forceinline__ void behind(Open open, Pair pair, Load load, Write write) {
+    constexpr int NK = 1 + CT, PSTEP = 24 * CT / (4 * NK);      // 4 | 3
+    if constexpr (M % PSTEP == 0 && M / PSTEP < 4 * NK) {
+      constexpr int q = M / PSTEP, k = q / 4, p = q % 4;
+      if constexpr (p == 0) open(IC<k>{});
+      pair(IC<k>{}, IC<p>{});
+    }
+    constexpr int L = load_at(CT, M);
+    if constexpr (L >= 0 && L < 8 * NK) load(IC<L / 8>{}, IC<L % 8>{});
+    constexpr int wk = write_at(CT, M);
+    if constexpr (wk >= 0 && wk < NK) write(IC<wk>{});
+  }
+  static __device__ __forceinline__ f16v mfma(const u4 &a, const u4 &b, const f16v &c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf8v, a), __builtin_bit_cast(bf8v, b), c, 0, 0, 0);
+  }
+  __device__ __forceinline__ void init_slot(const Args &, int, int) {}
+  template <int CT>
+  __device__ __forceinline__ void init_scales(const Args &, float *, int, int, int) {}
+  template <int K>
+  __device__ __forceinline__ void split(f2v xv, unsigned (&piece)[kPieces]) const {
+    const u2 xb = __builtin_bit_cast(u2, xv);
+    const f2v r = xv - __builtin_bit_cast(f2v, xb & 0xFFFF0000u);
+    const u2 rb = __builtin_bit_cast(u2, r);
+    const f2v l = r - __builtin_bit_cast(f2v, rb & 0xFFFF0000u);
+    const u2 lb = __builtin_bit_cast(u2, l);
+    piece[0] = __builtin_amdgcn_perm(xb.y, xb.x, 0x07060302u);
+    piece[1] = __builtin_amdgcn_perm(rb.y, rb.x, 0x07060302u);
+    piece[2] = __builtin_amdgcn_perm(lb.y, lb.x, 0x07060302u);
+  }
+  __device__ __forceinline__ float finish(int, float v) const { return v; }
+};
+
+// Bounds that let the weight gradient run on two fp16 pieces: the maximum of dybound[0 .. ndy) >= max |dy| (device), xinvstd[C]
+// the BatchNorm inverse standard deviations of x's columns about `center` (device), xfac >= sqrt(rows behind those statistics).
+struct WgradBounds {
+  const float *dybound;
+  int ndy;
+  const float *xinvstd;
+  float xfac;
+};
+
+// Two scaled fp16 pieces, three partial products instead of six.
+//
+// Ablation of the bf16 form on one box (round 4, 627 200 rows x 256 columns): the six bf16 products alone (no loads, no
+// conversion) take 150 of the kernel's 293 us at the 1.8 GHz the chip sustains under it, the memory path alone 191, and the
+// two do not hide each other; with three of the six products issued the kernel runs in 232.  Halving the matrix work needs
+// the fp16 split of the forward kernels (sn_gemm.hip: x = h + l, h = rn16(x), l = rn16(x - h), three exact products h·h +
+// (h·l + l·h)), and fp16 needs RANGE control.  The contraction runs over the rows, so the powers of two that bring the
+// operands into range must be constant along a COLUMN, and they must be known before the first row is converted.  Both come
+// from bounds the callers already hold:
+//   x - mean   BatchNorm's own statistics: sum_r (x[r][c] - mean[c])^2 = n·var[c], hence |x[r][c] - mean[c]| <= sqrt(n / invstd[c]^2)
+//              for EVERY row — rigorous, no pass over x (n = rows behind the statistics; the caller passes xfac >= sqrt(n));
+//   dy         one number for the whole operand, an upper bound of max |dy| left by the kernel that PRODUCED dy (the
+//              input-gradient GEMM's epilogue, the transposed sparse product's store, the loss backward: sn_absmax_* in
+//              sn_spmm.h); one global scale suffices for rigour, and accuracy survives it — below.
+// Scaled operands: bound -> [2^14, 2^15) (fp16 tops out at 65504), so nothing can overflow.  One accumulator, the low piece
+// unscaled: an element keeps 22 significant bits down to 2^-17 of the operand's bound, 2^-25 (scaled) absolute below.
+// Results leave multiplied by the exact inverse scales.  Two 32-row blocks in flight in registers, two LDS images of 51 KB
+// at C = 256.  (A second accumulator for low pieces scaled by 2^11, one or three blocks in flight and interleaved slabs all
+// measured slower: LABNOTES r4wgrad.)
+struct WgradHalf2 {
+  static constexpr int kPieces = 2, kProducts = 3, kSets = 2;
+  typedef WgradBounds Args;
+  // pieces of (dy, x) in product t: (l,h) (h,l) (h,h)
+  static constexpr int piece_a(int t) { return t == 0 ? 1 : 0; }
+  static constexpr int piece_b(int t) { return t == 1 ? 1 : 0; }
+  // The schedule, behind MFMA M of a block (NM = 12·CT of them): pair q of the conversion at pair_at(q), the reload of the
+  // two rows it freed right behind it (row j = 2p with its pair — the slot's window opened with the first —, j = 2p + 1 one
+  // MFMA later; the last slot's last row stays inside the block), the two LDS slots of a unit with its fourth pair.
+  static constexpr int pair_at(int CT, int q) { return q * (12 * CT) / (4 + 4 * CT); }
+  template <int CT, int M, class Open, class Pair, class Load, class Write>
+  static __device__ __forceinline__ void behind(Open open, Pair pair, Load load, Write write) {
+    constexpr int NM = 12 * CT;
+    static_for<0, 4 + 4 * CT>([&](auto qc) {
+      constexpr int q = decltype(qc)::value, k = q / 4, p = q % 4;
+      constexpr int m0 = pair_at(CT, q), m1 = m0 + 1 < NM ? m0 + 1 : NM - 1;
+      if constexpr (m0 == M) {
+        pair(IC<k>{}, IC<p>{});
+        if constexpr (p == 3) write(IC<k>{});
+        if constexpr (p == 0) open(IC<k>{});
+        load(IC<k>{}, IC<2 * p>{});
+      }
+      if constexpr (m1 == M) load(IC<k>{}, IC<2 * p + 1>{});
+    });
+  }
+  static __device__ __forceinline__ f16v mfma(const u4 &a, const u4 &b, const f16v &c) { return mfma_f16(a, b, c); }
+
+  float sc[3];       // scale of conversion slot k: dy's (k = 0), my x column's
+  float osc[2];      // inverse scale of my output column in each of my x tiles, times dy's
+  __device__ __forceinline__ void init_slot(const Args &a, int k, int c) {       // c: column of the image (>= 128: x)
+    sc[k] = k == 0 ? 1.f : pow2_up<15>(a.xfac / a.xinvstd[c - 128]);      // (slot 0: dy's scale, set after the first loads are out)
+  }
+  // dy's scale — from the maximum of the producer's per-workgroup maxima —, and the output scales; the whole workgroup calls
+  // this once the first blocks' rows are requested (the reduction of dy's maxima then runs under them).  sb: 8 floats of LDS
+  // nobody uses yet.
+  template <int CT>
+  __device__ __forceinline__ void init_scales(const Args &a, float *sb, int tid, int gb, int i) {
+    // up to ~20 000 maxima (one per workgroup of the transposed product that wrote dy): 16-byte loads, eight in flight per
+    // lane — one dependent load per iteration cost this prologue ≈12 us per launch (fixed cost 17 -> 29 us against the bf16
+    // form, from the launch times at two row counts)
+    float m = 0.f;
+    const int n4 = (reinterpret_cast<uintptr_t>(a.dybound) & 15u) == 0 ? a.ndy / 4 : 0;
+    const f4 *d4 = reinterpret_cast<const f4 *>(a.dybound);
+    int q = tid;
+    for (; q + 7 * kWgradThreads < n4; q += 8 * kWgradThreads) {
+      f4 v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = d4[q + u * kWgradThreads];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) m = fmaxf(m, fmaxf(fmaxf(v[u].x, v[u].y), fmaxf(v[u].z, v[u].w)));
+    }
+    for (; q < n4; q += kWgradThreads) {
+      const f4 v = d4[q];
+      m = fmaxf(m, fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));
+    }
+    for (int r = 4 * n4 + tid; r < a.ndy; r += kWgradThreads) m = fmaxf(m, a.dybound[r]);
+    unsigned mb = __float_as_uint(m);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned other = (unsigned)__shfl_xor((int)mb, o);
+      mb = other > mb ? other : mb;
+    }
+    if ((tid & 63) == 0) sb[__builtin_amdgcn_readfirstlane(tid >> 6)] = __uint_as_float(mb);
+    __syncthreads();
+    m = fmaxf(fmaxf(fmaxf(sb[0], sb[1]), fmaxf(sb[2], sb[3])), fmaxf(fmaxf(sb[4], sb[5]), fmaxf(sb[6], sb[7])));
+    __syncthreads();                                                   // (all have read before the first image write)
+    const float sdy = pow2_up<15>(m);
+#pragma unroll
+    for (int c = 0; c < CT; ++c) osc[c] = pow2_inv(pow2_up<15>(a.xfac / a.xinvstd[32 * (CT * gb + c) + i])) * pow2_inv(sdy);
+    sc[0] = sdy;
+  }
+  template <int K>
+  __device__ __forceinline__ void split(f2v xv, unsigned (&piece)[kPieces]) const {
+    xv *= sc[K];                                                     // exact (power of two; the bound keeps it below 2^15)
+    if constexpr (K > 0) {
+      // rows past the slab's end load as 0 and leave the centring as -mean, which no bound covers (a column sitting at
+      // -1 +- 1e-4 behind an ELU: |mean| / bound = 17): scaled it may pass fp16's range, and inf x the exact 0 of the padded dy row
+      // is NaN.  Clamped to the largest fp16 value the product with 0 is 0; rows inside the bound are untouched.
+      xv.x = __builtin_amdgcn_fmed3f(xv.x, -65504.f, 65504.f);
+      xv.y = __builtin_amdgcn_fmed3f(xv.y, -65504.f, 65504.f);
+    }
+    const h2v h = __builtin_convertvector(xv, h2v);                  // round to nearest
+    const f2v r = xv - __builtin_convertvector(h, f2v);              // exact remainder
+    const h2v l = __builtin_convertvector(r, h2v);
+    piece[0] = __builtin_bit_cast(unsigned, h);
+    piece[1] = __builtin_bit_cast(unsigned, l);
+  }
+  __device__ __forceinline__ float finish(int c, float v) const { return v * osc[c]; }
+};
+
+template <int CT /* C / 128: 1 or 2 */, class Pieces>
+__global__ __launch_bounds__(kWgradThreads, 1) void wgrad16_k(const float *__restrict__ dy, int64_t lddy,
                                                               const float *__restrict__ x, int64_t ldx,
                                                               const float *__restrict__ center, int64_t rows, int J, int C,
                                                               float *__restrict__ partial /* [grid][128][C] */,
                                                               float *__restrict__ colpart /* [grid][128] | NULL */,
                                                               int64_t seg_rows /* 0: even split of all rows */, int spm,
-                                                              const int64_t *__restrict__ slab_off /* [grid + 1] | NULL */) {
+                                                              const int64_t *__restrict__ slab_off /* [grid + 1] | NULL */,
+                                                              typename Pieces::Args pargs) {
+  constexpr int NP = Pieces::kPieces, SETS = Pieces::kSets;
   constexpr int NCG = 32 + 32 * CT;          // column groups of 4: 32 of dy, 32·CT of x
   constexpr int QP = NCG + 4;                // slots per (column % 4) plane; QP % 16 == 4 keeps fragment reads conflict-free
   constexpr int PL = 4 * QP;                 // slots per row group (8 rows)
   constexpr int NK = 1 + CT;                 // conversion slots per wave and block: one of dy, CT of x
-  constexpr int NM = 24 * CT;                // MFMAs per wave and block
+  constexpr int NM = 2 * Pieces::kProducts * 2 * CT;      // MFMAs per wave and block: 2 steps x products x 2·CT tiles
   static_assert(QP % 16 == 4, "slot permutation");
-  __shared__ u4 img[2][3][4 * PL];           // [buffer][piece][slot]; one block = 32 rows = 4 row groups
+  static_assert(SETS == 1 || SETS == 2, "block n lives in register set n % SETS, image n % 2");
+  __shared__ u4 img[2][NP][4 * PL];          // [buffer][piece][slot]; one block = 32 rows = 4 row groups
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   int64_t r0, r1;                            // row slab of this workgroup: from the caller's table (ragged meshes), or an even split
@@ -391,6 +546,7 @@ __global__ __launch_bounds__(kWgradThreads, 1) void wgrad_u_k(const float *__res
   // store's own VGPR-transfer time — left each lane quad 16 bytes apart and cost the loads 20 %: 127 against 101 µs for the
   // memory path alone at 322 624 rows)
   const int lcol = lane;
+  Pieces pol;
   int s_rg[NK];                  // row group of the block (scalar)
   const float *s_cur[NK];        // operand + first column of the half-block + first row of the slot in the block to load next
   int l_voff[NK];                // my byte offset in a row of the half-block; past any extent if my dy column does not exist
@@ -407,40 +563,33 @@ __global__ __launch_bounds__(kWgradThreads, 1) void wgrad_u_k(const float *__res
     s_cur[k] = k == 0 ? dy + 64 * (wave & 1) + (r0 + 8 * rg) * lddy : x + 64 * (xhb % (2 * CT)) + (r0 + 8 * rg) * ldx;
     l_voff[k] = (k == 0 && c >= J) ? 0x7fffff00 : 4 * lcol;
     l_mu[k] = (k > 0 && center) ? center[c - 128] : 0.f;
+    pol.init_slot(pargs, k, c);
     l_slot[k] = rg * PL + (c & 3) * QP + (c >> 2);
   }
-  float raw[1][NK][8];           // rows in flight: one register set (a second one, two blocks ahead, measured no faster)
-  u4 cH[NK], cM[NK], cL[NK];     // pieces of the slot being converted (filled pair by pair, written as three 16-byte slots)
+  float raw[SETS][NK][8];        // rows in flight
+  u4 cP[NP][NK];                 // pieces of the slot being converted (filled pair by pair, written as one 16-byte slot each)
   // The work of a slot, in chunks small enough to sit between two MFMAs:
-  //   conv_pair   rows 2p, 2p+1: centre (x) | column sum (dy), then x = h + m + l by packed fp32 subtractions — each piece the
-  //               upper 16 bits of an exact remainder (≈10 vector instructions);
-  //   conv_write  the three pieces of the 8 rows as one LDS slot each;
-  typedef float f2 __attribute__((ext_vector_type(2)));
-  typedef unsigned int u2v __attribute__((ext_vector_type(2)));
+  //   conv_pair   rows 2p, 2p+1: centre (x) | column sum (dy), then the split into pieces;
+  //   conv_write  the pieces of the 8 rows as one LDS slot each;
   auto conv_pair = [&](auto sc, auto kc, auto pc) {
     constexpr int set = decltype(sc)::value, k = decltype(kc)::value, p = decltype(pc)::value;
-    f2 xv = {raw[set][k][2 * p], raw[set][k][2 * p + 1]};
+    f2v xv = {raw[set][k][2 * p], raw[set][k][2 * p + 1]};
     if constexpr (k == 0) l_sum += xv.x + xv.y;
-    else xv -= f2{l_mu[k], l_mu[k]};
-    const u2v xb = __builtin_bit_cast(u2v, xv);
-    const f2 r = xv - __builtin_bit_cast(f2, xb & 0xFFFF0000u);
-    const u2v rb = __builtin_bit_cast(u2v, r);
-    const f2 l = r - __builtin_bit_cast(f2, rb & 0xFFFF0000u);
-    const u2v lb = __builtin_bit_cast(u2v, l);
-    cH[k][p] = __builtin_amdgcn_perm(xb.y, xb.x, 0x07060302u);
-    cM[k][p] = __builtin_amdgcn_perm(rb.y, rb.x, 0x07060302u);
-    cL[k][p] = __builtin_amdgcn_perm(lb.y, lb.x, 0x07060302u);
+    else xv -= f2v{l_mu[k], l_mu[k]};
+    unsigned piece[NP];
+    pol.template split<k>(xv, piece);
+#pragma unroll
+    for (int n = 0; n < NP; ++n) cP[n][k][p] = piece[n];
   };
   auto conv_write = [&](auto kc, int buf) {
     constexpr int k = decltype(kc)::value;
-    img[buf][0][l_slot[k]] = cH[k];
-    img[buf][1][l_slot[k]] = cM[k];
-    img[buf][2][l_slot[k]] = cL[k];
+#pragma unroll
+    for (int n = 0; n < NP; ++n) img[buf][n][l_slot[k]] = cP[n][k];
   };
   // open_slot: the descriptor of slot k's rows in block b (b counts up by one per slot and call: s_cur runs along).  Its
-  // extent ends with the slab: rows past it — whole blocks past it: the prefetch runs two blocks ahead — read as 0 without
-  // traffic.  Such a row is 0 in BOTH operands' raw data; the centred x is then -mu, but the dy row is exactly 0 in every
-  // piece, so it adds nothing to the products or to the column sums: no masks.
+  // extent ends with the slab: rows past it — whole blocks past it: the prefetch runs ahead — read as 0 without traffic.
+  // Such a row is 0 in BOTH operands' raw data; the centred x is then -mu, but the dy row is exactly 0 in every piece, so it
+  // adds nothing to the products or to the column sums: no masks.
   __amdgpu_buffer_rsrc_t s_rs[NK];
   auto open_slot = [&](auto kc, int b) {
     constexpr int k = decltype(kc)::value;
@@ -456,63 +605,55 @@ __global__ __launch_bounds__(kWgradThreads, 1) void wgrad_u_k(const float *__res
     const int rstep = k == 0 ? dy_rstep : x_rstep;
     raw[set][k][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(s_rs[k], l_voff[k] + j * rstep, 0, 0));
   };
-  // The other work of a block, dealt out behind its MFMAs (m = 0 .. NM-1) — the two co-resident waves of a SIMD run this
-  // same stream and a wave is in-order, so what overlaps the matrix pipe, the vector ALU and the memory pipe is the mix
-  // INSIDE the stream:
-  //   conversion of block b+1 into the other image: one pair of rows every PSTEP MFMAs;
-  //   requests of block b+2 into the registers just converted: ONE load at a time — eight in a row fill the memory
-  //     pipe's queue and stall the wave, hence the MFMAs behind them, for hundreds of cycles (the kernel is HBM-bound:
-  //     a CU's share of the bandwidth is one 256-byte load per ≈26 cycles);
-  //   the three LDS slots of a unit after its fourth pair.
-  constexpr int PSTEP = NM / (4 * NK);      // 4 | 3
+  // The other work of a block — the conversion of the next block into the other image, the requests of a later block into
+  // the registers just converted —, dealt out behind its MFMAs by the piece form's schedule
   auto behind_mfma = [&](auto sc, auto ic, auto mc, int b) {
-    constexpr int set = decltype(sc)::value, image = decltype(ic)::value, m = decltype(mc)::value;
-    if constexpr (m % PSTEP == 0 && m / PSTEP < 4 * NK) {
-      constexpr int q = m / PSTEP, k = q / 4, p = q % 4;
-      if constexpr (p == 0) open_slot(WIC<k>{}, b);
-      conv_pair(sc, WIC<k>{}, WIC<p>{});
-    }
-    constexpr int L = CT == 2 ? (m % 2 == 1 ? (m - 1) / 2 : -1) : (m % 3 != 0 ? (m / 3) * 2 + (m % 3 - 1) : -1);
-    if constexpr (L >= 0 && L < 8 * NK) load_row(sc, WIC<L / 8>{}, WIC<L % 8>{});
-    constexpr int wk = CT == 2 ? (m % 16 == 14 ? m / 16 : -1) : (m % 12 == 11 ? m / 12 : -1);
-    if constexpr (wk >= 0 && wk < NK) conv_write(WIC<wk>{}, image);
+    Pieces::template behind<CT, decltype(mc)::value>([&](auto kc) { open_slot(kc, b); },
+                                                     [&](auto kc, auto pc) { conv_pair(sc, kc, pc); },
+                                                     [&](auto kc, auto jc) { load_row(sc, kc, jc); },
+                                                     [&](auto kc) { conv_write(kc, decltype(ic)::value); });
   };
-#define SN_BLOCK_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-  auto multiply_block = [&](auto sc, int b) {
-    constexpr int buf = decltype(sc)::value;           // block b = image buf = b & 1
-    SN_BLOCK_BARRIER();                   // image buf complete; image buf^1 (read during block b-1) may be overwritten
+  auto multiply_block = [&](auto uc, int b) {
+    constexpr int buf = decltype(uc)::value;           // b % 2: block b = image buf, block n lives in register set n % SETS
+    constexpr int set = (buf + 1) % SETS;              // block b + 1 converts from its set while block b is multiplied
+    SN_LDS_BARRIER();                     // image buf complete; image buf^1 (read during block b-1) may be overwritten
     // fragments of both 16-row steps are requested up front (before any write of this block in program order)
-    u4 A[2][2][3], B[2][CT][3];
+    u4 A[2][2][NP], B[2][CT][NP];
 #pragma unroll
     for (int st = 0; st < 2; ++st)
 #pragma unroll
-      for (int p = 0; p < 3; ++p) {
+      for (int p = 0; p < NP; ++p) {
 #pragma unroll
         for (int a = 0; a < 2; ++a) A[st][a][p] = img[buf][p][fo + 2 * st * PL + 8 * (2 * ga + a)];
 #pragma unroll
         for (int c = 0; c < CT; ++c) B[st][c][p] = img[buf][p][fo + 2 * st * PL + 32 + 8 * (CT * gb + c)];
       }
-    // six partial products (pieces of dy, x): (l,h) (h,l) (m,m) (m,h) (h,m) (h,h) — small terms first; tile-inner, so
-    // consecutive MFMAs never share an accumulator; the order of the stream is pinned by sched_barrier
-    wstatic_for<0, NM>([&](auto mc) {
-      constexpr int m = decltype(mc)::value, g = m / (2 * CT), st = g / 6, t = g % 6;
+    // the partial products of a step, small terms first; tile-inner, so consecutive MFMAs never share an accumulator; the
+    // order of the stream is pinned by sched_barrier
+    static_for<0, NM>([&](auto mc) {
+      constexpr int m = decltype(mc)::value, g = m / (2 * CT), st = g / Pieces::kProducts, t = g % Pieces::kProducts;
       constexpr int a = (m % (2 * CT)) / CT, c = m % CT;
-      constexpr int pa = (0x001102 >> (4 * t)) & 15, pb = (0x010120 >> (4 * t)) & 15;
-      acc[a][c] = mfma_bf16(A[st][a][pa], B[st][c][pb], acc[a][c]);
-      behind_mfma(WIC<0>{}, WIC<buf ^ 1>{}, mc, b + 2);
+      acc[a][c] = Pieces::mfma(A[st][a][Pieces::piece_a(t)], B[st][c][Pieces::piece_b(t)], acc[a][c]);
+      behind_mfma(IC<set>{}, IC<buf ^ 1>{}, mc, b + 1 + SETS);
       __builtin_amdgcn_sched_barrier(0);
     });
   };
+  // the first SETS blocks are requested (before the piece form's scales are formed), block 0 converted into image 0 and
+  // block SETS requested into its registers
   if (nblocks > 0) {
-    // block 0 requested, converted into image 0, block 1 requested into its registers
-    wstatic_for<0, NK>([&](auto kc) {
-      open_slot(kc, 0);
-      wstatic_for<0, 8>([&](auto jc) { load_row(WIC<0>{}, kc, jc); });
+    static_for<0, SETS>([&](auto sc) {
+      static_for<0, NK>([&](auto kc) {
+        open_slot(kc, decltype(sc)::value);
+        static_for<0, 8>([&](auto jc) { load_row(sc, kc, jc); });
+      });
     });
-    wstatic_for<0, NM>([&](auto mc) { behind_mfma(WIC<0>{}, WIC<0>{}, mc, 1); });
+  }
+  pol.template init_scales<CT>(pargs, reinterpret_cast<float *>(&img[0][0][0]), tid, gb, i);
+  if (nblocks > 0) {
+    static_for<0, NM>([&](auto mc) { behind_mfma(IC<0>{}, IC<0>{}, mc, SETS); });
     for (int b = 0; b < nblocks; b += 2) {
-      multiply_block(WIC<0>{}, b);
-      if (b + 1 < nblocks) multiply_block(WIC<1>{}, b + 1);
+      multiply_block(IC<0>{}, b);
+      if (b + 1 < nblocks) multiply_block(IC<1>{}, b + 1);
     }
   }
   if (colpart) {                             // bias gradient: column sums of dy — one (row group, column) entry per wave
@@ -531,10 +672,10 @@ __global__ __launch_bounds__(kWgradThreads, 1) void wgrad_u_k(const float *__res
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const int jr = 32 * (2 * ga + a) + (e & 3) + 8 * (e >> 2) + 4 * kh;
-        P[(int64_t)jr * C + 32 * (CT * gb + c) + i] = acc[a][c][e];
+        P[(int64_t)jr * C + 32 * (CT * gb + c) + i] = pol.finish(c, acc[a][c][e]);
       }
-#undef SN_BLOCK_BARRIER
 }
+
 
 __global__ __launch_bounds__(kWG) void wgrad_reduce_k(const float *__restrict__ partial, int nslab, int J, int C,
                                                       float *__restrict__ G, const float *__restrict__ colpart,
@@ -1698,16 +1839,6 @@ inline int stat_blocks(int64_t rows) {
   return (int)b;
 }
 
-// SN_GEMM_VARIANT (shared with sn_gemm.hip): 0 = the fp32-MFMA kernels, the ONE A/B baseline of the Linear kernels; anything
-// else (default) = the 16-bit matrix-pipe kernels
-inline int gemm_variant() {
-  static const int v = [] {
-    const char *e = getenv("SN_GEMM_VARIANT");
-    return (e && atoi(e) == 0) ? 0 : 2;
-  }();
-  return v;
-}
-
 // ------------------------------------------------------------------------------------------------
 // Target of the dense-correspondence loss:  t[r] = argmin_j ( GA[r][pa[j]] + GB[pb[r]][j] )  — the torch.min over the
 // sum of two gathered (NA x NB) geodesic matrices of src/dense_correspondence/main.py:236-237, without materialising
@@ -1931,285 +2062,6 @@ inline int wgrad_slabs(int64_t rows) {
   return (int)b;
 }
 
-// ------------------------------------------------------------------------------------------------
-// wgrad_h_k — the uniform-wave weight gradient on TWO fp16 pieces (three partial products instead of six).
-//
-// Ablation of wgrad_u_k on one box (round 4, tools/scratch/wgrad_ab.sh, 627 200 rows x 256 columns): the six bf16 products
-// alone (no loads, no conversion) take 150 of the kernel's 293 us at the 1.8 GHz the chip sustains under it, the memory path
-// alone 191, and the two do not hide each other; with three of the six products issued the kernel runs in 232.  Halving the
-// matrix work needs the fp16 split of the forward kernels (sn_gemm.hip: x = h + l, h = rn16(x), l = rn16(x - h), three exact
-// products h·h + (h·l + l·h)), and fp16 needs RANGE control.  The contraction runs over the rows, so the powers of two
-// that bring the operands into range must be constant along a COLUMN, and they must be known before the first row is
-// converted.  Both come from bounds the callers already hold:
-//   x - mean   BatchNorm's own statistics: sum_r (x[r][c] - mean[c])^2 = n·var[c], hence |x[r][c] - mean[c]| <= sqrt(n / invstd[c]^2)
-//              for EVERY row — rigorous, no pass over x (n = rows behind the statistics; the caller passes xfac >= sqrt(n));
-//   dy         one number for the whole operand, an upper bound of max |dy| left by the kernel that PRODUCED dy (the
-//              input-gradient GEMM's epilogue, the transposed sparse product's store, the loss backward: sn_absmax_* in
-//              sn_spmm.h); one global scale suffices for rigour, and accuracy survives it — below.
-// Scaled operands: bound -> [2^14, 2^15) (fp16 tops out at 65504), so nothing can overflow.  LOW11: the low pieces carry a
-// further 2^11 (their two products go to a second accumulator, folded in with 2^-11 at the end, as in sn_gemm.hip): an
-// element keeps 22 significant bits while its scaled magnitude is >= 2^-14, i.e. down to 2^-28 of the operand's bound, and
-// 2^-36 of the bound in absolute terms below that.  !LOW11: one accumulator, the low piece unscaled: 22 bits down to 2^-17
-// of the bound, 2^-25 (scaled) absolute below.  Results leave multiplied by the exact inverse scales.
-// Structure (slots, images, barriers, slab tables, column sums of dy) as wgrad_u_k; two pieces: two LDS images of 51 KB at
-// C = 256 instead of three.  SETS = 2: two 32-row blocks in flight in registers instead of one.
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float pow2_up_for(float bound) {      // 2^(15 - E) for bound = f·2^E, f in [0.5, 1): bound -> [2^14, 2^15)
-  int e = (int)((__float_as_uint(bound) >> 23) & 0xffu) - 126;
-  e = e < -100 ? -100 : (e > 100 ? 100 : e);                     // zero / denormal / non-finite bounds: any finite scale
-  return __uint_as_float((unsigned)(127 + 15 - e) << 23);
-}
-__device__ __forceinline__ float pow2_inv(float p) {             // 1 / p for p = 2^k, k in [-115, 115]
-  return __uint_as_float((254u << 23) - __float_as_uint(p));
-}
-
-template <int CT /* C / 128 */, bool LOW11, int SETS>
-__global__ __launch_bounds__(kWgradThreads, 1) void wgrad_h_k(const float *__restrict__ dy, int64_t lddy,
-                                                              const float *__restrict__ x, int64_t ldx,
-                                                              const float *__restrict__ center, int64_t rows, int J, int C,
-                                                              float *__restrict__ partial /* [grid][128][C] */,
-                                                              float *__restrict__ colpart /* [grid][128] | NULL */,
-                                                              int64_t seg_rows, int spm, const int64_t *__restrict__ slab_off,
-                                                              const float *__restrict__ dybound /* [ndy]: max >= max |dy| */,
-                                                              int ndy, const float *__restrict__ xinvstd /* [C] */, float xfac,
-                                                              int interleave /* plain slabs only: 32-row blocks b, b + grid, ... */) {
-  constexpr int NCG = 32 + 32 * CT;          // column groups of 4: 32 of dy, 32·CT of x
-  constexpr int QP = NCG + 4;                // slots per (column % 4) plane; QP % 16 == 4 keeps fragment reads conflict-free
-  constexpr int PL = 4 * QP;                 // slots per row group (8 rows)
-  constexpr int NK = 1 + CT;                 // conversion slots per wave and block: one of dy, CT of x
-  constexpr int NM = 12 * CT;                // MFMAs per wave and block: 2 steps x 3 products x 2·CT tiles
-  constexpr int NPAIR = 4 * NK, NLOAD = 8 * NK;
-  constexpr int NACC = LOW11 ? 2 : 1;
-  static_assert(QP % 16 == 4, "slot permutation");
-  __shared__ u4 img[2][2][4 * PL];           // [buffer][piece][slot]; one block = 32 rows = 4 row groups
-  const int tid = threadIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-  int64_t r0, r1;                            // row slab of this workgroup (as wgrad_u_k)
-  if (slab_off) {
-    r0 = slab_off[blockIdx.x];
-    r1 = slab_off[blockIdx.x + 1];
-  } else if (seg_rows > 0) {
-    const int64_t mesh = blockIdx.x / spm, part = blockIdx.x % spm;
-    int64_t per = (seg_rows + spm - 1) / spm;
-    per = (per + 15) & ~(int64_t)15;
-    const int64_t mend = (mesh + 1) * seg_rows < rows ? (mesh + 1) * seg_rows : rows;
-    r0 = mesh * seg_rows + part * per;
-    r1 = r0 + per < mend ? r0 + per : mend;
-  } else if (interleave) {
-    r0 = 32 * (int64_t)blockIdx.x;             // my first block; the following ones lie G blocks apart, up to the operand's end
-    r1 = rows;
-  } else {
-    int64_t per = (rows + gridDim.x - 1) / gridDim.x;
-    per = (per + 15) & ~(int64_t)15;
-    r0 = (int64_t)blockIdx.x * per;
-    r1 = r0 + per < rows ? r0 + per : rows;
-  }
-  const int G = (interleave && !slab_off && seg_rows <= 0) ? (int)gridDim.x : 1;      // 32-row blocks between two of mine
-  const int nblocks = r1 > r0 ? (int)(((r1 - r0 + 31) / 32 + G - 1) / G) : 0;
-  const int span = r1 > r0 ? (int)(r1 - r0) : 0;
-  float *P = partial + (int64_t)blockIdx.x * 128 * C;
-
-  // ---- matrix role: dy tiles 2·ga, 2·ga + 1  x  x tiles CT·gb .. CT·gb + CT - 1 ----
-  const int i = lane & 31, kh = lane >> 5;
-  const int ga = wave >> 2, gb = wave & 3;
-  const int fo = kh * PL + (i & 3) * QP + (i >> 2);
-  f16v acc[NACC][2][CT];
-#pragma unroll
-  for (int n = 0; n < NACC; ++n)
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < CT; ++b)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[n][a][b][e] = 0.f;
-  // ---- conversion role (as wgrad_u_k: slot 0 = a dy half-block, slots 1.. = x half-blocks) ----
-  const int lcol = lane;
-  int s_rg[NK];
-  const float *s_cur[NK];
-  int l_voff[NK];
-  int l_slot[NK];
-  float l_mu[NK], l_sc[NK];
-  float l_sum = 0.f;
-  const int dy_rstep = 4 * (int)lddy, x_rstep = 4 * (int)ldx;
-#pragma unroll
-  for (int k = 0; k < NK; ++k) {
-    const int xhb = wave + 8 * (k - 1);
-    const int rg = k == 0 ? wave >> 1 : xhb / (2 * CT);
-    const int c = k == 0 ? 64 * (wave & 1) + lcol : 128 + 64 * (xhb % (2 * CT)) + lcol;      // column in the image
-    s_rg[k] = rg;
-    s_cur[k] = k == 0 ? dy + 64 * (wave & 1) + (r0 + 8 * rg) * lddy : x + 64 * (xhb % (2 * CT)) + (r0 + 8 * rg) * ldx;
-    l_voff[k] = (k == 0 && c >= J) ? 0x7fffff00 : 4 * lcol;
-    l_mu[k] = (k > 0 && center) ? center[c - 128] : 0.f;
-    l_sc[k] = k == 0 ? 1.f : pow2_up_for(xfac / xinvstd[c - 128]);          // (slot 0: dy's scale, set after the first loads are out)
-    l_slot[k] = rg * PL + (c & 3) * QP + (c >> 2);
-  }
-  float raw[SETS][NK][8];
-  u4 cH[NK], cL[NK];
-  auto conv_pair = [&](auto sc, auto kc, auto pc) {
-    constexpr int set = decltype(sc)::value, k = decltype(kc)::value, p = decltype(pc)::value;
-    f2v xv = {raw[set][k][2 * p], raw[set][k][2 * p + 1]};
-    if constexpr (k == 0) l_sum += xv.x + xv.y;
-    else xv -= f2v{l_mu[k], l_mu[k]};
-    xv *= l_sc[k];                                                   // exact (power of two; the bound keeps it below 2^15)
-    if constexpr (k > 0) {
-      // rows past the slab's end load as 0 and leave the centring as -mean, which no bound covers (a column sitting at
-      // -1 +- 1e-4 behind an ELU: |mean| / bound = 17): scaled it may pass fp16's range, and inf x the exact 0 of the padded dy row
-      // is NaN.  Clamped to the largest fp16 value the product with 0 is 0; rows inside the bound are untouched.
-      xv.x = __builtin_amdgcn_fmed3f(xv.x, -65504.f, 65504.f);
-      xv.y = __builtin_amdgcn_fmed3f(xv.y, -65504.f, 65504.f);
-    }
-    const h2v h = __builtin_convertvector(xv, h2v);                  // round to nearest
-    f2v r = xv - __builtin_convertvector(h, f2v);                    // exact remainder
-    if constexpr (LOW11) r *= 2048.f;
-    const h2v l = __builtin_convertvector(r, h2v);
-    cH[k][p] = __builtin_bit_cast(unsigned, h);
-    cL[k][p] = __builtin_bit_cast(unsigned, l);
-  };
-  auto conv_write = [&](auto kc, int buf) {
-    constexpr int k = decltype(kc)::value;
-    img[buf][0][l_slot[k]] = cH[k];
-    img[buf][1][l_slot[k]] = cL[k];
-  };
-  __amdgpu_buffer_rsrc_t s_rs[NK];
-  auto open_slot = [&](auto kc, int b) {
-    constexpr int k = decltype(kc)::value;
-    const int rstep = k == 0 ? dy_rstep : x_rstep;
-    int left = span - 32 * G * b - 8 * s_rg[k];
-    left = left < 0 ? 0 : (left > 8 ? 8 : left);
-    const int extent = __builtin_amdgcn_readfirstlane(left * rstep);
-    s_rs[k] = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(s_cur[k]), 0, extent, 0x00020000);
-    s_cur[k] += (int64_t)8 * rstep * G;
-  };
-  auto load_row = [&](auto sc, auto kc, auto jc) {
-    constexpr int set = decltype(sc)::value, k = decltype(kc)::value, j = decltype(jc)::value;
-    const int rstep = k == 0 ? dy_rstep : x_rstep;
-    raw[set][k][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(s_rs[k], l_voff[k] + j * rstep, 0, 0));
-  };
-  // Work dealt out behind MFMA m of a block: pair q of the conversion at m_pair(q), the reload of the two rows it freed right
-  // behind it (load L = 8k + j at m_pair(4k + j/2) + j % 2), the two LDS slots of a unit after its fourth pair.
-  auto behind_mfma = [&](auto sc, auto ic, auto mc, int b) {
-    constexpr int image = decltype(ic)::value, m = decltype(mc)::value;
-    wstatic_for<0, NPAIR>([&](auto qc) {
-      constexpr int q = decltype(qc)::value, k = q / 4, p = q % 4;
-      constexpr int mq = q * NM / NPAIR;
-      if constexpr (mq == m) {
-        conv_pair(sc, WIC<k>{}, WIC<p>{});
-        if constexpr (p == 3) conv_write(WIC<k>{}, image);
-      }
-      // (j = 2p reloads with its pair, j = 2p + 1 one MFMA later; the last slot's last row stays inside the block)
-      constexpr int m0 = mq, m1 = mq + 1 < NM ? mq + 1 : NM - 1;
-      if constexpr (m0 == m) {
-        if constexpr (p == 0) open_slot(WIC<k>{}, b);
-        load_row(sc, WIC<k>{}, WIC<2 * p>{});
-      }
-      if constexpr (m1 == m) load_row(sc, WIC<k>{}, WIC<2 * p + 1>{});
-    });
-  };
-#define SN_BLOCK_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-  auto multiply_block = [&](auto uc, int b) {
-    constexpr int u = decltype(uc)::value;             // b % lcm(2, SETS): block b = image b & 1, block n lives in set n % SETS
-    constexpr int buf = u & 1, set = (u + 1) % SETS;   // block b + 1 converts from its set while block b is multiplied
-    SN_BLOCK_BARRIER();
-    u4 A[2][2][2], B[2][CT][2];
-#pragma unroll
-    for (int st = 0; st < 2; ++st)
-#pragma unroll
-      for (int p = 0; p < 2; ++p) {
-#pragma unroll
-        for (int a = 0; a < 2; ++a) A[st][a][p] = img[buf][p][fo + 2 * st * PL + 8 * (2 * ga + a)];
-#pragma unroll
-        for (int c = 0; c < CT; ++c) B[st][c][p] = img[buf][p][fo + 2 * st * PL + 32 + 8 * (CT * gb + c)];
-      }
-    // three products per step and tile, small terms first: (l, h), (h, l) -> the correction accumulator (LOW11) | the one
-    // accumulator; (h, h) last; tile-inner, so consecutive MFMAs never share an accumulator
-    wstatic_for<0, NM>([&](auto mc) {
-      constexpr int m = decltype(mc)::value, g = m / (2 * CT), st = g / 3, t = g % 3;
-      constexpr int a = (m % (2 * CT)) / CT, c = m % CT;
-      constexpr int pa = t == 0 ? 1 : 0, pb = t == 1 ? 1 : 0;
-      constexpr int n = (LOW11 && t < 2) ? 1 : 0;
-      acc[n][a][c] = mfma_f16(A[st][a][pa], B[st][c][pb], acc[n][a][c]);
-      behind_mfma(WIC<set>{}, WIC<buf ^ 1>{}, mc, b + 1 + SETS);
-      __builtin_amdgcn_sched_barrier(0);
-    });
-  };
-  // the first blocks' rows are requested BEFORE the scales are formed (the reduction of dy's maxima then runs under them)
-  if (nblocks > 0) {
-    wstatic_for<0, SETS>([&](auto sc) {
-      wstatic_for<0, NK>([&](auto kc) {
-        open_slot(kc, decltype(sc)::value);
-        wstatic_for<0, 8>([&](auto jc) { load_row(sc, kc, jc); });
-      });
-    });
-  }
-  // scales: one for dy — from the maximum of the producer's per-workgroup maxima —, one per x column (mine as a converter,
-  // mine as the owner of output columns)
-  float sdy;
-  {
-    float *sb = reinterpret_cast<float *>(&img[0][0][0]);             // (the images are not in use yet)
-    // up to ~20 000 maxima (one per workgroup of the transposed product that wrote dy): 16-byte loads, eight in flight per
-    // lane — one dependent load per iteration cost this prologue ≈12 us per launch (fixed cost 17 -> 29 us against the bf16
-    // kernel, from the launch times at two row counts)
-    float m = 0.f;
-    const int n4 = (reinterpret_cast<uintptr_t>(dybound) & 15u) == 0 ? ndy / 4 : 0;
-    const f4 *d4 = reinterpret_cast<const f4 *>(dybound);
-    int q = tid;
-    for (; q + 7 * kWgradThreads < n4; q += 8 * kWgradThreads) {
-      f4 v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = d4[q + u * kWgradThreads];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) m = fmaxf(m, fmaxf(fmaxf(v[u].x, v[u].y), fmaxf(v[u].z, v[u].w)));
-    }
-    for (; q < n4; q += kWgradThreads) {
-      const f4 v = d4[q];
-      m = fmaxf(m, fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));
-    }
-    for (int r = 4 * n4 + tid; r < ndy; r += kWgradThreads) m = fmaxf(m, dybound[r]);
-    unsigned mb = __float_as_uint(m);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const unsigned other = (unsigned)__shfl_xor((int)mb, o);
-      mb = other > mb ? other : mb;
-    }
-    if (lane == 0) sb[wave] = __uint_as_float(mb);
-    __syncthreads();
-    m = fmaxf(fmaxf(fmaxf(sb[0], sb[1]), fmaxf(sb[2], sb[3])), fmaxf(fmaxf(sb[4], sb[5]), fmaxf(sb[6], sb[7])));
-    __syncthreads();                                                   // (all have read before the first image write)
-    sdy = pow2_up_for(m);
-  }
-  float osc[CT];                             // inverse scale of my output column in each of my x tiles, times dy's
-#pragma unroll
-  for (int c = 0; c < CT; ++c) osc[c] = pow2_inv(pow2_up_for(xfac / xinvstd[32 * (CT * gb + c) + i])) * pow2_inv(sdy);
-  l_sc[0] = sdy;
-  if (nblocks > 0) {
-    wstatic_for<0, NM>([&](auto mc) { behind_mfma(WIC<0>{}, WIC<0>{}, mc, SETS); });      // block 0 -> image 0, block SETS requested
-    constexpr int U = (SETS % 2 == 0) ? SETS : 2 * SETS;                                    // lcm(2, SETS)
-    for (int b = 0; b < nblocks; b += U) {
-      wstatic_for<0, U>([&](auto uc) {
-        if (b + decltype(uc)::value < nblocks) multiply_block(uc, b + decltype(uc)::value);
-      });
-    }
-  }
-  if (colpart) {
-    __syncthreads();
-    float *sm = reinterpret_cast<float *>(&img[0][0][0]);
-    sm[s_rg[0] * 128 + 64 * (wave & 1) + lcol] = l_sum;
-    __syncthreads();
-    if (tid < 128) colpart[(int64_t)blockIdx.x * 128 + tid] = (sm[tid] + sm[128 + tid]) + (sm[256 + tid] + sm[384 + tid]);
-  }
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int c = 0; c < CT; ++c)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int jr = 32 * (2 * ga + a) + (e & 3) + 8 * (e >> 2) + 4 * kh;
-        float v = acc[0][a][c][e];
-        if constexpr (LOW11) v = __builtin_fmaf(acc[1][a][c][e], 1.f / 2048.f, v);
-        P[(int64_t)jr * C + 32 * (CT * gb + c) + i] = v * osc[c];
-      }
-#undef SN_BLOCK_BARRIER
-}
 
 }  // namespace
 
@@ -2286,14 +2138,6 @@ size_t sn_wgrad_workspace_bytes(int64_t rows, int32_t J, int32_t C) {
   return (size_t)wgrad_slabs(rows) * 128 * ((size_t)C + 1) * sizeof(float);      // tile partials + column-sum partials
 }
 
-// Bounds that let the weight gradient run on two fp16 pieces (wgrad_h_k): dybound[0] >= max |dy| (device), xinvstd[C] the
-// BatchNorm inverse standard deviations of x's columns about `center` (device), xfac >= sqrt(rows behind those statistics).
-struct WgradBounds {
-  const float *dybound;      // ndy floats: their maximum bounds |dy|
-  int ndy;
-  const float *xinvstd;
-  float xfac;
-};
 static int wgrad_launch(const float *dy, int64_t lddy, const float *x, int64_t ldx, const float *center, int64_t rows,
                         int32_t J, int32_t C, float *G, double *dysum, int64_t rows_per_seg, float *seg_dysum,
                         void *workspace, size_t workspace_bytes, void *stream, const int64_t *slab_off = nullptr,
@@ -2338,31 +2182,18 @@ static int wgrad_launch(const float *dy, int64_t lddy, const float *x, int64_t l
   if (uni) sn_internal_timing_slot(0x400 | (segmented ? 1 : 0) | (ragged ? 2 : 0), rows, C, rows * 4 * ((int64_t)J + C), J, &t_start, &t_stop);
   const bool half = uni && bounds;
   if (bounds && ((bounds->ndy > 0 && !bounds->dybound) || bounds->ndy < 0 || !bounds->xinvstd || !(bounds->xfac > 0.f))) return SN_E_NULL;
-  if (half) {
-#define SN_WGH(CT_)                                                                                                                    \
-  do {                                                                                                                                 \
-    if (t_start)                                                                                                                       \
-      hipExtLaunchKernelGGL((wgrad_h_k<CT_, false, 2>), dim3(nslab), dim3(kWgradThreads), 0, s, t_start, t_stop, 0, dy, lddy, x, ldx,  \
-                            center, rows, (int)J, (int)C, partial, colpart, sr, spm, slab_off, bounds->dybound, bounds->ndy, bounds->xinvstd, \
-                            bounds->xfac, 0);                                                                                          \
-    else                                                                                                                               \
-      hipLaunchKernelGGL((wgrad_h_k<CT_, false, 2>), dim3(nslab), dim3(kWgradThreads), 0, s, dy, lddy, x, ldx, center, rows, (int)J,   \
-                         (int)C, partial, colpart, sr, spm, slab_off, bounds->dybound, bounds->ndy, bounds->xinvstd, bounds->xfac, 0); \
-  } while (0)
-    // one accumulator, two 32-row blocks in flight (LABNOTES r4wgrad: the other combinations measured slower)
-    if (C == 256) SN_WGH(2);
-    else SN_WGH(1);
-#undef SN_WGH
-  }
-  else if (uni && C == 128 && t_start)
-    hipExtLaunchKernelGGL((wgrad_u_k<1>), dim3(nslab), dim3(kWgradThreads), 0, s, t_start, t_stop, 0, dy, lddy, x, ldx, center, rows, (int)J, (int)C, partial, colpart, sr, spm, slab_off);
-  else if (uni && t_start)
-    hipExtLaunchKernelGGL((wgrad_u_k<2>), dim3(nslab), dim3(kWgradThreads), 0, s, t_start, t_stop, 0, dy, lddy, x, ldx, center, rows, (int)J, (int)C, partial, colpart, sr, spm, slab_off);
-  else if (uni && C == 128)
-    hipLaunchKernelGGL((wgrad_u_k<1>), dim3(nslab), dim3(kWgradThreads), 0, s, dy, lddy, x, ldx, center, rows, (int)J, (int)C, partial, colpart, sr, spm, slab_off);
-  else if (uni)
-    hipLaunchKernelGGL((wgrad_u_k<2>), dim3(nslab), dim3(kWgradThreads), 0, s, dy, lddy, x, ldx, center, rows, (int)J, (int)C, partial, colpart, sr, spm, slab_off);
-  else if (C == 128)
+  const dim3 grid(nslab), block(kWgradThreads);
+  if (half) {      // two fp16 pieces
+    if (C == 128)
+      launch_timed(wgrad16_k<1, WgradHalf2>, grid, block, s, t_start, t_stop, dy, lddy, x, ldx, center, rows, J, C, partial, colpart, sr, spm, slab_off, *bounds);
+    else
+      launch_timed(wgrad16_k<2, WgradHalf2>, grid, block, s, t_start, t_stop, dy, lddy, x, ldx, center, rows, J, C, partial, colpart, sr, spm, slab_off, *bounds);
+  } else if (uni) {      // three bf16 pieces
+    if (C == 128)
+      launch_timed(wgrad16_k<1, WgradBf3>, grid, block, s, t_start, t_stop, dy, lddy, x, ldx, center, rows, J, C, partial, colpart, sr, spm, slab_off, WgradBf3::Args{});
+    else
+      launch_timed(wgrad16_k<2, WgradBf3>, grid, block, s, t_start, t_stop, dy, lddy, x, ldx, center, rows, J, C, partial, colpart, sr, spm, slab_off, WgradBf3::Args{});
+  } else if (C == 128)
     hipLaunchKernelGGL((wgrad_mfma_k<1>), dim3(nslab), dim3(kWG), 0, s, dy, lddy, x, ldx, center, rows, (int)J, (int)C, partial, colpart);
   else
     hipLaunchKernelGGL((wgrad_mfma_k<2>), dim3(nslab), dim3(kWG), 0, s, dy, lddy, x, ldx, center, rows, (int)J, (int)C, partial, colpart);
@@ -2408,7 +2239,7 @@ int sn_wgrad_slabs_f32(const float *dy, int64_t lddy, const float *x, int64_t ld
                       nslab, seg_slab_ptr, nseg);
 }
 
-// The same three products with bounds (see WgradBounds / wgrad_h_k): two fp16 pieces, half the matrix work.  dybound: one
+// The same three products with bounds (see WgradBounds / WgradHalf2): two fp16 pieces, half the matrix work.  dybound: one
 // float on the device, >= max |dy| over the operand (sn_absmax_* leave it); xinvstd: the BatchNorm inverse standard deviations
 // of x's columns about `center`, from statistics over stat_rows rows that include every row of x (the local rows, or the
 // global batch under synchronised statistics).  Results agree with the bf16 forms to fp32 rounding.

@@ -13,22 +13,13 @@
 //   per SIMD keeps the matrix pipe busy: no LDS, no barriers.
 //   D layout: lane (n, h = l>>5) holds, for its data row n, the 16 outputs at columns 8g + 4h + q (g, q = 0..3):
 //   four 16-byte pieces per tile — the epilogue (bias / residual / ELU copy, or the BatchNorm tail) works on them.
-#include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
 #include <stdint.h>
 #include <stdlib.h>
 
-#include "sn_internal.h"
-#include "sn_spmm.h"
+#include "sn_dense_common.h"
 
 namespace {
 
-constexpr int kWG = 256;
-#define kCUs sn_internal_cu_count()      // compute units of the current device (256 on an MI355X in SPX mode)
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f16v __attribute__((ext_vector_type(16)));
-
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 // the split kernels keep a lane's byte offset inside a 32-row tile in 32 bits: leading dimensions below 2^24 elements
 inline bool ld32(int64_t a, int64_t b = 0, int64_t c = 0, int64_t d = 0, int64_t e = 0) {
   const int64_t lim = (int64_t)1 << 24;
@@ -222,9 +213,6 @@ __global__ __launch_bounds__(kWG, 1) void gemm_rows_k(const float *__restrict__ 
   }
 }
 
-typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u2 __attribute__((ext_vector_type(2)));
-
 // ------------------------------------------------------------------------------------------------
 // The Linear layers' products on the 16-bit matrix pipe (16x the fp32 MFMA rate per instruction) from an EXACT two-piece split.
 //
@@ -242,21 +230,13 @@ typedef unsigned int u2 __attribute__((ext_vector_type(2)));
 // applied to the fp32 result in the epilogue.  Elements more than 2^28 below their row's maximum lose low-order bits — an
 // error below 2^-37 of the row's scale.  Non-finite inputs give NaN, as in the bf16 form.
 // v_mfma_f32_32x32x16_f16 has the operand layout and rate of the bf16 instruction.
-typedef _Float16 h8v __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ f16v mfma_f16(const u4 &a, const u4 &b, const f16v &c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8v, a), __builtin_bit_cast(h8v, b), c, 0, 0, 0);
-}
 constexpr float kLowUp = 2048.f, kLowDown = 1.f / 2048.f;      // 2^11: the low pieces' own scale
 
 // scale_up = 2^(14 - E), scale_down = 2^(E - 14) for a row / column whose absolute maximum is m = f·2^E, f in [0.5, 1)
 __device__ __forceinline__ void pow2_scales(float m, float &up, float &down) {
-  int e = (int)((__float_as_uint(m) >> 23) & 0xffu) - 126;
-  e = e < -100 ? -100 : (e > 100 ? 100 : e);              // zero / denormal / non-finite rows: any finite scale will do
-  up = __uint_as_float((unsigned)(127 + 14 - e) << 23);
-  down = __uint_as_float((unsigned)(127 - 14 + e) << 23);
+  up = pow2_up<14>(m);
+  down = pow2_down<14>(m);
 }
-typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-typedef float f2v __attribute__((ext_vector_type(2)));
 // x·up -> fp16 pieces (round to nearest): H = rn16(x·up), L = rn16((x·up - H)·2^11); x·up and the remainder are exact in fp32
 __device__ __forceinline__ void split4_h2(const f4 &x, float up, u2 &H, u2 &L) {
   const f4 xs = x * up;
@@ -299,22 +279,7 @@ __device__ __forceinline__ unsigned row16_umax(unsigned v) {
 // loads (one wave instruction = 1 KiB contiguous), splits them ONCE and writes the three bf16 images of the tile to LDS
 // (row stride 2K+16 bytes: conflict-free ds_read_b128); all four waves then read their fragments of every image.  The
 // conversion of tile t+1 (and the global loads of tile t+2 into the registers it frees) is spread over the k-steps of tile
-// t, so the vector ALU works in the shadow of the matrix pipe; one workgroup barrier per tile.
-template <int I>
-struct IC {
-  static constexpr int value = I;
-};
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F &&f) {          // f(IC<I>{}) for I in [I, N): the index is a constant expression
-  if constexpr (I < N) {
-    f(IC<I>{});
-    static_for<I + 1, N>(f);
-  }
-}
-
-// LDS writes of this wave done, then the workgroup barrier — without the vmcnt(0) a __syncthreads() fence would add
-// (it would drain the global prefetch and wait for the previous tile's stores to be acknowledged).
-#define SN_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
+// t, so the vector ALU works in the shadow of the matrix pipe; one workgroup barrier per tile (SN_LDS_BARRIER).
 
 // ---- global accesses of the streaming kernel: raw buffer resources ----
 // With ONE wave per SIMD (the weights own the register file) every instruction of the wave — scalar, s_nop, address
@@ -363,9 +328,9 @@ __device__ __forceinline__ void bst4(rsrc_t r, int voff, const f4 &v) {         
 // RAWLOW (dgrad+elu only): the low half leaves as the BARE product — no BatchNorm tail, no activation derivative, no maximum —
 // and its side operand is never read: the transposed product that consumes it holds elu(.) in registers already and finishes
 // the gradient in its store (sn_spmm_q3_elubwd_tail_absmax_f32).  ep.v0 then points at column `half` of x.
-template <int PC, int K, int NT, bool TRANSW, int EPI, bool SIDE, bool ELU, bool SMALL = false, int WV = 4, bool RAWLOW = false,
+template <int K, int NT, bool TRANSW, int EPI, bool SIDE, bool ELU, bool SMALL = false, int WV = 4, bool RAWLOW = false,
           bool FRAME = false>
-__global__ __launch_bounds__(64 * WV, (PC == 2 && K == 128 && NT == 1 && WV == 4) ? 2 : 1) void gemm_rows_split_k(const float *__restrict__ In, int64_t ldi,
+__global__ __launch_bounds__(64 * WV, (K == 128 && NT == 1 && WV == 4) ? 2 : 1) void gemm_rows_split_k(const float *__restrict__ In, int64_t ldi,
                                                          const float *__restrict__ W, int64_t ldw,
                                                          float *__restrict__ Out, int64_t ldo, int64_t rows, EpiArgs ep) {
   constexpr int KS = K / 16;                 // MFMA k-steps per output tile
@@ -380,8 +345,7 @@ __global__ __launch_bounds__(64 * WV, (PC == 2 && K == 128 && NT == 1 && WV == 4
   constexpr int SROW = 16 * CPR + 16;        // bytes per staged output row (+16: conflict-free transposition)
   constexpr int RPI = 64 / CPR;              // output rows per store instruction (8 | 4)
   constexpr int NST = 32 / RPI;              // store instructions per slab (4 | 8)
-  static_assert(PC == 2, "two fp16 pieces");
-  __shared__ __attribute__((aligned(16))) unsigned char img[2][PC][PART];
+  __shared__ __attribute__((aligned(16))) unsigned char img[2][2][PART];      // [buffer][fp16 piece]
   __shared__ __attribute__((aligned(16))) unsigned char stg[WV][32 * SROW];
   __shared__ float s_rs[2][32];                         // inverse row scales of the tile held by each image
   __shared__ float s_amax[WV];                          // dgrad+elu: per-wave max |gact| (EpiArgs::absmax)
@@ -418,7 +382,7 @@ __global__ __launch_bounds__(64 * WV, (PC == 2 && K == 128 && NT == 1 && WV == 4
     // the register-bound kernels 5-10 % (input gradient through the activation, forward with residual; measured), and
     // there the prologue is 2 % of the launch.  The two K = 128 forward kernels without a side operand run two
     // workgroups per CU (256 registers) and would spill: two passes always.
-    constexpr bool ONEPASS = SMALL && !(PC == 2 && K == 128 && NT == 1 && !TRANSW && !SIDE);
+    constexpr bool ONEPASS = SMALL && !(K == 128 && NT == 1 && !TRANSW && !SIDE);
     f4 wp[ONEPASS ? KS : 1], wq[ONEPASS ? KS : 1];
     if constexpr (ONEPASS) {
 #pragma unroll
@@ -1092,41 +1056,27 @@ __global__ __launch_bounds__(512, 1) void gemm_fwd_w8_k(const float *__restrict_
   }
 }
 
-// SN_GEMM_VARIANT: default (unset / anything but 0) the two-piece fp16 kernels; 0 = the fp32-MFMA kernel above, the ONE A/B
-// baseline of the Linear kernels (exact fp32 products; no fused epilogues).  Read once per process.
-inline int gemm_variant() {
-  static const int v = [] {
-    const char *e = getenv("SN_GEMM_VARIANT");
-    return (e && atoi(e) == 0) ? 0 : 2;
-  }();
-  return v;
-}
-
 #define SN_UNPAREN(...) __VA_ARGS__
 constexpr int64_t kSmallRows = 131072;      // operands up to this many rows take the one-pass weight prologue (gemm_rows_split_k<…, SMALL>)
 inline bool small_operand(int64_t rows) { return rows <= kSmallRows; }
-// launch gemm_rows_split_k<2, TARGS...> (SMALL form for operands of at most kSmallRows rows); with the timing facility on
-// (sn_timing_enable: t_start / t_stop of the enclosing entry point) the kernel's own start / stop go into two events
+// launch gemm_rows_split_k<TARGS...> (SMALL form for operands of at most kSmallRows rows); t_start / t_stop of the enclosing
+// entry point: the events of the timing facility (sn_timing_enable), or NULL
 #define SN_SPLIT_LAUNCH(TARGS, ...)                                                                                    \
   do {                                                                                                                 \
-    if (small_operand(rows)) {                                                                                         \
-      if (t_start) hipExtLaunchKernelGGL((gemm_rows_split_k<2, SN_UNPAREN TARGS, true>), dim3(grid), dim3(kWG), 0, s, t_start, t_stop, 0, __VA_ARGS__); \
-      else hipLaunchKernelGGL((gemm_rows_split_k<2, SN_UNPAREN TARGS, true>), dim3(grid), dim3(kWG), 0, s, __VA_ARGS__); \
-    } else {                                                                                                           \
-      if (t_start) hipExtLaunchKernelGGL((gemm_rows_split_k<2, SN_UNPAREN TARGS>), dim3(grid), dim3(kWG), 0, s, t_start, t_stop, 0, __VA_ARGS__); \
-      else hipLaunchKernelGGL((gemm_rows_split_k<2, SN_UNPAREN TARGS>), dim3(grid), dim3(kWG), 0, s, __VA_ARGS__);     \
-    }                                                                                                                  \
+    if (small_operand(rows))                                                                                           \
+      launch_timed(gemm_rows_split_k<SN_UNPAREN TARGS, true>, dim3(grid), dim3(kWG), s, t_start, t_stop, __VA_ARGS__);  \
+    else                                                                                                               \
+      launch_timed(gemm_rows_split_k<SN_UNPAREN TARGS>, dim3(grid), dim3(kWG), s, t_start, t_stop, __VA_ARGS__);        \
   } while (0)
 // the raw-low-half form of the input gradient through the activation (gemm_rows_split_k<…, RAWLOW>), NT_ output tiles per wave
 #define SN_SPLIT_LAUNCH_RAW(NT_, ...)                                                                                  \
   do {                                                                                                                 \
-    if (small_operand(rows)) {                                                                                         \
-      if (t_start) hipExtLaunchKernelGGL((gemm_rows_split_k<2, 128, NT_, true, EPI_DGRAD_ELU, true, false, true, 4, true>), dim3(grid), dim3(kWG), 0, s, t_start, t_stop, 0, __VA_ARGS__); \
-      else hipLaunchKernelGGL((gemm_rows_split_k<2, 128, NT_, true, EPI_DGRAD_ELU, true, false, true, 4, true>), dim3(grid), dim3(kWG), 0, s, __VA_ARGS__); \
-    } else {                                                                                                           \
-      if (t_start) hipExtLaunchKernelGGL((gemm_rows_split_k<2, 128, NT_, true, EPI_DGRAD_ELU, true, false, false, 4, true>), dim3(grid), dim3(kWG), 0, s, t_start, t_stop, 0, __VA_ARGS__); \
-      else hipLaunchKernelGGL((gemm_rows_split_k<2, 128, NT_, true, EPI_DGRAD_ELU, true, false, false, 4, true>), dim3(grid), dim3(kWG), 0, s, __VA_ARGS__); \
-    }                                                                                                                  \
+    if (small_operand(rows))                                                                                           \
+      launch_timed(gemm_rows_split_k<128, NT_, true, EPI_DGRAD_ELU, true, false, true, 4, true>, dim3(grid), dim3(kWG), s, t_start, \
+                   t_stop, __VA_ARGS__);                                                                               \
+    else                                                                                                               \
+      launch_timed(gemm_rows_split_k<128, NT_, true, EPI_DGRAD_ELU, true, false, false, 4, true>, dim3(grid), dim3(kWG), s, t_start, \
+                   t_stop, __VA_ARGS__);                                                                               \
   } while (0)
 #define SN_SPLIT_LAUNCH_NT2(K_, EPI_, SIDE_, ...) SN_SPLIT_LAUNCH((K_, 2, true, EPI_, SIDE_, false), __VA_ARGS__)
 
@@ -1160,7 +1110,13 @@ extern "C" {
 
 // 0: the process runs the fp32-MFMA A/B baseline of the Linear kernels (SN_GEMM_VARIANT=0), 2: the shipped 16-bit matrix-pipe
 // kernels — what the Python launchers ask instead of reading the environment themselves
-int32_t sn_gemm_variant(void) { return gemm_variant(); }
+int32_t sn_gemm_variant(void) {
+  static const int v = [] {
+    const char *e = getenv("SN_GEMM_VARIANT");
+    return (e && atoi(e) == 0) ? 0 : 2;
+  }();
+  return v;
+}
 
 // (the largest grid any forward kernel uses: a kernel with a smaller one zeroes the blocks past its own)
 int32_t sn_linear_fwd_stats_blocks(int64_t rows) { return rows > 0 ? (int32_t)gemm_grid(rows, 2) : 0; }
@@ -1202,11 +1158,8 @@ int sn_linear_fwd_tiles_f32(const float *x, int64_t ldx, const float *W, int64_t
     sn_internal_timing_slot(0x100 | (residual ? 2 : 0) | (y_elu ? 1 : 0) | (y ? 4 : 0), rows, K,
                             rows * 4 * ((int64_t)K + (y ? J : 0) + (residual ? J : 0) + (y_elu ? J : 0)), J, &t_start, &t_stop);
 #define SN_X3_FWD(KK, RES, EL) SN_SPLIT_LAUNCH((KK, 1, false, EPI_FWD, RES, EL), x, ldx, W, ldw, y, ldy, rows, ep)
-#define SN_W8_FWD(KK, RES, EL)                                                                                         \
-  do {                                                                                                                 \
-    if (t_start) hipExtLaunchKernelGGL((gemm_fwd_w8_k<KK, RES, EL>), dim3(grid8), dim3(512), 0, s, t_start, t_stop, 0, x, ldx, W, ldw, y, ldy, rows, ep); \
-    else hipLaunchKernelGGL((gemm_fwd_w8_k<KK, RES, EL>), dim3(grid8), dim3(512), 0, s, x, ldx, W, ldw, y, ldy, rows, ep); \
-  } while (0)
+#define SN_W8_FWD(KK, RES, EL) \
+  launch_timed(gemm_fwd_w8_k<KK, RES, EL>, dim3(grid8), dim3(512), s, t_start, t_stop, x, ldx, W, ldw, y, ldy, rows, ep)
   // (eight waves of 16 columns where linear_fwd_form says so; the split launches below pick SMALL / large by the same predicate)
   if (linear_fwd_form(rows, K, J, residual != nullptr, y != nullptr, y_elu != nullptr, tile_sums != nullptr) == FWD_FORM_W8) {
     const unsigned grid8 = gemm_grid(rows, 1);
@@ -1256,10 +1209,8 @@ int sn_linear_fwd_frame_f32(const float *x, int64_t ldx, const float *W, int64_t
   sn_internal_timing_slot(0x100 | 4, rows, K, rows * 4 * ((int64_t)K + J + 3), J, &t_start, &t_stop);
   // the forward launches of sn_linear_fwd_tiles_f32 for a plain output (same grid, same SMALL / large choice) with the frame add
 #define SN_FRAME_FWD(KK, SM)                                                                                           \
-  do {                                                                                                                 \
-    if (t_start) hipExtLaunchKernelGGL((gemm_rows_split_k<2, KK, 1, false, EPI_FWD, false, false, SM, 4, false, true>), dim3(grid), dim3(kWG), 0, s, t_start, t_stop, 0, x, ldx, W, ldw, y, ldy, rows, ep); \
-    else hipLaunchKernelGGL((gemm_rows_split_k<2, KK, 1, false, EPI_FWD, false, false, SM, 4, false, true>), dim3(grid), dim3(kWG), 0, s, x, ldx, W, ldw, y, ldy, rows, ep); \
-  } while (0)
+  launch_timed(gemm_rows_split_k<KK, 1, false, EPI_FWD, false, false, SM, 4, false, true>, dim3(grid), dim3(kWG), s, t_start, \
+               t_stop, x, ldx, W, ldw, y, ldy, rows, ep)
   if (K == 256) {
     if (small_operand(rows)) SN_FRAME_FWD(256, true);
     else SN_FRAME_FWD(256, false);

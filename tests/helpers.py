@@ -54,7 +54,7 @@ def random_csr(M, K, density, seed, empty_rows=()):
     return A
 
 
-# ---- the Linear kernels address their operands through raw buffer windows (sn_gemm.hip RowWindow, wgrad_u_k): tests place
+# ---- the Linear kernels address their operands through raw buffer windows (sn_gemm.hip RowWindow, wgrad16_k): tests place
 # every operand as a strided view inside an arena of NaNs, every output as a view inside an arena of canaries ---------------
 def _arena(rows, width, pad_rows=3, pad_cols=8, seed=0, fill=float("nan"), device="cuda", values=None):
     """(arena, view): `view` = rows x width of random values (or of `values`, a rows x width tensor) inside a poisoned arena
@@ -137,9 +137,9 @@ def sigs_close(sigs, ref_of, tol=1e-4):
     return bad
 
 
-# ---- the two-piece fp16 weight gradient (wgrad_h_k, csrc/sn_dense.hip): a numpy model of its split and probe operands ----------
+# ---- the two-piece fp16 weight gradient (wgrad16_k<CT, WgradHalf2>, csrc/sn_dense.hip): a numpy model of its split and probe operands ----------
 def pow2_up_for(bound):
-    """The power of two wgrad_h_k scales an operand by: bound = f * 2^E, f in [0.5, 1)  ->  2^(15 - E), which brings the bound
+    """The power of two wgrad16_k<CT, WgradHalf2> scales an operand by: bound = f * 2^E, f in [0.5, 1)  ->  2^(15 - E), which brings the bound
     into [2^14, 2^15) (the exponent is clamped to +-100 for zero / denormal / non-finite bounds, as in the kernel)."""
     b = np.ascontiguousarray(bound, dtype=np.float32)
     e = ((b.view(np.uint32) >> np.uint32(23)) & np.uint32(0xFF)).astype(np.int64) - 126
@@ -190,7 +190,7 @@ def _probe_row(n, unit, seed):
 
 
 def split_probe_operands(J, C, rows, nz_row, seed=0):
-    """Operands that probe the split of wgrad_h_k element by element: dy and x are zero except in row `nz_row`, so
+    """Operands that probe the split of wgrad16_k<CT, WgradHalf2> element by element: dy and x are zero except in row `nz_row`, so
     G[j, c] = dy[j] * x[c] is ONE product per output (nothing for the fp32 accumulation to round but the pieces of that term).
     dy[j] = unit_dy * 2^-k_j * u_j and x[c] = unit_c * 2^-m_c * w_c, unit = the power of two at or below the operand's bound
     (what the kernel's scale maps to 2^14).  Returns a dict with the operands, the bounds and, per pair (j, c):

@@ -610,7 +610,7 @@ def test_split_fp16_row_and_column_scaling_covers_the_fp32_range():
     assert (np.abs(gotd - refd) / np.maximum(scaled, 1e-300)).max() <= 4 * 2.0 ** -24 * np.sqrt(J)
 
 
-# ---- the Linear kernels address their operands through raw buffer windows (sn_gemm.hip RowWindow, wgrad_u_k): every
+# ---- the Linear kernels address their operands through raw buffer windows (sn_gemm.hip RowWindow, wgrad16_k): every
 # operand below is a strided view inside an arena of NaNs, every output a view inside an arena of canaries (helpers._arena) ----
 @pytest.mark.parametrize("rows", [1, 31, 32, 33, 95, 1017, 8200])
 @pytest.mark.parametrize("K,J", [(128, 128), (256, 128), (128, 120), (256, 4), (128, 64)])

@@ -1,4 +1,4 @@
-"""The bounds behind the two-piece fp16 weight gradient (wgrad_h_k, csrc/sn_dense.hip), end to end on the device.
+"""The bounds behind the two-piece fp16 weight gradient (wgrad16_k<CT, WgradHalf2>, csrc/sn_dense.hip), end to end on the device.
 
   producers   the per-workgroup maxima the kernels that write dy leave (quaternion-packed Dirac product, the three
               input-gradient GEMM forms) are true, exact, complete, non-negative by bit pattern and stay inside their buffer;
@@ -352,7 +352,7 @@ def _flat_operands(rows, J, C, seed):
 
 @pytest.mark.parametrize("C", [128, 256])
 def test_scale_of_the_bounded_weight_gradient_depends_on_the_maximum_alone(C):
-    """The reduction over n_dybound inside wgrad_h_k (unaligned pointer, eight-deep 16-byte loads, 16-byte remainder, scalar
+    """The reduction over n_dybound inside wgrad16_k<CT, WgradHalf2> (unaligned pointer, eight-deep 16-byte loads, 16-byte remainder, scalar
     tail, the order of bit patterns across lanes): for every length, position of the maximum, alignment of the pointer and kind
     of filler the result has the bits of the launch that is handed [m] alone.  Fillers of m * 2^-20: a missed maximum moves the
     scale by twenty binary orders, the scaled dy then passes fp16's range (tests/test_wgrad_bounds.py:

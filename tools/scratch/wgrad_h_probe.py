@@ -1,5 +1,5 @@
 """Two-piece fp16 weight gradient (sn_wgrad_bounded_f32) against the bf16 form and float64: time per launch and error.
-usage: SN_WGRAD_H=<mode> python tools/scratch/wgrad_h_probe.py [tag]"""
+usage: python tools/scratch/wgrad_h_probe.py [tag]"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from surfacenetworks_amd import kernels  # noqa: E402
