@@ -23,14 +23,13 @@ import weakref
 import torch
 
 from . import kernels, plans
-from .functional import (SpmmTimer, _launch, _rows2d, product_form, avg_stage_backward, avg_stage_backward_ragged, avg_stage_forward,
-                         avg_stage_forward_ragged, bn_prepare, bnlin_backward,
+from .functional import (SpmmTimer, _launch, _rows2d, product_form, avg_stage_backward, avg_stage_forward, bn_prepare, bnlin_backward,
                          bnlin_backward_elu_input, bnlin_backward_zero_first, bnlin_forward, bnlin_forward_zero_first, stash, unstash,
                          zero_first_supported)
 from .graphs import active_capture
-from .operators import as_operator
+from .operators import MaskedSegments, PackedSegments, as_operator
 
-__all__ = ["lap_block", "dirac_block", "avg_block", "avg_block_ragged", "avg_block_ragged_ok", "take_activated", "attach_activated", "zero_faces_ok", "elu_conv", "elu_conv_ok",
+__all__ = ["lap_block", "dirac_block", "avg_block", "avg_block_ok", "take_activated", "attach_activated", "zero_faces_ok", "elu_conv", "elu_conv_ok",
            "elu_conv_frame_ok"]
 
 
@@ -163,15 +162,21 @@ def _bn_args(conv):
 # Every block below is written as two plain functions — `*_fwd(tensors..., operators..., constants...) -> (outputs, saved)` and
 # `*_bwd(saved, operators..., gradients..., constants...) -> gradients` — that launch through kernels.py.  The autograd nodes call
 # them directly (eager) or hand them to `_plan_forward` / `_plan_backward`, which record their launch list once per shape
-# signature and from then on enqueue it with one sn_plan_run.
+# signature and from then on enqueue it with one sn_plan_run; `_block_forward` / `_block_backward` make that choice for every node.
 _MISSING = object()
 
 
 def _op_operands(ops, ncols):
     """(arrays, key) of the forms in which the block multiplies its operators and their transposes (functional.product_form:
-    building a derived form launches and may synchronise — here, before anything is recorded)."""
+    building a derived form launches and may synchronise — here, before anything is recorded).  group None: not a sparse operator
+    but the segment layout of a global-average block (operators.MaskedSegments | PackedSegments): its device tables, its key."""
     arrays, key = [], []
     for op, group in ops:
+        if group is None:
+            tables, layout = op.plan_view()
+            arrays.extend(tables)
+            key.append(layout)
+            continue
         for o in (op, op.t()):
             kind, arr, scal = product_form(o, group, ncols)
             arrays.extend(arr)
@@ -298,6 +303,32 @@ _SITES = {name: plans.Site(name) for name in ("dirac_fwd", "dirac_bwd", "propaga
                                               "avg_ragged_fwd", "avg_ragged_bwd", "elu_conv_fwd", "elu_conv_bwd")}
 
 
+def _block_forward(ctx, site, impl, tensors, ops, consts, ncols, n_dyn, scan, counters, plan=True):
+    """The forward of a block node: `impl(*tensors, *operators, *consts)` from its launch plan (_plan_forward's arguments) when
+    plans apply (`plan`: and the node has nothing against one) and the block is plannable, else launched from here with what the
+    backward needs stashed on ctx.  counters: the running-mean buffers whose one-shot batch counter a planned call must drop.
+    Returns the block's outputs; _block_backward is the other half."""
+    outs = None
+    ctx._sn_plan = None
+    ctx._sn_ops = ops
+    if plan and plans.usable(tensors[0]):
+        outs = _plan_forward(ctx, _SITES[site], impl, tensors, ops, consts, ncols, n_dyn, scan)
+        if outs is not None:
+            _drop_counters(*counters)
+    ctx._sn_planned = outs is not None
+    if outs is None:
+        outs, saved = impl(*tensors, *[o for o, _ in ops], *consts)
+        stash(ctx, *saved)
+    return outs
+
+
+def _block_backward(ctx, site, impl, grads, consts):
+    """`impl(saved, *operators, *grads, *consts)` the way the node's forward ran: from a plan or launched from here."""
+    if ctx._sn_planned:
+        return _plan_backward(ctx, _SITES[site], impl, grads, consts)
+    return impl(unstash(ctx), *[o for o, _ in ctx._sn_ops], *grads, *consts)
+
+
 # ------------------------------------------------------------------------------------------------------------
 _NAN = {}
 
@@ -406,7 +437,6 @@ class _DiracBlock(torch.autograd.Function):
         if f is not None and pre_f is None:
             f = _rows2d(f)                     # (with a hand-off f is only a carrier — possibly the zero-stride NaN placeholder of
         ctx.f_zero = f is None                 #  need_f=False: making THAT contiguous wrote 321 MB per block at the ARAP batch)
-        ctx.ops = (opDi, opDiA)
         # Raw face gradient (DEFER_FACE_TAIL).  A block that ran with need_f=False hangs a one-element list on its nxt_f: the
         # only consumer its face gradient can have is the block that takes that hand-off, which says so here — the producer's
         # backward then expects a raw gradient and refuses anything else.
@@ -418,17 +448,8 @@ class _DiracBlock(torch.autograd.Function):
         ctx.rawbox = [False] if not need_f else None
         tensors = (v, f, pre_v, pre_f, g0, b0, W0, c0, rm0, rv0, g1, b1, W1, c1, rm1, rv1)
         consts = (need_f, need_v, avg_next, tr0, mo0, ep0, tr1, mo1, ep1)
-        outs = None
-        ctx._sn_plan = None
-        if plans.usable(v):
-            outs = _plan_forward(ctx, _SITES["dirac_fwd"], _dirac_fwd, tensors, ((opDi, 4), (opDiA, 4)), consts, v.shape[1], 4, (2, 3, 8, 14))
-            if outs is not None:
-                _drop_counters(rm0, rm1)
-        ctx._sn_planned = outs is not None
-        if outs is None:
-            outs, saved = _dirac_fwd(*tensors, opDi, opDiA, *consts)
-            stash(ctx, *saved)
-        v_new, f_out, nxt_v, nxt_f = outs
+        v_new, f_out, nxt_v, nxt_f = _block_forward(ctx, "dirac_fwd", _dirac_fwd, tensors, ((opDi, 4), (opDiA, 4)), consts, v.shape[1], 4,
+                                                    (2, 3, 8, 14), (rm0, rm1))
         if f_out is None:
             # The caller only chains f into the next Dirac block, which consumes the ACTIVATED hand-off: the pre-activation
             # face features are not written (321 MB per block at the ARAP batch).  What is returned in their place is a
@@ -448,7 +469,6 @@ class _DiracBlock(torch.autograd.Function):
     def backward(ctx, g_vnew, g_fout, _gv, _gf):
         if g_vnew is None and g_fout is None:
             return (None,) * 27
-        opDi, opDiA = ctx.ops
         g_vnew = g_vnew.contiguous() if g_vnew is not None else None
         g_fout = g_fout.contiguous() if g_fout is not None else None
         consts = (ctx.f_zero, bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1]), ctx.defer,
@@ -457,10 +477,7 @@ class _DiracBlock(torch.autograd.Function):
             raise RuntimeError("dirac_block: the gradient of the face output was left raw by the next Dirac block (DEFER_FACE_TAIL), but "
                                "what finishes it is gone — the gradient was copied, edited in place, or kernels.clear_absmax() ran "
                                "between the two backward calls")
-        if ctx._sn_planned:
-            r = _plan_backward(ctx, _SITES["dirac_bwd"], _dirac_bwd, (g_vnew, g_fout), consts)
-        else:
-            r = _dirac_bwd(unstash(ctx), opDi, opDiA, g_vnew, g_fout, *consts)
+        r = _block_backward(ctx, "dirac_bwd", _dirac_bwd, (g_vnew, g_fout), consts)
         none5 = (None,) * 5
         return (r[0], r[1], None, None, None, None, None, None, None) + r[2:6] + none5 + r[6:10] + none5
 
@@ -566,18 +583,9 @@ class _PropagateBlock(torch.autograd.Function):
         x = _rows2d(x)
         tensors = (x, pre, mask_rows, inv_count, g0, b0, W0, c0, rm0, rv0, g1, b1, W1, c1, rm1, rv1)
         consts = (nseg, avg_next, tr0, mo0, ep0, tr1, mo1, ep1)
-        ctx.op, ctx.nseg = op, nseg
-        ctx._sn_plan = None
-        outs = None
-        if op is not None and plans.usable(x):          # (the full-width average stage multiplies by 1/count with a torch op)
-            outs = _plan_forward(ctx, _SITES["propagate_fwd"], _propagate_fwd, tensors, ((op, 1),), consts, x.shape[1], 4, (1, 8, 14))
-            if outs is not None:
-                _drop_counters(rm0, rm1)
-        ctx._sn_planned = outs is not None
-        if outs is None:
-            outs, saved = _propagate_fwd(*tensors, op, *consts)
-            stash(ctx, *saved)
-        out, nxt = outs
+        ctx.nseg = nseg
+        out, nxt = _block_forward(ctx, "propagate_fwd", _propagate_fwd, tensors, ((op, 1),), consts, x.shape[1], 4, (1, 8, 14), (rm0, rm1),
+                                  plan=op is not None)      # (the full-width average stage multiplies by 1/count with a torch op)
         ctx.mark_non_differentiable(nxt)
         ctx.set_materialize_grads(False)          # else the engine fills a (rows, 2C) zero gradient for `nxt` every backward
         return out, nxt
@@ -588,67 +596,58 @@ class _PropagateBlock(torch.autograd.Function):
             return (None,) * 25
         g_out = g_out.contiguous()
         consts = (ctx.nseg, bool(ctx.needs_input_grad[0]))
-        if ctx._sn_planned:
-            r = _plan_backward(ctx, _SITES["propagate_bwd"], _propagate_bwd, (g_out,), consts)
-        else:
-            r = _propagate_bwd(unstash(ctx), ctx.op, g_out, *consts)
+        r = _block_backward(ctx, "propagate_bwd", _propagate_bwd, (g_out,), consts)
         none5 = (None,) * 5
         return (r[0], None, None, None, None, None, None) + r[1:5] + none5 + r[5:9] + none5
 
 
-def _avg_fwd(x, pre, mask_rows, inv_count, g0, b0, W0, c0, rm0, rv0, g1, b1, W1, c1, rm1, rv1, nseg, tr0, mo0, ep0, tr1, mo1, ep1):
+def _avg_fwd(x, pre, g0, b0, W0, c0, rm0, rv0, g1, b1, W1, c1, rm1, rv1, seg, tr0, mo0, ep0, tr1, mo1, ep1):
     """AvgResNet2 (utils_pt.py:230-243) at half width (functional.avg_stage_forward): the broadcast mean is never written,
     both Linear layers run over C instead of 2C columns, and the whole backward of a stage — BatchNorm tail, mean-path
-    gradient, ELU derivative, residual-path gradient — leaves the dgrad GEMM's epilogue."""
+    gradient, ELU derivative, residual-path gradient — leaves the dgrad GEMM's epilogue.  seg: how the rows divide into meshes
+    (operators.MaskedSegments: a padded batch, BatchNorm over every row as in the reference, utils_pt.py:97-99;
+    operators.PackedSegments: ragged meshes, no padding rows, BatchNorm over real rows only)."""
     rows, C = x.shape
-    per = rows // nseg
     cat = _activated(x, pre)
     e_a = cat[:, :C]
     e_b = torch.empty((rows, C), dtype=torch.float32, device=x.device)
     # per-mesh means and BatchNorm sums of a stage's operand: from what the GEMM that wrote it left (per-tile column sums +
-    # statistics partials) when there is such a producer — else one statistics pass over the operand
+    # statistics partials) when there is such a producer — else one statistics pass over the operand, which a packed batch
+    # spares too with the partials alone: only there is the first GEMM asked for them when it leaves no tile sums
     pb = _new_part(rows, C, x.device)
     tb = _new_tiles(rows, C, x.device, pb, True)
-    _, st0 = avg_stage_forward(e_a, mask_rows, inv_count, nseg, per, g0, b0, W0, c0, rm0, rv0, tr0, mo0, ep0, None, e_b,
-                               want_y=False, elu_stats=pb if tb is not None else None, tile_sums=tb,
-                               e_tiles=_tiles_of(cat))             # only elu(h) is needed downstream
+    _, st0 = avg_stage_forward(e_a, seg, g0, b0, W0, c0, rm0, rv0, mo0, ep0, None, e_b, want_y=False,
+                               elu_stats=pb if (tb is not None or seg.stats_from_partials) else None,
+                               part=getattr(cat, "_sn_part", None), tile_sums=tb, e_tiles=_tiles_of(cat))   # only elu(h) is needed downstream
     nxt = _new_cat(rows, C, x.device)
     pn = _new_part(rows, C, x.device)
-    out, st1 = avg_stage_forward(e_b, mask_rows, inv_count, nseg, per, g1, b1, W1, c1, rm1, rv1, tr1, mo1, ep1, x,
-                                 nxt[:, :C], elu_stats=pn, e_tiles=(tb, pb) if tb is not None else None)
+    out, st1 = avg_stage_forward(e_b, seg, g1, b1, W1, c1, rm1, rv1, mo1, ep1, x, nxt[:, :C], elu_stats=pn, part=pb,
+                                 e_tiles=(tb, pb) if tb is not None else None)
     _attach_part(nxt, pn)
-    return (out, nxt), (st0, st1, (mask_rows, inv_count))
+    return (out, nxt), (st0, st1)
 
 
-def _avg_bwd(saved, g_out, nseg, need_gx):
-    st0, st1, (mask_rows, inv_count) = saved
-    per = st0[0].shape[0] // nseg
-    g_h, dg1, db1, dW1, dc1 = avg_stage_backward(st1, mask_rows, inv_count, nseg, per, g_out, None)
-    g_x, dg0, db0, dW0, dc0 = avg_stage_backward(st0, mask_rows, inv_count, nseg, per, g_h, g_out)   # + residual path
+def _avg_bwd(saved, seg, g_out, need_gx):
+    st0, st1 = saved
+    g_h, dg1, db1, dW1, dc1 = avg_stage_backward(st1, seg, g_out, None)
+    g_x, dg0, db0, dW0, dc0 = avg_stage_backward(st0, seg, g_h, g_out)      # + residual path
     return (g_x if need_gx else None, dg0, db0, dW0, dc0, dg1, db1, dW1, dc1)
 
 
+_AVG_SITES = {MaskedSegments: ("avg_fwd", "avg_bwd"), PackedSegments: ("avg_ragged_fwd", "avg_ragged_bwd")}
+
+
 class _AvgBlock(torch.autograd.Function):
-    """AvgResNet2 at half width as one autograd node (_avg_fwd / _avg_bwd)."""
+    """AvgResNet2 at half width as one autograd node (_avg_fwd / _avg_bwd), on a padded or a packed batch.  The segment layout
+    reaches a launch plan the way a sparse operator does: its device tables are operands, its layout key is part of the plan's."""
 
     @staticmethod
-    def forward(ctx, x, mask_rows, inv_count, nseg, pre, g0, b0, W0, c0, rm0, rv0, tr0, mo0, ep0, g1, b1, W1, c1, rm1, rv1,
-                tr1, mo1, ep1):
+    def forward(ctx, x, seg, pre, g0, b0, W0, c0, rm0, rv0, tr0, mo0, ep0, g1, b1, W1, c1, rm1, rv1, tr1, mo1, ep1):
         x = _rows2d(x)
-        tensors = (x, pre, mask_rows, inv_count, g0, b0, W0, c0, rm0, rv0, g1, b1, W1, c1, rm1, rv1)
-        consts = (nseg, tr0, mo0, ep0, tr1, mo1, ep1)
-        ctx.nseg = nseg
-        ctx._sn_plan = None
-        outs = None
-        if plans.usable(x):
-            outs = _plan_forward(ctx, _SITES["avg_fwd"], _avg_fwd, tensors, (), consts, x.shape[1], 4, (1, 8, 14))
-            if outs is not None:
-                _drop_counters(rm0, rm1)
-        ctx._sn_planned = outs is not None
-        if outs is None:
-            outs, saved = _avg_fwd(*tensors, *consts)
-            stash(ctx, *saved)
-        out, nxt = outs
+        tensors = (x, pre, g0, b0, W0, c0, rm0, rv0, g1, b1, W1, c1, rm1, rv1)
+        consts = (tr0, mo0, ep0, tr1, mo1, ep1)
+        ctx.sites = _AVG_SITES[type(seg)]
+        out, nxt = _block_forward(ctx, ctx.sites[0], _avg_fwd, tensors, ((seg, None),), consts, x.shape[1], 2, (1, 6, 12), (rm0, rm1))
         ctx.mark_non_differentiable(nxt)
         ctx.set_materialize_grads(False)          # else the engine fills a (rows, 2C) zero gradient for `nxt` every backward
         return out, nxt
@@ -656,132 +655,20 @@ class _AvgBlock(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_out, _gn):
         if g_out is None:
-            return (None,) * 23
-        g_out = g_out.contiguous()
-        consts = (ctx.nseg, bool(ctx.needs_input_grad[0]))
-        if ctx._sn_planned:
-            r = _plan_backward(ctx, _SITES["avg_bwd"], _avg_bwd, (g_out,), consts)
-        else:
-            r = _avg_bwd(unstash(ctx), g_out, *consts)
-        none5 = (None,) * 5
-        return (r[0], None, None, None, None) + r[1:5] + none5 + r[5:9] + none5
-
-
-def _seg_tensors(seg):
-    """The device tables of a PackedSegments (operands of a plan) and what identifies its layout."""
-    return (seg.tiles, seg.seg_tile_ptr, seg.inv_count, seg.off_dev, seg.slab_off, seg.seg_slab_ptr, seg.len_f64), \
-        (seg.nseg, seg.rows, seg.nslab, seg.min_len, int(seg.tiles.shape[0]))
-
-
-def _avg_ragged_fwd(x, pre, g0, b0, W0, c0, rm0, rv0, g1, b1, W1, c1, rm1, rv1, t0, t1, t2, t3, t4, t5, t6, seg, seg_key, mo0, ep0,
-                    mo1, ep1):
-    """_avg_fwd on a PACKED batch: `seg` (operators.PackedSegments) gives the meshes' row ranges; no mask, every row is real
-    (BatchNorm over real rows only — the reference's padded batch includes the padding rows, utils_pt.py:97-99).
-    (t0..t6: seg's device tables, listed so that a launch plan knows them as operands; seg_key: their layout.)"""
-    rows, C = x.shape
-    cat = _activated(x, pre)
-    e_a = cat[:, :C]
-    e_b = torch.empty((rows, C), dtype=torch.float32, device=x.device)
-    pb = _new_part(rows, C, x.device)
-    tb = _new_tiles(rows, C, x.device, pb, True)      # (as _avg_fwd: means and statistics from what the producing GEMM left)
-    _, st0 = avg_stage_forward_ragged(e_a, seg, g0, b0, W0, c0, rm0, rv0, mo0, ep0, None, e_b, want_y=False, elu_stats=pb,
-                                      part=getattr(cat, "_sn_part", None), tile_sums=tb, e_tiles=_tiles_of(cat))
-    nxt = _new_cat(rows, C, x.device)
-    pn = _new_part(rows, C, x.device)
-    out, st1 = avg_stage_forward_ragged(e_b, seg, g1, b1, W1, c1, rm1, rv1, mo1, ep1, x, nxt[:, :C], elu_stats=pn, part=pb,
-                                        e_tiles=(tb, pb) if tb is not None else None)
-    _attach_part(nxt, pn)
-    return (out, nxt), (st0, st1)
-
-
-def _avg_ragged_bwd(saved, g_out, t0, t1, t2, t3, t4, t5, t6, seg, seg_key, need_gx):
-    st0, st1 = saved
-    g_h, dg1, db1, dW1, dc1 = avg_stage_backward_ragged(st1, seg, g_out, None)
-    g_x, dg0, db0, dW0, dc0 = avg_stage_backward_ragged(st0, seg, g_h, g_out)      # + residual path
-    return (g_x if need_gx else None, dg0, db0, dW0, dc0, dg1, db1, dW1, dc1)
-
-
-class _AvgBlockRagged(torch.autograd.Function):
-    """_AvgBlock on a PACKED batch (_avg_ragged_fwd / _avg_ragged_bwd)."""
-
-    @staticmethod
-    def forward(ctx, x, seg, pre, g0, b0, W0, c0, rm0, rv0, tr0, mo0, ep0, g1, b1, W1, c1, rm1, rv1, tr1, mo1, ep1):
-        x = _rows2d(x)
-        seg_t, seg_key = _seg_tensors(seg)
-        tensors = (x, pre, g0, b0, W0, c0, rm0, rv0, g1, b1, W1, c1, rm1, rv1, *seg_t)
-        consts = (_Opaque(seg), seg_key, mo0, ep0, mo1, ep1)
-        ctx.seg = seg
-        ctx._sn_plan = None
-        outs = None
-        if plans.usable(x):
-            outs = _plan_forward(ctx, _SITES["avg_ragged_fwd"], _avg_ragged_fwd_u, tensors, (), consts, x.shape[1], 2, (1, 6, 12))
-            if outs is not None:
-                _drop_counters(rm0, rm1)
-        ctx._sn_planned = outs is not None
-        if outs is None:
-            outs, saved = _avg_ragged_fwd(*tensors, seg, seg_key, mo0, ep0, mo1, ep1)
-            stash(ctx, *saved)
-        out, nxt = outs
-        ctx.mark_non_differentiable(nxt)
-        ctx.set_materialize_grads(False)
-        return out, nxt
-
-    @staticmethod
-    def backward(ctx, g_out, _gn):
-        if g_out is None:
             return (None,) * 21
-        g_out = g_out.contiguous()
-        seg = ctx.seg
-        seg_t, seg_key = _seg_tensors(seg)
-        need = bool(ctx.needs_input_grad[0])
-        if ctx._sn_planned:
-            r = _plan_backward(ctx, _SITES["avg_ragged_bwd"], _avg_ragged_bwd_u, (g_out, *seg_t), (_Opaque(seg), seg_key, need))
-        else:
-            r = _avg_ragged_bwd(unstash(ctx), g_out, *seg_t, seg, seg_key, need)
+        r = _block_backward(ctx, ctx.sites[1], _avg_bwd, (g_out.contiguous(),), (bool(ctx.needs_input_grad[0]),))
         none5 = (None,) * 5
         return (r[0], None, None) + r[1:5] + none5 + r[5:9] + none5
 
 
-class _Opaque:
-    """A host object a block needs (a PackedSegments) among a plan's constants: it takes no part in the plan's key — what
-    identifies it is listed next to it (`seg_key`) — and is handed to the block's function as it is."""
-    __slots__ = ("v",)
-
-    def __init__(self, v):
-        self.v = v
-
-    def __hash__(self):
-        return 0
-
-    def __eq__(self, other):
-        return isinstance(other, _Opaque)
-
-
-def _avg_ragged_fwd_u(*a):
-    return _avg_ragged_fwd(*a[:21], a[21].v, *a[22:])
-
-
-def _avg_ragged_bwd_u(saved, g_out, *a):
-    return _avg_ragged_bwd(saved, g_out, *a[:7], a[7].v, *a[8:])
-
-
-def avg_block_ragged_ok(mod, seg, inputs) -> bool:
+def avg_block_ok(mod, seg, inputs, a0=None, a1=None) -> bool:
+    """Does the half-width node (_AvgBlock) cover this AvgResNet2 on the segment layout `seg`?  Training-mode BatchNorm, float32,
+    two 2C -> C layers of a width and meshes of a size the stage kernels take.  (a0, a1: the modules' _bn_args, if the caller has them.)"""
     C = inputs.shape[-1]
-    a0, a1 = _bn_args(mod._modules["bn_fc0"]), _bn_args(mod._modules["bn_fc1"])
-    return bool(a0[6] and a1[6]) and inputs.dtype == torch.float32 and mod.bn_fc0.fc.weight.shape == (C, 2 * C) and \
-        mod.bn_fc1.fc.weight.shape == (C, 2 * C) and kernels.avg_stage_ragged_supported(C, C, seg) and \
-        seg.rows == inputs.shape[0] * inputs.shape[1]
-
-
-def avg_block_ragged(mod, seg, inputs):
-    """AvgResNet2 on a packed (1, sum V_i, C) batch as one autograd node at half width."""
-    B, V, C = inputs.shape
-    rows = B * V
-    pre = take_activated(inputs, rows, C)
-    _learn_avg_next(pre, rows)
-    out, nxt = _AvgBlockRagged.apply(inputs.reshape(rows, C), seg, pre, *_bn_args(mod.bn_fc0),
-                                     *_bn_args(mod.bn_fc1))
-    return attach_activated(out.view(B, V, C), nxt)
+    a0 = _bn_args(mod._modules["bn_fc0"]) if a0 is None else a0
+    a1 = _bn_args(mod._modules["bn_fc1"]) if a1 is None else a1
+    return bool(a0[6] and a1[6]) and inputs.dtype == torch.float32 and a0[2].shape == (C, 2 * C) and a1[2].shape == (C, 2 * C) and \
+        seg.stage_supported(C, C) and seg.rows == inputs.shape[0] * inputs.shape[1]
 
 
 def _elu_conv_fwd(v, pre, frame, g0, b0, W0, c0, rm0, rv0, tr0, mo0, ep0):
@@ -811,26 +698,12 @@ class _EluConv(torch.autograd.Function):
             v = _rows2d(v)                     # (with a hand-off v is only a carrier — possibly the NaN placeholder of need_v=False)
         tensors = (v, pre, frame, g0, b0, W0, c0, rm0, rv0)
         consts = (tr0, mo0, ep0)
-        ctx._sn_plan = None
-        outs = None
-        if plans.usable(v):
-            outs = _plan_forward(ctx, _SITES["elu_conv_fwd"], _elu_conv_fwd, tensors, (), consts, v.shape[1], 3, (1, 7))
-            if outs is not None:
-                _drop_counters(rm0)
-        ctx._sn_planned = outs is not None
-        if outs is None:
-            outs, saved = _elu_conv_fwd(*tensors, *consts)
-            stash(ctx, *saved)
-        return outs[0]
+        return _block_forward(ctx, "elu_conv_fwd", _elu_conv_fwd, tensors, (), consts, v.shape[1], 3, (1, 7), (rm0,))[0]
 
     @staticmethod
     def backward(ctx, dy):
         dy = dy.contiguous()
-        need = bool(ctx.needs_input_grad[0])
-        if ctx._sn_planned:
-            r = _plan_backward(ctx, _SITES["elu_conv_bwd"], _elu_conv_bwd, (dy,), (need,))
-        else:
-            r = _elu_conv_bwd(unstash(ctx), dy, need)
+        r = _block_backward(ctx, "elu_conv_bwd", _elu_conv_bwd, (dy,), (bool(ctx.needs_input_grad[0]),))
         return (r[0], None, None) + r[1:5] + (None,) * 5
 
 
@@ -886,9 +759,7 @@ def lap_block(mod, L, inputs, avg_next=None):
     return attach_activated(out.view(B, V, C), nxt)
 
 
-def avg_block(mod, mask, inputs):
-    B, V, C = inputs.shape
-    rows = B * V
+def _masked_segments(mask, B, V) -> MaskedSegments:
     # The 7 global-average blocks of a model share one mask: its flattened copy and the per-mesh 1/count are cached on the
     # mask object, keyed by its version (in-place edits invalidate).  NOT while a hipGraph is being captured: a value
     # computed eagerly during warm-up would be baked into the graph as a constant, and every replay on another batch
@@ -903,19 +774,29 @@ def avg_block(mod, mask, inputs):
     cached = getattr(mask, slot, None) if slot else None
     key = (B, V, _version_of(mask), gen)
     if cached is None or cached[0] != key:
-        cached = (key, mask.reshape(rows).contiguous(), 1.0 / mask.reshape(B, V).sum(1, keepdim=True))
+        cached = (key, MaskedSegments(mask, B, V))
         if slot:
             try:
                 setattr(mask, slot, cached)
             except AttributeError:
                 pass
-    _, mask_rows, inv_count = cached
+    return cached[1]
+
+
+def avg_block(mod, mask, inputs):
+    """AvgResNet2 on a padded (B, V, C) batch with its (B, V, 1) mask, or on a packed (1, sum V_i, C) batch with its
+    operators.PackedSegments in the mask's place, as one autograd node: at half width where avg_block_ok says so, else (padded
+    batches) at full width."""
+    B, V, C = inputs.shape
+    rows = B * V
+    seg = mask if isinstance(mask, PackedSegments) else _masked_segments(mask, B, V)
     a0, a1 = _bn_args(mod._modules["bn_fc0"]), _bn_args(mod._modules["bn_fc1"])
-    if a0[6] and a1[6] and kernels.avg_stage_supported(C, a0[2].shape[0], V) and a0[2].shape[1] == 2 * C and a1[2].shape[0] == C:
-        pre = take_activated(inputs, rows, C)
+    pre = take_activated(inputs, rows, C)
+    if avg_block_ok(mod, seg, inputs, a0, a1):
         _learn_avg_next(pre, rows)
-        out, nxt = _AvgBlock.apply(inputs.reshape(rows, C), mask_rows, inv_count, B, pre, *a0, *a1)
+        out, nxt = _AvgBlock.apply(inputs.reshape(rows, C), seg, pre, *a0, *a1)
+    elif isinstance(seg, MaskedSegments):
+        out, nxt = _PropagateBlock.apply(inputs.reshape(rows, C), None, seg.mask_rows, seg.inv_count, B, pre, False, *a0, *a1)
     else:
-        out, nxt = _PropagateBlock.apply(inputs.reshape(rows, C), None, mask_rows, inv_count, B, take_activated(inputs, rows, C),
-                                         False, *a0, *a1)
+        raise ValueError("avg_block: a packed batch the half-width stage does not cover (avg_block_ok)")
     return attach_activated(out.view(B, V, C), nxt)

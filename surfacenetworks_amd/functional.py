@@ -21,8 +21,8 @@ from . import _lib as _lib_mod
 from . import kernels
 from .operators import SparseOperator, as_operator
 
-__all__ = ["spmm", "lap_propagate", "dirac_face_stage", "dirac_vert_stage", "avg_propagate", "avg_propagate_ragged", "bn_linear", "bnlin_forward",
-           "bnlin_backward", "bn_prepare", "avg_stage_forward_ragged", "avg_stage_backward_ragged", "set_dirac_format", "set_laplacian_format", "SpmmTimer", "thin_linear", "thin_linear_supported"]
+__all__ = ["spmm", "lap_propagate", "dirac_face_stage", "dirac_vert_stage", "avg_propagate", "bn_linear", "bnlin_forward",
+           "bnlin_backward", "bn_prepare", "avg_stage_forward", "avg_stage_backward", "set_dirac_format", "set_laplacian_format", "SpmmTimer", "thin_linear", "thin_linear_supported"]
 
 _DIRAC_FORMAT = "q3"
 _LAPLACIAN_FORMAT = "ring"       # set_laplacian_format
@@ -721,19 +721,18 @@ def bnlin_backward_elu_input(state, dy):
     return dx, dgamma, dbeta, dW, db
 
 
-def avg_stage_forward(e, mask_rows, inv_count, nseg, per, gamma, beta, W, b, running_mean, running_var, training, momentum,
-                      eps, residual=None, elu_out=None, want_y=True, elu_stats=None, tile_sums=None, e_tiles=None):
+def avg_stage_forward(e, seg, gamma, beta, W, b, running_mean, running_var, momentum, eps, residual=None, elu_out=None, want_y=True,
+                      elu_stats=None, part=None, tile_sums=None, e_tiles=None):
     """One stage of AvgResNet2 (utils_pt.py:230-243), Lin(BN([e | global_average(e) broadcast])), at HALF width: the second
     half of the concat buffer is a per-mesh constant m, so it is never materialised — its BatchNorm statistics follow from
     m (nseg x C numbers), its share of the Linear product is a per-mesh bias m·Wf[:, C:]^T + bf, and the GEMM runs over the
-    C real columns only.  Training-mode BatchNorm only (the caller checks kernels.avg_stage_supported)."""
+    C real columns only.  `seg` says how the rows divide into meshes (operators.MaskedSegments: a padded batch and its mask;
+    operators.PackedSegments: ragged meshes, no padding rows, every row real) and launches what depends on that.
+    e_tiles / part: what the GEMM that wrote e left (seg.stage_stats).  Training-mode BatchNorm only (the caller checks
+    seg.stage_supported)."""
     e = _rows2d(e)
     rows, C = e.shape
-    if e_tiles is not None:
-        # the GEMM that wrote e left its per-tile column sums and its statistics partials: no pass over e
-        m, stats = kernels.avg_stats_from_tiles(e_tiles[0], e_tiles[1], e, mask_rows, inv_count, per, nseg)
-    else:
-        m, stats = kernels.avg_stats(e, mask_rows, inv_count, per, nseg)       # per-mesh mean + BatchNorm statistics, one pass over e
+    m, stats = seg.stage_stats(e, e_tiles, part)
     stats, rows_g = _sync_stats(stats, rows)
     if kernels.avg_merged_supported(W.shape[0], C, m.shape[0]):
         mean, invstd, s, t, Wf, bf, segb = kernels.bn_fold_seg(stats, rows_g, gamma, beta, W, b, eps, momentum, running_mean,
@@ -744,87 +743,29 @@ def avg_stage_forward(e, mask_rows, inv_count, nseg, per, gamma, beta, W, b, run
         segb = kernels.seg_affine(m, Wf[:, C:], bf)
     if residual is not None:
         residual = _rows2d(residual)
-    y = kernels.linear_fwd_segbias(e, Wf[:, :C], segb, per, residual, elu_out, want_y, elu_stats, tile_sums)
+    y = seg.linear_fwd_segbias(e, Wf[:, :C], segb, residual, elu_out, want_y, elu_stats, tile_sums)
     return y, (e, m, W, Wf, s, mean, invstd, beta, b is not None, rows_g)
 
 
-def avg_stage_backward(state, mask_rows, inv_count, nseg, per, dy, gadd):
+def avg_stage_backward(state, seg, dy, gadd):
     """Backward of avg_stage_forward THROUGH the ELU that produced e: returns (dL/d(pre-activation of e) + gadd, dgamma,
     dbeta, dW, db).  Second-half terms: G[:, C:] = sum_mesh S^T (m - mu2) with S the per-mesh column sums of dy; the gradient
-    of the mean path, inv_count * (S·Wf2 + per ((m - mu2) B2 + C2)), is added per row inside the dgrad GEMM's epilogue."""
+    of the mean path of mesh i, inv_count_i (S_i·Wf2 + len_i ((m_i - mu2) B2 + C2)) (len_i: the row period of a padded batch), is
+    added per row inside the dgrad GEMM's epilogue."""
     e, m, W, Wf, s, mean, invstd, beta, has_bias, rows_g = state
     dy = dy.contiguous()
     rows, C = e.shape
     bounds = _dy_bounds(dy, invstd[:C], rows_g, True)
-    G1, sdy, Sg = kernels.wgrad_seg(dy, e, mean[:C], per, bounds=bounds)   # per-mesh column sums of dy from the same pass
+    G1, sdy, Sg = seg.wgrad(dy, e, mean[:C], bounds)             # per-mesh column sums of dy from the same pass
     if _BN_SYNC is None and kernels.avg_merged_supported(dy.shape[1], C, m.shape[0], 2):
-        dW, db, dgamma, dbeta, Bc, Cc, segvec = kernels.avg_bn_bwd(G1, sdy, Sg, m, mean[C:], W, s, invstd, beta, rows_g, has_bias,
-                                                                   Wf[:, C:], inv_count, rows_per_seg=per)
-        g = kernels.linear_dgrad_eluseg(dy, Wf[:, :C], e, mean[:C], Bc[:C], Cc[:C], segvec, per, mask_rows, gadd)
-        return g, dgamma, dbeta, dW, db
-    Gc = kernels.avg_bwd_gc(G1, Sg, m, mean[C:])
-    Gc, sdy, scale = _sync_grad_stats(Gc, sdy)
-    dW, db, dgamma, dbeta, Bc, Cc = kernels.bn_bwd_coeffs(Gc, sdy, W, s, invstd, beta, rows_g, has_bias)
-    dW, db, dgamma, dbeta = _scale_param_grads(scale, dW, db, dgamma, dbeta)
-    segvec = kernels.avg_bwd_segvec(Sg, Wf[:, C:], m, mean[C:], Bc[C:], Cc[C:], inv_count, per)
-    g = kernels.linear_dgrad_eluseg(dy, Wf[:, :C], e, mean[:C], Bc[:C], Cc[:C], segvec, per, mask_rows, gadd)
-    return g, dgamma, dbeta, dW, db
-
-
-def avg_stage_forward_ragged(e, seg, gamma, beta, W, b, running_mean, running_var, momentum, eps, residual=None, elu_out=None,
-                             want_y=True, elu_stats=None, part=None, tile_sums=None, e_tiles=None):
-    """avg_stage_forward on a PACKED batch (`seg`: operators.PackedSegments — ragged meshes, no padding rows, every row
-    real): per-mesh means by sn_segment_colsum_ragged_f32; BatchNorm statistics of the first half from the partials `part`
-    the GEMM that wrote e left (else one more pass over e), of the broadcast half from the means (mesh i contributes
-    len_i·m_i and len_i·m_i²); the per-mesh bias enters the GEMM by mesh offsets (sn_linear_fwd_segbias_ragged_f32)."""
-    e = _rows2d(e)
-    rows, C = e.shape
-    if e_tiles is not None:
-        # the GEMM that wrote e left its per-tile column sums and its statistics partials: no pass over e at all
-        m, stats = kernels.avg_stats_from_tiles_ragged(e_tiles[0], e_tiles[1], e, seg)
+        dW, db, dgamma, dbeta, Bc, Cc, segvec = seg.avg_bn_bwd(G1, sdy, Sg, m, mean[C:], W, s, invstd, beta, rows_g, has_bias, Wf[:, C:])
     else:
-        m = seg.mean(e).contiguous()
-    # statistics of [e | mean broadcast] in one launch: the partials of the kernel that wrote e (or one more pass over e) and
-    # len_i m_i, len_i m_i^2 per mesh
-    if e_tiles is not None:
-        pass
-    elif part is not None and C == 128:
-        stats = kernels.avg_stats_ragged(m, seg, part, kernels.linear_fwd_stats_blocks(rows))
-    else:
-        stats = kernels.avg_stats_ragged(m, seg, kernels.colstats(e).reshape(1, 2, C), 1)
-    stats, rows_g = _sync_stats(stats, rows)
-    if kernels.avg_merged_supported(W.shape[0], C, m.shape[0]):
-        mean, invstd, s, t, Wf, bf, segb = kernels.bn_fold_seg(stats, rows_g, gamma, beta, W, b, eps, momentum, running_mean,
-                                                               running_var, m.contiguous(), _take_counter(running_mean))
-    else:
-        mean, invstd, s, t, Wf, bf = kernels.bn_fold(stats, rows_g, gamma, beta, W, b, eps, momentum, True, running_mean, running_var,
-                                                     _take_counter(running_mean))
-        segb = kernels.seg_affine(m, Wf[:, C:], bf)
-    if residual is not None:
-        residual = _rows2d(residual)
-    y = kernels.linear_fwd_segbias_ragged(e, Wf[:, :C], segb, seg, residual, elu_out, want_y, elu_stats, tile_sums)
-    return y, (e, m, W, Wf, s, mean, invstd, beta, b is not None, rows_g)
-
-
-def avg_stage_backward_ragged(state, seg, dy, gadd):
-    """Backward of avg_stage_forward_ragged through the ELU that produced e (as avg_stage_backward; the mean-path gradient of
-    mesh i is inv_count_i (S_i·Wf2 + len_i ((m_i - mu2) B2 + C2)))."""
-    e, m, W, Wf, s, mean, invstd, beta, has_bias, rows_g = state
-    dy = dy.contiguous()
-    rows, C = e.shape
-    bounds = _dy_bounds(dy, invstd[:C], rows_g, True)
-    G1, sdy, Sg = kernels.wgrad_slabs(dy, e, mean[:C], seg, bounds=bounds)
-    if _BN_SYNC is None and kernels.avg_merged_supported(dy.shape[1], C, m.shape[0], 2):
-        dW, db, dgamma, dbeta, Bc, Cc, segvec = kernels.avg_bn_bwd(G1, sdy, Sg, m.contiguous(), mean[C:], W, s, invstd, beta, rows_g,
-                                                                   has_bias, Wf[:, C:], seg.inv_count, segoff=seg.off_dev)
-        g = kernels.linear_dgrad_eluseg_ragged(dy, Wf[:, :C], e, mean[:C], Bc[:C], Cc[:C], segvec, seg, gadd)
-        return g, dgamma, dbeta, dW, db
-    Gc = kernels.avg_bwd_gc(G1, Sg, m, mean[C:])
-    Gc, sdy, scale = _sync_grad_stats(Gc, sdy)
-    dW, db, dgamma, dbeta, Bc, Cc = kernels.bn_bwd_coeffs(Gc, sdy, W, s, invstd, beta, rows_g, has_bias)
-    dW, db, dgamma, dbeta = _scale_param_grads(scale, dW, db, dgamma, dbeta)
-    segvec = kernels.avg_bwd_segvec_ragged(Sg, Wf[:, C:], m, mean[C:], Bc[C:], Cc[C:], seg)
-    g = kernels.linear_dgrad_eluseg_ragged(dy, Wf[:, :C], e, mean[:C], Bc[:C], Cc[:C], segvec, seg, gadd)
+        Gc = kernels.avg_bwd_gc(G1, Sg, m, mean[C:])
+        Gc, sdy, scale = _sync_grad_stats(Gc, sdy)
+        dW, db, dgamma, dbeta, Bc, Cc = kernels.bn_bwd_coeffs(Gc, sdy, W, s, invstd, beta, rows_g, has_bias)
+        dW, db, dgamma, dbeta = _scale_param_grads(scale, dW, db, dgamma, dbeta)
+        segvec = seg.bwd_segvec(Sg, Wf[:, C:], m, mean[C:], Bc[C:], Cc[C:])
+    g = seg.dgrad_eluseg(dy, Wf[:, :C], e, mean[:C], Bc[:C], Cc[:C], segvec, gadd)
     return g, dgamma, dbeta, dW, db
 
 
@@ -915,37 +856,9 @@ def thin_linear(x2d: torch.Tensor, fc: torch.nn.Linear, want_elu: bool = False):
 
 class _AvgPropagate(torch.autograd.Function):
     """cat = [e, mean_mesh(e)], e = elu(x): the propagate step of AvgResNet2 (src/utils/utils_pt.py:230-241) with
-    global_average (utils_pt.py:120-122) fused: ELU straight into the concat buffer, per-mesh masked column sums in one
-    pass, the mean broadcast written into the second half; backward folds the mean-path gradient into the ELU backward."""
-
-    @staticmethod
-    def forward(ctx, x, mask_rows, inv_count, nseg):
-        x = _rows2d(x)
-        rows, C = x.shape
-        per = rows // nseg
-        cat = torch.empty((rows, 2 * C), dtype=torch.float32, device=x.device)
-        e = cat[:, :C]
-        kernels.elu_into(x, e)
-        mean = kernels.segment_colsum(e, mask_rows, per, nseg) * inv_count          # (nseg, C) * (nseg, 1)
-        kernels.bcast_rows(mean, cat[:, C:], per)
-        ctx.save_for_backward(cat, mask_rows, inv_count)
-        ctx.per, ctx.nseg = per, nseg
-        return cat
-
-    @staticmethod
-    def backward(ctx, g_cat):
-        cat, mask_rows, inv_count = ctx.saved_tensors
-        g_cat = _rows2d(g_cat)
-        C = cat.shape[1] // 2
-        gm = kernels.segment_colsum(g_cat[:, C:], None, ctx.per, ctx.nseg) * inv_count   # d/d(mean) / count
-        g_x = torch.empty((cat.shape[0], C), dtype=torch.float32, device=cat.device)
-        kernels.elu_bwd_bcast(g_cat[:, :C], cat[:, :C], gm.contiguous(), mask_rows, g_x, ctx.per)
-        return g_x, None, None, None
-
-
-class _AvgPropagateRagged(torch.autograd.Function):
-    """_AvgPropagate on a PACKED batch: cat = [e, mean_mesh(e)] with meshes of different sizes and no padding rows
-    (operators.PackedSegments; sn_segment_colsum_ragged_f32 / sn_bcast_rows_ragged_f32)."""
+    global_average (utils_pt.py:120-122) fused: ELU straight into the concat buffer, per-mesh column means in one pass (masked
+    on a padded batch), the mean broadcast written into the second half; backward folds the mean-path gradient into the ELU
+    backward.  seg: operators.MaskedSegments | PackedSegments."""
 
     @staticmethod
     def forward(ctx, x, seg):
@@ -953,7 +866,7 @@ class _AvgPropagateRagged(torch.autograd.Function):
         rows, C = x.shape
         cat = torch.empty((rows, 2 * C), dtype=torch.float32, device=x.device)
         kernels.elu_into(x, cat[:, :C])
-        kernels.bcast_rows_ragged(seg.mean(cat[:, :C]), seg.tiles, cat[:, C:])
+        seg.bcast(seg.mean(cat[:, :C]), cat[:, C:])
         ctx.seg = seg
         ctx.save_for_backward(cat)
         return cat
@@ -961,25 +874,13 @@ class _AvgPropagateRagged(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_cat):
         (cat,) = ctx.saved_tensors
-        seg = ctx.seg
         g_cat = _rows2d(g_cat)
         C = cat.shape[1] // 2
-        gm = seg.mean(g_cat[:, C:])                               # (sum over the mesh's rows of d/d(mean)) / count
-        gb = torch.empty((cat.shape[0], C), dtype=torch.float32, device=cat.device)
-        kernels.bcast_rows_ragged(gm, seg.tiles, gb)
-        g_x = torch.empty_like(gb)
-        kernels.elu_bwd(g_cat[:, :C], cat[:, :C], g_x, False, gb)      # (g_e + broadcast mean-path gradient) * elu'(e)
+        g_x = torch.empty((cat.shape[0], C), dtype=torch.float32, device=cat.device)
+        ctx.seg.elu_bwd_mean(g_cat[:, :C], g_cat[:, C:], cat[:, :C], g_x)
         return g_x, None
 
 
-def avg_propagate_ragged(x2d: torch.Tensor, seg) -> torch.Tensor:
-    """x2d: (sum V_i, C) packed rows, seg: operators.PackedSegments -> (sum V_i, 2C) [elu(x), per-mesh mean of elu(x)]."""
-    return _AvgPropagateRagged.apply(x2d, seg)
-
-
-def avg_propagate(x: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
-    """x: (B, V, C), mask: (B, V, 1) -> (B*V, 2C) concat buffer [elu(x), per-mesh masked mean of elu(x)]."""
-    B, V, C = x.shape
-    mask_rows = mask.reshape(B * V).contiguous()
-    inv_count = 1.0 / mask.reshape(B, V).sum(1, keepdim=True)
-    return _AvgPropagate.apply(x.reshape(B * V, C), mask_rows, inv_count, B)
+def avg_propagate(x2d: torch.Tensor, seg) -> torch.Tensor:
+    """x2d: (rows, C), seg: operators.MaskedSegments | PackedSegments -> (rows, 2C) concat buffer [elu(x), per-mesh mean of elu(x)]."""
+    return _AvgPropagate.apply(x2d, seg)

@@ -163,7 +163,7 @@ _active_capture = None
 def active_capture():
     """Serial number of the GraphedStep capture in progress on this thread of control, else None.  Values derived from a
     batch tensor while THAT capture records (e.g. the per-mesh 1/count of a mask) are part of its graph — recomputed by every
-    replay — and may be shared by the blocks of the same capture; they must never outlive it (blocks.avg_block)."""
+    replay — and may be shared by the blocks of the same capture; they must never outlive it (blocks._masked_segments)."""
     return _active_capture
 
 

@@ -27,7 +27,7 @@ import torch
 
 from . import constants, kernels
 
-__all__ = ["SparseOperator", "OperatorPool", "PackedSegments", "as_operator", "dirac_operators_from_mesh",
+__all__ = ["SparseOperator", "OperatorPool", "PackedSegments", "MaskedSegments", "as_operator", "dirac_operators_from_mesh",
            "laplacian_operator_from_mesh", "geodesic_matrix_from_mesh", "spgemm", "amplify_sequence_operators",
            "clean_mesh", "CleanMesh", "repair_mesh", "RepairedMesh", "vertex_descriptors", "MeshDescriptors", "vertex_normals", "face_areas", "vertex_mass",
            "gaussian_curvature", "delaunay_2d", "Delaunay2D", "arap_deform", "ArapDeformation", "laplacian_eigenpairs", "Eigenpairs",
@@ -912,6 +912,105 @@ class PackedSegments:
         if x2d.shape[0] != self.rows:
             raise ValueError(f"PackedSegments: {self.rows} rows expected, got {x2d.shape[0]}")
         return kernels.segment_colsum_ragged(x2d, self.tiles, self.seg_tile_ptr, self.nseg, self.inv_count)
+
+    # ---- the global-average stage on this layout (functional.avg_stage_forward / avg_stage_backward; MaskedSegments has the same) ----
+    stats_from_partials = True    # stage_stats starts from the statistics partials alone: the stage GEMMs always leave them
+
+    def stage_supported(self, C: int, J: int) -> bool:
+        return kernels.avg_stage_ragged_supported(C, J, self)
+
+    def stage_stats(self, e, e_tiles=None, part=None):
+        """(m, stats): per-mesh means of e and the BatchNorm statistics of [e | mean broadcast] (mesh i contributes len_i·m_i and
+        len_i·m_i²).  e_tiles: the (tile sums, partials) the GEMM that wrote e left — no pass over e at all; part: its statistics
+        partials alone — the means take one pass, the statistics none; neither: one more pass over e, handed on as one block."""
+        if e_tiles is not None:
+            return kernels.avg_stats_from_tiles_ragged(e_tiles[0], e_tiles[1], e, self)
+        m = self.mean(e).contiguous()
+        C = e.shape[1]
+        if part is not None and C == 128:
+            return m, kernels.avg_stats_ragged(m, self, part, kernels.linear_fwd_stats_blocks(e.shape[0]))
+        return m, kernels.avg_stats_ragged(m, self, kernels.colstats(e).reshape(1, 2, C), 1)
+
+    def linear_fwd_segbias(self, e, W, segb, *epilogue):
+        return kernels.linear_fwd_segbias_ragged(e, W, segb, self, *epilogue)
+
+    def wgrad(self, dy, e, center, bounds):
+        return kernels.wgrad_slabs(dy, e, center, self, bounds=bounds)
+
+    def avg_bn_bwd(self, G1, sdy, Sg, m, *layer):
+        return kernels.avg_bn_bwd(G1, sdy, Sg, m.contiguous(), *layer, self.inv_count, segoff=self.off_dev)
+
+    def bwd_segvec(self, *terms):
+        return kernels.avg_bwd_segvec_ragged(*terms, self)
+
+    def dgrad_eluseg(self, dy, W, e, center, B, Cc, segvec, gadd):
+        return kernels.linear_dgrad_eluseg_ragged(dy, W, e, center, B, Cc, segvec, self, gadd)
+
+    def bcast(self, src, dst) -> None:
+        """dst[r, :] = src[mesh(r), :]."""
+        kernels.bcast_rows_ragged(src, self.tiles, dst)
+
+    def elu_bwd_mean(self, g_e, g_m, e, g_x) -> None:
+        """g_x = (g_e + the gradient the mesh's mean receives from g_m, the gradient of its broadcast, per row) * elu'(e)."""
+        gb = torch.empty_like(g_x)
+        self.bcast(self.mean(g_m), gb)                            # (sum over the mesh's rows of d/d(mean)) / count
+        kernels.elu_bwd(g_e, e, g_x, False, gb)
+
+    def plan_view(self):
+        """(device tables, layout key): what a launch plan takes as operands / what tells two layouts apart in a plan's key."""
+        return (self.tiles, self.seg_tile_ptr, self.inv_count, self.off_dev, self.slab_off, self.seg_slab_ptr, self.len_f64), \
+            ("packed", self.nseg, self.rows, self.nslab, self.min_len, int(self.tiles.shape[0]))
+
+
+class MaskedSegments:
+    """The meshes of a PADDED batch — B meshes of V rows each, real rows marked by the reference's (B, V, 1) `mask` — with the
+    same global-average stage methods as PackedSegments: the flattened mask, 1 / vertex count per mesh and the row period."""
+
+    stats_from_partials = False   # stage_stats needs the producer's tile sums too: without them the GEMM is not asked for partials
+
+    def __init__(self, mask: torch.Tensor, B: int, V: int):
+        self.nseg, self.rows_per_seg, self.rows = B, V, B * V
+        self.mask_rows = mask.reshape(self.rows).contiguous()
+        self.inv_count = 1.0 / mask.reshape(B, V).sum(1, keepdim=True)
+
+    def mean(self, x2d: torch.Tensor) -> torch.Tensor:
+        """(nseg, C): per-mesh masked column means of the (rows, C) operand."""
+        return kernels.segment_colsum(x2d, self.mask_rows, self.rows_per_seg, self.nseg) * self.inv_count
+
+    def stage_supported(self, C: int, J: int) -> bool:
+        return kernels.avg_stage_supported(C, J, self.rows_per_seg)
+
+    def stage_stats(self, e, e_tiles=None, part=None):
+        """(m, stats) as PackedSegments.stage_stats (padding rows count in the statistics, as in the reference): from the producer's
+        tile sums and partials, else one pass over e."""
+        if e_tiles is not None:
+            return kernels.avg_stats_from_tiles(e_tiles[0], e_tiles[1], e, self.mask_rows, self.inv_count, self.rows_per_seg, self.nseg)
+        return kernels.avg_stats(e, self.mask_rows, self.inv_count, self.rows_per_seg, self.nseg)
+
+    def linear_fwd_segbias(self, e, W, segb, *epilogue):
+        return kernels.linear_fwd_segbias(e, W, segb, self.rows_per_seg, *epilogue)
+
+    def wgrad(self, dy, e, center, bounds):
+        return kernels.wgrad_seg(dy, e, center, self.rows_per_seg, bounds=bounds)
+
+    def avg_bn_bwd(self, *terms):
+        return kernels.avg_bn_bwd(*terms, self.inv_count, rows_per_seg=self.rows_per_seg)
+
+    def bwd_segvec(self, *terms):
+        return kernels.avg_bwd_segvec(*terms, self.inv_count, self.rows_per_seg)
+
+    def dgrad_eluseg(self, dy, W, e, center, B, Cc, segvec, gadd):
+        return kernels.linear_dgrad_eluseg(dy, W, e, center, B, Cc, segvec, self.rows_per_seg, self.mask_rows, gadd)
+
+    def bcast(self, src, dst) -> None:
+        kernels.bcast_rows(src, dst, self.rows_per_seg)
+
+    def elu_bwd_mean(self, g_e, g_m, e, g_x) -> None:
+        gm = kernels.segment_colsum(g_m, None, self.rows_per_seg, self.nseg) * self.inv_count      # d/d(mean) / count
+        kernels.elu_bwd_bcast(g_e, e, gm.contiguous(), self.mask_rows, g_x, self.rows_per_seg)
+
+    def plan_view(self):
+        return (self.mask_rows, self.inv_count), ("masked", self.nseg, self.rows_per_seg, self.mask_rows.dtype)
 
 
 def as_operator(A) -> SparseOperator:

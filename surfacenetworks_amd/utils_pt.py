@@ -23,7 +23,7 @@ import torch.nn.functional as F
 
 from . import blocks as snB
 from . import functional as snF
-from .operators import PackedSegments, SparseOperator, as_operator
+from .operators import MaskedSegments, PackedSegments, SparseOperator, as_operator
 from .resident import LazySparse, batch_operator, reference_cat, reference_diag_cat
 
 __all__ = [
@@ -272,25 +272,21 @@ class AvgResNet2(_TwoStage):
 
     def forward(self, L, mask, inputs):
         b, n, c = inputs.size()
-        if isinstance(mask, PackedSegments):
-            # packed batch (1, sum V_i, C): per-mesh means over ragged row ranges, no padding rows anywhere; BatchNorm then
-            # sees the real rows only (the reference's padded batch includes the padding rows, utils_pt.py:97-99)
-            if self.training and snB.avg_block_ragged_ok(self, mask, inputs):
-                return snB.avg_block_ragged(self, mask, inputs)                 # half width, one autograd node
-            x2d = inputs.reshape(b * n, c)
-            h = self.bn_fc0.forward2d(snF.avg_propagate_ragged(x2d, mask))
-            h = self.bn_fc1.forward2d(snF.avg_propagate_ragged(h, mask), residual=x2d)
-            return h.view(b, n, c)
-        if c % 4 or 256 % (c // 4) or inputs.dtype != torch.float32:        # shapes the fused kernels do not cover
+        # mask = PackedSegments: a packed batch (1, sum V_i, C): per-mesh means over ragged row ranges, no padding rows anywhere;
+        # BatchNorm then sees the real rows only (the reference's padded batch includes the padding rows, utils_pt.py:97-99)
+        packed = isinstance(mask, PackedSegments)
+        if not packed and (c % 4 or 256 % (c // 4) or inputs.dtype != torch.float32):        # shapes the fused kernels do not cover
             x = F.elu(inputs)
             x = self.bn_fc0(torch.cat([x, global_average(x, mask).expand_as(x)], 2))
             x = F.elu(x)
             x = self.bn_fc1(torch.cat([x, global_average(x, mask).expand_as(x)], 2))
             return x + inputs
-        if _blocks_ok(self, inputs):
+        if (self.training and snB.avg_block_ok(self, mask, inputs)) if packed else _blocks_ok(self, inputs):
             return snB.avg_block(self, mask, inputs)                            # the whole block as one autograd node
-        h = self.bn_fc0.forward2d(snF.avg_propagate(inputs, mask))
-        h = self.bn_fc1.forward2d(snF.avg_propagate(h.view(b, n, c), mask), residual=inputs.reshape(b * n, c))
+        seg = mask if packed else MaskedSegments(mask, b, n)
+        x2d = inputs.reshape(b * n, c)
+        h = self.bn_fc0.forward2d(snF.avg_propagate(x2d, seg))
+        h = self.bn_fc1.forward2d(snF.avg_propagate(h, seg), residual=x2d)
         return h.view(b, n, c)
 
 

@@ -67,7 +67,8 @@ Form = collections.namedtuple("Form", list(_FORM_DEFAULTS), defaults=list(_FORM_
 # tiles        blocks._TILE_SUMS_MIN_ROWS = 0: the tile-sum hand-offs exist at these sizes (they start at 32 768 rows)
 # ring_rows    kernels.RING_MIN_ROWS lowered to this (the sliding-window kernel starts at 131 072 rows)
 
-GRIDS = {"u11": [(5, 7)] * 11, "u33": [(5, 7)] * 33, "ragged": [(5, 7), (6, 7), (4, 9)] * 3, "packed": [(5, 7), (6, 7), (4, 9)] * 3}
+GRIDS = {"u11": [(5, 7)] * 11, "u33": [(5, 7)] * 33, "ragged": [(5, 7), (6, 7), (4, 9)] * 3, "packed": [(5, 7), (6, 7), (4, 9)] * 3,
+         "packed33": [(5, 7), (6, 7), (4, 9)] * 11}
 
 
 # ---- batches -------------------------------------------------------------------------------------------------------------------------
@@ -76,7 +77,7 @@ class Batch:
     sum(V_i) rows; else (B, max V_i) rows per item, a prefix mask and operators padded with empty rows / columns."""
 
     def __init__(self, name):
-        self.name, self.packed = name, name == "packed"
+        self.name, self.packed = name, name.startswith("packed")
         per = []
         for k, (n, m) in enumerate(GRIDS[name]):
             V, Fc = mesh_ops.grid_cloth(n, m, np.random.default_rng(k))

@@ -808,7 +808,7 @@ def check_packed_model(dev):
     g = torch.Generator().manual_seed(0)
     x = torch.randn(seg.rows, 128, generator=g).to(dev).requires_grad_(True)
     w = torch.randn(seg.rows, 256, generator=g).to(dev)
-    cat = snF.avg_propagate_ragged(x, seg)
+    cat = snF.avg_propagate(x, seg)
     (cat * w).sum().backward()
     xr = x.detach().clone().requires_grad_(True)
     e = F.elu(xr)

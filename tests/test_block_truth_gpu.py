@@ -180,12 +180,13 @@ AVERAGE = [
     (Case("avg1", 128, "u33"), Form(plans=True), (), ()),
     (Case("avg1", 128, "ragged"), Form(plans=True), (), ()),                      # prefix mask, padding rows in the statistics
     (Case("avg1", 128, "ragged"), Form(), (), ()),
-    (Case("avg1", 128, "packed"), Form(plans=True), (), ()),                      # PackedSegments: avg_block_ragged
+    (Case("avg1", 128, "packed"), Form(plans=True), (), ()),                      # PackedSegments in the mask's place
     (Case("avg1", 128, "packed"), Form(), (), ("sn_avg_stats_from_tiles_ragged_f32",)),
     (Case("avg1", 128, "packed"), Form(tiles=True), ("sn_avg_stats_from_tiles_ragged_f32",), ()),
     (Case("avg1", 128, "packed"), Form(plans=True, tiles=True), (), ()),
     (Case("avg1", 128, "packed", train=False), Form(), (), ()),
     (Case("avg1", 64, "packed"), Form(), (), ()),
+    (Case("avg1", 128, "packed33"), Form(), ("sn_avg_bwd_segvec_ragged_f32",), (MERGED,)),   # packed, > AVG_BWD_MERGE_MAX meshes
 ]
 
 
@@ -194,8 +195,10 @@ def test_average_blocks_equal_the_float64_blocks(case, form, launched, not_launc
     """Chain (d): one AvgResNet2.  Uniform mask (11 meshes; 33 meshes: more than kernels.AVG_BWD_MERGE_MAX, the backward's three
     separate launches), prefix mask on the padded ragged batch (5 x 7, 6 x 7 and 4 x 9 vertex grids, three of each), and the packed
     form of the same batch (PackedSegments) with and without forced tile sums — its truth is ref_blocks on the packed rows only,
-    with a per-mesh mean (block_truth.PackedAvgResNet2).  Plans on and off, train and eval, C = 64 (full width)."""
+    with a per-mesh mean (block_truth.PackedAvgResNet2) — and repeated to 33 meshes (the packed backward's three separate
+    launches).  Plans on and off, train and eval, C = 64 (full width)."""
     from surfacenetworks_amd import kernels
 
     assert bt.batch("u33").meshes > kernels.AVG_BWD_MERGE_MAX >= bt.batch("u11").meshes
+    assert bt.batch("packed33").meshes > kernels.AVG_BWD_MERGE_MAX >= bt.batch("packed").meshes
     _run(case, form, monkeypatch, launched, not_launched)

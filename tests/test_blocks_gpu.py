@@ -366,9 +366,9 @@ def test_ragged_average_block_at_half_width_matches_the_full_width_composition(l
     res = []
     for blk, half in ((blk_a, True), (blk_b, False)):
         if not half:
-            monkeypatch.setattr(snB, "avg_block_ragged_ok", lambda *a: False)
+            monkeypatch.setattr(snB, "avg_block_ok", lambda *a: False)
         else:
-            assert snB.avg_block_ragged_ok(blk, seg, x)
+            assert snB.avg_block_ok(blk, seg, x)
         xi = x.clone().requires_grad_(True)
         y = blk(None, seg, xi)
         (y * w).sum().backward()
