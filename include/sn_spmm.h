@@ -497,6 +497,47 @@ int sn_masked_smooth_l1_fwdg_f32(const float *out, int64_t ldo, const float *tar
 int sn_masked_smooth_l1_bwdg_f32(const float *out, int64_t ldo, const float *target, int64_t ldt, const float *rowmask,
                                  int64_t rows, int32_t C, double scale, const float *gloss, float *gout, int64_t ldg,
                                  void *stream);
+/* ---- Normal prediction ----------------------------------------------------------------------------------------------------
+ * Squared-cosine loss, mean angle deviation and the loss gradient of the normal-prediction driver in one pass over the rows.
+ * Replaces: src/normal_predict/train_4_normal.py:113-123 (loss_fun, mean_angle_deviation: F.normalize, the inner product,
+ * masked_select and mean, each twice, and their backward passes).  Per row r, all fp32:
+ *   o = y[r, 0:3] (+ frame[r, 0:3] if a frame is given)
+ *   n = max(sqrt(o·o), 1e-12)        u = o / n          c = u·t[r]
+ *   l = 1 - c·c                      a = acos(min(|c|, 1))
+ *   S = { r : rowmask[r] != 0 }   (rowmask NULL: all rows)
+ *   loss = sum_S l / |S|           mad = sum_S a / |S|       (fp64 sums, a fixed order: the same bits every run)
+ *   g[r] = (gloss/|S|) · (-2c) · (t - c·u) / n      for r in S with sqrt(o·o) >= 1e-12
+ *   g[r] = (gloss/|S|) · (-2c) · t / 1e-12          for r in S below that
+ *   g[r] = 0 exactly                                 for r outside S
+ * A row outside S is never read: NaN there reaches neither the sums nor g (torch autograd turns 0 · NaN into NaN).  |S| = 0:
+ * loss and mad are NaN, as torch's empty mean, and g is all zero.
+ * y and g: rows of 3 floats with a pitch (ldy, ldg) of 3 or 4 floats (SN_E_SHAPE otherwise); a pitch-4 operand that is 16-byte
+ * aligned moves as one 16-byte word per row — the fourth float of EVERY row must be addressable.  The fourth column of a
+ * pitch-4 g is written 0, 16-byte aligned or not.  target: (rows, 3), ldt >= 3.  frame: NULL or a (rows, 3) view, ldf >= 3.  All 4-byte aligned (SN_E_ALIGN).
+ * out: 3 floats on the device — loss, mad and |S| (the number the gradient entries divide by).
+ *   sn_normal_cosine_fwd_f32   loss and mad only (evaluation).
+ *   sn_normal_cosine_fwdg_f32  the same sums in the same order — the same bits — and g for gloss == 1.  g needs 1/|S| before
+ *                   its first row is stored, so with a rowmask |S| is counted by a small launch AHEAD of the pass (4 bytes per
+ *                   row); without one it is `rows`.
+ *   sn_normal_cosine_bwd_f32   g for the DEVICE scalar gloss from the operands again; count = out + 2 of a forward call.
+ *   sn_normal_cosine_bwdg_f32  the same over a g that sn_normal_cosine_fwdg_f32 filled for the same operands: kept when
+ *                   gloss[0] == 1 (tested on the device), recomputed otherwise; the same bits as sn_normal_cosine_bwd_f32.
+ * No atomics, no memset, nothing that synchronises: every entry can be captured into a hipGraph.
+ * sn_normal_cosine_grid_rows: the rows one sweep of the forward grid covers (more rows: every thread walks on). */
+int64_t sn_normal_cosine_grid_rows(void);
+size_t sn_normal_cosine_workspace_bytes(int64_t rows);
+int sn_normal_cosine_fwd_f32(const float *y, int64_t ldy, const float *frame, int64_t ldf, const float *target, int64_t ldt,
+                             const float *rowmask, int64_t rows, float *out, void *workspace, size_t workspace_bytes,
+                             void *stream);
+int sn_normal_cosine_fwdg_f32(const float *y, int64_t ldy, const float *frame, int64_t ldf, const float *target, int64_t ldt,
+                              const float *rowmask, int64_t rows, float *out, float *gout, int64_t ldg, void *workspace,
+                              size_t workspace_bytes, void *stream);
+int sn_normal_cosine_bwd_f32(const float *y, int64_t ldy, const float *frame, int64_t ldf, const float *target, int64_t ldt,
+                             const float *rowmask, int64_t rows, const float *count, const float *gloss, float *gout,
+                             int64_t ldg, void *stream);
+int sn_normal_cosine_bwdg_f32(const float *y, int64_t ldy, const float *frame, int64_t ldf, const float *target, int64_t ldt,
+                              const float *rowmask, int64_t rows, const float *count, const float *gloss, float *gout,
+                              int64_t ldg, void *stream);
 /* sn_gather_segments_f32: batch assembly of dense per-sample windows (the ARAP sampler's inputs / targets,
  * src/as_rigid_as_possible/main.py:126-152): out[(i*rows_per_item + r)*len + c] = src[base[i] + r*row_stride + c],
  * i < nitems, r < rows_per_item, c < len; base is a DEVICE array of element offsets into the resident dataset. */

@@ -100,6 +100,12 @@ SIGNATURES = {
     "sn_masked_smooth_l1_bwd_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, C.c_double, _vp, _vp, _i64, _vp]),
     "sn_masked_smooth_l1_fwdg_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, C.c_double, _vp, _vp, _i64, _vp, _sz, _vp]),
     "sn_masked_smooth_l1_bwdg_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, C.c_double, _vp, _vp, _i64, _vp]),
+    "sn_normal_cosine_grid_rows": (_i64, []),
+    "sn_normal_cosine_workspace_bytes": (_sz, [_i64]),
+    "sn_normal_cosine_fwd_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "sn_normal_cosine_fwdg_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _sz, _vp]),
+    "sn_normal_cosine_bwd_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "sn_normal_cosine_bwdg_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "sn_pair_argmin_f32": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
     "sn_pair_ce_fwd_f32": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
     "sn_pair_ce_bwd_f32": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp]),

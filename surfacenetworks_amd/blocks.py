@@ -24,8 +24,8 @@ import torch
 
 from . import kernels, plans
 from .functional import (SpmmTimer, _launch, _rows2d, product_form, avg_stage_backward, avg_stage_forward, bn_prepare, bnlin_backward,
-                         bnlin_backward_elu_input, bnlin_backward_zero_first, bnlin_forward, bnlin_forward_zero_first, stash, unstash,
-                         zero_first_supported)
+                         bnlin_backward_elu_input, bnlin_backward_zero_first, bnlin_forward, bnlin_forward_zero_first, padded_linear_params, stash,
+                         unstash, zero_first_supported)
 from .graphs import active_capture
 from .operators import MaskedSegments, PackedSegments, as_operator
 
@@ -712,9 +712,13 @@ def _unwritten(t: torch.Tensor) -> bool:
     return t.numel() > 1 and not any(t.stride())
 
 
-def elu_conv(conv, v, frame=None):
+def elu_conv(conv, v, frame=None, pad_to: int = 0):
     """conv(F.elu(v)) for a GraphConv1x1 with batch_norm="pre" on a (B, N, C) tensor, as one autograd node.
-    frame ((B, N, 3), elu_conv_frame_ok): y[..., 3t + c] += frame[..., c] in the GEMM's store."""
+    frame ((B, N, 3), elu_conv_frame_ok): y[..., 3t + c] += frame[..., c] in the GEMM's store.
+    pad_to (J > conv.num_outputs; without a frame): for a layer with fewer outputs than the Linear kernels take (they want a
+    multiple of 4: normal_predict's 128 -> 3 head) the node runs a J-output layer whose rows num_outputs .. J-1 of W and b are a
+    zero pad made INSIDE autograd (functional.padded_linear_params) — the pad's backward drops its gradient rows, the real rows get
+    theirs, conv.fc keeps its shape.  Returns (B, N, J); the columns past num_outputs are the pad's exact zeros."""
     B, N, C = v.shape
     rows = B * N
     pre = take_activated(v, rows, C)
@@ -723,8 +727,15 @@ def elu_conv(conv, v, frame=None):
                            "activated hand-off that stands for them is gone (taken by another consumer, or the tensor was copied)")
     if frame is not None:
         frame = frame.detach().reshape(rows, 3)
-    y = _EluConv.apply(v.reshape(rows, C), pre, frame, *_bn_args(conv))
-    return y.view(B, N, conv.num_outputs)
+    g0, b0, W0, c0, rm0, rv0, tr0, mo0, ep0 = _bn_args(conv)
+    J = conv.num_outputs
+    if pad_to:
+        if frame is not None or pad_to < J:
+            raise ValueError("elu_conv: pad_to is at least the layer's width and goes without a frame")
+        J = int(pad_to)
+        W0, c0 = padded_linear_params(W0, c0, J)
+    y = _EluConv.apply(v.reshape(rows, C), pre, frame, g0, b0, W0, c0, rm0, rv0, tr0, mo0, ep0)
+    return y.view(B, N, J)
 
 
 def elu_conv_frame_ok(conv, v, frame) -> bool:

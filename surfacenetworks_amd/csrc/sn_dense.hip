@@ -7,7 +7,7 @@
 //                                   WgradBf3 (three bf16 pieces) and WgradHalf2 (two scaled fp16 pieces)
 //   affine_cols_acc_k               dx += x*B[c] + C[c]  (tail of the BatchNorm backward)
 //   ... and, each under its own banner below: BatchNorm fold and backward coefficients, the thin Linear layers, segment sums,
-//   global average, masked smooth-L1, segment gathers, and the losses on a MATERIALISED score matrix (pair_argmin*, pair_ce_*).
+//   global average, masked smooth-L1, the squared-cosine loss of normal prediction, segment gathers, and the losses on a MATERIALISED score matrix (pair_argmin*, pair_ce_*).
 //   The pair losses computed from the features, without the score matrix, are in sn_pair.hip.
 //
 // Interfaces and the reference code they replace: include/sn_spmm.h.
@@ -992,6 +992,181 @@ __global__ __launch_bounds__(kWG) void masked_sl1_fwdg_k(const float *__restrict
     __syncthreads();
   }
   if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+
+// ------------------------------------------------------------------------------------------------
+// Normal prediction: squared-cosine loss and mean angle deviation (src/normal_predict/train_4_normal.py:113-123), the
+// definition in include/sn_spmm.h ("Normal prediction").  One thread per row: 12 or 16 bytes of y, 12 of t, 4 of the mask,
+// 12 of the frame in, 12 or 16 bytes of g out.  Per workgroup three fp64 sums (loss, angle, rows counted) in the layout
+// partial[q * kLossBlocks + block]; normal_cos_final_k adds them in block order.  A row outside the mask is never loaded.
+//   fp32 roundings of a row, in order (the tests count them): o = y + frame 1 per component; ss 3 (product, two fma);
+//   sqrt 1; u = o / n 1 per component; c 3 (product, two fma); l = fma(-c, c, 1) 1.  Gradient: k = gloss * (1 / |S|) 2 (3 past
+//   2^24 rows); q = k * (-2c) 1; coef = q / n 1; d = fma(-c, u, t) 1 per component; g = coef * d 1 per component.
+// The gradient needs 1 / |S| before the first row is stored, so |S| cannot come from the sums of the same launch: with a mask
+// mask_count_k counts it ahead of the pass (4 bytes per row, at most kCountBlocks int64 partials, added by every thread of
+// the pass in block order); without one it is the row count, a launch argument.
+// ------------------------------------------------------------------------------------------------
+constexpr int kCountBlocks = 64;
+constexpr float kCosEps = 1e-12f;        // F.normalize's eps (train_4_normal.py:114)
+
+__global__ __launch_bounds__(kWG) void mask_count_k(const float *__restrict__ mask, int64_t rows, int64_t *__restrict__ cpart) {
+  __shared__ int red[kWG];
+  int n = 0;                               // (a thread sees at most rows / kWG / gridDim.x + 1 rows)
+  for (int64_t r = (int64_t)blockIdx.x * kWG + threadIdx.x; r < rows; r += (int64_t)gridDim.x * kWG) n += mask[r] != 0.f;
+  red[threadIdx.x] = n;
+  __syncthreads();
+  for (int s = kWG / 2; s > 0; s >>= 1) {
+    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) cpart[blockIdx.x] = red[0];
+}
+
+struct CosRow {
+  float ux, uy, uz, tx, ty, tz, c, n;
+  bool tiny;                               // sqrt(o·o) < eps: u = o / eps, the clamp has no derivative in o
+};
+
+template <bool V4>
+__device__ __forceinline__ CosRow cos_row(const float *__restrict__ y, int64_t ldy, const float *__restrict__ frame, int64_t ldf,
+                                          const float *__restrict__ t, int64_t ldt, int64_t r) {
+  float ox, oy, oz;
+  if constexpr (V4) {
+    const f4 v = ld4_s(y + r * 4, 1);
+    ox = v.x, oy = v.y, oz = v.z;
+  } else {
+    const float *p = y + r * ldy;
+    ox = p[0], oy = p[1], oz = p[2];
+  }
+  if (frame) {
+    const float *p = frame + r * ldf;
+    ox = __fadd_rn(ox, p[0]), oy = __fadd_rn(oy, p[1]), oz = __fadd_rn(oz, p[2]);
+  }
+  CosRow w;
+  const float *q = t + r * ldt;
+  w.tx = q[0], w.ty = q[1], w.tz = q[2];
+  const float nrm = __fsqrt_rn(fmaf(oz, oz, fmaf(oy, oy, __fmul_rn(ox, ox))));
+  w.tiny = nrm < kCosEps;
+  w.n = w.tiny ? kCosEps : nrm;            // (a NaN norm stays NaN, as torch's clamp_min leaves it)
+  w.ux = __fdiv_rn(ox, w.n), w.uy = __fdiv_rn(oy, w.n), w.uz = __fdiv_rn(oz, w.n);
+  w.c = fmaf(w.uz, w.tz, fmaf(w.uy, w.ty, __fmul_rn(w.ux, w.tx)));
+  return w;
+}
+
+// g of one row of S: coef * (t - c u) with coef = k (-2c) / n; below the clamp coef * t
+template <bool V4>
+__device__ __forceinline__ void cos_store_grad(const CosRow &w, float k, float *__restrict__ g, int64_t ldg, int64_t r) {
+  const float coef = __fdiv_rn(__fmul_rn(k, -2.f * w.c), w.n);
+  float gx, gy, gz;
+  if (w.tiny) {
+    gx = __fmul_rn(coef, w.tx), gy = __fmul_rn(coef, w.ty), gz = __fmul_rn(coef, w.tz);
+  } else {
+    gx = __fmul_rn(coef, fmaf(-w.c, w.ux, w.tx)), gy = __fmul_rn(coef, fmaf(-w.c, w.uy, w.ty)), gz = __fmul_rn(coef, fmaf(-w.c, w.uz, w.tz));
+  }
+  if constexpr (V4) {
+    st4_s(g + r * 4, f4{gx, gy, gz, 0.f}, 1);
+  } else {
+    float *p = g + r * ldg;
+    p[0] = gx, p[1] = gy, p[2] = gz;
+    if (ldg == 4) p[3] = 0.f;              // (a pitch-4 g off the 16-byte grid: the fourth column is written all the same)
+  }
+}
+
+template <bool V4>
+__device__ __forceinline__ void cos_store_zero(float *__restrict__ g, int64_t ldg, int64_t r) {
+  if constexpr (V4) {
+    st4_s(g + r * 4, f4{0.f, 0.f, 0.f, 0.f}, 1);
+  } else {
+    float *p = g + r * ldg;
+    p[0] = 0.f, p[1] = 0.f, p[2] = 0.f;
+    if (ldg == 4) p[3] = 0.f;
+  }
+}
+
+// |S| as the gradient kernels take it: the partials of mask_count_k (ncount of them) or, without a mask, the row count
+__device__ __forceinline__ float cos_count(const int64_t *__restrict__ cpart, int ncount, int64_t rows) {
+  if (!cpart) return (float)rows;
+  int64_t n = 0;
+  for (int b = 0; b < ncount; ++b) n += cpart[b];
+  return (float)n;
+}
+
+// YV4: y has pitch 4 and takes 16-byte loads.  GRAD: also g for gloss == 1 (GV4: g has pitch 4 and takes 16-byte stores; the
+// fourth column of a pitch-4 g is written 0 either way).
+template <bool YV4, bool GRAD, bool GV4>
+__global__ __launch_bounds__(kWG) void normal_cos_fwd_k(const float *__restrict__ y, int64_t ldy, const float *__restrict__ frame,
+                                                        int64_t ldf, const float *__restrict__ t, int64_t ldt,
+                                                        const float *__restrict__ mask, int64_t rows,
+                                                        const int64_t *__restrict__ cpart, int ncount,
+                                                        double *__restrict__ partial, float *__restrict__ g, int64_t ldg) {
+  __shared__ double red[3][kWG];
+  float k = 0.f;
+  if constexpr (GRAD) k = __fdiv_rn(1.0f, cos_count(cpart, ncount, rows));
+  double sl = 0, sa = 0, sn = 0;
+  for (int64_t r = (int64_t)blockIdx.x * kWG + threadIdx.x; r < rows; r += (int64_t)gridDim.x * kWG) {
+    if (mask && mask[r] == 0.f) {
+      if constexpr (GRAD) cos_store_zero<GV4>(g, ldg, r);
+      continue;
+    }
+    const CosRow w = cos_row<YV4>(y, ldy, frame, ldf, t, ldt, r);
+    float ac = fabsf(w.c);
+    ac = ac > 1.f ? 1.f : ac;              // (NaN stays NaN, as torch.clamp)
+    sl += (double)fmaf(-w.c, w.c, 1.f);
+    sa += (double)acosf(ac);
+    sn += 1.0;
+    if constexpr (GRAD) cos_store_grad<GV4>(w, k, g, ldg, r);
+  }
+  red[0][threadIdx.x] = sl, red[1][threadIdx.x] = sa, red[2][threadIdx.x] = sn;
+  __syncthreads();
+  for (int s = kWG / 2; s > 0; s >>= 1) {
+    if (threadIdx.x < s) {
+      red[0][threadIdx.x] += red[0][threadIdx.x + s];
+      red[1][threadIdx.x] += red[1][threadIdx.x + s];
+      red[2][threadIdx.x] += red[2][threadIdx.x + s];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < 3) partial[(int64_t)threadIdx.x * kLossBlocks + blockIdx.x] = red[threadIdx.x][0];
+}
+
+// out[0] = loss, out[1] = mean angle deviation, out[2] = |S| (the value the gradient kernels divide by); an empty S: NaN, NaN, 0
+__global__ __launch_bounds__(kWG) void normal_cos_final_k(const double *__restrict__ partial, int nblk, float *__restrict__ out) {
+  __shared__ double red[3][kWG];
+  double a[3] = {0, 0, 0};
+  for (int i = threadIdx.x; i < nblk; i += kWG)
+    for (int q = 0; q < 3; ++q) a[q] += partial[(int64_t)q * kLossBlocks + i];
+  for (int q = 0; q < 3; ++q) red[q][threadIdx.x] = a[q];
+  __syncthreads();
+  for (int s = kWG / 2; s > 0; s >>= 1) {
+    if (threadIdx.x < s)
+      for (int q = 0; q < 3; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    out[0] = (float)(red[0][0] / red[2][0]);
+    out[1] = (float)(red[1][0] / red[2][0]);
+    out[2] = (float)red[2][0];
+  }
+}
+
+// g for any gloss, from the operands again (count = out[2] of the forward).  SKIP1: g holds what normal_cos_fwd_k<.., true, ..>
+// wrote for gloss == 1 with this kernel's own expression — 1·(1/|S|) is 1/|S| exactly —: the launch is then over after one load.
+template <bool YV4, bool GV4, bool SKIP1>
+__global__ __launch_bounds__(kWG) void normal_cos_bwd_k(const float *__restrict__ y, int64_t ldy, const float *__restrict__ frame,
+                                                        int64_t ldf, const float *__restrict__ t, int64_t ldt,
+                                                        const float *__restrict__ mask, int64_t rows,
+                                                        const float *__restrict__ count, const float *__restrict__ gloss,
+                                                        float *__restrict__ g, int64_t ldg) {
+  if constexpr (SKIP1)
+    if (gloss[0] == 1.0f) return;
+  const float k = __fmul_rn(gloss[0], __fdiv_rn(1.0f, count[0]));
+  for (int64_t r = (int64_t)blockIdx.x * kWG + threadIdx.x; r < rows; r += (int64_t)gridDim.x * kWG) {
+    if (mask && mask[r] == 0.f) {
+      cos_store_zero<GV4>(g, ldg, r);
+      continue;
+    }
+    cos_store_grad<GV4>(cos_row<YV4>(y, ldy, frame, ldf, t, ldt, r), k, g, ldg, r);
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2735,6 +2910,129 @@ int sn_masked_smooth_l1_bwdg_f32(const float *out, int64_t ldo, const float *tar
                                  int64_t rows, int32_t C, double scale, const float *gloss, float *gout, int64_t ldg,
                                  void *stream) {
   return masked_sl1_bwd_launch(out, ldo, target, ldt, rowmask, rows, C, scale, gloss, gout, ldg, true, stream);
+}
+
+// ---- normal prediction: squared-cosine loss, mean angle deviation, gradient -----------------------------------------------
+int64_t sn_normal_cosine_grid_rows(void) { return (int64_t)kLossBlocks * kWG; }
+
+size_t sn_normal_cosine_workspace_bytes(int64_t rows) {
+  (void)rows;
+  return (size_t)3 * kLossBlocks * sizeof(double) + (size_t)kCountBlocks * sizeof(int64_t);
+}
+
+static int normal_cos_check(const float *y, int64_t ldy, const float *frame, int64_t ldf, const float *t, int64_t ldt,
+                            int64_t rows) {
+  if (rows < 0 || (ldy != 3 && ldy != 4) || ldt < 3 || (frame && ldf < 3)) return SN_E_SHAPE;
+  if (rows == 0) return SN_OK;
+  if (!y || !t) return SN_E_NULL;
+  if ((reinterpret_cast<uintptr_t>(y) & 3u) || (reinterpret_cast<uintptr_t>(t) & 3u) || (reinterpret_cast<uintptr_t>(frame) & 3u))
+    return SN_E_ALIGN;
+  return SN_OK;
+}
+
+static int normal_cos_forward(const float *y, int64_t ldy, const float *frame, int64_t ldf, const float *t, int64_t ldt,
+                              const float *mask, int64_t rows, float *out, float *g, int64_t ldg, bool grad, void *workspace,
+                              size_t workspace_bytes, void *stream) {
+  (void)hipGetLastError();      // a stale error left by an earlier runtime call of this thread is not ours to report
+  const int st = normal_cos_check(y, ldy, frame, ldf, t, ldt, rows);
+  if (st != SN_OK) return st;
+  if (grad && ldg != 3 && ldg != 4) return SN_E_SHAPE;
+  if (!out || !workspace || (grad && rows > 0 && !g)) return SN_E_NULL;
+  if (grad && (reinterpret_cast<uintptr_t>(g) & 3u)) return SN_E_ALIGN;
+  if (workspace_bytes < sn_normal_cosine_workspace_bytes(rows)) return SN_E_WORKSPACE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  double *partial = static_cast<double *>(workspace);
+  int64_t *cpart = reinterpret_cast<int64_t *>(partial + 3 * kLossBlocks);
+  if (rows == 0) {                                           // (the mean of nothing: NaN, NaN, 0)
+    hipLaunchKernelGGL(normal_cos_final_k, dim3(1), dim3(kWG), 0, s, partial, 0, out);
+    return launch_status();
+  }
+  const int nblk = loss_blocks(rows);
+  const bool yv = ldy == 4 && aligned16(y), gv = grad && ldg == 4 && aligned16(g);
+  int ncount = 0;
+  if (grad && mask) {
+    ncount = (int)((rows + 16 * kWG - 1) / (16 * kWG));
+    if (ncount > kCountBlocks) ncount = kCountBlocks;
+    hipLaunchKernelGGL(mask_count_k, dim3(ncount), dim3(kWG), 0, s, mask, rows, cpart);
+  }
+#define SN_COS_FWD(Y_, G_, GV_)                                                                                             \
+  hipLaunchKernelGGL((normal_cos_fwd_k<Y_, G_, GV_>), dim3(nblk), dim3(kWG), 0, s, y, ldy, frame, ldf, t, ldt, mask, rows, \
+                     (grad && mask) ? cpart : (const int64_t *)nullptr, ncount, partial, g, ldg)
+  if (!grad) {
+    if (yv) SN_COS_FWD(true, false, false);
+    else SN_COS_FWD(false, false, false);
+  } else if (yv) {
+    if (gv) SN_COS_FWD(true, true, true);
+    else SN_COS_FWD(true, true, false);
+  } else {
+    if (gv) SN_COS_FWD(false, true, true);
+    else SN_COS_FWD(false, true, false);
+  }
+#undef SN_COS_FWD
+  hipLaunchKernelGGL(normal_cos_final_k, dim3(1), dim3(kWG), 0, s, partial, nblk, out);
+  return launch_status();
+}
+
+int sn_normal_cosine_fwd_f32(const float *y, int64_t ldy, const float *frame, int64_t ldf, const float *target, int64_t ldt,
+                             const float *rowmask, int64_t rows, float *out, void *workspace, size_t workspace_bytes,
+                             void *stream) {
+  return normal_cos_forward(y, ldy, frame, ldf, target, ldt, rowmask, rows, out, nullptr, 0, false, workspace, workspace_bytes,
+                            stream);
+}
+
+int sn_normal_cosine_fwdg_f32(const float *y, int64_t ldy, const float *frame, int64_t ldf, const float *target, int64_t ldt,
+                              const float *rowmask, int64_t rows, float *out, float *gout, int64_t ldg, void *workspace,
+                              size_t workspace_bytes, void *stream) {
+  return normal_cos_forward(y, ldy, frame, ldf, target, ldt, rowmask, rows, out, gout, ldg, true, workspace, workspace_bytes,
+                            stream);
+}
+
+static int normal_cos_bwd_launch(const float *y, int64_t ldy, const float *frame, int64_t ldf, const float *t, int64_t ldt,
+                                 const float *mask, int64_t rows, const float *count, const float *gloss, float *g, int64_t ldg,
+                                 bool skip1, void *stream) {
+  (void)hipGetLastError();      // a stale error left by an earlier runtime call of this thread is not ours to report
+  const int st = normal_cos_check(y, ldy, frame, ldf, t, ldt, rows);
+  if (st != SN_OK) return st;
+  if (ldg != 3 && ldg != 4) return SN_E_SHAPE;
+  if (rows == 0) return SN_OK;
+  if (!count || !gloss || !g) return SN_E_NULL;
+  if (reinterpret_cast<uintptr_t>(g) & 3u) return SN_E_ALIGN;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool yv = ldy == 4 && aligned16(y), gv = ldg == 4 && aligned16(g);
+  int64_t blocks = (rows + kWG - 1) / kWG;
+  if (blocks > 16 * 1024) blocks = 16 * 1024;
+#define SN_COS_BWD(Y_, GV_)                                                                                                  \
+  do {                                                                                                                       \
+    if (skip1)                                                                                                               \
+      hipLaunchKernelGGL((normal_cos_bwd_k<Y_, GV_, true>), dim3((unsigned)blocks), dim3(kWG), 0, s, y, ldy, frame, ldf, t, \
+                         ldt, mask, rows, count, gloss, g, ldg);                                                             \
+    else                                                                                                                     \
+      hipLaunchKernelGGL((normal_cos_bwd_k<Y_, GV_, false>), dim3((unsigned)blocks), dim3(kWG), 0, s, y, ldy, frame, ldf, t, \
+                         ldt, mask, rows, count, gloss, g, ldg);                                                             \
+  } while (0)
+  if (yv) {
+    if (gv) SN_COS_BWD(true, true);
+    else SN_COS_BWD(true, false);
+  } else {
+    if (gv) SN_COS_BWD(false, true);
+    else SN_COS_BWD(false, false);
+  }
+#undef SN_COS_BWD
+  return launch_status();
+}
+
+int sn_normal_cosine_bwd_f32(const float *y, int64_t ldy, const float *frame, int64_t ldf, const float *target, int64_t ldt,
+                             const float *rowmask, int64_t rows, const float *count, const float *gloss, float *gout,
+                             int64_t ldg, void *stream) {
+  return normal_cos_bwd_launch(y, ldy, frame, ldf, target, ldt, rowmask, rows, count, gloss, gout, ldg, false, stream);
+}
+
+// gout holds what sn_normal_cosine_fwdg_f32 left for the same operands: kept when gloss[0] == 1 (tested on the device: gloss
+// may be a captured graph's scalar), recomputed as sn_normal_cosine_bwd_f32 otherwise
+int sn_normal_cosine_bwdg_f32(const float *y, int64_t ldy, const float *frame, int64_t ldf, const float *target, int64_t ldt,
+                              const float *rowmask, int64_t rows, const float *count, const float *gloss, float *gout,
+                              int64_t ldg, void *stream) {
+  return normal_cos_bwd_launch(y, ldy, frame, ldf, target, ldt, rowmask, rows, count, gloss, gout, ldg, true, stream);
 }
 
 int sn_gather_segments_f32(const float *src, const int64_t *base, int64_t nitems, int64_t rows_per_item, int64_t row_stride,

@@ -812,6 +812,25 @@ def bn_linear(x2d: torch.Tensor, bn: torch.nn.BatchNorm1d, fc: torch.nn.Linear, 
                            momentum, eps, residual)
 
 
+def padded_linear_params(W: torch.Tensor, b, J: int):
+    """(W, b) of a Linear with fewer than J outputs extended to J by zero rows, as differentiable functions of the parameters:
+    the pad's backward drops the gradient rows of the padding and hands the real rows theirs."""
+    extra = J - W.shape[0]
+    if extra < 0:
+        raise ValueError(f"padded_linear_params: the layer has {W.shape[0]} outputs, more than {J}")
+    if extra == 0:
+        return W, b
+    return torch.nn.functional.pad(W, (0, 0, 0, extra)), (torch.nn.functional.pad(b, (0, extra)) if b is not None else None)
+
+
+def bn_linear_padded(x2d: torch.Tensor, bn: torch.nn.BatchNorm1d, fc: torch.nn.Linear, J: int) -> torch.Tensor:
+    """bn_linear for a layer with fewer outputs than the Linear kernels take, run as a J-output layer (padded_linear_params):
+    (rows, J), the columns past fc.out_features the pad's exact zeros."""
+    training, momentum, eps = bn_prepare(bn)
+    W, b = padded_linear_params(fc.weight, fc.bias, J)
+    return _BNLinear.apply(x2d, bn.weight, bn.bias, W, b, bn.running_mean, bn.running_var, training, momentum, eps, None)
+
+
 class _ThinLinear(torch.autograd.Function):
     """nn.Linear with a handful of input channels on (rows, Cin <= 8) — the models' first layer,
     GraphConv1x1(6 | 3, C, batch_norm=None) (src/utils/utils_pt.py:99).  Forward: one output-streaming kernel that can also

@@ -23,6 +23,8 @@ __all__ = [
     "avg_stage_supported", "avg_fwd_prep", "avg_stats", "seg_affine", "avg_bwd_gc", "avg_bwd_segvec", "linear_fwd_segbias", "linear_dgrad_eluseg", "wgrad_seg", "wgrad_slabs", "avg_bwd_segvec_ragged", "linear_fwd_segbias_ragged", "linear_dgrad_eluseg_ragged", "avg_stage_ragged_supported", "wgrad_thin", "wgrad_thin_supported", "linear_thin_fwd", "masked_smooth_l1_fwd", "masked_smooth_l1_bwd", "gather_segments", "pair_argmin", "pair_ce_fwd", "pair_ce_bwd", "pair_fused_fwd", "pair_fused_bwd", "colstats_partial", "linear_fwd_stats_blocks", "elu_stats_supported", "new_elu_stats_part", "colstats_halves", "colstats_into", "colstats_from_part", "colstats_merge_into",
     "avg_merged_supported", "avg_stats_ragged", "avg_stats_from_tiles_ragged", "gather_segments_ragged",
 ]
+# (the list above is also what the tests' host twin of this module replaces, name by name.  Launchers that have no host twin —
+#  normal_cosine_*: normal_predict computes CPU tensors with its plain-torch reference functions — stay off it.)
 
 
 def _dev(*tensors) -> None:
@@ -2201,6 +2203,83 @@ def masked_smooth_l1_bwdg(out2d, target2d, rowmask, scale: float, gloss, g):
         raise ValueError("masked_smooth_l1_bwdg: g must be the contiguous (rows, C) float32 buffer of masked_smooth_l1_fwdg")
     _lib.call("sn_masked_smooth_l1_bwdg_f32", _p(out2d), _ld(out2d), _p(target2d), _ld(target2d), _p(rowmask), rows, C,
               float(scale), _p(gloss), _p(g), C, _stream())
+    return g
+
+
+def _cos_rows(y2d, target2d, rowmask, frame2d, what: str):
+    """Operand checks shared by the normal_cosine_* launchers: (rows, ldy, ldt, ldf).  y2d: (rows, 3) with a row pitch of 3 or 4
+    floats, or a contiguous (rows, 4) buffer whose first three columns are the operand (pitch 4 whatever the row count)."""
+    _dev(y2d, target2d, rowmask, frame2d)
+    for t in (y2d, target2d, rowmask, frame2d):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError(f"{what}: float32 operands expected")
+    if y2d.dim() != 2 or y2d.shape[1] not in (3, 4) or (y2d.shape[1] == 4 and not y2d.is_contiguous()):
+        raise ValueError(f"{what}: y is (rows, 3) or a contiguous (rows, 4) buffer, got {tuple(y2d.shape)} stride {y2d.stride()}")
+    rows = y2d.shape[0]
+    if tuple(target2d.shape) != (rows, 3) or (frame2d is not None and tuple(frame2d.shape) != (rows, 3)):
+        raise ValueError(f"{what}: target and frame are (rows, 3) for y {tuple(y2d.shape)}")
+    if rowmask is not None and (rowmask.numel() != rows or not rowmask.is_contiguous()):
+        raise ValueError(f"{what}: rowmask must hold one contiguous float per row")
+    ldy = 4 if y2d.shape[1] == 4 else _ld(y2d)
+    if ldy not in (3, 4):
+        raise ValueError(f"{what}: a row pitch of 3 or 4 floats expected, got {ldy}")
+    if ldy == 4 and rows and (y2d.storage_offset() + 4 * rows) * 4 > y2d.untyped_storage().nbytes():
+        raise ValueError(f"{what}: the fourth float of the last pitch-4 row lies outside the tensor's storage")
+    return rows, ldy, _ld(target2d), (_ld(frame2d) if frame2d is not None else 0)
+
+
+def normal_cosine_grid_rows() -> int:
+    """Rows one sweep of the loss grid covers (sn_normal_cosine_grid_rows): past it every thread takes more than one row."""
+    return int(_lib.load().sn_normal_cosine_grid_rows())
+
+
+def normal_cosine_fwd(y2d, target2d, rowmask=None, frame2d=None):
+    """float32[3] on the device: squared-cosine loss, mean angle deviation and |S| of the rows rowmask selects (None: all) —
+    sn_normal_cosine_fwd_f32, the definition in include/sn_spmm.h ("Normal prediction")."""
+    rows, ldy, ldt, ldf = _cos_rows(y2d, target2d, rowmask, frame2d, "normal_cosine_fwd")
+    out = torch.empty(3, dtype=torch.float32, device=y2d.device)
+    ws, ws_bytes = _workspace("sn_normal_cosine_workspace_bytes", y2d.device, rows, least=0)
+    _lib.call("sn_normal_cosine_fwd_f32", _p(y2d), ldy, _p(frame2d), ldf, _p(target2d), ldt, _p(rowmask), rows, _p(out), _p(ws),
+              ws_bytes, _stream())
+    return out
+
+
+def normal_cosine_fwdg(y2d, target2d, rowmask=None, frame2d=None, pitch: int = 0):
+    """(out, g): normal_cosine_fwd's three numbers — the same bits — and, from the same pass, the gradient of the loss w.r.t. y for
+    gloss == 1 (sn_normal_cosine_fwdg_f32).  g: a fresh contiguous (rows, pitch) buffer, pitch 3 or 4 (0: that of y2d); the fourth
+    column of a pitch-4 buffer is written 0.  normal_cosine_bwd(..., g=g) finishes it for any gloss."""
+    rows, ldy, ldt, ldf = _cos_rows(y2d, target2d, rowmask, frame2d, "normal_cosine_fwdg")
+    pitch = pitch or ldy
+    if pitch not in (3, 4):
+        raise ValueError("normal_cosine_fwdg: pitch 3 or 4")
+    out = torch.empty(3, dtype=torch.float32, device=y2d.device)
+    g = torch.empty((rows, pitch), dtype=torch.float32, device=y2d.device)
+    ws, ws_bytes = _workspace("sn_normal_cosine_workspace_bytes", y2d.device, rows, least=0)
+    _lib.call("sn_normal_cosine_fwdg_f32", _p(y2d), ldy, _p(frame2d), ldf, _p(target2d), ldt, _p(rowmask), rows, _p(out), _p(g),
+              pitch, _p(ws), ws_bytes, _stream())
+    return out, g
+
+
+def normal_cosine_bwd(y2d, target2d, rowmask, frame2d, out, gloss, g=None, pitch: int = 0):
+    """Gradient of the loss w.r.t. y times the device scalar gloss, a contiguous (rows, pitch) buffer.  g=None: a fresh one
+    (sn_normal_cosine_bwd_f32; pitch as normal_cosine_fwdg).  g = the buffer normal_cosine_fwdg returned for the same operands, out
+    its three numbers: kept when gloss is 1 — tested on the device — and recomputed otherwise, the same bits either way
+    (sn_normal_cosine_bwdg_f32)."""
+    rows, ldy, ldt, ldf = _cos_rows(y2d, target2d, rowmask, frame2d, "normal_cosine_bwd")
+    _dev(out, gloss, g)
+    if out.dtype != torch.float32 or out.numel() != 3 or not out.is_contiguous() or gloss.dtype != torch.float32 or gloss.numel() != 1:
+        raise ValueError("normal_cosine_bwd: out is the float32[3] of a forward call, gloss one float32")
+    name = "sn_normal_cosine_bwdg_f32"
+    if g is None:
+        name = "sn_normal_cosine_bwd_f32"
+        pitch = pitch or ldy
+        if pitch not in (3, 4):
+            raise ValueError("normal_cosine_bwd: pitch 3 or 4")
+        g = torch.empty((rows, pitch), dtype=torch.float32, device=y2d.device)
+    elif g.dtype != torch.float32 or g.dim() != 2 or g.shape[0] != rows or g.shape[1] not in (3, 4) or not g.is_contiguous():
+        raise ValueError("normal_cosine_bwd: g must be the contiguous (rows, 3 | 4) float32 buffer normal_cosine_fwdg returned")
+    _lib.call(name, _p(y2d), ldy, _p(frame2d), ldf, _p(target2d), ldt, _p(rowmask), rows, _p(out[2:]), _p(gloss), _p(g), g.shape[1],
+              _stream())
     return g
 
 
