@@ -538,6 +538,59 @@ int sn_normal_cosine_bwd_f32(const float *y, int64_t ldy, const float *frame, in
 int sn_normal_cosine_bwdg_f32(const float *y, int64_t ldy, const float *frame, int64_t ldf, const float *target, int64_t ldt,
                               const float *rowmask, int64_t rows, const float *count, const float *gloss, float *gout,
                               int64_t ldg, void *stream);
+/* ---- Sibling-pair pooling ---------------------------------------------------------------------------------------------------
+ * The two parameter-free pooling operations of the cascade model (cascade.LapCascade) and their backward passes, over the node
+ * axis of a hierarchy whose siblings are neighbours: fine rows 2 j and 2 j + 1 are the children of coarse row j.
+ * Replaces: src/normal_predict/models.py:568-576 (EfficientCascade._Pooling: MaxPool1d(2, stride=2) and
+ * F.interpolate(scale_factor=2) between two transposes) and the in-place skip `x += down_series[-i]` of models.py:597.
+ * Operands are row-major fp32 matrices of C >= 1 columns with leading dimensions >= C (SN_E_SHAPE otherwise): `pairs` coarse rows,
+ * 2 * pairs fine rows.  A (B, V, C) batch with even V is the matrix of B * V fine rows: no pair crosses a sample.
+ *   sn_pool_max2_fwd_f32     y[j, c] = second ? x[2 j + 1, c] : x[2 j, c],   second = x[2 j + 1, c] > x[2 j, c] or x[2 j + 1, c] is NaN
+ *                            — torch's MaxPool1d choice: a tie keeps the first, (NaN, v) keeps the first (the NaN), (v, NaN) and
+ *                            (NaN, NaN) take the second.  The chosen element is copied: its bits, a NaN's payload included.
+ *   sn_pool_max2_bwd_f32     gx[2 j + s, c] = g[j, c] for the chosen s, 0 for the other; the choice is made again from x (no index
+ *                            tensor is kept).  Every element of gx is written.
+ *   sn_unpool2_add_fwd_f32   y[2 j + s, c] = x[j, c] + skip[2 j + s, c],  s = 0, 1: nearest-neighbour upsampling and the skip
+ *                            connection in one pass, one fp32 add per element.  No operand may alias an output.
+ *   sn_unpool2_bwd_f32       gx[j, c] = g[2 j, c] + g[2 j + 1, c]   (the gradient of skip is g itself: no kernel)
+ * C a multiple of 4 with 16-byte aligned bases and leading dimensions that are multiples of 4 moves 16 bytes per lane; anything
+ * else one float.  One item per thread and a grid-stride loop past INT_MAX workgroups; no atomics, no memset, nothing that
+ * synchronises: every entry can be captured into a hipGraph. */
+int sn_pool_max2_fwd_f32(const float *x, int64_t ldx, int64_t pairs, int32_t C, float *y, int64_t ldy, void *stream);
+int sn_pool_max2_bwd_f32(const float *x, int64_t ldx, const float *g, int64_t ldg, int64_t pairs, int32_t C, float *gx,
+                         int64_t ldgx, void *stream);
+int sn_unpool2_add_fwd_f32(const float *x, int64_t ldx, const float *skip, int64_t lds, int64_t pairs, int32_t C, float *y,
+                           int64_t ldy, void *stream);
+int sn_unpool2_bwd_f32(const float *g, int64_t ldg, int64_t pairs, int32_t C, float *gx, int64_t ldgx, void *stream);
+/* ---- Mesh hierarchy -------------------------------------------------------------------------------------------------------------
+ * One coarsening step of the hierarchy the cascade model's per-level operators come from (operators.mesh_hierarchy; the numpy
+ * statement is mesh_ops.mesh_hierarchy).  The reference names the coarsening of Defferrard et al. 2017 ("the specific construction
+ * of permuted nodes", src/normal_predict/models.py:591) and contains no code for it: this is the project's own definition.
+ * L: square CSR, fp32, columns ascending inside a row.  All arithmetic fp32, no contraction, divisions correctly rounded.
+ *   score     for a stored off-diagonal entry  s_ij = fl(|L_ij| / |L_ii|) + fl(|L_ji| / |L_jj|),  L_ji the stored entry or 0;
+ *             s_ij = 0 where either diagonal entry is 0 or absent.  s_ij and s_ji have the same bits (the add commutes).  For
+ *             L = M^-1 C the mass cancels: w_ij (1 / d_i + 1 / d_j), the normalised cut of Graclus.
+ *   matching  in a round every unmatched i proposes to the unmatched neighbour j with the largest s_ij > 0, ties to the smallest j;
+ *             mutual proposals become pairs; rounds repeat until one makes no pair; what is left are singletons.  Every round
+ *             with an eligible edge makes a pair (the smallest endpoint among the globally best edges and its choice are mutual).
+ *             A round past max_rounds that would still make a pair makes none and raises SN_HIER_NOT_FINISHED.
+ *   weights   r_i = m_i / (m_i + m_mate(i)) and msum_i = fl(m_i + m_mate(i)) for a matched i, r_i = 1 and msum_i = m_i for a
+ *             singleton; mass NULL: every m_i = 1.
+ * The rest of a level is built from these by the caller: clusters numbered by the rank of their smallest member, P (n x n_c, ones)
+ * and R (n_c x n, the r of a cluster's members in ascending order), and the coarse operator R (L P) with sn_csr_spgemm_f32 and its
+ * summation order, i.e.  L_c[c, d] = fl(fl(r_a t_ad) + fl(r_b t_bd)),  t_id = the sequential sum of L_ij over parent(j) = d in
+ * ascending j, exact zeros dropped: the aggregation Galerkin operator M_c^-1 P^T M L P.
+ * sn_mesh_match_f32: ONE workgroup of SN_HIER_THREADS threads walks the operator; the rounds run inside the kernel, propose and
+ * accept separated by barriers, no host read-back.  mate[n]: partner or -1; r[n], msum[n]; out[2] = {rounds that made pairs,
+ * status word}.  A column index outside 0 .. n-1 raises SN_HIER_BAD_COLUMN and nothing is matched.
+ * workspace: sn_mesh_match_workspace_bytes(n, nnz). */
+#define SN_HIER_NOT_FINISHED  1
+#define SN_HIER_BAD_COLUMN    2
+#define SN_HIER_THREADS       1024
+size_t sn_mesh_match_workspace_bytes(int64_t n, int64_t nnz);
+int sn_mesh_match_f32(const int32_t *rowptr, const int32_t *colind, const float *vals, const float *mass, int64_t n, int64_t nnz,
+                      int32_t max_rounds, int32_t *mate, float *r, float *msum, int32_t *out, void *workspace,
+                      size_t workspace_bytes, void *stream);
 /* sn_gather_segments_f32: batch assembly of dense per-sample windows (the ARAP sampler's inputs / targets,
  * src/as_rigid_as_possible/main.py:126-152): out[(i*rows_per_item + r)*len + c] = src[base[i] + r*row_stride + c],
  * i < nitems, r < rows_per_item, c < len; base is a DEVICE array of element offsets into the resident dataset. */

@@ -106,6 +106,12 @@ SIGNATURES = {
     "sn_normal_cosine_fwdg_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _sz, _vp]),
     "sn_normal_cosine_bwd_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "sn_normal_cosine_bwdg_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "sn_pool_max2_fwd_f32": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _i64, _vp]),
+    "sn_pool_max2_bwd_f32": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp]),
+    "sn_unpool2_add_fwd_f32": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp]),
+    "sn_unpool2_bwd_f32": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _i64, _vp]),
+    "sn_mesh_match_workspace_bytes": (_sz, [_i64, _i64]),
+    "sn_mesh_match_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sn_pair_argmin_f32": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
     "sn_pair_ce_fwd_f32": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
     "sn_pair_ce_bwd_f32": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp]),

@@ -45,6 +45,10 @@ ARAP_JACOBI_SWEEPS = 6
 ARAP_RANK_EPS = 1e-20
 ARAP_MAX_CG = 65536
 
+# Mesh hierarchy
+HIER_NOT_FINISHED, HIER_BAD_COLUMN = 1, 2
+HIER_THREADS = 1024                  # the one workgroup that walks an operator
+
 # Sparse x sparse products
 SPGEMM_MAX_WINDOW = 131072
 SPGEMM_BAD_COLUMN, SPGEMM_TOO_WIDE, SPGEMM_TOO_LARGE, CSR_NO_OFFDIAGONAL = 1, 2, 4, 8
@@ -98,6 +102,8 @@ _SENTENCES = {
     "ARAP_BAD_FACE": BAD_FACE_SENTENCE,
     "ARAP_DEGREE": "a vertex has more incident faces than SN_LAP_MAX_DEGREE and got no weights",
     "ARAP_TOO_LARGE": "a mesh was too large for the launch and was left at rest",
+    "HIER_NOT_FINISHED": "the matching is not finished after max_rounds rounds",
+    "HIER_BAD_COLUMN": "a column index is outside the operator",
 }
 
 
@@ -118,6 +124,7 @@ STATUS_FAMILIES = {
     "descriptors": _family("DESC_", "CURV_", "EIG_"),
     "curvature": _family("DESC_BAD_FACE", "CURV_"),
     "arap": _family("ARAP_"),
+    "hierarchy": _family("HIER_NOT_FINISHED", "HIER_BAD_COLUMN"),
 }
 
 

@@ -22,7 +22,8 @@ from . import kernels
 from .operators import SparseOperator, as_operator
 
 __all__ = ["spmm", "lap_propagate", "dirac_face_stage", "dirac_vert_stage", "avg_propagate", "bn_linear", "bnlin_forward",
-           "bnlin_backward", "bn_prepare", "avg_stage_forward", "avg_stage_backward", "set_dirac_format", "set_laplacian_format", "SpmmTimer", "thin_linear", "thin_linear_supported"]
+           "bnlin_backward", "bn_prepare", "avg_stage_forward", "avg_stage_backward", "set_dirac_format", "set_laplacian_format", "SpmmTimer", "thin_linear", "thin_linear_supported", "pool_max2",
+           "unpool2_add"]
 
 _DIRAC_FORMAT = "q3"
 _LAPLACIAN_FORMAT = "ring"       # set_laplacian_format
@@ -903,3 +904,42 @@ class _AvgPropagate(torch.autograd.Function):
 def avg_propagate(x2d: torch.Tensor, seg) -> torch.Tensor:
     """x2d: (rows, C), seg: operators.MaskedSegments | PackedSegments -> (rows, 2C) concat buffer [elu(x), per-mesh mean of elu(x)]."""
     return _AvgPropagate.apply(x2d, seg)
+
+
+class _PoolMax2(torch.autograd.Function):
+    """y[b, j] = the larger of x[b, 2 j] and x[b, 2 j + 1] (MaxPool1d(2) over the node axis, models.py:568-576).  Backward: the
+    gradient goes to the chosen row, zero to the other; the choice is made again from the saved x, no index tensor is kept."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.save_for_backward(x)
+        return kernels.pool_max2_fwd(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        return kernels.pool_max2_bwd(x, g)
+
+
+def pool_max2(x: torch.Tensor) -> torch.Tensor:
+    """(B, V, C) fp32, V even -> (B, V / 2, C): the maximum over each pair of sibling rows with torch's MaxPool1d(2) choice (the
+    second iff it is larger or a NaN) — `pool(x.transpose(1, 2)).transpose(1, 2)` of the reference's cascade as one pass."""
+    return _PoolMax2.apply(x)
+
+
+class _Unpool2Add(torch.autograd.Function):
+    """y[b, 2 j + s] = x[b, j] + skip[b, 2 j + s].  Backward: gx[b, j] = g[b, 2 j] + g[b, 2 j + 1]; gskip is g itself."""
+
+    @staticmethod
+    def forward(ctx, x, skip):
+        return kernels.unpool2_add_fwd(x, skip)
+
+    @staticmethod
+    def backward(ctx, g):
+        return (kernels.unpool2_bwd(g) if ctx.needs_input_grad[0] else None), (g if ctx.needs_input_grad[1] else None)
+
+
+def unpool2_add(x: torch.Tensor, skip: torch.Tensor) -> torch.Tensor:
+    """x (B, V / 2, C), skip (B, V, C), fp32 -> (B, V, C): F.interpolate(scale_factor=2) over the node axis followed by
+    `x += skip` (models.py:596-597) in one pass."""
+    return _Unpool2Add.apply(x, skip)

@@ -2283,6 +2283,99 @@ def normal_cosine_bwd(y2d, target2d, rowmask, frame2d, out, gloss, g=None, pitch
     return g
 
 
+def mesh_match(rowptr, colind, vals, n: int, mass=None, max_rounds: int = 1024):
+    """(mate int32[n], r fp32[n], msum fp32[n], out int32[2]) of one coarsening step of a square CSR operator
+    (sn_mesh_match_f32; include/sn_spmm.h "Mesh hierarchy"): the handshake matching on the edge scores, the restriction
+    weights and the merged masses; out = (rounds, status word) stays on the device — the caller reads it."""
+    _dev(rowptr, colind, vals, mass)
+    if rowptr.dtype != torch.int32 or colind.dtype != torch.int32 or vals.dtype != torch.float32 or rowptr.numel() != n + 1:
+        raise ValueError("mesh_match: int32 rowptr[n + 1] / colind and float32 vals expected")
+    if mass is not None and (mass.dtype != torch.float32 or mass.numel() != n or not mass.is_contiguous()):
+        raise ValueError(f"mesh_match: mass must hold {n} contiguous float32 values")
+    dev = rowptr.device
+    nnz = int(colind.numel())
+    mate = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+    r = torch.empty(max(n, 1), dtype=torch.float32, device=dev)[:n]
+    msum = torch.empty(max(n, 1), dtype=torch.float32, device=dev)[:n]
+    out = torch.empty(2, dtype=torch.int32, device=dev)
+    ws, ws_bytes = _workspace("sn_mesh_match_workspace_bytes", dev, n, nnz)
+    _lib.call("sn_mesh_match_f32", _p(rowptr), _p(colind), _p(vals), _p(mass), n, nnz, int(max_rounds), _p(mate), _p(r), _p(msum),
+              _p(out), _p(ws), ws_bytes, _stream())
+    return mate, r, msum, out
+
+
+def _pool_rows(what: str, *tensors):
+    """Operand checks shared by the sibling-pair pooling launchers (include/sn_spmm.h, "Sibling-pair pooling"): fp32 (B, V, C)
+    device tensors with C >= 1; returns them as (B * V, C) matrices with contiguous rows — views where the rows have one pitch
+    (a contiguous tensor, a column slice of one), else copies."""
+    _dev(*tensors)
+    out = []
+    for t in tensors:
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what}: float32 operands expected, got {t.dtype}")
+        if t.dim() != 3 or t.shape[2] < 1:
+            raise ValueError(f"{what}: (B, V, C) operands with C >= 1 expected, got {tuple(t.shape)}")
+        B, V, C = t.shape
+        pitch = C
+        if not t.is_contiguous():
+            if V > 1 and (C == 1 or t.stride(2) == 1) and t.stride(1) >= C and (B == 1 or t.stride(0) == V * t.stride(1)):
+                pitch = t.stride(1)
+            else:
+                t = t.contiguous()
+        out.append(t.as_strided((B * V, C), (pitch, 1)))
+    return out
+
+
+def _even_nodes(what: str, t) -> None:
+    if t.dim() == 3 and t.shape[1] % 2:
+        raise ValueError(f"{what}: the node axis holds sibling pairs, so its length must be even; got {tuple(t.shape)}")
+
+
+def pool_max2_fwd(x):
+    """(B, V / 2, C): the larger of each sibling pair of rows of x (B, V, C), torch's MaxPool1d(2) choice (sn_pool_max2_fwd_f32)."""
+    _even_nodes("pool_max2_fwd", x)
+    (x2,) = _pool_rows("pool_max2_fwd", x)
+    B, V, C = x.shape
+    y = torch.empty((B, V // 2, C), dtype=torch.float32, device=x.device)
+    _lib.call("sn_pool_max2_fwd_f32", _p(x2), _ld(x2), B * V // 2, C, _p(y), C, _stream())
+    return y
+
+
+def pool_max2_bwd(x, g):
+    """(B, V, C): g (B, V / 2, C) routed to the row of each pair that pool_max2_fwd chose, zero to the other; the choice is made
+    again from x (sn_pool_max2_bwd_f32)."""
+    _even_nodes("pool_max2_bwd", x)
+    x2, g2 = _pool_rows("pool_max2_bwd", x, g)
+    B, V, C = x.shape
+    if tuple(g.shape) != (B, V // 2, C):
+        raise ValueError(f"pool_max2_bwd: g must be {(B, V // 2, C)} for x {tuple(x.shape)}, got {tuple(g.shape)}")
+    gx = torch.empty((B, V, C), dtype=torch.float32, device=x.device)
+    _lib.call("sn_pool_max2_bwd_f32", _p(x2), _ld(x2), _p(g2), _ld(g2), B * V // 2, C, _p(gx), C, _stream())
+    return gx
+
+
+def unpool2_add_fwd(x, skip):
+    """(B, V, C): y[b, 2 j + s] = x[b, j] + skip[b, 2 j + s] for x (B, V / 2, C) and skip (B, V, C) (sn_unpool2_add_fwd_f32)."""
+    _even_nodes("unpool2_add_fwd", skip)
+    x2, s2 = _pool_rows("unpool2_add_fwd", x, skip)
+    B, V, C = skip.shape
+    if tuple(x.shape) != (B, V // 2, C):
+        raise ValueError(f"unpool2_add_fwd: x must be {(B, V // 2, C)} for skip {tuple(skip.shape)}, got {tuple(x.shape)}")
+    y = torch.empty((B, V, C), dtype=torch.float32, device=x.device)
+    _lib.call("sn_unpool2_add_fwd_f32", _p(x2), _ld(x2), _p(s2), _ld(s2), B * V // 2, C, _p(y), C, _stream())
+    return y
+
+
+def unpool2_bwd(g):
+    """(B, V / 2, C): gx[b, j] = g[b, 2 j] + g[b, 2 j + 1] for g (B, V, C) (sn_unpool2_bwd_f32)."""
+    _even_nodes("unpool2_bwd", g)
+    (g2,) = _pool_rows("unpool2_bwd", g)
+    B, V, C = g.shape
+    gx = torch.empty((B, V // 2, C), dtype=torch.float32, device=g.device)
+    _lib.call("sn_unpool2_bwd_f32", _p(g2), _ld(g2), B * V // 2, C, _p(gx), C, _stream())
+    return gx
+
+
 def linear_fwd_segbias(x, W, segbias, rows_per_seg: int, residual=None, y_elu=None, want_y: bool = True, elu_stats=None,
                        tile_sums=None):
     """y = x·W^T + segbias[row // rows_per_seg] (+ residual), optionally elu(y) into y_elu; want_y=False: only y_elu is written.

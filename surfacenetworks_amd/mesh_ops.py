@@ -53,6 +53,7 @@ __all__ = [
     "cot_pencil", "spectral_start", "cheb_filter_step", "cheb_filter_scalars", "eig_normalised_mass", "eig_guard",
     "laplacian_eigenpairs", "wks_weights", "wks_contract", "wave_kernel_signature", "Eigenpairs", "EIG_NOT_CONVERGED",
     "EIG_CLIPPED_MASS", "EIG_MASS_FLOOR",
+    "hierarchy_scores", "handshake_matching", "coarsen_operator", "mesh_hierarchy", "MeshHierarchy",
 ]
 
 _PERMS = np.array([[0, 1, 2], [0, 2, 1], [1, 0, 2], [1, 2, 0], [2, 0, 1], [2, 1, 0]])  # itertools.permutations order
@@ -1974,3 +1975,175 @@ def wave_kernel_signature(V, F, N: int = 100, k: int = 300, eigenpairs: Eigenpai
     W, C = wks_weights(ep.values, N)
     order = np.argsort(np.abs(ep.values), kind="stable")
     return wks_contract(ep.vectors[:, order], W, C).astype(dtype)
+
+
+# ---- mesh hierarchy: heavy-edge matching, Galerkin coarse operators, sibling positions ------------------------------------------------
+# The numpy statement of the hierarchy `cascade.LapCascade` takes its per-level operators from (the coarsening of Defferrard et
+# al. 2017 the reference names and does not contain).  No device twin yet: this is the definition one will have to equal.
+MeshHierarchy = collections.namedtuple("MeshHierarchy", "L real order position sizes singletons rounds mate parent positions")
+
+
+def hierarchy_scores(L: sp.csr_matrix) -> np.ndarray:
+    """One fp32 score per stored entry of L (square CSR, fp32, columns ascending): for an off-diagonal entry
+    s_ij = fl(|L_ij| / |L_ii|) + fl(|L_ji| / |L_jj|) with L_ji the stored entry or 0, and 0 where either diagonal entry is 0 or
+    absent; 0 on the diagonal.  s_ij and s_ji have the same bits (the fp32 add commutes).  For L = M^-1 C this is
+    w_ij (1 / d_i + 1 / d_j): the normalised cut of Graclus, whatever the mass convention."""
+    n = L.shape[0]
+    indptr, col, val = L.indptr.astype(np.int64), L.indices.astype(np.int64), np.abs(L.data.astype(np.float32))
+    row = np.repeat(np.arange(n, dtype=np.int64), np.diff(indptr))
+    d = np.zeros(n, np.float32)
+    d[row[row == col]] = val[row == col]
+    key = row * n + col                                     # ascending: rows ascending, columns ascending inside a row
+    rev = np.searchsorted(key, col * n + row)
+    rev_c = np.minimum(rev, max(len(key) - 1, 0))
+    back = np.where((rev < len(key)) & (key[rev_c] == col * n + row), val[rev_c], np.float32(0)) if len(key) else val
+    ok = (d[row] > 0) & (d[col] > 0) & (row != col)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        s = (val / d[row]).astype(np.float32) + (back / d[col]).astype(np.float32)
+    return np.where(ok, s, np.float32(0)).astype(np.float32)
+
+
+def handshake_matching(L: sp.csr_matrix, max_rounds: int = 1024):
+    """(mate, rounds): in a round every unmatched i proposes to the unmatched neighbour j with the largest s_ij > 0, ties to the
+    smallest j; mutual proposals become pairs; rounds repeat until one makes no pair.  mate[i] = the partner or -1 (singleton);
+    rounds = the rounds that made pairs.  Every round with an eligible edge makes a pair (the smallest endpoint among the
+    globally best edges and its choice are mutual); a round past max_rounds that would still make one raises RuntimeError."""
+    n = L.shape[0]
+    col = L.indices.astype(np.int64)
+    row = np.repeat(np.arange(n, dtype=np.int64), np.diff(L.indptr))
+    s = hierarchy_scores(L)
+    mate = np.full(n, -1, np.int64)
+    rounds = 0
+    while True:
+        live = (mate[row] < 0) & (mate[col] < 0) & (s > 0)
+        r, c, v = row[live], col[live], s[live]
+        o = np.lexsort((c, -v.astype(np.float64), r))       # per row: largest score first, then smallest column
+        r, c = r[o], c[o]
+        first = np.ones(len(r), bool)
+        first[1:] = r[1:] != r[:-1]
+        prop = np.full(n, -1, np.int64)
+        prop[r[first]] = c[first]
+        i = np.flatnonzero(prop >= 0)
+        i = i[(prop[prop[i]] == i) & (i < prop[i])]
+        if not len(i):
+            return mate, rounds
+        if rounds >= max_rounds:
+            raise RuntimeError(f"mesh_hierarchy: the matching is not finished after max_rounds = {max_rounds} rounds")
+        mate[i], mate[prop[i]] = prop[i], i
+        rounds += 1
+
+
+def _pair_sums(keys, vals):
+    """Groups of at most two consecutive equal keys: (index of each group's first entry, fl(first + second) or first)."""
+    first = np.ones(len(keys), bool)
+    first[1:] = keys[1:] != keys[:-1]
+    k = np.flatnonzero(first)
+    two = np.zeros(len(keys), bool)
+    two[:-1] = first[:-1] & ~first[1:]
+    assert not (~first[1:] & ~first[:-1]).any() if len(keys) > 1 else True
+    nxt = np.minimum(k + 1, max(len(keys) - 1, 0))
+    return k, np.where(two[k], (vals[k] + vals[nxt]).astype(np.float32), vals[k]).astype(np.float32)
+
+
+def coarsen_operator(L: sp.csr_matrix, mate: np.ndarray, mass: np.ndarray):
+    """(L_c, m_c, parent): clusters = pairs and singletons, numbered by the rank of their smallest member; per fine row i,
+    t_id = the sequential fp32 sum of L_ij over parent(j) = d in ascending j; L_c[c, d] = fl(fl(r_a t_ad) + fl(r_b t_bd)) for the
+    members a < b of c (a missing term skipped), r_a = m_a / (m_a + m_b), r_b = m_b / (m_a + m_b), r = 1 for a singleton, all
+    fp32 without contraction; m_c = fl(m_a + m_b); exact zeros dropped.  This is R (L P), the aggregation Galerkin operator
+    M_c^-1 P^T M L P."""
+    n = L.shape[0]
+    idx = np.arange(n, dtype=np.int64)
+    rep = np.where((mate >= 0) & (mate < idx), mate, idx)
+    is_rep = rep == idx
+    parent = (np.cumsum(is_rep) - 1)[rep]
+    nc = int(is_rep.sum())
+    mass = np.asarray(mass, np.float32)
+    pair = mate >= 0
+    msum = np.where(pair, mass + mass[np.where(pair, mate, idx)], mass).astype(np.float32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(pair, (mass / msum).astype(np.float32), np.float32(1)).astype(np.float32)
+    col = L.indices.astype(np.int64)
+    row = np.repeat(idx, np.diff(L.indptr))
+    val = L.data.astype(np.float32)
+    o = np.lexsort((col, parent[col], row))
+    k, t = _pair_sums((row * nc + parent[col])[o], val[o])
+    ti, td = row[o][k], parent[col][o][k]
+    keep = t != 0                                                        # (the product L P drops its exact zeros)
+    ti, td, t = ti[keep], td[keep], t[keep]
+    o = np.lexsort((ti, td, parent[ti]))
+    k, v = _pair_sums((parent[ti] * nc + td)[o], (r[ti] * t).astype(np.float32)[o])
+    ci, cd = parent[ti][o][k], td[o][k]
+    keep = v != 0
+    Lc = sp.csr_matrix((v[keep], (ci[keep], cd[keep])), shape=(nc, nc), dtype=np.float32)
+    Lc.sort_indices()
+    mc = np.zeros(nc, np.float32)
+    mc[parent[is_rep]] = msum[is_rep]
+    return Lc, mc, parent
+
+
+def _to_positions(L: sp.csr_matrix, pos: np.ndarray, size: int) -> sp.csr_matrix:
+    M = L.tocoo()
+    out = sp.csr_matrix((M.data.astype(np.float32), (pos[M.row], pos[M.col])), shape=(size, size), dtype=np.float32)
+    out.sort_indices()
+    return out
+
+
+def mesh_hierarchy(L, levels: int = 4, mass=None, pad_coarsest_to: int = 1, max_rounds: int = 1024, blocks=None) -> MeshHierarchy:
+    """Hierarchy of a square fp32 CSR operator with ascending columns, level 0 the coarsest as `Laps` is indexed.
+
+    levels - 1 times: handshake_matching on the scores of the current operator, coarsen_operator with the current masses (mass:
+    (n,) fp32 restriction weights of the finest level, None = ones).  Positions: pos_0(c) = c; pos_k(child) = 2 pos_{k-1}(parent)
+    + slot, slot 0 for the child with the smaller level-k number; a singleton takes slot 0 and its slot 1 is a fake node (empty
+    row and column, fake descendants).  pad_coarsest_to rounds the coarsest count up with fake clusters.  blocks: the row counts
+    of the meshes of a block-diagonal batch (None: one mesh); the batch coarsens block by block (no entry crosses meshes, and
+    the cluster numbering keeps the meshes apart), every mesh gets the coarsest size of the largest, and positions are per mesh:
+    mesh b owns positions b n_0 2^k .. (b + 1) n_0 2^k of level k.
+
+    Returns MeshHierarchy: L[k] the operator of level k in position order, (B n_0 2^k) square; real[k] its real-node mask;
+    order: position -> id in the given operator or -1; position: id -> position; sizes[k] real nodes of level k; singletons[k],
+    rounds[k] of the matching that coarsened level k (0 at level 0); mate[k], parent[k] of that matching in level-k numbering
+    (None at level 0); positions[k]: level-k number -> position (positions[-1] is position).  levels = 1 returns L unchanged with the identity order."""
+    L = sp.csr_matrix(L, dtype=np.float32)
+    L.sort_indices()
+    n = L.shape[0]
+    if L.shape[0] != L.shape[1] or levels < 1 or pad_coarsest_to < 1:
+        raise ValueError("mesh_hierarchy: a square operator, levels >= 1 and pad_coarsest_to >= 1 are required")
+    blocks = [n] if blocks is None else [int(b) for b in blocks]
+    if sum(blocks) != n:
+        raise ValueError(f"mesh_hierarchy: blocks sum to {sum(blocks)}, the operator has {n} rows")
+    m = np.ones(n, np.float32) if mass is None else np.asarray(mass, np.float32).reshape(n)
+    ops, mates, parents, rounds = [L], [None], [None], [0]
+    block_of = np.repeat(np.arange(len(blocks)), blocks)
+    owners = [block_of]
+    for _ in range(levels - 1):
+        mate, r = handshake_matching(ops[0], max_rounds)
+        Lc, m, parent = coarsen_operator(ops[0], mate, m)
+        mates[0], parents[0], rounds[0] = mate, parent, r
+        own = np.zeros(Lc.shape[0], np.int64)
+        own[parent] = owners[0]
+        ops.insert(0, Lc); mates.insert(0, None); parents.insert(0, None); rounds.insert(0, 0); owners.insert(0, own)
+    B = len(blocks)
+    counts0 = np.bincount(owners[0], minlength=B)
+    if levels == 1:                                                      # L unchanged, the identity order, whatever the blocks
+        B, n0, pos = 1, n, np.arange(n, dtype=np.int64)
+    else:
+        n0 = int(-(-max(int(counts0.max()), 1) // pad_coarsest_to) * pad_coarsest_to)
+        first0 = np.concatenate([[0], np.cumsum(counts0)[:-1]])
+        pos = owners[0] * n0 + (np.arange(ops[0].shape[0]) - first0[owners[0]])
+    out_L, real, sizes, single, positions = [], [], [], [], []
+    for k in range(levels):
+        if k > 0:
+            mate = mates[k]
+            idx = np.arange(len(mate))
+            pos = 2 * pos[parents[k]] + ((mate >= 0) & (mate < idx))
+        size = B * n0 << k
+        positions.append(pos.astype(np.int64))
+        out_L.append(_to_positions(ops[k], pos, size))
+        mask = np.zeros(size, bool)
+        mask[pos] = True
+        real.append(mask)
+        sizes.append(int(ops[k].shape[0]))
+        single.append(int((mates[k] < 0).sum()) if mates[k] is not None else 0)
+    order = np.full(len(real[-1]), -1, np.int64)
+    order[pos] = np.arange(n)
+    return MeshHierarchy(out_L, real, order, positions[-1], sizes, single, rounds, mates, parents, positions)

@@ -11,7 +11,10 @@ the pitch-4 gradient that comes back are what the loss kernels read and write (k
 from one pass); `forward` returns the first three columns.
 
 Not here, and refused rather than approximated: bottleneck widths, nofirstId, bnmode other than '', GatDeepModel,
-EfficientCascade, LapMATModel.
+LapMATModel.  `EfficientCascade` refuses under its own name too: the reference's multiresolution model lives in
+cascade.LapCascade (naive pooling, equal widths), which takes the per-level operators of a batch (`Batch.Laps`) and runs through
+forward_loss / train_step / graphed_train_step here unchanged; NormalFrames(model="cas") builds each frame's mesh hierarchy
+(operators.mesh_hierarchy) and samples such batches, and to_mesh_order maps their rows back to vertex ids.
 """
 from __future__ import annotations
 
@@ -32,7 +35,7 @@ from .operators import OperatorPool
 __all__ = [
     "LapDeepModel", "DirDeepModel", "AvgModel", "GatDeepModel", "EfficientCascade", "LapMATModel", "repeating_expand",
     "loss_reference", "mad_reference", "cosine_loss", "mean_angle_deviation", "loss_and_mad", "Batch", "NormalFrames",
-    "forward_loss", "train_step", "graphed_train_step", "make_optimizer", "halve_lr", "evaluate", "predict",
+    "to_mesh_order", "forward_loss", "train_step", "graphed_train_step", "make_optimizer", "halve_lr", "evaluate", "predict",
 ]
 
 
@@ -307,7 +310,8 @@ class GatDeepModel(nn.Module):
 class EfficientCascade(nn.Module):
     def __init__(self, *args, **kwargs):
         super().__init__()
-        _refuse("EfficientCascade", "the pooling cascade (models.py:529-609)")
+        _refuse("EfficientCascade", "the pooling cascade (models.py:529-609) under this name — cascade.LapCascade is that model at "
+                                    "naive pooling and equal widths, on a list of per-level operators —")
 
 
 class LapMATModel(nn.Module):
@@ -326,11 +330,25 @@ class Batch:
     Di: Optional[object]
     DiA: Optional[object]
     names: List[object]
+    Laps: Optional[List[object]] = None      # cascade.LapCascade: the operators of the hierarchy's levels, coarsest first
+    positions: Optional[List[torch.Tensor]] = None      # model="cas": per mesh, vertex id -> row of the node axis (to_mesh_order)
 
     @property
     def operator(self):
-        """What the models take first: L, or (Di, DiA)."""
+        """What the models take first: Laps where the batch carries them, else L, or (Di, DiA)."""
+        if self.Laps is not None:
+            return self.Laps
         return self.L if self.L is not None else (self.Di, self.DiA)
+
+    def graph_tensors(self):
+        """graphs.batch_tensors' own list — inputs, targets, mask, the arrays of L / Di / DiA — then those of every level of Laps:
+        what a captured step reads and GraphedStep.load overwrites."""
+        from .graphs import operator_tensors
+
+        out = [t for t in (self.inputs, self.targets, self.mask) if t is not None]
+        for op in (self.L, self.Di, self.DiA, *(self.Laps or ())):
+            out.extend(operator_tensors(op))
+        return out
 
 
 def _as_scipy(op):
@@ -342,9 +360,15 @@ class NormalFrames:
     target normals stay where they are, the operators of the requested tower go into OperatorPools; `sample_batch` pads to the
     BATCH maximum of vertices and faces and assembles the block-diagonal operators on the device (sampler.py:93-181)."""
 
-    def __init__(self, frames, model="lap", device="cuda"):
-        if model not in ("lap", "dir"):
-            raise ValueError(f'NormalFrames: model must be "lap" or "dir", got {model!r}')
+    def __init__(self, frames, model="lap", device="cuda", levels=4, mass=None):
+        """model="cas": the frames of model="lap" for cascade.LapCascade.  Each frame's hierarchy is built once from frame["L"]
+        (operators.mesh_hierarchy; levels; mass None | "voronoi" | "barycentric": the restriction weights, operators.vertex_mass
+        of the frame's V, F), one OperatorPool per level keeps the operators in position order, and inputs and targets are stored
+        in position order with zero rows at fake nodes."""
+        if model not in ("lap", "dir", "cas"):
+            raise ValueError(f'NormalFrames: model must be "lap", "dir" or "cas", got {model!r}')
+        if mass not in (None, "voronoi", "barycentric"):
+            raise ValueError(f'NormalFrames: mass must be None, "voronoi" or "barycentric", got {mass!r}')
         kept = [fr for fr in frames if fr is not None]
         self.dropped = len(frames) - len(kept)           # frames read_npz gave up on (sampler.py:121 skips them while sampling)
         if not kept:
@@ -356,7 +380,7 @@ class NormalFrames:
         need = ("Di", "DiA") if model == "dir" else ("L",)
         for fr in kept:
             if any(fr.get(k) is None for k in need):
-                raise ValueError(f'NormalFrames(model="{model}"): a frame lacks {need} (build it with the same model)')
+                raise ValueError(f'NormalFrames(model="{model}"): a frame lacks {need} (build it with model="{"dir" if model == "dir" else "lap"}")')
         self.nv = np.array([int(fr["V"].shape[0]) for fr in kept])
         self.nf = np.array([int(fr["F"].shape[0]) for fr in kept])
         self.inputs = [torch.as_tensor(fr["input"], dtype=torch.float32).to(self.device) for fr in kept]
@@ -366,6 +390,8 @@ class NormalFrames:
         if model == "dir":
             self.pool_Di = OperatorPool([_as_scipy(fr["Di"]) for fr in kept], self.device, want_bsr4=True)
             self.pool_DiA = OperatorPool([_as_scipy(fr["DiA"]) for fr in kept], self.device, want_bsr4=True)
+        elif model == "cas":
+            self._build_hierarchies(kept, int(levels), mass)
         else:
             self.pool_L = OperatorPool([_as_scipy(fr["L"]) for fr in kept], self.device)
         self.next_id = 0             # sample_batch.train_id / test_id (sampler.py:105-114)
@@ -373,14 +399,39 @@ class NormalFrames:
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
 
+    def _build_hierarchies(self, kept, levels, mass):
+        from . import operators as snO
+
+        if levels < 1:
+            raise ValueError(f"NormalFrames: levels must be at least 1, got {levels}")
+        self.levels = levels
+        self.hierarchies, per_level = [], [[] for _ in range(levels)]
+        for i, fr in enumerate(kept):
+            L = fr["L"] if isinstance(fr["L"], snO.SparseOperator) else snO.SparseOperator.from_scipy(_as_scipy(fr["L"]), self.device)
+            m = None
+            if mass is not None:
+                m = snO.vertex_mass(torch.as_tensor(fr["V"], dtype=torch.float32, device=self.device),
+                                    torch.as_tensor(fr["F"], device=self.device), mass)
+            h = snO.mesh_hierarchy(L, levels=levels, mass=m)
+            self.hierarchies.append(h)
+            for k in range(levels):
+                per_level[k].append(h.L[k].to_scipy())
+            nodes = int(h.real[-1].numel())
+            for store in (self.inputs, self.targets):                      # position order, zero rows at fake nodes
+                rows = torch.zeros(nodes, store[i].shape[1], device=self.device)
+                rows[h.position] = store[i]
+                store[i] = rows
+        self.pool_Laps = [OperatorPool(mats, self.device) for mats in per_level]
+        self.n0 = np.array([int(h.L[0].shape[0]) for h in self.hierarchies])
+
     @classmethod
-    def from_meshes(cls, meshes, model="lap", device="cuda", **frame_kwargs):
+    def from_meshes(cls, meshes, model="lap", device="cuda", levels=4, mass=None, **frame_kwargs):
         """From raw (V, F) pairs: datasets.normal_frame_from_mesh builds each frame first (frame_kwargs: its arguments)."""
         from .datasets import normal_frame_from_mesh
 
-        frames = [normal_frame_from_mesh(V, F_, model=model, device=device, **{"name": i, **frame_kwargs})
+        frames = [normal_frame_from_mesh(V, F_, model="lap" if model == "cas" else model, device=device, **{"name": i, **frame_kwargs})
                   for i, (V, F_) in enumerate(meshes)]
-        return cls(frames, model=model, device=device)
+        return cls(frames, model=model, device=device, levels=levels, mass=mass)
 
     def _walk(self, batch_size):
         """sampler.py:101-123 with pre-loaded frames: the next batch_size frames in order, wrapping around (the flag is raised
@@ -401,6 +452,8 @@ class NormalFrames:
             ids = rng.integers(0, self.n, size=batch_size) if rng is not None else self._walk(batch_size)
         ids = np.asarray(ids, dtype=np.int64)
         B = len(ids)
+        if self.kind == "cas":
+            return self._sample_cascade(ids)
         nv, nf = int(self.nv[ids].max()), int(self.nf[ids].max())
         inputs = torch.zeros(B, nv, self.input_features, device=self.device)
         targets = torch.zeros(B, nv, 3, device=self.device)
@@ -417,6 +470,32 @@ class NormalFrames:
         else:
             L = self.pool_L.assemble(ids, nv, nv)
         return Batch(inputs, targets, mask, L, Di, DiA, [self.names[i] for i in ids])
+
+    def _sample_cascade(self, ids) -> Batch:
+        """Level k of the batch is padded to 2^k max n_0 nodes per mesh (the padding behind a mesh's own nodes, so padded siblings
+        have padded parents); `mask` is the real-node mask of the finest level — not a prefix: fake nodes lie between real ones."""
+        B, top = len(ids), self.levels - 1
+        n0 = int(self.n0[ids].max())
+        nodes = n0 << top
+        inputs = torch.zeros(B, nodes, self.input_features, device=self.device)
+        targets = torch.zeros(B, nodes, 3, device=self.device)
+        mask = torch.zeros(B, nodes, 1, device=self.device)
+        for b, i in enumerate(ids):
+            own = self.inputs[i].shape[0]
+            inputs[b, :own] = self.inputs[i]
+            targets[b, :own] = self.targets[i]
+            mask[b, :own, 0] = self.hierarchies[i].real[-1]
+        Laps = [self.pool_Laps[k].assemble(ids, n0 << k, n0 << k) for k in range(self.levels)]
+        return Batch(inputs, targets, mask, None, None, None, [self.names[i] for i in ids], Laps=Laps,
+                     positions=[self.hierarchies[i].position for i in ids])
+
+
+def to_mesh_order(batch: Batch, outputs):
+    """[(nV_i, C) tensor per mesh]: the rows of `outputs` (B, nodes, C) of a model="cas" batch back in vertex order — row v of
+    mesh b is outputs[b, position_b[v]]; fake and padded nodes are dropped."""
+    if batch.positions is None:
+        raise ValueError("to_mesh_order: the batch carries no positions (it is not a model=\"cas\" batch)")
+    return [outputs[b][pos] for b, pos in enumerate(batch.positions)]
 
 
 # ---- step and evaluation ---------------------------------------------------------------------------------------------------------
@@ -511,6 +590,9 @@ def predict(model, frames: NormalFrames, batch_size: int):
     with torch.no_grad():
         for batch in _eval_batches(frames, batch_size):
             outputs = model(batch.operator, batch.mask, batch.inputs)
+            if batch.positions is not None:                          # model="cas": vertex order through the positions
+                found.extend((name, out.clone()) for name, out in zip(batch.names, to_mesh_order(batch, outputs)))
+                continue
             counts = batch.mask.reshape(batch.mask.shape[0], -1).sum(1).long().tolist()
             for name, out, n in zip(batch.names, outputs, counts):
                 found.append((name, out[:n].clone()))

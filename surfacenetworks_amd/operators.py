@@ -31,7 +31,7 @@ __all__ = ["SparseOperator", "OperatorPool", "PackedSegments", "MaskedSegments",
            "laplacian_operator_from_mesh", "geodesic_matrix_from_mesh", "spgemm", "amplify_sequence_operators",
            "clean_mesh", "CleanMesh", "repair_mesh", "RepairedMesh", "vertex_descriptors", "MeshDescriptors", "vertex_normals", "face_areas", "vertex_mass",
            "gaussian_curvature", "delaunay_2d", "Delaunay2D", "arap_deform", "ArapDeformation", "laplacian_eigenpairs", "Eigenpairs",
-           "wave_kernel_signature", "principal_curvatures", "PrincipalCurvatures", "curv4"]
+           "wave_kernel_signature", "principal_curvatures", "PrincipalCurvatures", "curv4", "mesh_hierarchy", "MeshHierarchy"]
 
 # A BSR4 copy is kept when zero-fill costs at most this much extra storage over CSR entries.
 _BSR4_MAX_FILL = 1.6
@@ -1532,3 +1532,101 @@ def wave_kernel_signature(V, F, N: int = 100, k: int = 300, eigenpairs: Optional
     phi = ep.vectors.gather(1, order[seg])
     out = kernels.wks_contract(phi, ep.voff, W, C, dtype)
     return out.view(V.shape[0], V.shape[1], N) if torch.is_tensor(V) and V.dim() == 3 else out
+
+
+# ---- mesh hierarchy (include/sn_spmm.h "Mesh hierarchy"; the numpy statement is mesh_ops.mesh_hierarchy) ------------------------------
+MeshHierarchy = collections.namedtuple("MeshHierarchy", "L real order position sizes singletons rounds status positions")
+
+
+def _csr_rows(rowptr, n: int):
+    return torch.repeat_interleave(torch.arange(n, device=rowptr.device, dtype=torch.int64), torch.diff(rowptr.long()))
+
+
+def _csr_from_sorted(rows, cols, vals, shape):
+    """SparseOperator from COO triples in any order with distinct (row, column) pairs: sorted by row, then column."""
+    M, K = shape
+    order = torch.argsort(rows * K + cols)
+    rowptr = torch.zeros(M + 1, dtype=torch.int64, device=rows.device)
+    rowptr[1:] = torch.cumsum(torch.bincount(rows, minlength=M), 0)
+    return SparseOperator(rowptr.int(), cols[order].int(), vals[order].contiguous(), (M, K))
+
+
+def mesh_hierarchy(L: SparseOperator, levels: int = 4, mass=None, pad_coarsest_to: int = 1, max_rounds: int = 1024,
+                   blocks=None) -> MeshHierarchy:
+    """Hierarchy of a square fp32 CSR operator with ascending columns on the device, level 0 the coarsest as the `Laps` of
+    cascade.LapCascade are indexed; equal to mesh_ops.mesh_hierarchy bit for bit (integers as integers, fp32 by bit pattern).
+
+    levels - 1 times: the handshake matching on the Graclus scores and the restriction weights in one launch
+    (kernels.mesh_match), clusters numbered by the rank of their smallest member, the coarse operator R (L P) by two spgemm
+    products.  Positions: pos_0(c) = c; pos_k(child) = 2 pos_{k-1}(parent) + slot, slot 0 for the child with the smaller number;
+    a singleton's slot 1 is a fake node with an empty row and column.  mass: (n,) fp32 restriction weights, None = ones
+    (vertex_mass fits).  pad_coarsest_to rounds the coarsest count up with fake clusters.  blocks: the row counts of the meshes of
+    a block-diagonal batch (None: one mesh): every mesh gets the coarsest size of the largest and owns positions
+    b n_0 2^k .. (b + 1) n_0 2^k of level k.  Per level the host reads the cluster count (it sizes the next level) together with
+    the rounds and the status word.  RuntimeError past max_rounds, ValueError for a column outside the operator.
+
+    Returns MeshHierarchy: L[k] SparseOperators in position order, (B n_0 2^k) square; real[k] bool masks; order: position -> id or
+    -1; position: id -> position; sizes, singletons, rounds per level (lists of int); status; positions[k]: level-k number ->
+    position.  levels = 1 returns L unchanged with the identity order."""
+    if not isinstance(L, SparseOperator):
+        raise TypeError("mesh_hierarchy wants a SparseOperator")
+    kernels._dev(L.rowptr, mass if torch.is_tensor(mass) else None)
+    n, K = L._shape
+    if n != K or levels < 1 or pad_coarsest_to < 1:
+        raise ValueError("mesh_hierarchy: a square operator, levels >= 1 and pad_coarsest_to >= 1 are required")
+    blocks = [n] if blocks is None else [int(b) for b in blocks]
+    if sum(blocks) != n:
+        raise ValueError(f"mesh_hierarchy: blocks sum to {sum(blocks)}, the operator has {n} rows")
+    dev = L.rowptr.device
+    i64 = dict(dtype=torch.int64, device=dev)
+    m = None if mass is None else torch.as_tensor(mass, dtype=torch.float32, device=dev).reshape(n).contiguous()
+    ops, mates, parents, rounds, singles = [L], [None], [None], [0], [0]
+    owners = [torch.repeat_interleave(torch.arange(len(blocks), **i64), torch.tensor(blocks, **i64))]
+    status = 0
+    for _ in range(levels - 1):
+        cur = ops[0]
+        nk = cur._shape[0]
+        mate, r, msum, out = kernels.mesh_match(cur.rowptr, cur.colind, cur.vals, nk, m, max_rounds)
+        idx = torch.arange(nk, **i64)
+        mate = mate.long()
+        rep = torch.where((mate >= 0) & (mate < idx), mate, idx)
+        is_rep = rep == idx
+        parent = (torch.cumsum(is_rep.long(), 0) - 1)[rep]
+        nc, nsingle, nrounds, st = (int(v) for v in torch.stack([is_rep.sum(), (mate < 0).sum(), out[0].long(), out[1].long()]).tolist())
+        status |= st
+        kernels.raise_for_status("mesh_hierarchy", "hierarchy", st, ((constants.HIER_BAD_COLUMN, ValueError),
+                                                                     (constants.HIER_NOT_FINISHED, RuntimeError)))
+        P = SparseOperator(torch.arange(nk + 1, dtype=torch.int32, device=dev), parent.int(), torch.ones(nk, device=dev), (nk, nc))
+        R = _csr_from_sorted(parent, idx, r, (nc, nk))
+        Lc = spgemm(R, spgemm(cur, P))
+        m = msum[is_rep].contiguous()
+        own = owners[0][is_rep]
+        mates[0], parents[0], rounds[0], singles[0] = mate, parent, nrounds, nsingle
+        ops.insert(0, Lc); mates.insert(0, None); parents.insert(0, None); rounds.insert(0, 0); singles.insert(0, 0)
+        owners.insert(0, own)
+    if levels == 1:
+        eye = torch.arange(n, **i64)
+        return MeshHierarchy([L], [torch.ones(n, dtype=torch.bool, device=dev)], eye, eye, [n], [0], [0], 0, [eye])
+    B = len(blocks)
+    counts0 = torch.bincount(owners[0], minlength=B)
+    n0 = -(-max(int(counts0.max()), 1) // pad_coarsest_to) * pad_coarsest_to
+    first0 = torch.cumsum(counts0, 0) - counts0
+    pos = owners[0] * n0 + (torch.arange(ops[0]._shape[0], **i64) - first0[owners[0]])
+    out_L, real, sizes, positions = [], [], [], []
+    for k in range(levels):
+        if k > 0:
+            mate = mates[k]
+            pos = 2 * pos[parents[k]] + ((mate >= 0) & (mate < torch.arange(mate.numel(), **i64))).long()
+        size = (B * n0) << k
+        op = ops[k]
+        nk = op._shape[0]
+        rows = _csr_rows(op.rowptr, nk)
+        out_L.append(_csr_from_sorted(pos[rows], pos[op.colind.long()], op.vals, (size, size)))
+        mask = torch.zeros(size, dtype=torch.bool, device=dev)
+        mask[pos] = True
+        real.append(mask)
+        sizes.append(nk)
+        positions.append(pos)
+    order = torch.full((real[-1].numel(),), -1, **i64)
+    order[pos] = torch.arange(n, **i64)
+    return MeshHierarchy(out_L, real, order, pos, sizes, singles, rounds, status, positions)
