@@ -562,6 +562,54 @@ int sn_pool_max2_bwd_f32(const float *x, int64_t ldx, const float *g, int64_t ld
 int sn_unpool2_add_fwd_f32(const float *x, int64_t ldx, const float *skip, int64_t lds, int64_t pairs, int32_t C, float *y,
                            int64_t ldy, void *stream);
 int sn_unpool2_bwd_f32(const float *g, int64_t ldg, int64_t pairs, int32_t C, float *gx, int64_t ldgx, void *stream);
+/* ---- Graph attention ----------------------------------------------------------------------------------------------------------
+ * The propagation rule of the graph-attention block (attention.GatResNet2, attention.LapGatModel): the weights of the product are
+ * computed from the features, per stored entry and per call, with a softmax over each row.  The reference names the block
+ * (`pygat.GatResNet2`, src/normal_predict/models.py:85-124) and contains no code for it, and its driver runs it on a dense N x N
+ * adjacency only: the definition below is this project's own (pattern-only attention, no dropout); the statement in torch
+ * operations is attention.attn_propagate_reference.
+ *   A      square CSR operator of R rows, int32.  Only rowptr and colind are read: the values never are.  A stored explicit zero is
+ *          an entry like any other.  Column indices must lie in 0 .. R-1 (the kernels do not check, like the products).
+ *   e      (R, C) fp32;  H heads, slice k = channels [k C / H, (k + 1) C / H);  a (2, C) fp32, contiguous: row 0 scores a row as a
+ *          source, row 1 as a destination;  SN_ATTN_SLOPE = 0.2.
+ *   s[j, k]     = sum over slice k of a[0, c] e[j, c]          s[i, H + k] likewise with a[1]                  (s: R x 2H)
+ *   u_ij^k      = leaky_relu(s[i, H + k] + s[j, k], SN_ATTN_SLOPE)             for every stored entry (i, j)
+ *   alpha_ij^k  = exp(u_ij^k - m_i^k) / z_i^k,   m_i^k = max over row i of u,   z_i^k = sum over row i of exp(u - m)
+ *   p[i, slice k] = sum over row i of alpha_ij^k e[j, slice k]
+ * A row without a stored entry gives p[i, :] = 0 (and m = z = 0) and sends no gradient anywhere.  The maximum is subtracted before
+ * every exponential.  A NaN logit makes the head's slice of that row NaN, as the torch statement does.
+ * Supported: C % 4 == 0, 4 <= C <= SN_ATTN_MAX_CHANNELS, C % H == 0, (C / H) % 4 == 0 (sn_attn_supported says 1; SN_E_UNSUPPORTED
+ * otherwise); M == K (SN_E_SHAPE otherwise); dense operands with 16-byte aligned bases and leading dimensions that are multiples
+ * of 4 and >= C (SN_E_ALIGN / SN_E_LD).  Nothing of size nnz is stored anywhere; no atomics, no memset, nothing that synchronises:
+ * two runs give the same bits and every entry can be captured into a hipGraph.
+ *   sn_attn_elu_scores_f32     e = elu(x) (the library's ELU, as sn_elu_into_f32) written with leading dimension lde — the first half
+ *                              of a stage's (R, 2C) concat buffer — and s from the same registers: one streaming pass.
+ *   sn_attn_propagate_fwd_f32  p (leading dimension ldp: the second half of the concat buffer), m and z ((R, H) each, kept for the
+ *                              backward pass).  Row-wise over A: a first sweep over a row's column indices takes the maximum from s
+ *                              alone, a second one accumulates exp and the weighted rows.
+ *   sn_attn_propagate_bwd_f32  g: the gradient of p.  dx = de, or with ge (the gradient of the e half of the concat buffer, may be
+ *                              NULL)  dx = (de + ge) * elu'(e)  — the gradient of x;  da (2, C).  With D_i^k = <g[i, k], p[i, k]> and
+ *                              dpre_ij = alpha_ij (<g[i, k], e[j, k]> - D_i^k) * (1 where the logit's argument is > 0, else the slope):
+ *                                pass 1, rows of A:    ds[i, H + k] = sum_j dpre_ij
+ *                                pass 2, rows of A^T:  ds[j, k] = sum_i dpre_ij,   de[j, slice k] = sum_i alpha_ij g[i, slice k]
+ *                                                      + ds[j, k] a[0] + ds[j, H + k] a[1]        (alpha recomputed from s, m, z)
+ *                                da = column sums of ds (x) e: one partial per workgroup of pass 2, added in a fixed order in float64.
+ *                              t_rowptr / t_colind: the CSR pattern of A^T.  workspace: sn_attn_propagate_bwd_workspace_bytes(R, C, H),
+ *                              else SN_E_WORKSPACE.  dx must not overlap an input. */
+#define SN_ATTN_MAX_CHANNELS 256
+#define SN_ATTN_SLOPE        0.2
+int32_t sn_attn_supported(int32_t C, int32_t H);
+int sn_attn_elu_scores_f32(const float *x, int64_t ldx, const float *a, int64_t R, int32_t C, int32_t H, float *e, int64_t lde,
+                           float *s, void *stream);
+int sn_attn_propagate_fwd_f32(const int32_t *rowptr, const int32_t *colind, int64_t M, int64_t K, int64_t nnz, const float *e,
+                              int64_t lde, const float *s, int32_t C, int32_t H, float *p, int64_t ldp, float *m, float *z,
+                              void *stream);
+size_t sn_attn_propagate_bwd_workspace_bytes(int64_t R, int32_t C, int32_t H);
+int sn_attn_propagate_bwd_f32(const int32_t *rowptr, const int32_t *colind, const int32_t *t_rowptr, const int32_t *t_colind,
+                              int64_t M, int64_t K, int64_t nnz, const float *g, int64_t ldg, const float *ge, int64_t ldge,
+                              const float *e, int64_t lde, const float *p, int64_t ldp, const float *s, const float *m,
+                              const float *z, const float *a, int32_t C, int32_t H, float *dx, int64_t lddx, float *da,
+                              void *workspace, size_t workspace_bytes, void *stream);
 /* ---- Mesh hierarchy -------------------------------------------------------------------------------------------------------------
  * One coarsening step of the hierarchy the cascade model's per-level operators come from (operators.mesh_hierarchy; the numpy
  * statement is mesh_ops.mesh_hierarchy).  The reference names the coarsening of Defferrard et al. 2017 ("the specific construction

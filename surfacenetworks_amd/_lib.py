@@ -110,6 +110,12 @@ SIGNATURES = {
     "sn_pool_max2_bwd_f32": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp]),
     "sn_unpool2_add_fwd_f32": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp]),
     "sn_unpool2_bwd_f32": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _i64, _vp]),
+    "sn_attn_supported": (_i32, [_i32, _i32]),
+    "sn_attn_elu_scores_f32": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "sn_attn_propagate_fwd_f32": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
+    "sn_attn_propagate_bwd_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "sn_attn_propagate_bwd_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp,
+                                            _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),
     "sn_mesh_match_workspace_bytes": (_sz, [_i64, _i64]),
     "sn_mesh_match_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sn_pair_argmin_f32": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),

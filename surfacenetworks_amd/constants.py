@@ -49,6 +49,10 @@ ARAP_MAX_CG = 65536
 HIER_NOT_FINISHED, HIER_BAD_COLUMN = 1, 2
 HIER_THREADS = 1024                  # the one workgroup that walks an operator
 
+# Graph attention
+ATTN_MAX_CHANNELS = 256              # C / 4 lanes of one wave hold a row
+ATTN_SLOPE = 0.2                     # the negative slope of the logits' leaky ReLU (part of the definition)
+
 # Sparse x sparse products
 SPGEMM_MAX_WINDOW = 131072
 SPGEMM_BAD_COLUMN, SPGEMM_TOO_WIDE, SPGEMM_TOO_LARGE, CSR_NO_OFFDIAGONAL = 1, 2, 4, 8

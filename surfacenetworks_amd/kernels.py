@@ -2558,3 +2558,71 @@ def arap_frames(V0, weights: ArapWeights, voff, hoff, handles, H, max_mesh_verti
                   min(chunk, T - begin), iters, float(tol), max_cg, _p(frames), _p(cg_iters), _p(energy), _p(status), _p(R_first),
                   _p(rhs_first), _p(ws), ws_bytes, _stream())
     return ArapFrames(frames, cg_iters, energy, status, R_first, rhs_first)
+
+
+# ---- graph attention (include/sn_spmm.h, "Graph attention"; torch statement attention.attn_propagate_reference) --------------------
+def attn_supported(C: int, heads: int) -> bool:
+    """Whether the attention kernels take C channels in `heads` heads (sn_attn_supported)."""
+    return bool(_lib.load().sn_attn_supported(int(C), int(heads)))
+
+
+def _attn_check(what: str, rows: int, C: int, heads: int, a, *dense) -> None:
+    if not attn_supported(C, heads):
+        raise ValueError(f"{what}: C = {C} channels in {heads} heads is outside the supported set (C % 4 == 0, C <= "
+                         f"{ATTN_MAX_CHANNELS}, C % heads == 0, (C / heads) % 4 == 0)")
+    if a.dtype != torch.float32 or tuple(a.shape) != (2, C) or not a.is_contiguous():
+        raise ValueError(f"{what}: a must be a contiguous (2, {C}) float32 tensor, got {tuple(a.shape)} {a.dtype}")
+    for t in dense:
+        if t is None:
+            continue
+        if t.dtype != torch.float32:
+            raise TypeError(f"{what}: float32 operands expected, got {t.dtype}")
+        if tuple(t.shape) != (rows, C):
+            raise ValueError(f"{what}: ({rows}, {C}) operands expected, got {tuple(t.shape)}")
+        _ld(t)
+
+
+def attn_elu_scores(x, a, heads: int, e):
+    """e <- elu(x) (e: a (rows, C) view with contiguous rows, e.g. the first half of a concat buffer) and the (rows, 2 heads) scores
+    of e under a, from one pass (sn_attn_elu_scores_f32).  Returns the scores."""
+    _dev(x, a, e)
+    rows, C = x.shape
+    _attn_check("attn_elu_scores", rows, C, heads, a, x, e)
+    s = torch.empty((rows, 2 * heads), dtype=torch.float32, device=x.device)
+    _lib.call("sn_attn_elu_scores_f32", _p(x), _ld(x), _p(a), rows, C, int(heads), _p(e), _ld(e), _p(s), _stream())
+    return s
+
+
+def attn_propagate_fwd(rowptr, colind, M: int, K: int, e, s, heads: int, p):
+    """p <- the attention-weighted sum of the rows of e over the pattern (rowptr, colind) (sn_attn_propagate_fwd_f32).  Returns
+    (m, z), the (rows, heads) maxima and normalisers the backward pass reads."""
+    _dev(rowptr, colind, e, s, p)
+    if M != K:
+        raise ValueError(f"attn_propagate_fwd: a square operator is required, got {(M, K)}")
+    C = e.shape[1]
+    if not attn_supported(C, heads):
+        raise ValueError(f"attn_propagate_fwd: C = {C} channels in {heads} heads is outside the supported set")
+    if tuple(e.shape) != (M, C) or tuple(p.shape) != (M, C) or tuple(s.shape) != (M, 2 * heads) or not s.is_contiguous():
+        raise ValueError(f"attn_propagate_fwd: operands do not fit {M} rows of {C} channels in {heads} heads")
+    m = torch.empty((M, heads), dtype=torch.float32, device=e.device)
+    z = torch.empty((M, heads), dtype=torch.float32, device=e.device)
+    _lib.call("sn_attn_propagate_fwd_f32", _p(rowptr), _p(colind), M, K, int(colind.numel()), _p(e), _ld(e), _p(s), C, int(heads),
+              _p(p), _ld(p), _p(m), _p(z), _stream())
+    return m, z
+
+
+def attn_propagate_bwd(rowptr, colind, t_rowptr, t_colind, M: int, K: int, g, ge, e, p, s, m, z, a, heads: int):
+    """(dx, da) of sn_attn_propagate_bwd_f32: g the gradient of p, ge the gradient of the e half (or None: dx is then the gradient
+    of e itself, without the ELU's derivative); (t_rowptr, t_colind): the pattern of the transpose."""
+    _dev(rowptr, colind, t_rowptr, t_colind, g, ge, e, p, s, m, z, a)
+    if M != K:
+        raise ValueError(f"attn_propagate_bwd: a square operator is required, got {(M, K)}")
+    C = e.shape[1]
+    _attn_check("attn_propagate_bwd", M, C, heads, a, g, ge, e, p)
+    dx = torch.empty((M, C), dtype=torch.float32, device=e.device)
+    da = torch.empty((2, C), dtype=torch.float32, device=e.device)
+    ws, ws_bytes = _workspace("sn_attn_propagate_bwd_workspace_bytes", e.device, M, C, int(heads))
+    _lib.call("sn_attn_propagate_bwd_f32", _p(rowptr), _p(colind), _p(t_rowptr), _p(t_colind), M, K, int(colind.numel()), _p(g), _ld(g),
+              _p(ge), _ld(ge) if ge is not None else 0, _p(e), _ld(e), _p(p), _ld(p), _p(s), _p(m), _p(z), _p(a), C, int(heads),
+              _p(dx), C, _p(da), _p(ws), ws_bytes, _stream())
+    return dx, da

@@ -10,8 +10,11 @@ row of W and b is a zero pad made inside autograd (blocks.elu_conv(pad_to=4), fu
 the pitch-4 gradient that comes back are what the loss kernels read and write (kernels.normal_cosine_*: loss, metric and gradient
 from one pass); `forward` returns the first three columns.
 
-Not here, and refused rather than approximated: bottleneck widths, nofirstId, bnmode other than '', GatDeepModel,
-LapMATModel.  `EfficientCascade` refuses under its own name too: the reference's multiresolution model lives in
+Not here, and refused rather than approximated: bottleneck widths, nofirstId, bnmode other than '', LapMATModel.  `GatDeepModel`
+refuses under its own name: the graph-attention model lives in attention.LapGatModel (the reference's dense-adjacency `pygat` block
+is not in its tree; the block there is this project's own definition on the sparse operator's pattern) and runs through
+forward_loss / train_step / graphed_train_step / evaluate / predict here unchanged, on NormalFrames(model="lap") batches.
+`EfficientCascade` refuses under its own name too: the reference's multiresolution model lives in
 cascade.LapCascade (naive pooling, equal widths), which takes the per-level operators of a batch (`Batch.Laps`) and runs through
 forward_loss / train_step / graphed_train_step here unchanged; NormalFrames(model="cas") builds each frame's mesh hierarchy
 (operators.mesh_hierarchy) and samples such batches, and to_mesh_order maps their rows back to vertex ids.
@@ -304,7 +307,9 @@ DirDeepModel.fuzzy_load = AvgModel.fuzzy_load        # models.py:276-280 filters
 class GatDeepModel(nn.Module):
     def __init__(self, *args, **kwargs):
         super().__init__()
-        _refuse("GatDeepModel", "the graph-attention model (models.py:85-124)")
+        _refuse("GatDeepModel", "the graph-attention model (models.py:85-124) under this name — attention.LapGatModel is that model "
+                                "on the sparse operator's pattern, by this project's own definition of the block the reference names "
+                                "and does not contain —")
 
 
 class EfficientCascade(nn.Module):
